@@ -7,6 +7,8 @@ synthetic dependency graphs already resident in HBM.  Workload = BASELINE.json c
 4096 graphs x 32 tokens, avg degree 4 (nnz = 524288 incl. self loops), hidden = 768, fp32.
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full          # + box, other precisions, CPU baseline, appendices
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR   # + the last timed step's outputs as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --config 4          # BASELINE.json configs[3]: 256 x 512-token graphs, hidden 1024, fp16 features
@@ -32,6 +34,8 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 MFMA_BF16_PEAK_TF = 2500.0   # dense bf16 MFMA peak (spec, no sparsity)
 MFMA_F32_PEAK_TF = 157.3     # f32-input MFMA peak
 SURVEY_8D_BYTES_PER_LAYER = 822873092   # 2*4*N*H + 4(N+1) + 4E + 4*B*H + 4H^2 + 4H
+DUMP_BUDGET_BYTES = 60 << 20            # --dump-outputs: all files together (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 20251016             # --dump-outputs: which rows of an output too large to write whole
 
 ISSUE_NOTE = {
     "f16mx6": "the f16mx6 linear spends 96 matrix-pipe cycles per 32x32x32 block (64 fp16 + 32 block-scaled fp6) where plain "
@@ -107,7 +111,21 @@ def parse():
                     help="N = 1, config 2: skip the compact configs[3] block (a child run of this script with --config 4)")
     ap.add_argument("--no-box", action="store_true", help="N = 1: skip the `box` block (power / clock under load / MFMA calibration after the timed region)")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch (N > 1 without torch.distributed.run): rendezvous port, 0 = pick a free one")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline after the timed region: the `box` block, other precisions "
+                         "and their accuracy (alt_precisions, max_abs_err, product_default), the CPU baseline and, at N = 1 with "
+                         "config 2, the eval / ACE-cased / config 4 / 512-graph-shard appendices (the --no-* options still drop "
+                         "single legs).  Without it the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step computed (rank 0's outputs of the path, and at "
+                         "N > 1 the last gathered payload) as DIR/<name>.npy in float32; an output larger than its share of "
+                         "%d MiB is written as a fixed, seeded sample of its rows (the `dump` block of the line says which)"
+                         % (DUMP_BUDGET_BYTES >> 20))
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not a.full:   # a plain run: the headline figure alone
+        a.no_box = a.no_alt = a.no_cpu_baseline = a.no_config4 = True
     d = {2: (4096, 32, 768, 4.0, 4096), 4: (256, 512, 1024, 6.0, 16)}[a.config]
     a.graphs = a.graphs or d[0]
     a.tokens = a.tokens or d[1]
@@ -203,6 +221,34 @@ def percentiles(v):
     return {"median": statistics.median(v), "p10": pick(0.10), "p90": pick(0.90), "min": v[0], "max": v[-1]}
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy in float32 (float64 stays float64).  Smallest first, every array
+    gets an equal share of what is left of DUMP_BUDGET_BYTES; one larger than its share is written as the rows (first axis)
+    that a fixed seed picks, in ascending order, so that two builds given the same arguments write the same sample.
+    Returns what was written."""
+    import numpy as np
+    import torch
+    arrays = {k: v.detach() for k, v in arrays.items() if isinstance(v, torch.Tensor)}
+    arrays = {k: v.double() if v.dtype == torch.float64 else v.float() for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    written = {}
+    for i, name in enumerate(sorted(arrays, key=lambda k: (arrays[k].numel() * arrays[k].element_size(), k))):
+        t = arrays[name]
+        share = left // (len(arrays) - i)
+        row_bytes = t[0].numel() * t.element_size() if t.dim() and t.shape[0] else 0
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+        if t.dim() and row_bytes and t.numel() * t.element_size() > share:
+            n = max(1, share // row_bytes)
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.shape[0], size=n, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+            entry.update({"rows_written": int(n), "rows_seed": DUMP_SAMPLE_SEED})
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+        left -= t.numel() * t.element_size()
+        written[name] = entry
+    return dict(sorted(written.items()))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` typed as is, N > 1: this process has not touched the GPU yet (torch is not even
     imported), so it starts N fresh rank processes through torch.distributed.run -- as a CHILD, never an exec -- relays
@@ -223,10 +269,10 @@ def self_launch(args):
 
 def config4_block(timeout_s=600):
     """BASELINE.json configs[3] measured by a child run of this script (`--config 4`) AFTER this process's own timed
-    region: a compact block for the default line, so that the driver's one command records it."""
+    region: a compact block of the --full line, so that one command records it."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--config", "4", "--steps", "60", "--warmup", "20",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -242,7 +288,7 @@ def config4_block(timeout_s=600):
             "forward_hbm_frac": r["forward_hbm_frac"],
             "max_abs_err": (r.get("max_abs_err") or {}).get("value"),
             "max_abs_err_gate": "2e-3 (fp16 features, SURVEY 8d)",
-            "measured_by": "child process `bench.py --config 4 --steps 60 --warmup 20` after the headline's timed region"}
+            "measured_by": "child process `bench.py --config 4 --steps 60 --warmup 20 --full` after the headline's timed region"}
 
 
 def shard512_block(ms_full, timeout_s=300):
@@ -800,7 +846,7 @@ def main():
     marks = [0]
     for i in range(args.steps):
         sampling[0] = (i % k_stride) == 0
-        step()
+        r_last = step()
         if (i + 1) % ev_stride == 0 or i + 1 == args.steps:
             step_pool[i + 1].record()
             marks.append(i + 1)
@@ -825,6 +871,15 @@ def main():
     else:
         nnz_total = nnz
     ms_per_step = elapsed / args.steps * 1e3
+    # ---- what the last timed step computed, before anything else runs a step (graph replay reuses its output buffers) ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        outs = {k: v for k, v in r_last.items() if not k.startswith("_") and not (k == "payload" and "logits" in r_last)}
+        if dist_on and last_gathered[0] is not None:
+            outs["gathered"] = last_gathered[0]
+        dumped = {"dir": args.dump_outputs, "outputs": dump_outputs(args.dump_outputs, outs),
+                  "note": "the last timed step's outputs (rank 0); an output over its share of %d MiB holds the rows a fixed seed "
+                          "picks" % (DUMP_BUDGET_BYTES >> 20)}
 
     # ---- N > 1: what the collective moved, and (on request) the gathered payload against the unsharded batch ----
     rccl = gather_check = None
@@ -1022,6 +1077,8 @@ def main():
             "roofline": roofline,
             "kernels": kernels,
         }
+        if dumped is not None:
+            result["dump"] = dumped
         if box is not None:
             result["box"] = box
         if rccl is not None:

@@ -1967,6 +1967,54 @@ def test_bench_distributed_loop_over_rccl_with_a_process_group_of_one(pkg, dev, 
     assert r["value"] > 0 and "roofline" in r
 
 
+def test_bench_plain_run_times_k_steps_and_dumps_what_the_last_one_computed(pkg, dev, tmp_path):
+    """A plain `bench.py` run measures the headline alone (no appendix leg: those run under --full) and `--dump-outputs DIR`
+    writes the block's outputs of the last timed step; the same seeded inputs through gated_gcn_block in this process give
+    the same arrays."""
+    import json, os, subprocess, sys
+    from ed_gated_gcn_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, T, H = 64, 32, 768
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--graphs", str(B), "--steps", "7", "--warmup", "2",
+           "--precondition", "4", "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 7 and r["warmup"] == 2 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["metric"] == "gated_gcn_forward_edges_per_sec" and r["unit"] == "edges/s" and r["higher_is_better"] is True
+    for k in ("box", "alt_precisions", "max_abs_err", "product_default", "cpu_baseline", "eval_logits_only", "ace_cased",
+              "config4", "scaling_ceiling"):
+        assert k not in r, k
+    names = {"x1", "y1", "xy", "x", "out"}
+    assert set(r["dump"]["outputs"]) == names and sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, n + ".npy")) for n in names) <= 64e6
+
+    adj = synth.dependency_batch(B, T, 4.0, seed=synth.SEED)
+    rp, ci, _ = synth.csr_from_dense_host(adj)
+    csr = pkg.BatchedCSR.from_arrays(rp, ci, B, T, dev)
+    gen = torch.Generator().manual_seed(synth.SEED)
+    x = torch.randn(B, T, H, generator=gen)
+    g1, g2 = torch.sigmoid(torch.randn(B, H, generator=gen)), torch.sigmoid(torch.randn(B, H, generator=gen))
+    layers = []
+    for seed in (1, 2):
+        w, b = synth.layer_params(H, H, seed=seed)
+        m = pkg.GraphConvolution(H, H, opt=None).to(dev)
+        m.precision, m.fused = "f16mx8", True
+        with torch.no_grad():
+            m.weight.copy_(torch.from_numpy(w))
+            m.bias.copy_(torch.from_numpy(b))
+        layers.append(m.eval())
+    with torch.no_grad():
+        want = pkg.gated_gcn_block(x.to(dev), csr, g1.to(dev), g2.to(dev), *layers)
+    for n in names:
+        np.testing.assert_allclose(got[n], want[n].cpu().numpy(), rtol=0, atol=1e-6, err_msg=n)
+
+
 def test_range_report_reaches_a_process_that_never_asks(pkg, dev):
     """the lazy report needs a LATER forward to surface; a process with a single forward (or none after the
     violation) used to exit silently.  Now the snapshot is taken behind the first guarded forward and whatever is still

@@ -6,7 +6,7 @@ TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
-cd $R && python3 bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+cd $R && python3 bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 # (the profiled runs carry no appendix: no child processes, no box probes -- only the timed loop's kernels)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $R/bench.py --no-cpu-baseline --no-alt --no-config4 --no-box "$@" > $OUT/stats.log 2>&1
