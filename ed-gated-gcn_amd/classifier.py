@@ -120,11 +120,13 @@ class GatedGCNEventDetector(nn.Module):
             self._proved = (key, ok, float(m1))
         _, ok, m1 = self._proved
         if ok and not (m1 <= self.F16MX8_WINDOW):
-            # gcn1 may leave the window: fine only where no main loop ever splits it -- the one-launch block
+            # gcn1 may leave the window: fine only where no main loop ever splits it -- the one-launch block, which runs only
+            # without autograd (gated_gcn_block takes two launches when a gradient is wanted: gc2's main loop splits gcn1)
             before = (self.gc1.precision, self.gc2.precision)
             self.gc1.precision = self.gc2.precision = "f16mx8"
             try:
-                ok = x is not None and takes_block_path(x, csr, self.gc1, self.gc2)
+                grad = x is not None and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+                ok = x is not None and not grad and takes_block_path(x, csr, self.gc1, self.gc2)
             finally:
                 self.gc1.precision, self.gc2.precision = before
         return "f16mx8" if ok else "bf16x3"

@@ -207,7 +207,7 @@ __device__ __forceinline__ BufX<AT> make_bufx(const AT *X, int64_t ldx, int64_t 
 #endif
 // XS (ggcn_linear_scaled: the backward's dX): every value is multiplied by the power of two `xscale` before it is split -- rows
 // whose magnitudes lie anywhere in the fp32 range (gradients) are brought to |x| < 256 first; the caller undoes it at the store.
-// XP (fused_block8.hip, an experiment): this thread STAGES only XP of the tile's passes -- pass0, pass0 + 1, ... in the slots 0 ..
+// XP (fused_block8.hip, the block's large-batch kernel): this thread STAGES only XP of the tile's passes -- pass0, pass0 + 1, ... in the slots 0 ..
 // XP - 1 of arow / avalid / bufx -- while its wavefront still multiplies all NB row blocks: two four-wavefront groups of one
 // 512-thread workgroup share one set of X planes (each stages half of it) and meet at the same barriers.  SLOT0: the stage's slot
 // (= 32-row block of MFMAs) behind which this thread's first staging pass sits -- the second group takes slots 2, 3, so that the two

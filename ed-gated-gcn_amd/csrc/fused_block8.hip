@@ -1,13 +1,15 @@
-// EXPERIMENT (`ggcn_lab_block_fused8`, nothing in the product calls it): the two-layer block with ONE
-// workgroup of EIGHT wavefronts per (row block, 256-column slice) that shares a row block's X planes between its W1 and its W12
-// column tiles.  Wavefronts 0-3 (group 0) own the slice's W1 tiles, wavefronts 4-7 (group 1) its W12 tiles; every thread stages 2
+// What ggcn_block_fused runs for large batches (the headline's kernel; ggcn_lab_block_fused8 reaches it directly): the two-layer
+// block with ONE workgroup of EIGHT wavefronts per (row block, 256-column slice) that shares a row block's X planes between its W1
+// and its W12 column tiles.  Dispatch rule (block8_shape / block8_takes below, ggcn_block_fused_form): every output of the block
+// (no gcn1), f16mx8, T <= 32, K % 32 == 0, F a multiple of 256, 16-byte aligned operands, and a batch that makes >= 6 rounds of
+// one workgroup per CU or >= 3 whole rounds (2048 x 768 and up; 1024 x 768); GGCN_BLOCK_FORM=4 keeps the four-wavefront kernel.
+// Wavefronts 0-3 (group 0) own the slice's W1 tiles, wavefronts 4-7 (group 1) its W12 tiles; every thread stages 2
 // of the stage's 4 passes (mx8::mainloop<..., XP = 2>), so X is loaded, split and written to LDS once for both layers -- half the
 // X-side work per output (48 + 24 us of the elimination ladder) and one fetch of X per slice instead of one per part.
 // What it gives up is what DESIGN.md 5b says it gives up: 8 x 235 registers fill the CU, so ONE workgroup is resident and both
 // groups' epilogues run under nothing.  Block ids that share an XCD take a contiguous run of (slice-major) work items, so an XCD
 // holds at most two column slices of both weight images (2.5 MB of its 4 MiB L2) -- the price: a row block's three slices sit on
-// three XCDs.  Same tiles, same arithmetic, same order as ggcn_block_fused: results are bit-identical (test).  f16mx8, T <= 32,
-// fast shapes (K % 32 == 0, 16-byte rows), no gcn1 output.
+// three XCDs.  Same tiles, same arithmetic, same order as the four-wavefront kernel: results are bit-identical (tests).
 #include "fused_common.h"
 
 #include <cstdlib>
@@ -19,6 +21,22 @@ constexpr int kB8Threads = 512;
 constexpr int kB8Lds = kLdsBytes + 2 * kEpiLdsBytes;   // one set of stage buffers, two sets of epilogue operands: 94.5 KiB
 
 __device__ __forceinline__ bool getenv_slot_same(const FusedArgs &a) { return (a.k_steps & 0x20000000) != 0; }   // (lab: both groups stage behind slots 0, 1)
+
+// max |mid bias| of the slice from the W12 group's staged operands (LDS-DMA: the raw row, reduced per wavefront; else the
+// per-wavefront maxima stage_epilogue_operands left) -- what dma_range_verdict / fused_range_verdict read
+template <int BASE>
+__device__ __forceinline__ float staged_mid_max(const char *lds, bool dma, int lane)
+{
+    if (dma) {
+        const float4 m4 = *reinterpret_cast<const float4 *>(lds + EpiLds<BASE>::kBias + BN * 4 + lane * 16);
+        float mm = fmaxf(fmaxf(fabsf(m4.x), fabsf(m4.y)), fmaxf(fabsf(m4.z), fabsf(m4.w)));
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) mm = fmaxf(mm, __shfl_xor(mm, d));
+        return mm;
+    }
+    const float4 mm = *reinterpret_cast<const float4 *>(lds + EpiLds<BASE>::kMidMax);
+    return fmaxf(fmaxf(mm.x, mm.y), fmaxf(mm.z, mm.w));
+}
 
 template <bool FULLT, bool VST>
 __global__ __launch_bounds__(kB8Threads, 1) void block_fused8_kernel(const FusedArgs a)
@@ -74,6 +92,10 @@ __global__ __launch_bounds__(kB8Threads, 1) void block_fused8_kernel(const Fused
 
     f32x16 acc[4][RN];
     float amax;
+    const int64_t pack_bytes = (int64_t)n_tiles_total * (k_steps / 2) * mx8::STAGE_PACK_BYTES;
+    // both weight images' hidden-value factors (their trailers), asked for before the main loop: no load waits behind it
+    const float bw1 = *reinterpret_cast<const float *>(a.part[0].wpack + pack_bytes);
+    const float bw12 = *reinterpret_cast<const float *>(a.part[1].wpack + pack_bytes);
     const unsigned long long t_loop0 = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     mx8::BufX<float> bx = mx8::make_bufx<float>(a.X, a.ldx, (int64_t)gt0 * T, (int64_t)B * T, rel, tid);
     // (two instantiations that meet at the same barriers: group 1's staging passes sit behind the stage's LAST two row blocks)
@@ -83,16 +105,16 @@ __global__ __launch_bounds__(kB8Threads, 1) void block_fused8_kernel(const Fused
     else
         mx8::mainloop<float, true, true, !FULLT, false, true, 4, false, 2, 2>(arow, avalid, lp.wpack, K, k_steps / 2, 0, nt0, n_tiles_total, lds, acc, 0, 4,
                                                                                &amax, &bx, 1.0f, 2 * group);
-    const int64_t pack_bytes = (int64_t)n_tiles_total * (k_steps / 2) * mx8::STAGE_PACK_BYTES;
     unsigned long long t_loop1 = 0;
     if (a.stamps) { asm volatile("" :: "v"(acc[3][RN - 1][15])); t_loop1 = __builtin_amdgcn_s_memrealtime(); }
+    // Each row of the tile is split by ONE group (group 0: graphs gt0, gt0 + 1; group 1: gt0 + 2, gt0 + 3), so each group judges
+    // its amax against BOTH weight images' hidden-value bounds -- W1's, and W12's plus max |mid| from group 1's staged mid row
+    // (written before the main loop; its barriers make it visible to all eight wavefronts, and no epilogue writes it)
+    mx8::range_verdict(amax, bw12, staged_mid_max<kLdsBytes + kEpiLdsBytes>(lds, dma, tid & 63), true);
+    mx8::range_verdict(amax, bw1, 0.0f, false);
     if (group == 0) {
-        if (dma) dma_range_verdict<kLdsBytes>(amax, lp.wpack, pack_bytes, lds, tid & 63);
-        else fused_range_verdict<kLdsBytes>(amax, lp.wpack, pack_bytes, lds, true);
         epilogue<1, FULLT, VST, false, false, kLdsBytes>(a, lp, acc, g0, nt0, n_tiles_total, lds, tid);
     } else {
-        if (dma) dma_range_verdict<kLdsBytes + kEpiLdsBytes>(amax, lp.wpack, pack_bytes, lds, tid & 63);
-        else fused_range_verdict<kLdsBytes + kEpiLdsBytes>(amax, lp.wpack, pack_bytes, lds, true);
         if (lp.out) epilogue<1, FULLT, VST, true, true, kLdsBytes + kEpiLdsBytes>(a, lp, acc, g0, nt0, n_tiles_total, lds, tid);
         else epilogue<1, FULLT, VST, true, false, kLdsBytes + kEpiLdsBytes>(a, lp, acc, g0, nt0, n_tiles_total, lds, tid);
     }
@@ -129,10 +151,13 @@ bool block8_shape(int B, int T, int K, int F)
     const int64_t total = (int64_t)((B + 3) / 4) * (F / BN), cus = device_cu_count();
     return total >= 6 * cus || (total >= 3 * cus && total % cus == 0);
 }
-bool block8_takes(const float *X, int64_t ldx, int B, int T, int K, int F, const float *gate1, const float *gate2, const float *bias1,
-                  const float *bias_mid, const float *bias2, const void *graph_ops, const void *graph_ops2, const float *x_out, int64_t ld2)
+bool block8_takes(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, int B, int T, int K, int F, const float *gate1,
+                  const float *gate2, const float *bias1, const float *bias_mid, const float *bias2, const void *graph_ops,
+                  const void *graph_ops2, const float *x_out, int64_t ld2)
 {
     if (!block8_shape(B, T, K, F)) return false;
+    // what launch_fused would refuse goes there, so that both forms answer a bad call with the same code and message
+    if (ldx < K || !aligned16(wpack1) || !aligned16(wpack12) || (x_out && ld2 < F)) return false;
     if (!((ldx % 4 == 0) && aligned16(X) && (int64_t)ldx * 4 * 257 < ((int64_t)1 << 31))) return false;
     if (!graph_ops || !graph_ops2 || !gate1 || !gate2 || !bias_mid) return false;
     if (!(aligned16(gate1) && aligned16(gate2) && aligned16(bias1) && aligned16(bias2) && aligned16(bias_mid) && aligned16(graph_ops) &&
@@ -153,6 +178,10 @@ int lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const void
     if (!X || !wpack1 || !wpack12 || !graph_ops || !graph_ops2 || !gate1 || !gate2 || !x1 || !y1 || !bias_mid)
         return fail(GGCN_EINVAL, "%s: null pointer", who);
     if (B <= 0 || T <= 0 || T > 32 || K <= 0 || F <= 0) return fail(GGCN_EUNSUPPORTED, "%s: B=%d T=%d K=%d F=%d (graphs of <= 32 nodes)", who, B, T, K, F);
+    // launch_fused's checks (fused_layer.hip), with its messages
+    if (ldx < K) return fail(GGCN_EINVAL, "%s: ldx < K", who);
+    if (!aligned16(wpack1) || !aligned16(wpack12)) return fail(GGCN_EINVAL, "%s: wpack must be 16-byte aligned", who);
+    if (x_out && ld2 < F) return fail(GGCN_EINVAL, "%s: leading dimension of the output too small", who);
     const bool avec = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(X) && (int64_t)ldx * 4 * 257 < ((int64_t)1 << 31);
     if (!avec || K % BK != 0) return fail(GGCN_EUNSUPPORTED, "%s: fast shapes only (K %% 32 == 0, 16-byte aligned rows)", who);
     if (!x_out && !pool_out) return fail(GGCN_EINVAL, "%s: neither x nor its pool requested", who);

@@ -617,7 +617,7 @@ int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpa
     // column slice (fused_block8.hip: bit-identical results, 2 % less time in steady state from 2048 graphs up).
     // GGCN_BLOCK_FORM=4 (read per call) keeps the four-wavefront kernel: A/B timing, tests.
     if (layer1 && !gcn1 && !stamps && precision == GGCN_PREC_F16MX8 && X && wpack1 && wpack12 && bias_mid &&
-        block8_takes(X, ldx, B, T, K, F, gate1, gate2, bias1, bias_mid, bias2, graph_ops, graph_ops2, x_out, ld2)) {
+        block8_takes(X, ldx, wpack1, wpack12, B, T, K, F, gate1, gate2, bias1, bias_mid, bias2, graph_ops, graph_ops2, x_out, ld2)) {
         const char *form = getenv("GGCN_BLOCK_FORM");
         if (!(form && form[0] == '4'))
             return lab_block_fused8(X, ldx, wpack1, wpack12, graph_ops, graph_ops2, bias1, bias_mid, bias2, B, T, K, F, gate1, gate2, x_out,

@@ -505,9 +505,12 @@ int ggcn_debug_mfma_calibrate(int n_wg, int stages, uint64_t *stamps, float *sin
  * GGCN_BLOCK_FORM=4 in the environment (read per call) keeps the four-wavefront kernel. */
 int ggcn_block_fused_form(int B, int T, int K, int F);
 
-/* EXPERIMENT, called by nothing in the product (tools/block8_timing.py, one parity test): ggcn_block_fused's tiles in workgroups of
- * EIGHT wavefronts that share a row block's X planes between the W1 and the W12 column tiles of a 256-column slice (f16mx8, T <= 32,
- * K % 32 == 0, 16-byte rows, no gcn1).  Bit-identical results; measured slower. */
+/* The eight-wavefront kernel of the block called directly (fused_block8.hip): the kernel ggcn_block_fused itself runs for large
+ * batches (the rule of ggcn_block_fused_form above: every output, GGCN_PREC_F16MX8, T <= 32, K % 32 == 0, F a multiple of 256,
+ * 16-byte aligned operands, >= 6 rounds of one workgroup per CU or >= 3 whole rounds).  Workgroups of EIGHT wavefronts share a row
+ * block's X planes between the W1 and the W12 column tiles of a 256-column slice (no gcn1).  Bit-identical to the four-wavefront
+ * kernel; the same argument checks and messages.  Here for tools/block8_timing.py and the tests; the XCD mapping and staging
+ * switches of the experiment are read from the environment (GGCN_LAB_BLOCK8_*). */
 int ggcn_lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
                           const void *graph_ops2, const float *bias1, const float *bias_mid, const float *bias2,
                           int B, int T, int K, int F, const float *gate1, const float *gate2, float *x_out, int64_t ld2,

@@ -197,3 +197,30 @@ def test_default_precision_and_range_check_need_a_gpu():
     with pytest.raises(RuntimeError, match="GPU"):
         m.check_range()
 
+
+
+@pytest.mark.parametrize("B", [64, 2048], ids=["four-wavefront", "eight-wavefront"])
+def test_block_fused_checks_its_arguments_before_the_large_batch_dispatch(B):
+    """ggcn_block_fused hands batches of >= 2048 graphs (f16mx8, every output) to the eight-wavefront kernel (fused_block8.hip);
+    that dispatch must refuse what the four-wavefront path refuses -- ldx < K, ld2 < F, a misaligned weight image -- with the
+    same code and message, before any launch (a launch would read X out of bounds).  Fake 16-byte aligned pointers: nothing
+    is dereferenced on these paths; without a device the CU count falls back to 256, so B = 2048 takes form 8 here too."""
+    lib = pkg.load_library()
+    T, K, F = 32, 768, 768
+    assert lib.ggcn_block_fused_form(B, T, K, F) == (8 if B >= 2048 else 4)
+    p = {k: 0x10000000 + 0x100000 * i for i, k in enumerate(
+        ("X", "w1", "w12", "ops", "ops2", "b1", "mid", "b2", "g1", "g2", "xo", "x1", "y1", "out", "part"))}
+
+    def block(ldx=K, ld2=F, w12=p["w12"]):
+        return lib.ggcn_block_fused(p["X"], ldx, p["w1"], w12, p["ops"], p["ops2"], p["b1"], p["mid"], p["b2"], B, T, K, F, p["g1"],
+                                    p["g2"], None, F, p["xo"], ld2, p["x1"], p["y1"], p["out"], p["part"], _capi.PREC["f16mx8"], None)
+
+    def lab(ldx=K, ld2=F, w12=p["w12"]):
+        return lib.ggcn_lab_block_fused8(p["X"], ldx, p["w1"], w12, p["ops"], p["ops2"], p["b1"], p["mid"], p["b2"], B, T, K, F,
+                                         p["g1"], p["g2"], p["xo"], ld2, p["x1"], p["y1"], p["out"], p["part"], None, None)
+    for fn, who in ((block, b"ggcn_block_fused"), (lab, b"ggcn_lab_block_fused8")):
+        for kw, msg in ((dict(ldx=K - 4), b"ldx < K"), (dict(ld2=F - 4), b"leading dimension of the output too small"),
+                        (dict(w12=p["w12"] + 8), b"wpack must be 16-byte aligned")):
+            rc = fn(**kw)
+            err = lib.ggcn_last_error()
+            assert rc == 1 and err == who + b": " + msg, (who, kw, rc, err)

@@ -27,6 +27,15 @@ def test_dense_restatement_is_bit_equal_on_config1(golden_dir):
     np.testing.assert_allclose(out.numpy(), g["out"], rtol=0, atol=1e-6)
 
 
+def test_dense_restatement_in_float64_on_config1(golden_dir):
+    """The float64 form (the high-precision reference of the GPU tests) is the same operation: within 1e-5 of the fixture."""
+    g = _load(golden_dir, "gcn_config1.npz")
+    t = lambda k: torch.from_numpy(g[k]).double()   # noqa: E731
+    out = ref_dense.graph_convolution(t("text"), torch.from_numpy(g["adj"]), t("weight"), t("bias"), dtype=torch.float64)
+    assert out.dtype == torch.float64 and out.shape == (1, 32, 300)
+    np.testing.assert_allclose(out.numpy(), g["out"], rtol=0, atol=1e-5)
+
+
 def _sweep_cases(golden_dir):
     g = _load(golden_dir, "gcn_sweep.npz")
     for i, desc in enumerate(g["cases"]):
