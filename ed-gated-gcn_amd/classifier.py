@@ -149,6 +149,10 @@ class GatedGCNEventDetector(nn.Module):
         rows = torch.arange(B, device=x.device)
         anchor_rep = self.dropout(x[rows, anchor])                          # :604-608: the anchor token's row
         x, _ = self.lstm(x)                                                 # :610
+        if x.dtype == torch.float16 and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16:
+            # under bf16 autocast the ROCm LSTM still returns float16; the reference's first consumers of x (gc1's matmul,
+            # gcn.py:34) cast it to bf16, so the layers are handed that bf16 tensor directly
+            x = x.to(torch.bfloat16)
         aspect = x[rows, anchor]                                            # :615-618
         x = x.contiguous()
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
@@ -162,7 +166,7 @@ class GatedGCNEventDetector(nn.Module):
                 self._assign(self._proved_precision(adj, x))
             want = ("out",) if self.eval_logits_only else None     # train.py:227: logits only -> only `out` of the block
             if nogate:   # :736-752: gc2(gc1(x)) and its max-pool -- the block with unit gates (one launch for T <= 32)
-                ones = x.new_ones(B, 2 * self.hidden_dim)
+                ones = x.new_ones(B, 2 * self.hidden_dim, dtype=torch.float32)   # (float32 gates for bf16 x too)
                 r = gated_gcn_block(x, adj, ones, ones, self.gc1, self.gc2, want=want)
                 xy = 0.0
             else:
@@ -218,7 +222,8 @@ class GatedGCNEventDetector(nn.Module):
         else:
             gate1 = self.gate1(aspect)                                                 # dropout is the identity here
             gate2 = self.gate2(aspect)
-            r = gated_gcn_block(x, adj, gate1.contiguous(), gate2.contiguous(), self.gc1, self.gc2)   # :626-640
+            # (under bf16 autocast the gate MLPs give bf16: the block takes float32 gates, the cast is differentiable)
+            r = gated_gcn_block(x, adj, gate1.float().contiguous(), gate2.float().contiguous(), self.gc1, self.gc2)   # :626-640
             xy, xg, out = r["xy"], r["x"], r["out"]
         if v54:
             pooled_d = self.dropout(pooled)                                 # :531

@@ -6,6 +6,12 @@
 // bf16(x - hi), residual <= 2^-16 |x|); each product is three bf16 MFMAs with fp32 accumulation:
 //     x.w ~= hi.hi + lo.hi + hi.lo            (dropped lo.lo <= 2^-16 |x.w|)
 //
+// bf16 A (features that arrive as bf16, e.g. under torch.autocast): x is exact in the MFMA's operand type, so lo = 0
+// and the lo.hi product vanishes: x.w ~= hi.hi + hi.lo, TWO MFMAs per product, and the 16-B loads go to LDS as they
+// arrive (the hi plane; no split in registers).  The lo plane's half of the A buffers is left unused: the tile stays
+// 128 x 256 with two workgroups per CU (launch bounds, 128 accumulator VGPRs), so a smaller footprint would not add
+// a resident workgroup, and the fused layer's epilogue keeps the LDS offsets it is built on (kLdsBytes).
+//
 // Geometry (MI355X): workgroup = 256 threads = 4 wavefronts side by side along F, tile
 // 128 (rows) x 256 (columns), two workgroups per CU (2 wavefronts per SIMD, from DIFFERENT
 // workgroups, so one's split/LDS-write/barrier phase overlaps the other's MFMAs).  Each
@@ -59,7 +65,7 @@ constexpr int kThreads = 256;
 constexpr int kLdsBytes = 2 * 2 * BM * ROWB;  // [buffer][plane][BM rows x 64 B] = 32 KiB (64 KiB when BM = 256)
 
 // Staging geometry of one 128 x 32 stage of A for element type AT: every thread moves 16 B per
-// pass.  fp32: 8 threads per row, 32 rows per pass, 4 passes;  fp16: 4 per row, 64 rows, 2 passes.
+// pass.  fp32: 8 threads per row, 32 rows per pass, 4 passes;  fp16 / bf16: 4 per row, 64 rows, 2 passes.
 template <typename AT>
 struct Geom {
     static constexpr int EPT = 16 / (int)sizeof(AT);  // elements per thread per pass
@@ -99,6 +105,10 @@ inline int64_t grid_for(int64_t m_tiles, int n_wg)
 __device__ __forceinline__ float elem_to_float(float v) { return v; }
 __device__ __forceinline__ float elem_to_float(__half v) { return __half2float(v); }
 
+// bf16 A operand: staged into the hi plane as it is loaded (see the header)
+template <typename AT>
+constexpr bool kBf16A = std::is_same<AT, __bf16>::value;
+
 // 16 B of AT from global memory as EPT floats
 template <typename AT>
 __device__ __forceinline__ void load16(const AT *p, float (&v)[Geom<AT>::EPT])
@@ -120,7 +130,7 @@ __device__ __forceinline__ void load16(const AT *p, float (&v)[Geom<AT>::EPT])
 
 // arow[i]: this thread's NP source rows (already clamped to valid memory); avalid[i]: false =>
 // the row is padding and must read as zeros.  AT: element type of A (float or __half: an fp16
-// value is exactly hi + lo, so the same three products apply).  AVEC: 16-B loads allowed
+// value is exactly hi + lo, so the same three products apply; __bf16: hi alone, two products).  AVEC: 16-B loads allowed
 // (K % EPT == 0, aligned).  KFULL: K % 32 == 0.  ZROWS: some rows are padding (graph slots with
 // T < 32 / past the batch).
 // RBLK: only the first `nblk` of this wavefront's four 32-row blocks hold nodes (f16mx8_core.h): the others' MFMAs are skipped.
@@ -131,6 +141,7 @@ __device__ __forceinline__ void mainloop(const AT *const (&arow)[Geom<AT>::NP], 
 {
     using G = Geom<AT>;
     constexpr int EPT = G::EPT, NP = G::NP;
+    constexpr bool XB = kBf16A<AT>;
     const int tid = threadIdx.x & (kThreads - 1);   // (a 512-thread workgroup runs two 128-row halves side by side: fused_layer.hip, wide8)
     const int lane = tid & 63;
     const int s_k = (tid % G::TPR) * EPT;  // first k of this thread's 16-B piece
@@ -138,10 +149,18 @@ __device__ __forceinline__ void mainloop(const AT *const (&arow)[Geom<AT>::NP], 
     // Global loads are issued raw (clamped address, no select on the result): the validity select
     // is applied one stage later, at the split -- a select next to the load would make hipcc wait
     // for the load inside the issuing block (measured: 460 -> 640 us).
-    float ra[NP][EPT];
+    float ra[NP][XB ? 1 : EPT];
+    bf16x8 rb[XB ? NP : 1];   // bf16 A: the raw 16 B of each pass
     auto load_a_pass = [&](int i, int k0) {
         const int gk = k0 + s_k;
-        if constexpr (AVEC) {
+        if constexpr (XB) {
+            if constexpr (AVEC) {
+                rb[i] = *reinterpret_cast<const bf16x8 *>(arow[i] + ((KFULL || gk < K) ? gk : 0));
+            } else {
+#pragma unroll
+                for (int c = 0; c < EPT; ++c) rb[i][c] = arow[i][(gk + c < K) ? gk + c : 0];
+            }
+        } else if constexpr (AVEC) {
             load16<AT>(arow[i] + ((KFULL || gk < K) ? gk : 0), ra[i]);
         } else {
 #pragma unroll
@@ -159,6 +178,20 @@ __device__ __forceinline__ void mainloop(const AT *const (&arow)[Geom<AT>::NP], 
         const int row = stage_row<AT>(i);
         const int off = a_lds_off(row, s_k >> 3) + (s_k & 4) * 2;
         const int gk = k0 + s_k;
+        if constexpr (XB) {   // one plane, the loaded bits themselves (padding and k >= K as zeros)
+            bf16x8 v = rb[i];
+            if constexpr (!KFULL || ZROWS) {
+#pragma unroll
+                for (int c = 0; c < EPT; ++c) {
+                    bool in = true;
+                    if constexpr (!KFULL) in = gk + c < K;
+                    if constexpr (ZROWS) in = in && avalid[i];
+                    v[c] = in ? v[c] : (__bf16)0.0f;
+                }
+            }
+            *reinterpret_cast<bf16x8 *>(hi_plane + off) = v;
+            return;
+        } else {
         __bf16 hi[EPT], lo[EPT];
 #pragma unroll
         for (int c = 0; c < EPT; ++c) {
@@ -178,6 +211,7 @@ __device__ __forceinline__ void mainloop(const AT *const (&arow)[Geom<AT>::NP], 
         } else {
             *reinterpret_cast<bf16x8 *>(hi_plane + off) = bf16x8{hi[0], hi[1], hi[2], hi[3], hi[4], hi[5], hi[6], hi[7]};
             *reinterpret_cast<bf16x8 *>(lo_plane + off) = bf16x8{lo[0], lo[1], lo[2], lo[3], lo[4], lo[5], lo[6], lo[7]};
+        }
         }
     };
 
@@ -211,6 +245,14 @@ __device__ __forceinline__ void mainloop(const AT *const (&arow)[Geom<AT>::NP], 
         const char *lo_plane = hi_plane + BM * ROWB;
         const int off = a_lds_off(f_row + i * 32, s * 2 + f_half);
         const bf16x8 a_hi = *reinterpret_cast<const bf16x8 *>(hi_plane + off);
+        if constexpr (XB) {   // exact bf16 A: hi.lo + hi.hi
+#pragma unroll
+            for (int j = 0; j < RN; ++j) {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b[j][1], acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b[j][0], acc[i][j], 0, 0, 0);
+            }
+            return;
+        }
         const bf16x8 a_lo = *reinterpret_cast<const bf16x8 *>(lo_plane + off);
 #pragma unroll
         for (int j = 0; j < RN; ++j) {

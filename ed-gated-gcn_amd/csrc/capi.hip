@@ -183,6 +183,40 @@ int ggcn_linear(const float *X, int64_t ldx, const float *W, int64_t ldw, const 
     }
 }
 
+int ggcn_linear_bf16(const void *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F,
+                     ggcn_stream_t stream)
+{
+    if (!X || !Y || !wpack) return fail(GGCN_EINVAL, "ggcn_linear_bf16: null pointer");
+    if (M <= 0 || K <= 0 || F <= 0)
+        return fail(GGCN_EINVAL, "ggcn_linear_bf16: M=%lld K=%d F=%d must be positive", (long long)M, K, F);
+    if (ldx < K || ldy < F) return fail(GGCN_EINVAL, "ggcn_linear_bf16: leading dimension too small");
+    if (reinterpret_cast<uintptr_t>(X) % 2 || reinterpret_cast<uintptr_t>(Y) % 4)
+        return fail(GGCN_EINVAL, "ggcn_linear_bf16: X / Y not aligned to their element size");
+    return linear_bf16(X, ldx, wpack, Y, ldy, M, K, F, as_stream(stream));
+}
+
+int ggcn_linear_out_bf16(const float *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy, int64_t M, int K, int F,
+                         ggcn_stream_t stream)
+{
+    if (!X || !Y || !wpack) return fail(GGCN_EINVAL, "ggcn_linear_out_bf16: null pointer");
+    if (M <= 0 || K <= 0 || F <= 0)
+        return fail(GGCN_EINVAL, "ggcn_linear_out_bf16: M=%lld K=%d F=%d must be positive", (long long)M, K, F);
+    if (ldx < K || ldy < F) return fail(GGCN_EINVAL, "ggcn_linear_out_bf16: leading dimension too small");
+    if (reinterpret_cast<uintptr_t>(X) % 4 || reinterpret_cast<uintptr_t>(Y) % 2)
+        return fail(GGCN_EINVAL, "ggcn_linear_out_bf16: X / Y not aligned to their element size");
+    return linear_out_bf16(X, ldx, wpack, Y, ldy, M, K, F, as_stream(stream));
+}
+
+int ggcn_layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const void *graph_ops, const float *bias, int B, int T,
+                          int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out,
+                          int64_t ldo, float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in,
+                          float *overlap_out, ggcn_stream_t stream)
+{
+    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "ggcn_layer_fused_bf16: X not 2-byte aligned");
+    return layer_fused_bf16(X, ldx, wpack, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo, pool_a,
+                            pool_b, overlap_partial, overlap_in, overlap_out, GGCN_PREC_BF16X3, as_stream(stream));
+}
+
 int ggcn_aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,
                    const float *vals, const float *bias, int B, int T, int F, const float *store_gate,
                    const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
@@ -332,6 +366,22 @@ int ggcn_dweight(const float *X, int64_t ldx, const float *dH, int64_t ldg, int6
     if (precision != GGCN_PREC_BF16X3)
         return fail(GGCN_EUNSUPPORTED, "ggcn_dweight: precision %d (gradients need fp32 range: use bf16x3 or fp32)", precision);
     return dweight_bx3(X, ldx, dH, ldg, n_rows, K, F, dW, lddw, workspace, as_stream(stream));
+}
+
+size_t ggcn_dweight_bf16_workspace_bytes(int64_t n_rows, int K, int F) { return dweight_bf16_workspace_bytes(n_rows, K, F); }
+
+int ggcn_dweight_bf16(const void *X, int64_t ldx, const float *dH, int64_t ldg, int64_t n_rows, int K, int F, float *dW,
+                      int64_t lddw, void *workspace, ggcn_stream_t stream)
+{
+    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "ggcn_dweight_bf16: X not 2-byte aligned");
+    return dweight_bf16(X, ldx, dH, ldg, n_rows, K, F, dW, lddw, workspace, as_stream(stream));
+}
+
+int ggcn_subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *X, int64_t x_batch,
+                           int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D,
+                           ggcn_stream_t stream)
+{
+    return subword_pool_bf16(A, sa_b, sa_r, sa_c, X, x_batch, ldx, Y, y_batch, ldy, B, R, C, D, as_stream(stream));
 }
 
 int ggcn_subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const float *X, int64_t x_batch,

@@ -50,6 +50,9 @@ int linear_scaled(const float *X, int64_t ldx, const void *wpack, float *Y, int6
                   hipStream_t st);
 int linear_packed_h(const void *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy, int64_t M, int K,
                     int F, int precision, hipStream_t st);
+// bf16 features (linear_split.hip): bf16 X -> fp32 Y, and fp32 X -> bf16 Y (dX of the backward), both on the bf16x3 image
+int linear_bf16(const void *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F, hipStream_t st);
+int linear_out_bf16(const float *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy, int64_t M, int K, int F, hipStream_t st);
 int aggregate_t(const float *G, int64_t ldg, const int32_t *rowptr_t, const int32_t *colidx_t,
                 const float *vals_t, const float *src_scale, int B, int T, int F, float *out, int64_t ldo,
                 hipStream_t st);
@@ -70,6 +73,8 @@ int aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t
 
 int subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const float *X, int64_t x_batch,
                  int64_t ldx, float *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, hipStream_t st);
+int subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *X, int64_t x_batch,
+                      int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, hipStream_t st);
 int csr_rowmask(const int32_t *rowptr, const int32_t *colidx, int B, int T, uint32_t *rowmask, hipStream_t st);
 int graph_operands(const uint32_t *rowmask, int B, int T, void *ops, hipStream_t st);
 int graph_edge_lists(const uint32_t *rowmask, int B, int T, void *lists, hipStream_t st);   // fused_wide8.hip
@@ -85,6 +90,10 @@ int layer_fused(const float *X, int64_t ldx, const void *wpack, const uint32_t *
                 const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b,
                 float *overlap_partial, const float *overlap_in, float *overlap_out, int precision, hipStream_t st,
                 const struct DropSpec *drop = nullptr, const float *bias_pre = nullptr);
+int layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const void *graph_ops, const float *bias, int B, int T, int K, int F,
+                     const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
+                     float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out, int precision,
+                     hipStream_t st);
 int dropout_mask(int64_t rows, int F, float p, uint64_t seed, int sel, float *out, hipStream_t st);
 
 int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,
@@ -120,6 +129,9 @@ int dweight_tn(const float *X, int64_t ldx, const float *G, int64_t ldg, int64_t
                void *workspace, hipStream_t st);
 int dweight_bx3(const float *X, int64_t ldx, const float *G, int64_t ldg, int64_t N, int K, int F, float *dW,
                 int64_t lddw, void *workspace, hipStream_t st);
+size_t dweight_bf16_workspace_bytes(int64_t N, int K, int F);
+int dweight_bf16(const void *X, int64_t ldx, const float *G, int64_t ldg, int64_t N, int K, int F, float *dW,
+                 int64_t lddw, void *workspace, hipStream_t st);
 int weight_pack_rows(const float *W, int64_t ldw, int64_t K_valid, int F, int k_steps_total, void *pack, hipStream_t st);
 int dweight(const float *X, int64_t ldx, const float *G, int64_t ldg, int64_t N, int K, int F, float *dW,
             int64_t lddw, void *workspace, hipStream_t st);

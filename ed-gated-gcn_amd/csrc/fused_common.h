@@ -37,6 +37,8 @@ struct FusedArgs {
     LayerPart part[2];
     DropSpec drop;              // training-mode keep masks of the gates (thr = 0: none); one part only
     unsigned long long *stamps; // diagnostics only (ggcn_debug_block_fused_stamped): [workgroup][2] = d(s_memtime), d(s_memrealtime) around the main loop
+    const __bf16 *Xb;           // bf16 features (ggcn_layer_fused_bf16: one layer, graphs of <= 32 nodes, bf16x3 image); X then only
+                                // names readable memory (the weight image) for the epilogue staging's discarded fallback reads
 };
 
 

@@ -191,9 +191,18 @@ __global__ __launch_bounds__(256) void graph_operands_w_kernel(const int32_t *__
 // STAMP (diagnostic instantiation only, ggcn_debug_block_fused_stamped): thread 0 of every workgroup stamps s_memtime (shader
 // cycles) and s_memrealtime (100 MHz) around the main loop into a.stamps, a buffer nothing else reads -- the clock the chip
 // holds under THIS kernel's load (MI355X_MICROARCH.md "DVFS give-back" (6)).  No product launch executes a stamp.
-template <int SCH, bool AVEC, bool KFULL, bool FULLT, bool VST, bool STAMP = false>
+template <typename XT>
+__device__ __forceinline__ const XT *fused_x(const FusedArgs &a)
+{
+    if constexpr (std::is_same<XT, float>::value) return a.X;
+    else return a.Xb;
+}
+
+// XT: element type of the features -- float, or __bf16 (a.Xb; bf16x3 image, two MFMAs per product: bf16x3_core.h)
+template <int SCH, bool AVEC, bool KFULL, bool FULLT, bool VST, bool STAMP = false, typename XT = float>
 __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(const FusedArgs a)
 {
+    static_assert(std::is_same<XT, float>::value || (SCH == 0 && !STAMP), "bf16 features: the bf16x3 main loop");
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes + kEpiLdsBytes + GGCN_LAB_LDS_PAD];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
     // bert_amir5.py:638 for the launch BEFORE this one on the stream: block 0 adds the per-(graph,
@@ -231,16 +240,16 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(co
     const int nt0 = n_wgi * (BN / NT) + wn * RN;
 
     // tile row 32*slot + r  <->  node r of graph g0+slot
-    constexpr int NP = Geom<float>::NP;
-    const float *arow[NP];
+    constexpr int NP = Geom<XT>::NP;
+    const XT *arow[NP];
     bool avalid[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        const int row = stage_row<float>(i);
+        const int row = stage_row<XT>(i);
         const int g = gt0 + (row >> 5), r = row & 31;
         avalid[i] = (g < B) && (FULLT || r < T);
         const int64_t node = avalid[i] ? (int64_t)g * T + r : 0;  // clamped, zeroed by the select
-        arow[i] = a.X + node * a.ldx;
+        arow[i] = fused_x<XT>(a) + node * a.ldx;
     }
 
 #if !GGCN_LAB_NO_DMA_STAGE
@@ -265,7 +274,7 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(co
         stamp_w = __builtin_amdgcn_s_memrealtime();
     }
     if constexpr (SCH == 0)
-        bx3::mainloop<float, AVEC, KFULL, !FULLT>(arow, avalid, wpack, K, a.k_steps, wm, nt0, n_tiles_total, lds, acc);
+        bx3::mainloop<XT, AVEC, KFULL, !FULLT>(arow, avalid, wpack, K, a.k_steps, wm, nt0, n_tiles_total, lds, acc);
     else {
         float amax;
         // fast shapes (16-byte rows, K % 32 == 0): buffer loads -- the tile's X rows behind one resource (the launcher
@@ -391,7 +400,8 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
     if (precision == GGCN_PREC_F16MX6)
         return fail(GGCN_EUNSUPPORTED, "%s: f16mx6 is an experiment this library was built without (make F16MX6=1); use f16mx8", who);
 #endif
-    if (!a.X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
+    if (!a.X && !a.Xb) return fail(GGCN_EINVAL, "%s: null input pointer", who);   // (bf16: a.X is the weight image, see layer_fused_bf16)
+    if (a.Xb && a.T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (use ggcn_linear_bf16 + ggcn_aggregate)", who, a.T);
     if (a.T > 32 ? !a.rowmask : !a.graph_ops)
         return fail(GGCN_EINVAL, "%s: graphs of %d nodes need %s", who, a.T,
                     a.T > 32 ? "the row masks" : "the per-graph operand blocks of ggcn_graph_operands");
@@ -420,6 +430,31 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
         }
     }
     vst = vst && any_out;
+    if (a.Xb) {   // bf16 features: one layer, graphs of <= 32 nodes, the bf16x3 image (bf16 pair form, two MFMAs per product)
+        if (precision != GGCN_PREC_BF16X3)
+            return fail(GGCN_EUNSUPPORTED, "%s: bf16 features take the bf16x3 weight image (precision %d)", who, precision);
+        if (a.n_parts != 1 || a.drop.thr != 0 || a.stamps || a.part[0].mid)
+            return fail(GGCN_EUNSUPPORTED, "%s: one plain layer (no block, gate dropout or stamps)", who);
+        const bool avecb = (a.K % 8 == 0) && (a.ldx % 8 == 0) && aligned16(a.Xb);
+        const bool kfullb = (a.K % BK == 0);
+        a.k_steps = round_up(a.K, BK) / KSTEP;
+        a.n_wg = (a.F + BN - 1) / BN;
+        const int64_t g_tiles = ((int64_t)a.B + 4 * WM - 1) / (4 * WM);
+        const int64_t grid = grid_for(g_tiles, a.n_wg);
+        if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
+        a.g_tiles = (int)g_tiles;
+        const bool fullt = (a.T == 32) && (a.B % (4 * WM) == 0);
+#define GGCN_LAUNCH_B(AV, KF, FT, VS) \
+    hipLaunchKernelGGL((layer_fused_kernel<0, AV, KF, FT, VS, false, __bf16>), dim3((unsigned)grid), dim3(kThreads), 0, st, a)
+        if (avecb && kfullb && fullt && vst) GGCN_LAUNCH_B(true, true, true, true);
+        else if (avecb && kfullb && vst) GGCN_LAUNCH_B(true, true, false, true);
+        else if (avecb && kfullb) GGCN_LAUNCH_B(true, true, false, false);
+        else if (avecb && vst) GGCN_LAUNCH_B(true, false, false, true);
+        else if (avecb) GGCN_LAUNCH_B(true, false, false, false);
+        else GGCN_LAUNCH_B(false, false, false, false);
+#undef GGCN_LAUNCH_B
+        return check_launch(who);
+    }
     // (the fast shapes address a tile's 128 rows with 32-bit byte offsets from its first row: buffer loads)
     const bool avec = (a.K % 4 == 0) && (a.ldx % 4 == 0) && aligned16(a.X) && (int64_t)a.ldx * 4 * 257 < ((int64_t)1 << 31);
     const bool kfull = (a.K % BK == 0);
@@ -593,6 +628,28 @@ int layer_fused(const float *X, int64_t ldx, const void *wpack, const uint32_t *
     if (bias_pre && drop)
         return fail(GGCN_EUNSUPPORTED, "ggcn_layer_fused_prebias: an inference form (no gate dropout)");
     return launch_fused("ggcn_layer_fused", a, precision, st);
+}
+
+int layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const void *graph_ops, const float *bias, int B, int T, int K, int F,
+                     const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
+                     float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out, int precision,
+                     hipStream_t st)
+{
+    const char *who = "ggcn_layer_fused_bf16";
+    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
+    if ((overlap_in == nullptr) != (overlap_out == nullptr)) return fail(GGCN_EINVAL, "%s: overlap_in and overlap_out go together", who);
+    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: ldo too large", who);
+    FusedArgs a = {};
+    // a.X stays the epilogue staging's fallback READ address for an absent gate / bias (stage_epilogue_operands loads
+    // unconditionally and discards the value): it must be valid memory, and the weight image always is (>= 4 KiB; its
+    // NULL case is refused before the launch)
+    a.X = static_cast<const float *>(wpack);
+    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx; a.graph_ops = static_cast<const char *>(graph_ops);
+    a.ov_in = overlap_in; a.ov_out = overlap_out;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, nullptr, nullptr, store_gate, pool_gate_a, pool_gate_b,
+                          out, pool_a, pool_b, overlap_partial, (int)ldo};
+    return launch_fused(who, a, precision, st);
 }
 
 int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,

@@ -190,8 +190,11 @@ __global__ __launch_bounds__(64) void weight_pack_mx6_kernel(const float *__rest
 
 __device__ __forceinline__ void store_elem(float *p, float v) { *p = v; }
 __device__ __forceinline__ void store_elem(__half *p, float v) { *p = __float2half_rn(v); }
+__device__ __forceinline__ void store_elem(__bf16 *p, float v) { *p = (__bf16)v; }   // RNE (v_cvt_pk_bf16_f32)
 
 // ET: element type of X and Y (float, or __half with fp32 accumulation); SCH: 0 = bf16x3, 1 = f16mx8
+// YT (bf16x3 only): Y's own element type where it differs from X's -- bf16 X -> fp32 Y (ggcn_linear_bf16), fp32 X -> bf16 Y
+// rounded to nearest even in the store (ggcn_linear_out_bf16)
 // VST (fp32 output, F and ldy multiples of 4, Y 16-byte aligned): 16-byte row stores through LDS
 // XS (ggcn_linear_scaled, f16mx8 fast shapes only): *amax (device memory) = the largest |x| of the whole matrix, left there by the
 // kernel that produced X; every workgroup derives the same power of two s from it (|x| * s < 256: inside fp16's range and the fp8
@@ -207,12 +210,13 @@ __device__ __forceinline__ void scale_from_amax(const float *amax, float &s, flo
     s = ok ? __uint_as_float((uint32_t)se << 23) : 1.0f;
     inv_s = ok ? __uint_as_float((uint32_t)(254 - se) << 23) : 1.0f;
 }
-template <int SCH, typename ET, bool AVEC, bool KFULL, bool VST, bool XS = false>
+template <int SCH, typename ET, bool AVEC, bool KFULL, bool VST, bool XS = false, typename YT = ET>
 __global__ __launch_bounds__(kThreads, kWavesPerSimd) void linear_split_kernel(
     const ET *__restrict__ X, int64_t ldx, const char *__restrict__ wpack,
-    ET *__restrict__ Y, int64_t ldy, int64_t M, int K, int F, int m_tiles, int n_wg, int k_steps, const float *__restrict__ amax_in = nullptr)
+    YT *__restrict__ Y, int64_t ldy, int64_t M, int K, int F, int m_tiles, int n_wg, int k_steps, const float *__restrict__ amax_in = nullptr)
 {
     static_assert(!XS || (SCH == 1 && AVEC && KFULL && VST && sizeof(ET) == 4), "the scaled form exists for the fast fp32 shapes of f16mx8");
+    static_assert(std::is_same<YT, ET>::value || (SCH == 0 && !XS && (!VST || std::is_same<YT, float>::value)), "mixed X / Y types: bf16x3 only");
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     int m_tile, n_wgi;
     if (!tile_of_block(blockIdx.x, m_tiles, n_wg, m_tile, n_wgi)) return;  // before any barrier
@@ -308,7 +312,7 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void linear_split_kernel(
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t gmb = m0 + wm * 128 + i * 32 + 4 * (lane >> 5);
-            ET *yb = Y + gmb * ldy + gn;
+            YT *yb = Y + gmb * ldy + gn;
             if (full_rows) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) store_elem(yb + (int64_t)((r & 3) + 8 * (r >> 2)) * ldy, acc[i][j][r]);
@@ -387,8 +391,8 @@ int launch_linear_f16(const __half *X, int64_t ldx, const void *wpack, __half *Y
     return check_launch("ggcn_linear_h(f16)");
 }
 
-template <int SCH, typename ET>
-int launch_linear(const ET *X, int64_t ldx, const void *wpack, ET *Y, int64_t ldy, int64_t M, int K, int F,
+template <int SCH, typename ET, typename YT = ET>
+int launch_linear(const ET *X, int64_t ldx, const void *wpack, YT *Y, int64_t ldy, int64_t M, int K, int F,
                   hipStream_t st)
 {
     if (!wpack) return fail(GGCN_EINVAL, "ggcn_linear(bf16x3): wpack is NULL (call ggcn_weight_pack first)");
@@ -403,9 +407,9 @@ int launch_linear(const ET *X, int64_t ldx, const void *wpack, ET *Y, int64_t ld
     const int64_t grid = grid_for(m_tiles, n_wg);
     if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "ggcn_linear(bf16x3): M too large");
     const char *wp = static_cast<const char *>(wpack);
-    const bool vst = std::is_same<ET, float>::value && (F % 4 == 0) && (ldy % 4 == 0) && aligned16(Y);
+    const bool vst = std::is_same<YT, float>::value && (F % 4 == 0) && (ldy % 4 == 0) && aligned16(Y);
 #define GGCN_LAUNCH(AV, KF, VS)                                                                                     \
-    hipLaunchKernelGGL((linear_split_kernel<SCH, ET, AV, KF, VS && std::is_same<ET, float>::value>), dim3((unsigned)grid), \
+    hipLaunchKernelGGL((linear_split_kernel<SCH, ET, AV, KF, VS && std::is_same<YT, float>::value, false, YT>), dim3((unsigned)grid), \
                        dim3(kThreads), 0, st, X, ldx, wp, Y, ldy, M, K, F, (int)m_tiles, n_wg, k_steps)
     if (avec && kfull && vst) GGCN_LAUNCH(true, true, true);
     else if (avec && kfull) GGCN_LAUNCH(true, true, false);
@@ -559,6 +563,18 @@ int linear_packed_h(const void *X, int64_t ldx, const void *wpack, void *Y, int6
     if (precision == GGCN_PREC_F16) return launch_linear_f16(x, ldx, wpack, y, ldy, M, K, F, st);
     if (precision == GGCN_PREC_F16MX8) return launch_linear<1, __half>(x, ldx, wpack, y, ldy, M, K, F, st);
     return launch_linear<0, __half>(x, ldx, wpack, y, ldy, M, K, F, st);
+}
+
+// bf16 features: Y (fp32) = X (bf16) . W on the bf16x3 image, two MFMAs per product (bf16x3_core.h)
+int linear_bf16(const void *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F, hipStream_t st)
+{
+    return launch_linear<0, __bf16, float>(static_cast<const __bf16 *>(X), ldx, wpack, Y, ldy, M, K, F, st);
+}
+
+// dX of the backward for bf16 features: Y (bf16, RNE in the store) = X (fp32) . W on the bf16x3 image
+int linear_out_bf16(const float *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy, int64_t M, int K, int F, hipStream_t st)
+{
+    return launch_linear<0, float, __bf16>(X, ldx, wpack, static_cast<__bf16 *>(Y), ldy, M, K, F, st);
 }
 
 GGCN_RANGE_FLAG_TU(range_flag_linear)

@@ -8,6 +8,8 @@
 // A is addressed with element strides, so the reference's non-contiguous slice
 // `inputs['transform'][:, :T, :L]` is taken as it is, and the transposed product of the backward
 // pass (dX = A^T . dY) is the same launch with the two strides swapped.
+// XT = __bf16 (ggcn_subword_pool_bf16, x from BERT under bf16 autocast): X and Y in bf16, the sums in fp32, Y rounded to
+// nearest even once -- what torch.bmm gives under autocast.
 #include "common.h"
 
 namespace ggcn {
@@ -16,10 +18,23 @@ namespace {
 constexpr int kMaxCols = 2048;  // columns of A per row held in LDS as (index, value) pairs
 constexpr int kSlab = 1024;     // features per workgroup: 256 threads x 4
 
-template <bool VEC>
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 load4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 load4(const __bf16 *p)
+{
+    const bf16x4_t v = *reinterpret_cast<const bf16x4_t *>(p);
+    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+__device__ __forceinline__ void store4(float *p, const float4 &v) { *reinterpret_cast<float4 *>(p) = v; }
+__device__ __forceinline__ void store4(__bf16 *p, const float4 &v)
+{
+    *reinterpret_cast<bf16x4_t *>(p) = bf16x4_t{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
+}
+
+template <bool VEC, typename XT = float>
 __global__ __launch_bounds__(256) void subword_pool_kernel(const float *__restrict__ A, int64_t sa_b, int64_t sa_r,
-                                                          int64_t sa_c, const float *__restrict__ X,
-                                                          int64_t x_batch, int64_t ldx, float *__restrict__ Y,
+                                                          int64_t sa_c, const XT *__restrict__ X,
+                                                          int64_t x_batch, int64_t ldx, XT *__restrict__ Y,
                                                           int64_t y_batch, int64_t ldy, int R, int C, int D)
 {
     __shared__ int s_idx[kMaxCols];
@@ -51,16 +66,16 @@ __global__ __launch_bounds__(256) void subword_pool_kernel(const float *__restri
         __syncthreads();
     }
     const int n = s_total;
-    const float *xb = X + b * x_batch;
-    float *yrow = Y + b * y_batch + (int64_t)r * ldy;
+    const XT *xb = X + b * x_batch;
+    XT *yrow = Y + b * y_batch + (int64_t)r * ldy;
     const int f = blockIdx.y * kSlab + tid * 4;
     if (VEC) {
         if (f >= D) return;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         int e = 0;
         for (; e + 1 < n; e += 2) {  // two rows in flight
-            const float4 x0 = *reinterpret_cast<const float4 *>(xb + (int64_t)s_idx[e] * ldx + f);
-            const float4 x1 = *reinterpret_cast<const float4 *>(xb + (int64_t)s_idx[e + 1] * ldx + f);
+            const float4 x0 = load4(xb + (int64_t)s_idx[e] * ldx + f);
+            const float4 x1 = load4(xb + (int64_t)s_idx[e + 1] * ldx + f);
             const float v0 = s_val[e], v1 = s_val[e + 1];
             acc.x = fmaf(v0, x0.x, acc.x); acc.y = fmaf(v0, x0.y, acc.y);
             acc.z = fmaf(v0, x0.z, acc.z); acc.w = fmaf(v0, x0.w, acc.w);
@@ -68,20 +83,20 @@ __global__ __launch_bounds__(256) void subword_pool_kernel(const float *__restri
             acc.z = fmaf(v1, x1.z, acc.z); acc.w = fmaf(v1, x1.w, acc.w);
         }
         if (e < n) {
-            const float4 x0 = *reinterpret_cast<const float4 *>(xb + (int64_t)s_idx[e] * ldx + f);
+            const float4 x0 = load4(xb + (int64_t)s_idx[e] * ldx + f);
             const float v0 = s_val[e];
             acc.x = fmaf(v0, x0.x, acc.x); acc.y = fmaf(v0, x0.y, acc.y);
             acc.z = fmaf(v0, x0.z, acc.z); acc.w = fmaf(v0, x0.w, acc.w);
         }
-        *reinterpret_cast<float4 *>(yrow + f) = acc;
+        store4(yrow + f, acc);
     } else {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int fq = blockIdx.y * kSlab + q * 256 + tid;  // coalesced scalar form
             if (fq >= D) continue;
             float acc = 0.0f;
-            for (int e = 0; e < n; ++e) acc = fmaf(s_val[e], xb[(int64_t)s_idx[e] * ldx + fq], acc);
-            yrow[fq] = acc;
+            for (int e = 0; e < n; ++e) acc = fmaf(s_val[e], (float)xb[(int64_t)s_idx[e] * ldx + fq], acc);
+            yrow[fq] = (XT)acc;
         }
     }
 }
@@ -107,6 +122,30 @@ int subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const
         hipLaunchKernelGGL(subword_pool_kernel<false>, grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, X, x_batch, ldx, Y,
                            y_batch, ldy, R, C, D);
     return check_launch("ggcn_subword_pool");
+}
+
+int subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *Xv, int64_t x_batch,
+                      int64_t ldx, void *Yv, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, hipStream_t st)
+{
+    const __bf16 *X = static_cast<const __bf16 *>(Xv);
+    __bf16 *Y = static_cast<__bf16 *>(Yv);
+    if (!A || !X || !Y) return fail(GGCN_EINVAL, "ggcn_subword_pool_bf16: null pointer");
+    if (B <= 0 || R <= 0 || C <= 0 || D <= 0)
+        return fail(GGCN_EINVAL, "ggcn_subword_pool_bf16: B=%d R=%d C=%d D=%d must be positive", B, R, C, D);
+    if (C > kMaxCols) return fail(GGCN_EUNSUPPORTED, "ggcn_subword_pool_bf16: C=%d > %d columns", C, kMaxCols);
+    if (ldx < D || ldy < D) return fail(GGCN_EINVAL, "ggcn_subword_pool_bf16: leading dimension too small");
+    if ((int64_t)B * R > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "ggcn_subword_pool_bf16: too many rows");
+    // (8-byte loads and stores of four bf16)
+    const bool vec = (D % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (x_batch % 4 == 0) && (y_batch % 4 == 0) &&
+                     (reinterpret_cast<uintptr_t>(X) % 8 == 0) && (reinterpret_cast<uintptr_t>(Y) % 8 == 0);
+    const dim3 grid((unsigned)(B * R), (unsigned)((D + kSlab - 1) / kSlab));
+    if (vec)
+        hipLaunchKernelGGL((subword_pool_kernel<true, __bf16>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, X, x_batch, ldx, Y,
+                           y_batch, ldy, R, C, D);
+    else
+        hipLaunchKernelGGL((subword_pool_kernel<false, __bf16>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, X, x_batch, ldx, Y,
+                           y_batch, ldy, R, C, D);
+    return check_launch("ggcn_subword_pool_bf16");
 }
 
 }  // namespace ggcn

@@ -121,6 +121,20 @@ def takes_block_path(x, csr, gc1, gc2):
             and gc1.out_features == gc2.in_features and gc1.out_features == gc2.out_features)
 
 
+def _layer2_input(x, gc1):
+    """What gc2's dispatch is judged by: gc2 reads gcn1, which is float32 whatever x is (bfloat16 features give a float32
+    layer output).  For float32 x that is x itself -- every float32 decision stays as it was; for bf16 x a float32
+    stand-in of gcn1's shape (an expanded single element: nothing of [B,T,H] is allocated)."""
+    if x.dtype == torch.float32:
+        return x
+    return torch.zeros(1, dtype=torch.float32, device=x.device).expand(x.shape[0], x.shape[1], gc1.out_features)
+
+
+def _layer1_takes_fused(x, csr, gc1):
+    """gc1 runs as one launch: the float32 one-launch layer, or the bf16 one (graphs of <= 32 nodes)."""
+    return gc1.takes_fused_path(x, csr) or gc1.takes_bf16_fused_path(x, csr)
+
+
 BLOCK_OUTPUTS = ("x1", "y1", "xy", "x", "out")
 
 
@@ -234,7 +248,7 @@ def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch
         if _defer_xy and part is not None:
             r["_xy_partials"] = part
         return r
-    if (not training and gc1.takes_fused_path(x, csr) and gc2.takes_fused_path(x, csr)
+    if (not training and _layer1_takes_fused(x, csr, gc1) and gc2.takes_fused_path(_layer2_input(x, gc1), csr)
             and gc1.out_features == gc2.out_features):
         # two launches in all: layer 1 leaves its share of sum_f x1*y1 per (graph, 64 columns), layer 2's
         # launch adds them up before it starts on its own tiles (:638 costs no launch of its own)

@@ -20,14 +20,20 @@ from . import _capi, range_guard
 from .csr import BatchedCSR, cached_from_dense, tensor_version
 
 
-def _require_gpu_f32(name, t, allow_half=False):
+def _require_gpu_f32(name, t, allow_half=False, allow_bf16=False):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
     if not t.is_cuda:
         raise RuntimeError("%s is on %s: this layer only runs on the GPU (libggcn_hip.so); "
                            "there is no CPU fallback" % (name, t.device))
-    if t.dtype != torch.float32 and not (allow_half and t.dtype == torch.float16):
-        raise RuntimeError("%s must be float32%s, got %s" % (name, " or float16" if allow_half else "", t.dtype))
+    if t.dtype != torch.float32 and not (allow_half and t.dtype == torch.float16) and not (allow_bf16 and t.dtype == torch.bfloat16):
+        raise RuntimeError("%s must be float32%s%s, got %s" % (name, " or float16" if allow_half else "",
+                                                               " or bfloat16" if allow_bf16 else "", t.dtype))
+
+
+# precisions that mean "the bf16 pair form" for bfloat16 features: x is exact in bf16, so every product is hi.Whi + hi.Wlo,
+# two bf16 MFMAs on the bf16x3 image of W (include/ggcn.h ggcn_linear_bf16)
+BF16_PRECISIONS = ("bf16x3", "f16mx8", "f16mx6")
 
 
 class _GatedLayerFunction(torch.autograd.Function):
@@ -38,9 +44,9 @@ class _GatedLayerFunction(torch.autograd.Function):
 
         dY, d_sg, d_ga, d_gb   HIP, one pass over the stored output (gate_pool_backward.hip)
         dH = A^T.(D.dY)        HIP, one wavefront per SOURCE node on the transposed CSR
-        dX = dH.W^T            HIP bf16x3 MFMA linear on the packed W^T
-        dW = X^T.dH            HIP split-K: bf16x3 main loop on X^T and packed dH (dweight_bx3.hip), or the
-                               exact-fp32 MFMA form for precision 'fp32' (dweight_fp32.hip)
+        dX = dH.W^T            HIP bf16x3 MFMA linear on the packed W^T (bfloat16 features: stored as bf16, RNE)
+        dW = X^T.dH            HIP split-K: bf16x3 main loop on X^T and packed dH (dweight_bx3.hip; bfloat16 features:
+                               X^T in bf16, ggcn_dweight_bf16), or the exact-fp32 MFMA form for precision 'fp32' (dweight_fp32.hip)
         db = sum_rows dY       HIP: per-graph sums from the gate/pool pass + ggcn_colsum
     """
 
@@ -100,7 +106,8 @@ class _GatedLayerFunction(torch.autograd.Function):
                    and csr.graph_ops is not None and csr.graph_ops_t is not None)
             # (the scaled linear wants its reduction length F % 32 == 0 and 16-byte rows; the scalar launch hands max |dH| over for
             # whole wavefronts of columns only)
-            scaled_dx = (one_pass and need[0] and layer.precision == "f16mx8" and K % 4 == 0 and F % 32 == 0 and (mma or F % 256 == 0)
+            bf16 = text.dtype == torch.bfloat16
+            scaled_dx = (one_pass and need[0] and not bf16 and layer.precision == "f16mx8" and K % 4 == 0 and F % 32 == 0 and (mma or F % 256 == 0)
                          and os.environ.get("GGCN_DX_PRECISION", "f16mx8") == "f16mx8")
             dh_amax = torch.zeros(1, dtype=torch.float32, device=dev) if scaled_dx else None
             if mma:
@@ -137,7 +144,13 @@ class _GatedLayerFunction(torch.autograd.Function):
                                                  _capi.ptr(csr_t.vals), _capi.ptr(inv), B, T, F, _capi.ptr(dh), F, st),
                             "ggcn_aggregate_t")
             dw = db = None
-            if need[0]:
+            if need[0] and bf16:   # bfloat16 features: dX in bf16 (the reference's gradient dtype under autocast), rounded in the store
+                dx = torch.empty(B * T, K, dtype=torch.bfloat16, device=dev)
+                pack_t = layer._packed_weight(lib, st, transposed=True)
+                _capi.check(lib.ggcn_linear_out_bf16(_capi.ptr(dh), F, _capi.ptr(pack_t), _capi.ptr(dx), K, B * T, F, K, st),
+                            "ggcn_linear_out_bf16(dX)")
+                dx = dx.view(B, T, K)
+            elif need[0]:
                 dx = torch.empty(B * T, K, dtype=torch.float32, device=dev)
                 if scaled_dx:
                     pack_t = layer._packed_weight(lib, st, transposed=True, precision="f16mx8")
@@ -157,7 +170,15 @@ class _GatedLayerFunction(torch.autograd.Function):
                     _capi.check(lib.ggcn_linear(_capi.ptr(dh), F, _capi.ptr(wt), K, None, _capi.ptr(dx), K,
                                                 B * T, F, K, _capi.PREC["fp32"], st), "ggcn_linear(dX)")
                 dx = dx.view(B, T, K)
-            if need[1]:
+            if need[1] and bf16:
+                x2d = text.reshape(B * T, K)
+                if x2d.stride(1) != 1:
+                    x2d = x2d.contiguous()
+                dw = torch.empty(K, F, dtype=torch.float32, device=dev)
+                ws = torch.empty(lib.ggcn_dweight_bf16_workspace_bytes(B * T, K, F), dtype=torch.uint8, device=dev)
+                _capi.check(lib.ggcn_dweight_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(dh), F, B * T, K, F,
+                                                  _capi.ptr(dw), F, _capi.ptr(ws), st), "ggcn_dweight_bf16")
+            elif need[1]:
                 x2d = text.reshape(B * T, K)
                 if x2d.stride(1) != 1:
                     x2d = x2d.contiguous()
@@ -266,7 +287,18 @@ class GraphConvolution(nn.Module):
     def _check(self, text):
         # float16 features (BASELINE configs[3]) are an extension: the reference itself raises a
         # dtype mismatch for half inputs.  Weights, bias, gates stay float32.
-        _require_gpu_f32("text", text, allow_half=True)
+        # bfloat16 features: the layer under torch.autocast(dtype=torch.bfloat16) -- float32 out and pools (the reference's
+        # `/ denom` promotes), bf16 dX; every split precision runs the bf16 pair form (BF16_PRECISIONS).
+        _require_gpu_f32("text", text, allow_half=True, allow_bf16=True)
+        if text.dtype == torch.bfloat16:
+            if self.precision not in BF16_PRECISIONS:
+                raise RuntimeError("bfloat16 features need precision 'bf16x3', 'f16mx8' or 'f16mx6' (all run the bf16 pair form); "
+                                   "precision=%r does not apply to them" % (self.precision,))
+            if text.dim() != 3 or text.shape[2] != self.in_features:
+                raise RuntimeError("text must be [B,T,%d], got %s" % (self.in_features, tuple(text.shape)))
+            if self.weight.device != text.device:
+                raise RuntimeError("weight is on %s but text is on %s" % (self.weight.device, text.device))
+            return
         if self.precision == "f16" and text.dtype != torch.float16:
             raise RuntimeError("precision='f16' (plain fp16 MFMA) is for float16 features only; float32 features take "
                                "'bf16x3', 'f16mx8' or 'fp32'")
@@ -315,6 +347,12 @@ class GraphConvolution(nn.Module):
         dev = x2d.device
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
+            if x2d.dtype == torch.bfloat16:   # float32 hidden from bf16 features: two bf16 MFMAs per product on the bf16x3 image
+                y = torch.empty(x2d.shape[0], self.out_features, dtype=torch.float32, device=dev)
+                pack = self._packed_weight(lib, st, precision="bf16x3")
+                _capi.check(lib.ggcn_linear_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(y), y.stride(0),
+                                                 x2d.shape[0], self.in_features, self.out_features, st), "ggcn_linear_bf16")
+                return y
             y = torch.empty(x2d.shape[0], self.out_features, dtype=x2d.dtype, device=dev)
             kprec = self.kernel_precision()   # "f16mx6" has no stand-alone linear: f16mx8
             if x2d.dtype == torch.float16:
@@ -372,6 +410,13 @@ class GraphConvolution(nn.Module):
         rounds = -(-wgs // cus)
         return rounds >= 2 and wgs >= self.WIDE_AUTO_FILL * rounds * cus
 
+    def takes_bf16_fused_path(self, text, csr):
+        """True when ``forward_gated`` (inference or the forward of training) runs bfloat16 features as ONE launch
+        (``ggcn_layer_fused_bf16``): graphs of <= 32 nodes, 0/1 adjacency, a split precision (``BF16_PRECISIONS``).  Longer
+        graphs and weighted adjacencies take ``ggcn_linear_bf16`` + ``ggcn_aggregate``; no gate dropout in the launch."""
+        return (self.fused and text.dtype == torch.bfloat16 and self.precision in BF16_PRECISIONS and csr.is_binary
+                and csr.T <= 32 and csr.T <= self.fused_max_t and csr.rowmask is not None and csr.rowmask.is_cuda)
+
     def takes_weighted_path(self, text, csr):
         """True when ``forward_gated`` (inference) will run a REAL-valued adjacency (``gcn.py:33`` accepts any ``adj``) as ONE
         launch (``ggcn_layer_fused_weighted``): graphs of <= 32 nodes, float32 features, a split-precision linear, every entry
@@ -400,7 +445,8 @@ class GraphConvolution(nn.Module):
                       overlap_partial=None, overlap_reduce=None, dropout=None):
         """``_forward_gated`` between the two halves of the lazy f16mx8 range report (``range_guard``: no device
         synchronisation; a violation of an EARLIER launch raises here)."""
-        guarded = (not _internal and self.precision in ("f16mx8", "f16mx6") and isinstance(text, torch.Tensor) and text.is_cuda)
+        guarded = (not _internal and self.precision in ("f16mx8", "f16mx6") and isinstance(text, torch.Tensor) and text.is_cuda
+                   and text.dtype != torch.bfloat16)   # (bf16 features run no fp16 arithmetic: no range to report)
         if guarded:
             range_guard.before(text.device)
         r = self._forward_gated(text, adj, store_gate, pool_gate_a, pool_gate_b, want_out, want_pool_a, want_pool_b, _internal,
@@ -435,14 +481,14 @@ class GraphConvolution(nn.Module):
         self._check(text)
         if text.shape[0] == 0:   # an empty batch is a valid input of the reference (gcn.py:30-45): empty outputs
             B, T, F = 0, text.shape[1], self.out_features
-            z = text.new_zeros((0, T, F))
+            z = text.new_zeros((0, T, F), dtype=torch.float32 if text.dtype == torch.bfloat16 else text.dtype)
             return ((z if want_out else None), (text.new_zeros((0, F), dtype=torch.float32) if want_pool_a else None),
                     (text.new_zeros((0, F), dtype=torch.float32) if want_pool_b else None))
         csr = self._as_csr(adj, text)
         if not _internal and self._needs_grad(text, store_gate, pool_gate_a, pool_gate_b):
             # training: the same kernels, wrapped in an autograd Function with a HIP backward
-            if text.dtype != torch.float32:
-                raise RuntimeError("training through the HIP layer needs float32 features")
+            if text.dtype not in (torch.float32, torch.bfloat16):
+                raise RuntimeError("training through the HIP layer needs float32 features (or bfloat16 ones)")
             if dropout is not None and not self.takes_dropout_path(text, csr):
                 raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
             out, pa, pb = _GatedLayerFunction.apply(text, self.weight, self.bias, store_gate, pool_gate_a,
@@ -462,18 +508,20 @@ class GraphConvolution(nn.Module):
                     raise RuntimeError("%s must be a contiguous [B,F]=[%d,%d] tensor, got %s"
                                        % (name, B, F, tuple(g.shape)))
         half = text.dtype == torch.float16
+        bf16 = text.dtype == torch.bfloat16
         use_fused = self.takes_fused_path(text, csr)
+        use_bf16 = bf16 and self.takes_bf16_fused_path(text, csr)
         if dropout is not None and not (use_fused and self.takes_dropout_path(text, csr)):
             raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
-        if (overlap_partial is not None or overlap_reduce is not None) and not use_fused:
+        if (overlap_partial is not None or overlap_reduce is not None) and not (use_fused or use_bf16):
             raise RuntimeError("overlap_partial / overlap_reduce need the one-launch layer (takes_fused_path)")
         use_long = ((not use_fused) and self.takes_long_path(text, csr) and x2d.data_ptr() % 16 == 0
                     and x2d.stride(0) % 8 == 0)   # ggcn_layer_fused_h wants 16-byte aligned rows; other views: linear_h + aggregate_h
         use_weighted = (not use_fused) and dropout is None and self.takes_weighted_path(text, csr)
-        hidden = None if (use_fused or use_long or use_weighted) else self.linear(x2d)
+        hidden = None if (use_fused or use_long or use_weighted or use_bf16) else self.linear(x2d)
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
-            out = torch.empty(B * T, F, dtype=text.dtype, device=dev) if want_out else None
+            out = torch.empty(B * T, F, dtype=torch.float32 if bf16 else text.dtype, device=dev) if want_out else None
             pa = torch.empty(B, F, dtype=torch.float32, device=dev) if want_pool_a else None
             pb = torch.empty(B, F, dtype=torch.float32, device=dev) if want_pool_b else None
             bias = None if self.bias is None else self.bias.detach()
@@ -499,6 +547,16 @@ class GraphConvolution(nn.Module):
                                                  _capi.ptr(overlap_reduce[1]) if overlap_reduce else None,
                                                  _capi.PREC[kprec], st),
                             "ggcn_layer_fused")
+                return (None if out is None else out.view(B, T, F)), pa, pb
+            if use_bf16:   # bfloat16 features, graphs of <= 32 nodes: one launch on the bf16x3 image
+                pack = self._packed_weight(lib, st, precision="bf16x3")
+                _capi.check(lib.ggcn_layer_fused_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.graph_ops),
+                                                      _capi.ptr(bias), B, T, self.in_features, F, _capi.ptr(store_gate),
+                                                      _capi.ptr(pool_gate_a), _capi.ptr(pool_gate_b), _capi.ptr(out), F,
+                                                      _capi.ptr(pa), _capi.ptr(pb), _capi.ptr(overlap_partial),
+                                                      _capi.ptr(overlap_reduce[0]) if overlap_reduce else None,
+                                                      _capi.ptr(overlap_reduce[1]) if overlap_reduce else None, st),
+                            "ggcn_layer_fused_bf16")
                 return (None if out is None else out.view(B, T, F)), pa, pb
             if use_weighted:   # real-valued adjacency, graphs of <= 32 nodes: one launch on D.A_w operand blocks
                 kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"

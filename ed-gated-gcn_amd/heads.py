@@ -42,7 +42,10 @@ def _gate_linears(seq):
 
 
 def gate_mlps(aspect, gate1_seq, gate2_seq):
-    """``gate1(aspect), gate2(aspect)`` -> two contiguous ``[B,H]`` float32 tensors, one launch."""
+    """``gate1(aspect), gate2(aspect)`` -> two contiguous ``[B,H]`` float32 tensors, one launch.  A bfloat16 ``aspect``
+    (the BiLSTM under bf16 autocast) is taken as float32 here: [B,H], negligible next to the block."""
+    if isinstance(aspect, torch.Tensor) and aspect.dtype == torch.bfloat16:
+        aspect = aspect.float()
     if not (aspect.is_cuda and aspect.dtype == torch.float32 and aspect.dim() == 2):
         raise RuntimeError("aspect must be a float32 [B,H] GPU tensor (no CPU path exists)")
     lib = _capi.load_library()
@@ -69,7 +72,9 @@ def gate_mlps(aspect, gate1_seq, gate2_seq):
 
 
 def scores_and_kl(x, aspect, logits, fc_linear, dist):
-    """``models/bert_amir5.py:645-648``: ``(scores [B,T], kl scalar)`` from the block's gated output ``x [B,T,H]``."""
+    """``models/bert_amir5.py:645-648``: ``(scores [B,T], kl scalar)`` from the block's gated output ``x [B,T,H]``.
+    bfloat16 operands (``aspect`` and ``logits`` under bf16 autocast) are taken as float32 here."""
+    x, aspect, logits = (t.float() if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 else t for t in (x, aspect, logits))
     for name, t in (("x", x), ("aspect", aspect), ("logits", logits)):
         if not (t.is_cuda and t.dtype == torch.float32):
             raise RuntimeError("%s must be a float32 GPU tensor (no CPU path exists)" % name)

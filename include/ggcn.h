@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GGCN_ABI_VERSION 13
+#define GGCN_ABI_VERSION 14
 #define GGCN_MASK_MAX_T 256   /* largest graph the row-mask (one-launch) path takes */
 
 typedef void *ggcn_stream_t;
@@ -534,6 +534,39 @@ int ggcn_subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
                       const float *X, int64_t x_batch, int64_t ldx,
                       float *Y, int64_t y_batch, int64_t ldy,
                       int B, int R, int C, int D, ggcn_stream_t stream);
+/* The same with X and Y in bfloat16 (x from BERT under torch.autocast(dtype=torch.bfloat16)): fp32 sums, Y rounded to
+ * nearest even once -- torch.bmm's result under autocast.  A stays float32. */
+int ggcn_subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
+                           const void *X, int64_t x_batch, int64_t ldx,
+                           void *Y, int64_t y_batch, int64_t ldy,
+                           int B, int R, int C, int D, ggcn_stream_t stream);
+
+/* ---- bfloat16 features (training and inference under torch.autocast(dtype=torch.bfloat16)) ----------------------
+ * X (the layer's input) in bfloat16; weights, bias, gates, `out`, pools and dW stay float32, dX is bfloat16 -- the
+ * dtypes of the reference layer under bf16 autocast (models/gcn.py:34-43: the `/ denom` promotes to float32).  A bf16
+ * value is exact in the MFMA's operand type, so every product is TWO bf16 MFMAs on the GGCN_PREC_BF16X3 image of W
+ * (hi.Whi + hi.Wlo; ggcn_weight_pack(..., GGCN_PREC_BF16X3)): the accuracy class of GGCN_PREC_BF16X3, the fp32 range.
+ *   ggcn_linear_bf16      Y [M,F] float32 = X [M,K] bf16 (row stride ldx) . W            (then ggcn_aggregate)
+ *   ggcn_linear_out_bf16  Y [M,F] bf16 (RNE in the store) = X [M,K] float32 . W          (dX = dH.W^T on the W^T image)
+ *   ggcn_layer_fused_bf16 ggcn_layer_fused on bf16 X for graphs of <= 32 nodes (graph_ops of ggcn_graph_operands),
+ *                         same gates, pools, overlap partials / reduction and bias (or NULL); no precision argument
+ *   ggcn_dweight_bf16     dW [K,F] float32 = X^T . dH with bf16 X, float32 dH: X is transposed in bf16 and dH packed,
+ *                         then the split-K form of ggcn_dweight(GGCN_PREC_BF16X3); deterministic; workspace of
+ *                         ggcn_dweight_bf16_workspace_bytes(n_rows, K, F) bytes, 16-byte aligned
+ * Null pointers, ldx < K, ldy < F and misaligned elements return GGCN_EINVAL without a launch. */
+int ggcn_linear_bf16(const void *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy,
+                     int64_t M, int K, int F, ggcn_stream_t stream);
+int ggcn_linear_out_bf16(const float *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy,
+                         int64_t M, int K, int F, ggcn_stream_t stream);
+int ggcn_layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const void *graph_ops,
+                          const float *bias, int B, int T, int K, int F,
+                          const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
+                          float *out, int64_t ldo, float *pool_a, float *pool_b,
+                          float *overlap_partial, const float *overlap_in, float *overlap_out,
+                          ggcn_stream_t stream);
+size_t ggcn_dweight_bf16_workspace_bytes(int64_t n_rows, int K, int F);
+int ggcn_dweight_bf16(const void *X, int64_t ldx, const float *dH, int64_t ldg, int64_t n_rows, int K, int F,
+                      float *dW, int64_t lddw, void *workspace, ggcn_stream_t stream);
 
 #ifdef __cplusplus
 }
