@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from .csr import tensor_version
-from .gated_block import gated_gcn_block, takes_block_path
+from .gated_block import _layer2_input, gated_gcn_block, takes_block_path
 from .gcn import GraphConvolution
 from .heads import gate_mlps, scores_and_kl
 from .pooling import subword_pool
@@ -131,6 +131,12 @@ class GatedGCNEventDetector(nn.Module):
                 self.gc1.precision, self.gc2.precision = before
         return "f16mx8" if ok else "bf16x3"
 
+    def _takes_dropout_launches(self, x, csr):
+        """Both layers draw the gates' dropout inside their own launches: gc1 on x (float32, or bfloat16 under autocast), gc2 on
+        its real input, the float32 gcn1."""
+        return ((self.gc1.takes_dropout_path(x, csr) or self.gc1.takes_bf16_dropout_path(x, csr))
+                and self.gc2.takes_dropout_path(_layer2_input(x, self.gc1), csr))
+
     def forward(self, inputs):
         B = inputs["sentence_length"].shape[0]                              # :579-589
         L = int(inputs["cls_text_sep_length"].max())                        # one host sync, as :580-581
@@ -190,7 +196,7 @@ class GatedGCNEventDetector(nn.Module):
             gcn1 = self.gc1(x, csr)                                                    # :736
             xg, out, _ = self.gc2.forward_gated(gcn1, csr, want_pool_a=True)           # :748-749
             xy = 0.0
-        elif dropping and self.gc1.takes_dropout_path(x, csr) and self.gc2.takes_dropout_path(x, csr):
+        elif dropping and self._takes_dropout_launches(x, csr):
             # ---- training with dropout on the one-launch path (graphs of <= 256 nodes): the reference drops entries of the REPEATED [B,T,H] gates
             # (:621-625), one draw per token and feature.  The layers draw those keep factors in their own epilogues from a
             # counter-based hash of (seed, element) -- stream 1 for gate1, stream 2 for gate2 in BOTH layers, as the
@@ -198,7 +204,8 @@ class GatedGCNEventDetector(nn.Module):
             # size [B,T,H] is materialised for the gates, and the pools stay in the layer launches. ----
             p = float(self.dropout.p)
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())          # CPU generator: follows torch.manual_seed, no device sync
-            g1, g2 = self.gate1(aspect).contiguous(), self.gate2(aspect).contiguous()
+            # (under bf16 autocast the gate MLPs give bf16: the layers take float32 gates, the cast is differentiable)
+            g1, g2 = self.gate1(aspect).float().contiguous(), self.gate2(aspect).float().contiguous()
             gcn1, x1, y1 = self.gc1.forward_gated(x, csr, pool_gate_a=g1, pool_gate_b=g2, want_pool_a=True, want_pool_b=True,
                                                   dropout=(p, seed, (0, 1, 2)))          # :626-636
             xy = (x1 * y1).sum(1).mean()                                               # :638

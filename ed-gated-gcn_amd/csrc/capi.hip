@@ -207,14 +207,55 @@ int ggcn_linear_out_bf16(const float *X, int64_t ldx, const void *wpack, void *Y
     return linear_out_bf16(X, ldx, wpack, Y, ldy, M, K, F, as_stream(stream));
 }
 
+namespace {
+// what the three bf16 one-launch entries check alike before anything else: X's alignment, the gates' keep streams
+int bf16_entry_checks(const char *who, const void *X, float p, int sel_store, int sel_a, int sel_b)
+{
+    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
+    if (!(p >= 0.0f && p < 1.0f) || sel_store < 0 || sel_store > 2 || sel_a < 0 || sel_a > 2 || sel_b < 0 || sel_b > 2)
+        return fail(GGCN_EINVAL, "%s: p=%g streams %d %d %d", who, (double)p, sel_store, sel_a, sel_b);
+    return GGCN_OK;
+}
+}  // namespace
+
 int ggcn_layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const void *graph_ops, const float *bias, int B, int T,
                           int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out,
                           int64_t ldo, float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in,
                           float *overlap_out, ggcn_stream_t stream)
 {
-    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "ggcn_layer_fused_bf16: X not 2-byte aligned");
-    return layer_fused_bf16(X, ldx, wpack, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo, pool_a,
-                            pool_b, overlap_partial, overlap_in, overlap_out, GGCN_PREC_BF16X3, as_stream(stream));
+    const char *who = "ggcn_layer_fused_bf16";
+    if (int rc = bf16_entry_checks(who, X, 0.0f, 0, 0, 0)) return rc;
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (use ggcn_layer_fused_bf16_wide up to %d nodes, ggcn_linear_bf16 + ggcn_aggregate beyond)", who, T, GGCN_MASK_MAX_T);
+    return layer_fused_bf16(who, X, ldx, wpack, nullptr, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo, pool_a,
+                            pool_b, overlap_partial, overlap_in, overlap_out, as_stream(stream));
+}
+
+int ggcn_layer_fused_bf16_drop(const void *X, int64_t ldx, const void *wpack, const void *graph_ops, const float *bias, int B, int T,
+                               int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out,
+                               int64_t ldo, float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in,
+                               float *overlap_out, float p, uint64_t seed, int sel_store, int sel_a, int sel_b, ggcn_stream_t stream)
+{
+    const char *who = "ggcn_layer_fused_bf16_drop";
+    if (int rc = bf16_entry_checks(who, X, p, sel_store, sel_a, sel_b)) return rc;
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (use ggcn_layer_fused_bf16_wide up to %d nodes)", who, T, GGCN_MASK_MAX_T);
+    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);
+    return layer_fused_bf16(who, X, ldx, wpack, nullptr, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo, pool_a,
+                            pool_b, overlap_partial, overlap_in, overlap_out, as_stream(stream), &d);
+}
+
+int ggcn_layer_fused_bf16_wide(const void *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *edge_lists,
+                               const float *bias, int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a,
+                               const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b, float *overlap_partial,
+                               const float *overlap_in, float *overlap_out, float p, uint64_t seed, int sel_store, int sel_a, int sel_b,
+                               ggcn_stream_t stream)
+{
+    const char *who = "ggcn_layer_fused_bf16_wide";
+    if (int rc = bf16_entry_checks(who, X, p, sel_store, sel_a, sel_b)) return rc;
+    if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32 (use ggcn_layer_fused_bf16 / ggcn_layer_fused_bf16_drop)", who, T);
+    if (T > GGCN_MASK_MAX_T) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > %d (use ggcn_linear_bf16 + ggcn_aggregate)", who, T, GGCN_MASK_MAX_T);
+    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);   // p = 0: thr = 0, nothing is dropped
+    return layer_fused_bf16(who, X, ldx, wpack, rowmask, T > 128 ? edge_lists : nullptr, bias, B, T, K, F, store_gate, pool_gate_a,
+                            pool_gate_b, out, ldo, pool_a, pool_b, overlap_partial, overlap_in, overlap_out, as_stream(stream), &d);
 }
 
 int ggcn_aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,

@@ -37,8 +37,9 @@ struct FusedArgs {
     LayerPart part[2];
     DropSpec drop;              // training-mode keep masks of the gates (thr = 0: none); one part only
     unsigned long long *stamps; // diagnostics only (ggcn_debug_block_fused_stamped): [workgroup][2] = d(s_memtime), d(s_memrealtime) around the main loop
-    const __bf16 *Xb;           // bf16 features (ggcn_layer_fused_bf16: one layer, graphs of <= 32 nodes, bf16x3 image); X then only
-                                // names readable memory (the weight image) for the epilogue staging's discarded fallback reads
+    const __bf16 *Xb;           // bf16 features (ggcn_layer_fused_bf16[_drop]: graphs of <= 32 nodes, ggcn_layer_fused_bf16_wide: 33..256;
+                                // one layer, bf16x3 image); X then only names readable memory (the weight image) for the
+                                // discarded fallback reads of an absent gate / bias
 };
 
 
@@ -50,6 +51,14 @@ int launch_fused6(const char *who, const FusedArgs &a, bool fullt, bool vst, int
 namespace {
 
 using namespace bx3;
+
+// the features of a launch in the kernel's element type: float (a.X) or __bf16 (a.Xb)
+template <typename XT>
+__device__ __forceinline__ const XT *fused_x(const FusedArgs &a)
+{
+    if constexpr (std::is_same<XT, float>::value) return a.X;
+    else return a.Xb;
+}
 
 // acc -> two bf16 planes (hi + lo, residual <= 2^-17 |v|) as B-operand fragments of the two k-steps
 __device__ __forceinline__ void split2(const f32x16 &acc, bf16x8 (&frag)[2][2])

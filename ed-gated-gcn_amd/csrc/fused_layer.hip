@@ -191,13 +191,6 @@ __global__ __launch_bounds__(256) void graph_operands_w_kernel(const int32_t *__
 // STAMP (diagnostic instantiation only, ggcn_debug_block_fused_stamped): thread 0 of every workgroup stamps s_memtime (shader
 // cycles) and s_memrealtime (100 MHz) around the main loop into a.stamps, a buffer nothing else reads -- the clock the chip
 // holds under THIS kernel's load (MI355X_MICROARCH.md "DVFS give-back" (6)).  No product launch executes a stamp.
-template <typename XT>
-__device__ __forceinline__ const XT *fused_x(const FusedArgs &a)
-{
-    if constexpr (std::is_same<XT, float>::value) return a.X;
-    else return a.Xb;
-}
-
 // XT: element type of the features -- float, or __bf16 (a.Xb; bf16x3 image, two MFMAs per product: bf16x3_core.h)
 template <int SCH, bool AVEC, bool KFULL, bool FULLT, bool VST, bool STAMP = false, typename XT = float>
 __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(const FusedArgs a)
@@ -401,7 +394,6 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
         return fail(GGCN_EUNSUPPORTED, "%s: f16mx6 is an experiment this library was built without (make F16MX6=1); use f16mx8", who);
 #endif
     if (!a.X && !a.Xb) return fail(GGCN_EINVAL, "%s: null input pointer", who);   // (bf16: a.X is the weight image, see layer_fused_bf16)
-    if (a.Xb && a.T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (use ggcn_linear_bf16 + ggcn_aggregate)", who, a.T);
     if (a.T > 32 ? !a.rowmask : !a.graph_ops)
         return fail(GGCN_EINVAL, "%s: graphs of %d nodes need %s", who, a.T,
                     a.T > 32 ? "the row masks" : "the per-graph operand blocks of ggcn_graph_operands");
@@ -430,15 +422,29 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
         }
     }
     vst = vst && any_out;
-    if (a.Xb) {   // bf16 features: one layer, graphs of <= 32 nodes, the bf16x3 image (bf16 pair form, two MFMAs per product)
+    if (a.Xb) {   // bf16 features: one layer on the bf16x3 image (bf16 pair form, two MFMAs per product); the entry points fix the range of T
         if (precision != GGCN_PREC_BF16X3)
             return fail(GGCN_EUNSUPPORTED, "%s: bf16 features take the bf16x3 weight image (precision %d)", who, precision);
-        if (a.n_parts != 1 || a.drop.thr != 0 || a.stamps || a.part[0].mid)
-            return fail(GGCN_EUNSUPPORTED, "%s: one plain layer (no block, gate dropout or stamps)", who);
+        if (a.n_parts != 1 || a.stamps || a.part[0].mid || a.part[0].pre)
+            return fail(GGCN_EUNSUPPORTED, "%s: one plain layer (no block, folded bias or stamps)", who);
+        if ((int64_t)a.B * a.T * a.F >= ((int64_t)1 << 32) && a.drop.thr != 0)
+            return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)a.B * a.T * a.F);
         const bool avecb = (a.K % 8 == 0) && (a.ldx % 8 == 0) && aligned16(a.Xb);
         const bool kfullb = (a.K % BK == 0);
         a.k_steps = round_up(a.K, BK) / KSTEP;
         a.n_wg = (a.F + BN - 1) / BN;
+        if (a.T > 32) {   // 64-, 128- or 256-row graph slots, as for float32 features below
+            const int sb = a.T <= 64 ? 2 : a.T <= 128 ? 4 : 8;
+            const int gpt = sb == 2 ? 2 : 1;
+            const int64_t gt = ((int64_t)a.B + gpt - 1) / gpt;
+            const int64_t gridw = grid_for(gt, a.n_wg);
+            if (gridw > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
+            a.g_tiles = (int)gt;
+            // (a launch without `out` stores no rows: the vector-store form is as good as any, and it is the fast shape's only form)
+            const bool vstw = vst || !any_out;
+            if (sb == 8) return launch_fused_wide8(who, a, precision, avecb && kfullb, vstw, gridw, st);
+            return launch_fused_wide(who, a, precision, sb, avecb && kfullb, vstw, gridw, st);
+        }
         const int64_t g_tiles = ((int64_t)a.B + 4 * WM - 1) / (4 * WM);
         const int64_t grid = grid_for(g_tiles, a.n_wg);
         if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
@@ -630,26 +636,28 @@ int layer_fused(const float *X, int64_t ldx, const void *wpack, const uint32_t *
     return launch_fused("ggcn_layer_fused", a, precision, st);
 }
 
-int layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const void *graph_ops, const float *bias, int B, int T, int K, int F,
+// bf16 features.  who: the entry point, which has checked the graph size it takes (ggcn_layer_fused_bf16[_drop]: <= 32 nodes on
+// graph_ops; ggcn_layer_fused_bf16_wide: 33..256 on the row masks, graph_ops = optional edge-list blocks); drop: NULL or the gates' keep streams
+int layer_fused_bf16(const char *who, const void *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops,
+                     const float *bias, int B, int T, int K, int F,
                      const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-                     float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out, int precision,
-                     hipStream_t st)
+                     float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out,
+                     hipStream_t st, const DropSpec *drop)
 {
-    const char *who = "ggcn_layer_fused_bf16";
     if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
     if ((overlap_in == nullptr) != (overlap_out == nullptr)) return fail(GGCN_EINVAL, "%s: overlap_in and overlap_out go together", who);
     if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: ldo too large", who);
     FusedArgs a = {};
-    // a.X stays the epilogue staging's fallback READ address for an absent gate / bias (stage_epilogue_operands loads
-    // unconditionally and discards the value): it must be valid memory, and the weight image always is (>= 4 KiB; its
-    // NULL case is refused before the launch)
+    // a.X stays the fallback READ address for an absent gate / bias (the epilogues load unconditionally and discard the
+    // value): it must be valid memory, and the weight image always is (>= 4 KiB; its NULL case is refused before the launch)
     a.X = static_cast<const float *>(wpack);
-    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx; a.graph_ops = static_cast<const char *>(graph_ops);
+    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx; a.rowmask = rowmask; a.graph_ops = static_cast<const char *>(graph_ops);
     a.ov_in = overlap_in; a.ov_out = overlap_out;
     a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    if (drop) a.drop = *drop;
     a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, nullptr, nullptr, store_gate, pool_gate_a, pool_gate_b,
                           out, pool_a, pool_b, overlap_partial, (int)ldo};
-    return launch_fused(who, a, precision, st);
+    return launch_fused(who, a, GGCN_PREC_BF16X3, st);
 }
 
 int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,

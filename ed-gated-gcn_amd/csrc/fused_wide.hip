@@ -22,10 +22,13 @@ namespace {
 // DROP (training, bert_amir5.py:621-625): the three gates are dropped per (token, feature) -- keep factors from the
 // counter-based hash of dropout_hash.h, the same ones ggcn_gate_pool_backward_drop and ggcn_dropout_mask draw -- and the
 // pools maximise the gated, kept values themselves (every element has its own factor: no max / min shortcut).
-template <int SCH, bool AVEC, bool KFULL, bool VST, int SB, bool DROP = false>
+// XT: element type of the features -- float, or __bf16 (a.Xb; bf16x3 image, two MFMAs per product: bf16x3_core.h); the epilogue
+// works on the float32 accumulators and is the same for both.
+template <int SCH, bool AVEC, bool KFULL, bool VST, int SB, bool DROP = false, typename XT = float>
 __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_fused_wide_kernel(const FusedArgs a)
 {
     static_assert(SB == 2 || SB == 4 || SB == 8, "a graph slot is 64, 128 or 256 rows");
+    static_assert(std::is_same<XT, float>::value || (SCH == 0 && SB != 8), "bf16 features: the bf16x3 main loop, 64- and 128-row slots");
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
     if (a.ov_in && blockIdx.x == 0) reduce_partials(a.ov_in, B * ((F + 63) / 64), B, a.ov_out, reinterpret_cast<float *>(lds));
@@ -50,24 +53,24 @@ __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_f
     const int nt0 = n_wgi * (BN / NT) + wn * RN;
     const int W = (T + 31) >> 5;
 
-    constexpr int NP = Geom<float>::NP;
+    constexpr int NP = Geom<XT>::NP;
     // every accumulator tile -> its two bf16 planes (B-operand fragments of the aggregation MFMAs), in place
     bf16x8 hf[4 * HALVES][RN][2][2];
 #pragma unroll
     for (int hh = 0; hh < HALVES; ++hh) {
-        const float *arow[NP];
+        const XT *arow[NP];
         bool avalid[NP];
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const int row = stage_row<float>(i) + 128 * hh;
+            const int row = stage_row<XT>(i) + 128 * hh;
             const int g = g0 + row / S, r = row % S;
             avalid[i] = (g < B) && (r < T);
             const int64_t node = avalid[i] ? (int64_t)g * T + r : 0;
-            arow[i] = a.X + node * a.ldx;
+            arow[i] = fused_x<XT>(a) + node * a.ldx;
         }
         f32x16 acc[4][RN];
         if constexpr (SCH == 0)
-            bx3::mainloop<float, AVEC, KFULL, true>(arow, avalid, lp.wpack, K, a.k_steps, wm, nt0, n_tiles_total, lds, acc);
+            bx3::mainloop<XT, AVEC, KFULL, true>(arow, avalid, lp.wpack, K, a.k_steps, wm, nt0, n_tiles_total, lds, acc);
         else {
             constexpr bool BUF = AVEC && KFULL;   // buffer loads (f16mx8_core.h): offsets from the workgroup's first graph
             mx8::BufX<float> bx;
@@ -85,7 +88,8 @@ __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_f
         }
         // `pre` (ggcn_layer_fused_prebias): y = D.A.(hidden + 1.pre^T) + bias -- the folded second layer of the eval form, whose
         // input rows are already aggregated once (gated_block.py).  Workgroup-uniform; padding rows are nobody's neighbours.
-        if (lp.pre) {
+        // (float32 features only: the bf16 launches refuse `pre`, and without this branch their accumulators are never live twice)
+        if (std::is_same<XT, float>::value && lp.pre) {
 #pragma unroll
             for (int j = 0; j < RN; ++j) {
                 const int gn = (nt0 + j) * NT + (lane & 31);
@@ -287,6 +291,21 @@ int launch_fused_wide(const char *who, const FusedArgs &a, int precision, int sb
         if (a.drop.thr != 0) GGCN_PICKWD(SC, SBV, true);                     \
         else GGCN_PICKWD(SC, SBV, false);                                    \
     } while (0)
+    if (a.Xb) {   // bf16 features (bf16x3 image): the fast shape or the general form per slot size and DROP
+        if (sb != 2 && sb != 4) return fail(GGCN_EUNSUPPORTED, "%s: no %d-row graph slot for bf16 features in this build", who, 32 * sb);
+#define GGCN_LAUNCHWB(AV, KF, VS, SBV, DR) \
+    hipLaunchKernelGGL((layer_fused_wide_kernel<0, AV, KF, VS, SBV, DR, __bf16>), dim3((unsigned)gridw), dim3(kThreads), 0, st, a)
+#define GGCN_PICKWB(SBV, DR)                                                 \
+    do {                                                                     \
+        if (fast && vst) GGCN_LAUNCHWB(true, true, true, SBV, DR);           \
+        else GGCN_LAUNCHWB(false, false, false, SBV, DR);                    \
+    } while (0)
+        if (a.drop.thr != 0) { if (sb == 2) GGCN_PICKWB(2, true); else GGCN_PICKWB(4, true); }
+        else { if (sb == 2) GGCN_PICKWB(2, false); else GGCN_PICKWB(4, false); }
+#undef GGCN_PICKWB
+#undef GGCN_LAUNCHWB
+        return check_launch(who);
+    }
 #if GGCN_LAB_WIDE_SB8
     if (sb == 8) { if (precision == GGCN_PREC_F16MX8) GGCN_PICKW(1, 8); else GGCN_PICKW(0, 8); return check_launch(who); }
 #endif

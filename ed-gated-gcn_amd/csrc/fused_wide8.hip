@@ -33,10 +33,12 @@ static_assert(2 * kLdsBytes <= kW8Ex && kW8Lds <= 160 * 1024, "the stage buffers
 
 // DROP (training, bert_amir5.py:621-625): per-(token, feature) keep factors of the three gates (dropout_hash.h), the pools
 // maximise the gated, kept values (edge-list epilogue only).
-template <int SCH, bool AVEC, bool KFULL, bool VST, bool DROP = false>
+// XT: element type of the features -- float, or __bf16 (a.Xb; bf16x3 image, two MFMAs per product: bf16x3_core.h).
+template <int SCH, bool AVEC, bool KFULL, bool VST, bool DROP = false, typename XT = float>
 __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const FusedArgs a)
 {
     static_assert(!(DROP && GGCN_LAB_WIDE8_DENSE), "gate dropout lives in the edge-list epilogue");
+    static_assert(std::is_same<XT, float>::value || SCH == 0, "bf16 features: the bf16x3 main loop");
     extern __shared__ __attribute__((aligned(16))) char lds8[];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -116,16 +118,16 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
     }
 
     // ---- hidden = X . W for both row groups at once ----
-    constexpr int NP = Geom<float>::NP;
+    constexpr int NP = Geom<XT>::NP;
     f32x16 acc[4][RN];
     {
-        const float *arow[NP];
+        const XT *arow[NP];
         bool avalid[NP];
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const int r = stage_row<float>(i) + 128 * rg;
+            const int r = stage_row<XT>(i) + 128 * rg;
             avalid[i] = r < T;
-            arow[i] = a.X + ((int64_t)g * T + (avalid[i] ? r : 0)) * a.ldx;
+            arow[i] = fused_x<XT>(a) + ((int64_t)g * T + (avalid[i] ? r : 0)) * a.ldx;
         }
         char *stage = lds8 + rg * kLdsBytes;
         // 32-row blocks of this row group that hold nodes: T = 160 leaves the second group one block of four -- its other MFMAs
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
         const int rows_here = T - 128 * rg;
         const int nblk = rows_here >= 128 ? 4 : rows_here <= 0 ? 0 : (rows_here + 31) >> 5;
         if constexpr (SCH == 0)
-            bx3::mainloop<float, AVEC, KFULL, true, true>(arow, avalid, lp.wpack, K, a.k_steps, 0, nt0, n_tiles_total, stage, acc, nblk);
+            bx3::mainloop<XT, AVEC, KFULL, true, true>(arow, avalid, lp.wpack, K, a.k_steps, 0, nt0, n_tiles_total, stage, acc, nblk);
         else {
             constexpr bool BUF = AVEC && KFULL;   // buffer loads (f16mx8_core.h): offsets from the graph's first node
             mx8::BufX<float> bx;
@@ -628,6 +630,22 @@ int launch_fused_wide8(const char *who, const FusedArgs &a, int precision, bool 
         else if (fast) GGCN_LAUNCH8(SC, true, true, false);         \
         else GGCN_LAUNCH8(SC, false, false, false);                 \
     } while (0)
+    if (a.Xb) {   // bf16 features (bf16x3 image): the fast shape or the general form, each with and without DROP
+#define GGCN_LAUNCH8B(AV, KF, VS, DR)                                                                                     \
+    do {                                                                                                                  \
+        auto kern = layer_fused_wide8_kernel<0, AV, KF, VS, DR, __bf16>;                                                   \
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,         \
+                                kW8Lds) != hipSuccess)                                                                    \
+            return fail(GGCN_ELAUNCH, "%s: cannot reserve %d bytes of LDS", who, kW8Lds);                                 \
+        hipLaunchKernelGGL(kern, dim3((unsigned)gridw), dim3(kW8Threads), kW8Lds, st, a);                                 \
+    } while (0)
+        constexpr bool kDrop8 = !GGCN_LAB_WIDE8_DENSE;
+        if (a.drop.thr != 0 && !kDrop8) return fail(GGCN_EUNSUPPORTED, "%s: gate dropout lives in the edge-list epilogue", who);
+        if (a.drop.thr != 0) { if (fast && vst) GGCN_LAUNCH8B(true, true, true, kDrop8); else GGCN_LAUNCH8B(false, false, false, kDrop8); }
+        else { if (fast && vst) GGCN_LAUNCH8B(true, true, true, false); else GGCN_LAUNCH8B(false, false, false, false); }
+#undef GGCN_LAUNCH8B
+        return check_launch(who);
+    }
     if (precision == GGCN_PREC_F16MX8) GGCN_PICK8(1);
     else GGCN_PICK8(0);
 #undef GGCN_PICK8

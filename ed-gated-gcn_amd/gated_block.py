@@ -131,8 +131,8 @@ def _layer2_input(x, gc1):
 
 
 def _layer1_takes_fused(x, csr, gc1):
-    """gc1 runs as one launch: the float32 one-launch layer, or the bf16 one (graphs of <= 32 nodes)."""
-    return gc1.takes_fused_path(x, csr) or gc1.takes_bf16_fused_path(x, csr)
+    """gc1 runs as one launch: the float32 one-launch layer, or a bf16 one (graphs of <= 32 nodes, or 33..256 on the row masks)."""
+    return gc1.takes_fused_path(x, csr) or gc1.takes_bf16_fused_path(x, csr) or gc1.takes_bf16_wide_path(x, csr)
 
 
 BLOCK_OUTPUTS = ("x1", "y1", "xy", "x", "out")

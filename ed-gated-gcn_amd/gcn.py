@@ -412,10 +412,55 @@ class GraphConvolution(nn.Module):
 
     def takes_bf16_fused_path(self, text, csr):
         """True when ``forward_gated`` (inference or the forward of training) runs bfloat16 features as ONE launch
-        (``ggcn_layer_fused_bf16``): graphs of <= 32 nodes, 0/1 adjacency, a split precision (``BF16_PRECISIONS``).  Longer
-        graphs and weighted adjacencies take ``ggcn_linear_bf16`` + ``ggcn_aggregate``; no gate dropout in the launch."""
+        (``ggcn_layer_fused_bf16``): graphs of <= 32 nodes, 0/1 adjacency, a split precision (``BF16_PRECISIONS``).  Graphs of
+        33..256 nodes: ``takes_bf16_wide_path``; gate dropout in either launch: ``takes_bf16_dropout_path``.  Anything else
+        (longer graphs, weighted adjacencies) takes ``ggcn_linear_bf16`` + ``ggcn_aggregate``."""
         return (self.fused and text.dtype == torch.bfloat16 and self.precision in BF16_PRECISIONS and csr.is_binary
                 and csr.T <= 32 and csr.T <= self.fused_max_t and csr.rowmask is not None and csr.rowmask.is_cuda)
+
+    BF16_WIDE_MIN_FILL = 0.75   # 33..128 nodes: one launch when the graph fills this share of its 64- or 128-row slot
+
+    def takes_bf16_wide_path(self, text, csr):
+        """True when ``forward_gated`` runs bfloat16 features of graphs of 33..256 nodes as ONE launch
+        (``ggcn_layer_fused_bf16_wide``: the 64- / 128-row slot kernel up to 128 nodes, the eight-wavefront kernel beyond, both
+        with the bf16 pair main loop on the bf16x3 image): ``fused``, a precision of ``BF16_PRECISIONS``, 0/1 adjacency, row
+        masks on the device.  ``fused_max_t = 256`` sends every such graph there, ``fused = False`` none; in between the
+        rule is the measured one (``tools/bf16_wide_timing.py``, H = 768, DESIGN.md 4.2bf: the one launch is the default only
+        where its median beat ``ggcn_linear_bf16`` + ``ggcn_aggregate`` by more than the spread between the timing windows):
+
+        * up to ``fused_max_t`` (128 by default) nodes, when the graph fills >= 75 % of its row slot -- 48..64 and 96..128
+          nodes (512 x 48: 79 vs 105 us, 512 x 64: 90 vs 122, 512 x 96: 146 vs 187, 512 x 100: 160 vs 199, 512 x 128: 186 vs 261,
+          4096 x 100: 1332 vs 1540, 128 x 100: 54 vs 64).  Emptier slots tie or lose on large batches (512 x 33: 74 vs 70,
+          512 x 40: 76 vs 77, 4096 x 33: 549 vs 525, 512 x 65: 134 vs 135, 128 x 80: 50 vs 46) and keep the two launches;
+        * 129..256 nodes (the 256-row slot), when the workgroups fill whole rounds of the device (``WIDE_AUTO_FILL``):
+          512 x 129: 244 vs 265 us, 512 x 160: 262 vs 326, 512 x 192: 297 vs 385, 512 x 231: 352 vs 459, 512 x 256: 378 vs
+          508, 256 x 231: 172 vs 236.  A fraction of a round loses or ties for EVERY length, 193..256 included (128 x 129:
+          81 vs 68, 128 x 160: 85 vs 76, 128 x 193: 101 vs 96, 128 x 231: 110 vs 104, 128 x 256: 119 vs 115) -- unlike
+          float32 bf16x3, whose 193..256 rule is unconditional and whose full-rounds threshold is 161; here it is 129.
+
+        The choice depends on the batch size and the device's CU count, and the two paths sum in different orders (both
+        inside the parity gate): ``fused_max_t = 256`` or ``fused = False`` pin it."""
+        if not (self.fused and text.dtype == torch.bfloat16 and self.precision in BF16_PRECISIONS and csr.is_binary
+                and csr.rowmask is not None and csr.rowmask.is_cuda and 32 < csr.T <= 256):
+            return False
+        if self.fused_max_t >= 256:
+            return True
+        if csr.T <= 128:
+            slot = 64 if csr.T <= 64 else 128
+            return csr.T <= self.fused_max_t and csr.T >= self.BF16_WIDE_MIN_FILL * slot
+        if self.fused_max_t < 128 or not text.is_cuda:
+            return False
+        wgs = text.shape[0] * ((self.out_features + 255) // 256)
+        cus = torch.cuda.get_device_properties(text.device).multi_processor_count
+        rounds = -(-wgs // cus)
+        return rounds >= 2 and wgs >= self.WIDE_AUTO_FILL * rounds * cus
+
+    def takes_bf16_dropout_path(self, text, csr):
+        """True when the gates' training-mode dropout (``bert_amir5.py:621-625``) of bfloat16 features is drawn inside the
+        layer launch (``ggcn_layer_fused_bf16_drop`` for graphs of <= 32 nodes, ``ggcn_layer_fused_bf16_wide`` up to 256):
+        one of the two bf16 one-launch paths and an element index below 2^32."""
+        return ((self.takes_bf16_fused_path(text, csr) or self.takes_bf16_wide_path(text, csr))
+                and text.shape[0] * text.shape[1] * self.out_features < 2 ** 32)
 
     def takes_weighted_path(self, text, csr):
         """True when ``forward_gated`` (inference) will run a REAL-valued adjacency (``gcn.py:33`` accepts any ``adj``) as ONE
@@ -470,12 +515,13 @@ class GraphConvolution(nn.Module):
         ``out = y * store_gate`` and ``pool_x = max_t (y * pool_gate_x)``, ``y`` being the
         plain layer output.  Gates are ``[B,F]`` (broadcast over tokens).
 
-        One-launch path only (``takes_fused_path``): ``overlap_partial`` (float32 ``[B, ceil(F/64)]``)
+        One-launch path only (``takes_fused_path``; bfloat16 features: ``takes_bf16_fused_path`` / ``takes_bf16_wide_path``): ``overlap_partial`` (float32 ``[B, ceil(F/64)]``)
         receives this layer's share of ``sum_f pool_a*pool_b``; ``overlap_reduce=(partials, xy)`` makes
         this launch reduce the partials an earlier launch wrote into the scalar ``xy``
         (``bert_amir5.py:638`` without its own launches).
 
-        ``dropout=(p, seed, (stream_store, stream_a, stream_b))`` (one-launch path: ``takes_dropout_path``): the three gates
+        ``dropout=(p, seed, (stream_store, stream_a, stream_b))`` (one-launch path: ``takes_dropout_path``, or
+        ``takes_bf16_dropout_path`` for bfloat16 features): the three gates
         are dropped per (token, feature) like the reference's repeated ``[B,T,H]`` gates (``bert_amir5.py:621-625``);
         stream 0 = not dropped, 1 / 2 = the two independent Bernoulli streams of ``seed`` (``include/ggcn.h``)."""
         self._check(text)
@@ -489,7 +535,7 @@ class GraphConvolution(nn.Module):
             # training: the same kernels, wrapped in an autograd Function with a HIP backward
             if text.dtype not in (torch.float32, torch.bfloat16):
                 raise RuntimeError("training through the HIP layer needs float32 features (or bfloat16 ones)")
-            if dropout is not None and not self.takes_dropout_path(text, csr):
+            if dropout is not None and not (self.takes_dropout_path(text, csr) or self.takes_bf16_dropout_path(text, csr)):
                 raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
             out, pa, pb = _GatedLayerFunction.apply(text, self.weight, self.bias, store_gate, pool_gate_a,
                                                     pool_gate_b, self, csr, want_pool_a, want_pool_b, dropout)
@@ -511,14 +557,16 @@ class GraphConvolution(nn.Module):
         bf16 = text.dtype == torch.bfloat16
         use_fused = self.takes_fused_path(text, csr)
         use_bf16 = bf16 and self.takes_bf16_fused_path(text, csr)
-        if dropout is not None and not (use_fused and self.takes_dropout_path(text, csr)):
+        use_bf16_wide = bf16 and self.takes_bf16_wide_path(text, csr)
+        if dropout is not None and not ((use_fused and self.takes_dropout_path(text, csr))
+                                        or ((use_bf16 or use_bf16_wide) and self.takes_bf16_dropout_path(text, csr))):
             raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
-        if (overlap_partial is not None or overlap_reduce is not None) and not (use_fused or use_bf16):
+        if (overlap_partial is not None or overlap_reduce is not None) and not (use_fused or use_bf16 or use_bf16_wide):
             raise RuntimeError("overlap_partial / overlap_reduce need the one-launch layer (takes_fused_path)")
         use_long = ((not use_fused) and self.takes_long_path(text, csr) and x2d.data_ptr() % 16 == 0
                     and x2d.stride(0) % 8 == 0)   # ggcn_layer_fused_h wants 16-byte aligned rows; other views: linear_h + aggregate_h
         use_weighted = (not use_fused) and dropout is None and self.takes_weighted_path(text, csr)
-        hidden = None if (use_fused or use_long or use_weighted or use_bf16) else self.linear(x2d)
+        hidden = None if (use_fused or use_long or use_weighted or use_bf16 or use_bf16_wide) else self.linear(x2d)
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
             out = torch.empty(B * T, F, dtype=torch.float32 if bf16 else text.dtype, device=dev) if want_out else None
@@ -548,15 +596,25 @@ class GraphConvolution(nn.Module):
                                                  _capi.PREC[kprec], st),
                             "ggcn_layer_fused")
                 return (None if out is None else out.view(B, T, F)), pa, pb
-            if use_bf16:   # bfloat16 features, graphs of <= 32 nodes: one launch on the bf16x3 image
+            if use_bf16 or use_bf16_wide:   # bfloat16 features: one launch on the bf16x3 image (<= 32 nodes; 33..256 on the row masks)
                 pack = self._packed_weight(lib, st, precision="bf16x3")
-                _capi.check(lib.ggcn_layer_fused_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.graph_ops),
-                                                      _capi.ptr(bias), B, T, self.in_features, F, _capi.ptr(store_gate),
-                                                      _capi.ptr(pool_gate_a), _capi.ptr(pool_gate_b), _capi.ptr(out), F,
-                                                      _capi.ptr(pa), _capi.ptr(pb), _capi.ptr(overlap_partial),
-                                                      _capi.ptr(overlap_reduce[0]) if overlap_reduce else None,
-                                                      _capi.ptr(overlap_reduce[1]) if overlap_reduce else None, st),
-                            "ggcn_layer_fused_bf16")
+                dp, dseed, (ss, sa, sb) = dropout if dropout is not None else (0.0, 0, (0, 0, 0))
+                ov = (_capi.ptr(overlap_partial), _capi.ptr(overlap_reduce[0]) if overlap_reduce else None,
+                      _capi.ptr(overlap_reduce[1]) if overlap_reduce else None)
+                tail = (B, T, self.in_features, F, _capi.ptr(store_gate), _capi.ptr(pool_gate_a), _capi.ptr(pool_gate_b),
+                        _capi.ptr(out), F, _capi.ptr(pa), _capi.ptr(pb)) + ov
+                if use_bf16_wide:
+                    lists = csr.edge_lists if (T > 128 and os.environ.get("GGCN_EDGE_LISTS", "1") != "0") else None
+                    _capi.check(lib.ggcn_layer_fused_bf16_wide(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.rowmask),
+                                                               _capi.ptr(lists), _capi.ptr(bias), *tail, float(dp), int(dseed),
+                                                               ss, sa, sb, st), "ggcn_layer_fused_bf16_wide")
+                elif dropout is not None:
+                    _capi.check(lib.ggcn_layer_fused_bf16_drop(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.graph_ops),
+                                                               _capi.ptr(bias), *tail, float(dp), int(dseed), ss, sa, sb, st),
+                                "ggcn_layer_fused_bf16_drop")
+                else:
+                    _capi.check(lib.ggcn_layer_fused_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.graph_ops),
+                                                          _capi.ptr(bias), *tail, st), "ggcn_layer_fused_bf16")
                 return (None if out is None else out.view(B, T, F)), pa, pb
             if use_weighted:   # real-valued adjacency, graphs of <= 32 nodes: one launch on D.A_w operand blocks
                 kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"

@@ -35,6 +35,8 @@
 extern "C" {
 #endif
 
+/* Bumped when a prototype, struct or enum CHANGES.  Added functions alone do not bump it: a binding that declares a function
+ * an older library lacks fails at load time on the missing symbol (14 also covers ggcn_layer_fused_bf16_drop / _wide). */
 #define GGCN_ABI_VERSION 14
 #define GGCN_MASK_MAX_T 256   /* largest graph the row-mask (one-launch) path takes */
 
@@ -550,10 +552,17 @@ int ggcn_subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t s
  *   ggcn_linear_out_bf16  Y [M,F] bf16 (RNE in the store) = X [M,K] float32 . W          (dX = dH.W^T on the W^T image)
  *   ggcn_layer_fused_bf16 ggcn_layer_fused on bf16 X for graphs of <= 32 nodes (graph_ops of ggcn_graph_operands),
  *                         same gates, pools, overlap partials / reduction and bias (or NULL); no precision argument
+ *   ggcn_layer_fused_bf16_drop  the same launch with the gates' training-mode dropout drawn in its epilogue: p, seed and the
+ *                         three stream selectors of ggcn_layer_fused_drop (same hash, same ggcn_dropout_mask, same backward)
+ *   ggcn_layer_fused_bf16_wide  graphs of 33..256 nodes in one launch: row masks (ggcn_rowmask_from_dense / ggcn_csr_rowmask),
+ *                         edge_lists = NULL or the ggcn_graph_edge_lists blocks (read for T > 128 only), overlap partials /
+ *                         reduction as ggcn_layer_fused; p = 0: no dropout, else as ggcn_layer_fused_bf16_drop
+ *                         A T outside an entry's range returns GGCN_EUNSUPPORTED and names the entry to use; dropout needs
+ *                         B*T*F < 2^32; overlap_in and overlap_out go together.
  *   ggcn_dweight_bf16     dW [K,F] float32 = X^T . dH with bf16 X, float32 dH: X is transposed in bf16 and dH packed,
  *                         then the split-K form of ggcn_dweight(GGCN_PREC_BF16X3); deterministic; workspace of
  *                         ggcn_dweight_bf16_workspace_bytes(n_rows, K, F) bytes, 16-byte aligned
- * Null pointers, ldx < K, ldy < F and misaligned elements return GGCN_EINVAL without a launch. */
+ * Null pointers, ldx < K, ldy / ldo < F, misaligned elements and images or blocks off 16 bytes return GGCN_EINVAL without a launch. */
 int ggcn_linear_bf16(const void *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy,
                      int64_t M, int K, int F, ggcn_stream_t stream);
 int ggcn_linear_out_bf16(const float *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy,
@@ -564,6 +573,18 @@ int ggcn_layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const v
                           float *out, int64_t ldo, float *pool_a, float *pool_b,
                           float *overlap_partial, const float *overlap_in, float *overlap_out,
                           ggcn_stream_t stream);
+int ggcn_layer_fused_bf16_drop(const void *X, int64_t ldx, const void *wpack, const void *graph_ops,
+                               const float *bias, int B, int T, int K, int F,
+                               const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
+                               float *out, int64_t ldo, float *pool_a, float *pool_b,
+                               float *overlap_partial, const float *overlap_in, float *overlap_out,
+                               float p, uint64_t seed, int stream_store, int stream_a, int stream_b, ggcn_stream_t stream);
+int ggcn_layer_fused_bf16_wide(const void *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *edge_lists,
+                               const float *bias, int B, int T, int K, int F,
+                               const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
+                               float *out, int64_t ldo, float *pool_a, float *pool_b,
+                               float *overlap_partial, const float *overlap_in, float *overlap_out,
+                               float p, uint64_t seed, int stream_store, int stream_a, int stream_b, ggcn_stream_t stream);
 size_t ggcn_dweight_bf16_workspace_bytes(int64_t n_rows, int K, int F);
 int ggcn_dweight_bf16(const void *X, int64_t ldx, const float *dH, int64_t ldg, int64_t n_rows, int K, int F,
                       float *dW, int64_t lddw, void *workspace, ggcn_stream_t stream);
