@@ -523,7 +523,9 @@ class GraphConvolution(nn.Module):
         ``dropout=(p, seed, (stream_store, stream_a, stream_b))`` (one-launch path: ``takes_dropout_path``, or
         ``takes_bf16_dropout_path`` for bfloat16 features): the three gates
         are dropped per (token, feature) like the reference's repeated ``[B,T,H]`` gates (``bert_amir5.py:621-625``);
-        stream 0 = not dropped, 1 / 2 = the two independent Bernoulli streams of ``seed`` (``include/ggcn.h``)."""
+        stream 0 = not dropped, 1 / 2 = the two independent Bernoulli streams of ``seed`` (``include/ggcn.h``).  Under autograd a
+        dropped store gate (stream 1 / 2) wants every pool in use on its own stream (the block's layer 2: ``(2, 2, 0)`` with one
+        pool): the backward reads y back from the stored output, and anything else is refused."""
         self._check(text)
         if text.shape[0] == 0:   # an empty batch is a valid input of the reference (gcn.py:30-45): empty outputs
             B, T, F = 0, text.shape[1], self.out_features
@@ -537,6 +539,14 @@ class GraphConvolution(nn.Module):
                 raise RuntimeError("training through the HIP layer needs float32 features (or bfloat16 ones)")
             if dropout is not None and not (self.takes_dropout_path(text, csr) or self.takes_bf16_dropout_path(text, csr)):
                 raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
+            if dropout is not None:
+                # the backward recovers y from the stored out = y*sg*k_store: a token whose store factor is 0 leaves nothing to
+                # recover, which is exact only for pools that drop the same tokens (include/ggcn.h ggcn_gate_pool_backward_drop)
+                ss, sa, sb = dropout[2]
+                if ss != 0 and ((want_pool_a and sa != ss) or (want_pool_b and sb != ss)):
+                    raise RuntimeError("dropout streams %r: under autograd a pool must share the store gate's keep stream (or the "
+                                       "store gate stay undropped, stream 0) -- the backward reads y back from the stored output, "
+                                       "which a dropped store gate zeroes" % ((ss, sa, sb),))
             out, pa, pb = _GatedLayerFunction.apply(text, self.weight, self.bias, store_gate, pool_gate_a,
                                                     pool_gate_b, self, csr, want_pool_a, want_pool_b, dropout)
             return (out if want_out else None), pa, pb
