@@ -66,6 +66,9 @@ PROTOTYPES = {
     "ggcn_layer_fused_bf16_wide": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                            c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            ctypes.c_float, ctypes.c_uint64, c_i32, c_i32, c_i32, c_vp]),
+    "ggcn_block_fused_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32,
+                                      c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ggcn_aggregate_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "ggcn_dweight_bf16_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32]),
     "ggcn_dweight_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp]),
     "ggcn_weight_pack_bytes": (c_sz, [c_i32, c_i32, c_i32]),

@@ -103,6 +103,54 @@ struct Seg<__half, 1> {
     static __device__ __forceinline__ void store(__half *p, const float (&v)[1]) { *p = __float2half_rn(v[0]); }
 };
 
+// bf16 features (ggcn_aggregate_bf16): a bf16 value IS the upper half of an fp32 value, so loads widen by a shift and the LDS
+// tile keeps the raw 16 bits (the store's narrowing shift drops only zeros); sums and outputs are fp32 (Seg<float, VEC>)
+template <>
+struct Seg<float, 8> {
+    static __device__ __forceinline__ void store(float *p, const float (&v)[8])
+    {
+        reinterpret_cast<float4 *>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+        reinterpret_cast<float4 *>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+    }
+};
+template <int VEC>
+struct Seg<__bf16, VEC> {
+    static_assert(VEC == 8 || VEC == 4 || VEC == 1, "16-, 8- or 2-byte accesses");
+    typedef unsigned short u16;
+    static __device__ __forceinline__ void load(const __bf16 *p, float (&v)[VEC])
+    {
+        if constexpr (VEC == 1) {
+            v[0] = __uint_as_float((uint32_t)*reinterpret_cast<const u16 *>(p) << 16);
+        } else {
+            uint32_t w[VEC / 2];
+            if constexpr (VEC == 8) {
+                const uint4 t = *reinterpret_cast<const uint4 *>(p);
+                w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+            } else {
+                const uint2 t = *reinterpret_cast<const uint2 *>(p);
+                w[0] = t.x; w[1] = t.y;
+            }
+#pragma unroll
+            for (int i = 0; i < VEC / 2; ++i) {
+                v[2 * i] = __uint_as_float(w[i] << 16);
+                v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+            }
+        }
+    }
+    static __device__ __forceinline__ void store(__bf16 *p, const float (&v)[VEC])   // (the LDS tile only: v came out of load)
+    {
+        if constexpr (VEC == 1) {
+            *reinterpret_cast<u16 *>(p) = (u16)(__float_as_uint(v[0]) >> 16);
+        } else {
+            uint32_t w[VEC / 2];
+#pragma unroll
+            for (int i = 0; i < VEC / 2; ++i) w[i] = (__float_as_uint(v[2 * i]) >> 16) | (__float_as_uint(v[2 * i + 1]) & 0xFFFF0000u);
+            if constexpr (VEC == 8) *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+            else *reinterpret_cast<uint2 *>(p) = make_uint2(w[0], w[1]);
+        }
+    }
+};
+
 // max for floats through integer atomics (order-independent, hence deterministic): values with a
 // clear sign bit order like signed ints, values with the sign bit set like unsigned ints reversed.
 // -inf is the identity.  The branch is on the SIGN BIT, not on v >= 0: -0.0 (what y * gate gives for
@@ -130,7 +178,8 @@ __device__ __forceinline__ void load_f32(const float *p, float (&v)[VEC])
 }
 
 // grid.x = B * n_slabs ; block = 256.  slab = 64*VEC columns.  E = feature element type
-// (float, or __half with fp32 accumulation: BASELINE configs[3]); bias, gates, pools are fp32.
+// (float, or __half with fp32 accumulation: BASELINE configs[3]); bias, gates, pools are fp32.  O = element type of `out`
+// (E, except ggcn_aggregate_bf16: bf16 features in, fp32 out).
 // NORM = true: the forward (divide by rowsum+1, bias, gates, pools).  NORM = false: the plain
 // weighted sum out[i] = sum_e vals[e] * src_scale[colidx[e]] * Hd[colidx[e]] used by the backward
 // pass (the transposed adjacency applied to D.dY: src_scale = 1/(rowsum+1) of the SOURCE row).
@@ -141,14 +190,14 @@ __device__ __forceinline__ void load_f32(const float *p, float (&v)[VEC])
 constexpr int kChunkRows = 16;   // destination rows per workgroup when a graph is cut into chunks
 constexpr int kTiledMaxT = 48;  // static 8-16 KiB + 48 KiB of tile stays within the default 64 KiB LDS limit
 
-template <typename E, int VEC, bool HAS_VALS, bool NORM = true, bool TILED = false>
+template <typename E, int VEC, bool HAS_VALS, bool NORM = true, bool TILED = false, typename O = E>
 __global__ __launch_bounds__(256) void aggregate_rows(
     const E *__restrict__ Hd, int64_t ldh, const int32_t *__restrict__ rowptr,
     const int32_t *__restrict__ colidx, const float *__restrict__ vals,
     const float *__restrict__ src_scale,
     const float *__restrict__ bias, int n_graphs, int T, int F, int n_slabs, int n_chunks, int chunk_rows,
     const float *__restrict__ store_gate, const float *__restrict__ pool_gate_a,
-    const float *__restrict__ pool_gate_b, E *__restrict__ out, int64_t ldo,
+    const float *__restrict__ pool_gate_b, O *__restrict__ out, int64_t ldo,
     float *__restrict__ pool_a, float *__restrict__ pool_b)
 {
     constexpr int kSlab = kWave * VEC;
@@ -296,7 +345,7 @@ __global__ __launch_bounds__(256) void aggregate_rows(
                     pa[k] = fmaxf(pa[k], y[k] * vga[k]);
                     pb[k] = fmaxf(pb[k], y[k] * vgb[k]);
                 }
-                if (out) Seg<E, VEC>::store(out + row[r] * ldo + col, o);
+                if (out) Seg<O, VEC>::store(out + row[r] * ldo + col, o);
             }
         }
     }
@@ -608,6 +657,32 @@ int launch(const E *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colid
     return check_launch("ggcn_aggregate");
 }
 
+// ggcn_aggregate_bf16: the launch shapes of launch<float, VEC> (tiled up to kTiledMaxT nodes, chunks of kChunkRows rows beyond),
+// bf16 rows in, fp32 rows out, no side inputs
+template <int VEC>
+int launch_bf16(const __bf16 *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int K,
+                float *Z, int64_t ldz, hipStream_t st)
+{
+    const int slab = kWave * VEC;
+    const int n_slabs = (K + slab - 1) / slab;
+    const bool tiled = (VEC > 1) && (T <= kTiledMaxT);
+    const int chunk_rows = tiled ? T : kChunkRows;
+    const int n_chunks = tiled ? 1 : (T + kChunkRows - 1) / kChunkRows;
+    const int64_t blocks = (n_chunks == 1 ? (int64_t)B : ((int64_t)B + 7) / 8 * 8) * n_slabs * n_chunks;
+    if (blocks > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "ggcn_aggregate_bf16: grid too large");
+    const size_t lds = tiled ? (size_t)T * slab * sizeof(__bf16) : 0;
+#define GGCN_AGGB(HV, TL)                                                                                                \
+    hipLaunchKernelGGL((aggregate_rows<__bf16, VEC, HV, true, TL, float>), dim3((unsigned)blocks), dim3(256), lds, st, X, ldx, \
+                       rowptr, colidx, vals, nullptr, nullptr, B, T, K, n_slabs, n_chunks, chunk_rows, nullptr, nullptr, nullptr, \
+                       Z, ldz, nullptr, nullptr)
+    if (vals && tiled) GGCN_AGGB(true, true);
+    else if (vals) GGCN_AGGB(true, false);
+    else if (tiled) GGCN_AGGB(false, true);
+    else GGCN_AGGB(false, false);
+#undef GGCN_AGGB
+    return check_launch("ggcn_aggregate_bf16");
+}
+
 template <int VEC>
 int launch_t(const float *G, int64_t ldg, const int32_t *rowptr, const int32_t *colidx, const float *vals,
              const float *src_scale, int B, int T, int F, float *out, int64_t ldo, hipStream_t st)
@@ -677,6 +752,27 @@ int aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t
                                 pool_gate_b, out, ldo, pool_a, pool_b, st);
     return launch<float, 1>(Hd, ldh, rowptr, colidx, vals, bias, B, T, F, store_gate, pool_gate_a,
                             pool_gate_b, out, ldo, pool_a, pool_b, st);
+}
+
+int aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int K,
+                   float *Z, int64_t ldz, hipStream_t st)
+{
+    const char *who = "ggcn_aggregate_bf16";
+    if (!X || !rowptr || !colidx) return fail(GGCN_EINVAL, "%s: null input pointer", who);
+    if (!Z) return fail(GGCN_EINVAL, "%s: null output pointer", who);
+    if (B <= 0 || T <= 0 || K <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d K=%d must be positive", who, B, T, K);
+    if (ldx < K) return fail(GGCN_EINVAL, "%s: ldx < K", who);
+    if (ldz < K) return fail(GGCN_EINVAL, "%s: ldz < K", who);
+    if (reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(Z) % 4) return fail(GGCN_EINVAL, "%s: Z not 4-byte aligned", who);
+    if ((int64_t)B * T >= (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: B*T does not fit int32 node ids", who);
+    const __bf16 *x = static_cast<const __bf16 *>(X);
+    // the vector forms where ggcn_aggregate on the float32 copy of X takes its own (K % 4 == 0, 16-byte rows of Z), so that the
+    // tiled / chunked choice is the same: 16-byte loads for K % 8 == 0 and 16-byte aligned rows of X, 8-byte loads otherwise
+    const bool zvec = (K % 4 == 0) && (ldz % 4 == 0) && aligned16(Z);
+    if (zvec && (K % 8 == 0) && (ldx % 8 == 0) && aligned16(X)) return launch_bf16<8>(x, ldx, rowptr, colidx, vals, B, T, K, Z, ldz, st);
+    if (zvec && (ldx % 4 == 0) && (reinterpret_cast<uintptr_t>(X) & 7u) == 0) return launch_bf16<4>(x, ldx, rowptr, colidx, vals, B, T, K, Z, ldz, st);
+    return launch_bf16<1>(x, ldx, rowptr, colidx, vals, B, T, K, Z, ldz, st);
 }
 
 int aggregate_t(const float *G, int64_t ldg, const int32_t *rowptr_t, const int32_t *colidx_t,

@@ -258,6 +258,22 @@ int ggcn_layer_fused_bf16_wide(const void *X, int64_t ldx, const void *wpack, co
                             pool_gate_b, out, ldo, pool_a, pool_b, overlap_partial, overlap_in, overlap_out, as_stream(stream), &d);
 }
 
+int ggcn_block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
+                          const void *graph_ops2, const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K,
+                          int F, const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
+                          float *x1, float *y1, float *pool_out, float *overlap_partial, ggcn_stream_t stream)
+{
+    if (int rc = bf16_entry_checks("ggcn_block_fused_bf16", X, 0.0f, 0, 0, 0)) return rc;
+    return block_fused_bf16(X, ldx, wpack1, wpack12, graph_ops, graph_ops2, bias1, bias_mid, bias2, B, T, K, F, gate1, gate2, gcn1, ld1,
+                            x_out, ld2, x1, y1, pool_out, overlap_partial, as_stream(stream));
+}
+
+int ggcn_aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T,
+                        int K, float *Z, int64_t ldz, ggcn_stream_t stream)
+{
+    return aggregate_bf16(X, ldx, rowptr, colidx, vals, B, T, K, Z, ldz, as_stream(stream));
+}
+
 int ggcn_aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,
                    const float *vals, const float *bias, int B, int T, int F, const float *store_gate,
                    const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,

@@ -71,6 +71,10 @@ int aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t
               const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
               float *pool_a, float *pool_b, hipStream_t st);
 
+// Z = D.A.X on bf16 features (aggregate.hip): ggcn_aggregate's sums, bit for bit, without the float32 copy of X
+int aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int K,
+                   float *Z, int64_t ldz, hipStream_t st);
+
 int subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const float *X, int64_t x_batch,
                  int64_t ldx, float *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, hipStream_t st);
 int subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *X, int64_t x_batch,
@@ -95,6 +99,10 @@ int layer_fused_bf16(const char *who, const void *X, int64_t ldx, const void *wp
                      const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
                      float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out,
                      hipStream_t st, const struct DropSpec *drop = nullptr);
+int block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,
+                     const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
+                     const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
+                     float *x1, float *y1, float *pool_out, float *overlap_partial, hipStream_t st);
 int dropout_mask(int64_t rows, int F, float p, uint64_t seed, int sel, float *out, hipStream_t st);
 
 int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,

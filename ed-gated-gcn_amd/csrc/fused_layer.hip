@@ -422,11 +422,18 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
         }
     }
     vst = vst && any_out;
-    if (a.Xb) {   // bf16 features: one layer on the bf16x3 image (bf16 pair form, two MFMAs per product); the entry points fix the range of T
+    if (a.Xb) {   // bf16 features on the bf16x3 image (bf16 pair form, two MFMAs per product); the entry points fix the range of T
         if (precision != GGCN_PREC_BF16X3)
             return fail(GGCN_EUNSUPPORTED, "%s: bf16 features take the bf16x3 weight image (precision %d)", who, precision);
-        if (a.n_parts != 1 || a.stamps || a.part[0].mid || a.part[0].pre)
-            return fail(GGCN_EUNSUPPORTED, "%s: one plain layer (no block, folded bias or stamps)", who);
+        // one layer, or the two-layer block of graphs of <= 32 nodes (ggcn_block_fused_bf16: W1 + W12 tiles, or the W12 tiles alone)
+        bool folded = a.n_parts != 1;
+        for (int p = 0; p < a.n_parts; ++p) folded = folded || a.part[p].mid;
+        if (a.stamps || a.part[0].pre || a.part[a.n_parts - 1].pre)
+            return fail(GGCN_EUNSUPPORTED, "%s: bf16 features take no bias_pre and no stamps", who);
+        if (folded && (a.T > 32 || !a.graph_ops2 || !aligned16(a.graph_ops2)))
+            return fail(GGCN_EUNSUPPORTED, "%s: the two-layer form takes graphs of <= 32 nodes and their ggcn_graph_operands2 blocks (T=%d)", who, a.T);
+        if (folded && a.drop.thr != 0)
+            return fail(GGCN_EUNSUPPORTED, "%s: gate dropout is built into the one-launch LAYER, not the two-layer block", who);
         if ((int64_t)a.B * a.T * a.F >= ((int64_t)1 << 32) && a.drop.thr != 0)
             return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)a.B * a.T * a.F);
         const bool avecb = (a.K % 8 == 0) && (a.ldx % 8 == 0) && aligned16(a.Xb);
@@ -446,16 +453,20 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
             return launch_fused_wide(who, a, precision, sb, avecb && kfullb, vstw, gridw, st);
         }
         const int64_t g_tiles = ((int64_t)a.B + 4 * WM - 1) / (4 * WM);
-        const int64_t grid = grid_for(g_tiles, a.n_wg);
+        // the block: W1 tiles on four XCDs, W12 tiles on the other four (layer_fused_kernel), as for float32 features below
+        const int64_t grid = a.n_parts == 1 ? grid_for(g_tiles, a.n_wg) : (g_tiles + 3) / 4 * a.n_wg * 8;
         if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
         a.g_tiles = (int)g_tiles;
         const bool fullt = (a.T == 32) && (a.B % (4 * WM) == 0);
+        // the block's eval form without `x` stores no rows: the vector-store instantiations (the fast shape's only ones) serve it
+        // with the same arithmetic.  A plain layer keeps the instantiation it always had.
+        const bool vstb = vst || (folded && !any_out);
 #define GGCN_LAUNCH_B(AV, KF, FT, VS) \
     hipLaunchKernelGGL((layer_fused_kernel<0, AV, KF, FT, VS, false, __bf16>), dim3((unsigned)grid), dim3(kThreads), 0, st, a)
-        if (avecb && kfullb && fullt && vst) GGCN_LAUNCH_B(true, true, true, true);
-        else if (avecb && kfullb && vst) GGCN_LAUNCH_B(true, true, false, true);
+        if (avecb && kfullb && fullt && vstb) GGCN_LAUNCH_B(true, true, true, true);
+        else if (avecb && kfullb && vstb) GGCN_LAUNCH_B(true, true, false, true);
         else if (avecb && kfullb) GGCN_LAUNCH_B(true, true, false, false);
-        else if (avecb && vst) GGCN_LAUNCH_B(true, false, false, true);
+        else if (avecb && vstb) GGCN_LAUNCH_B(true, false, false, true);
         else if (avecb) GGCN_LAUNCH_B(true, false, false, false);
         else GGCN_LAUNCH_B(false, false, false, false);
 #undef GGCN_LAUNCH_B
@@ -707,6 +718,48 @@ int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpa
         a.part[0] = second;   // every XCD runs W12 tiles (tile_of_block: the column tiles of a row block share an XCD)
     }
     return launch_fused("ggcn_block_fused", a, precision, st);
+}
+
+// ggcn_block_fused on bf16 features: the bf16 pair main loop on the bf16x3 images of W1 and W12, bf16 planes of (D.A)^2
+// (ggcn_graph_operands2 plane 0).  Every refusal comes before the launch and names its argument.
+int block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
+                     const void *graph_ops2, const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
+                     const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
+                     float *x1, float *y1, float *pool_out, float *overlap_partial, hipStream_t st)
+{
+    const char *who = "ggcn_block_fused_bf16";
+    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
+    if (T > 32)
+        return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (one ggcn_layer_fused_bf16_wide per layer up to %d nodes)", who, T, GGCN_MASK_MAX_T);
+    if (!gate2) return fail(GGCN_EINVAL, "%s: gate2 is required", who);
+    const bool layer1 = x1 || y1 || gcn1 || overlap_partial;   // none of them: the eval form (only the W12 tiles are launched)
+    if (layer1 && (!x1 || !y1 || !gate1))
+        return fail(GGCN_EINVAL, "%s: layer 1's outputs go together (gate1, x1 and y1; all NULL with gcn1 and overlap_partial = the eval form)", who);
+    if (!x_out && !pool_out) return fail(GGCN_EINVAL, "%s: neither x nor its pool requested", who);
+    if ((gcn1 && ld1 > (int64_t)INT32_MAX) || (x_out && ld2 > (int64_t)INT32_MAX))
+        return fail(GGCN_EUNSUPPORTED, "%s: leading dimension too large", who);
+    if (!wpack12 || (layer1 && !wpack1)) return fail(GGCN_EINVAL, "%s: null weight image", who);
+    if (!graph_ops2) return fail(GGCN_EINVAL, "%s: graph_ops2 (the ggcn_graph_operands2 blocks of plane 0) is required", who);
+    if (!aligned16(graph_ops2)) return fail(GGCN_EINVAL, "%s: graph_ops2 must be 16-byte aligned", who);
+    if (layer1 && !graph_ops) return fail(GGCN_EINVAL, "%s: layer 1 needs the per-graph operand blocks of ggcn_graph_operands", who);
+    if (!bias_mid) return fail(GGCN_EINVAL, "%s: bias_mid (W2^T.b1, zeros when gc1 has no bias) is required", who);
+    FusedArgs a = {};
+    // (the fallback read address of absent gates and biases: layer_fused_bf16)
+    a.X = static_cast<const float *>(wpack12);
+    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx;
+    a.graph_ops = static_cast<const char *>(graph_ops); a.graph_ops2 = static_cast<const char *>(graph_ops2);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = layer1 ? 2 : 1;
+    const LayerPart second = LayerPart{static_cast<const char *>(wpack12), bias2, bias_mid, nullptr, gate2, gate2, nullptr,
+                                       x_out, pool_out, nullptr, nullptr, (int)ld2};
+    if (layer1) {
+        a.part[0] = LayerPart{static_cast<const char *>(wpack1), bias1, nullptr, nullptr, nullptr, gate1, gate2,
+                              gcn1, x1, y1, overlap_partial, (int)ld1};
+        a.part[1] = second;
+    } else {
+        if (!a.graph_ops) a.graph_ops = a.graph_ops2;   // (the W12 tiles read graph_ops2 only; launch_fused insists on a block pointer)
+        a.part[0] = second;
+    }
+    return launch_fused(who, a, GGCN_PREC_BF16X3, st);
 }
 
 int overlap_reduce(const float *partials, int B, int F, float *xy, hipStream_t st)

@@ -19,6 +19,7 @@ import torch
 
 from . import _capi, range_guard
 from .csr import BatchedCSR, tensor_version
+from .gcn import BF16_PRECISIONS
 
 
 def gate_overlap(x1, y1):
@@ -82,9 +83,14 @@ def takes_folded_eval_path(x, csr, gc1, gc2):
 
 
 def _folded_eval(x, csr, gate2, gc1, gc2, want_x):
-    """``(x or None, out)`` of ``bert_amir5.py:639-640`` through the folded weight, two launches, no product with W1."""
+    """``(x or None, out)`` of ``bert_amir5.py:639-640`` through the folded weight, two launches, no product with W1.
+    bfloat16 features (``takes_bf16_folded_eval_path``): ``Z`` comes from ``ggcn_aggregate_bf16`` (float32, the sums of
+    ``ggcn_aggregate`` on ``x.float()`` bit for bit) and the folded launch always runs ``bf16x3``, whatever split precision
+    the layers name -- bf16 features carry no fp16 range contract and acquire none here."""
     gc1._check(x)
-    range_guard.before(x.device)
+    bf16 = x.dtype == torch.bfloat16
+    if not bf16:
+        range_guard.before(x.device)
     lib = _capi.load_library()
     B, T, K = x.shape
     F = gc2.out_features
@@ -97,12 +103,16 @@ def _folded_eval(x, csr, gate2, gc1, gc2, want_x):
         raise RuntimeError("gate2 must be a contiguous float32 [B,F]=[%d,%d] GPU tensor" % (B, F))
     with torch.cuda.device(dev):
         st = _capi.stream_of(dev)
-        prec = gc1.precision
+        prec = "bf16x3" if bf16 else gc1.precision
         _, pack12, mid = _block_operands(gc1, gc2, lib, st, precision=prec)
         z = torch.empty(B * T, K, dtype=torch.float32, device=dev)
         # Z = D.A.X: gcn.py:35,41 applied to the features themselves (no bias, no gate, no pool)
-        _capi.check(lib.ggcn_aggregate(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(csr.rowptr), _capi.ptr(csr.colidx), _capi.ptr(csr.vals),
-                                       None, B, T, K, None, None, None, _capi.ptr(z), K, None, None, st), "ggcn_aggregate(D.A.X)")
+        if bf16:
+            _capi.check(lib.ggcn_aggregate_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(csr.rowptr), _capi.ptr(csr.colidx),
+                                                _capi.ptr(csr.vals), B, T, K, _capi.ptr(z), K, st), "ggcn_aggregate_bf16(D.A.X)")
+        else:
+            _capi.check(lib.ggcn_aggregate(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(csr.rowptr), _capi.ptr(csr.colidx), _capi.ptr(csr.vals),
+                                           None, B, T, K, None, None, None, _capi.ptr(z), K, None, None, st), "ggcn_aggregate(D.A.X)")
         xo = torch.empty(B * T, F, dtype=torch.float32, device=dev) if want_x else None
         out = torch.empty(B, F, dtype=torch.float32, device=dev)
         b2 = None if gc2.bias is None else gc2.bias.detach()
@@ -112,6 +122,30 @@ def _folded_eval(x, csr, gate2, gc1, gc2, want_x):
     if prec == "f16mx8":
         range_guard.after(x.device)
     return (None if xo is None else xo.view(B, T, F)), out
+
+
+def _bf16_block_on(x, gc1):
+    """The opt-in of the bf16 block forms (``GraphConvolution.bf16_block``) on bfloat16 GPU features."""
+    return bool(getattr(gc1, "bf16_block", False)) and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.bfloat16
+
+
+def takes_bf16_block_path(x, csr, gc1, gc2):
+    """True when inference on bfloat16 features runs the block as ONE launch (``ggcn_block_fused_bf16``): the option
+    ``gc1.bf16_block`` (``opt.ggcn_bf16_block`` / ``GGCN_BF16_BLOCK=1``; off by default), graphs of <= 32 nodes that gc1 would run
+    as one bf16 layer launch, gc2 on the one-launch path, split precisions on both layers (all of them mean the bf16 pair form on
+    the ``bf16x3`` images) and square widths."""
+    return (_bf16_block_on(x, gc1) and csr.T <= 32 and gc1.takes_bf16_fused_path(x, csr) and bool(gc2.fused)
+            and gc1.precision in BF16_PRECISIONS and gc2.precision in BF16_PRECISIONS
+            and gc1.out_features == gc2.in_features and gc1.out_features == gc2.out_features)
+
+
+def takes_bf16_folded_eval_path(x, csr, gc1, gc2):
+    """``takes_folded_eval_path`` for bfloat16 features (same option as ``takes_bf16_block_path``): graphs of 33..256 nodes with a
+    0/1 adjacency and row masks on the device, gc2 on the float32 one-launch path for its float32 input, square widths.
+    ``Z = D.A.X`` by ``ggcn_aggregate_bf16``, then one ``ggcn_layer_fused_prebias`` launch in ``bf16x3``."""
+    return (_bf16_block_on(x, gc1) and 32 < csr.T <= 256 and bool(csr.is_binary) and csr.rowmask is not None and csr.rowmask.is_cuda
+            and gc1.precision in BF16_PRECISIONS and gc2.takes_fused_path(_layer2_input(x, gc1), csr)
+            and gc1.out_features == gc2.in_features and gc1.in_features == gc1.out_features == gc2.out_features)
 
 
 def takes_block_path(x, csr, gc1, gc2):
@@ -176,6 +210,53 @@ def gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch=
     return _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1, one_launch, want)
 
 
+def _bf16_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, pick, defer_xy):
+    """``bert_amir5.py:626-640`` on bfloat16 features of graphs of <= 32 nodes as ONE launch (``ggcn_block_fused_bf16``; + the
+    1-block launch that finishes ``:638`` unless the caller's dense head does).  The float32 block's outputs and options, all
+    float32; no range report -- bf16 features run no fp16 arithmetic."""
+    gc1._check(x)
+    w_l1 = any(k in want for k in ("x1", "y1", "xy"))
+    lib = _capi.load_library()
+    B, T, K = x.shape
+    F = gc2.out_features
+    dev = x.device
+    x2d = x.reshape(B * T, K)
+    if x2d.stride(1) != 1:
+        x2d = x2d.contiguous()
+    layer1 = w_l1 or want_gcn1   # False: the eval form -- only the W12 column tiles are launched
+    for name, g in (("gate1", gate1), ("gate2", gate2)):
+        if g is None and name == "gate1" and not layer1:
+            continue   # the eval form never reads gate1
+        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float32
+                and tuple(g.shape) == (B, F) and g.is_contiguous()):
+            raise RuntimeError("%s must be a contiguous float32 [B,F]=[%d,%d] GPU tensor" % (name, B, F))
+    with torch.cuda.device(dev):
+        st = _capi.stream_of(dev)
+        pack1, pack12, mid = _block_operands(gc1, gc2, lib, st, precision="bf16x3")
+        gcn1 = torch.empty(B * T, F, dtype=torch.float32, device=dev) if want_gcn1 else None
+        xo = torch.empty(B * T, F, dtype=torch.float32, device=dev) if "x" in want else None
+        x1 = torch.empty(B, F, dtype=torch.float32, device=dev) if layer1 else None
+        y1 = torch.empty(B, F, dtype=torch.float32, device=dev) if layer1 else None
+        out = torch.empty(B, F, dtype=torch.float32, device=dev)
+        part = torch.empty(B, (F + 63) // 64, dtype=torch.float32, device=dev) if "xy" in want else None
+        xy = torch.empty((), dtype=torch.float32, device=dev) if "xy" in want else None
+        b1 = None if gc1.bias is None else gc1.bias.detach()
+        b2 = None if gc2.bias is None else gc2.bias.detach()
+        _capi.check(lib.ggcn_block_fused_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack1 if layer1 else None), _capi.ptr(pack12),
+                                              _capi.ptr(csr.graph_ops), _capi.ptr(csr.graph_ops2(0)),
+                                              _capi.ptr(b1), _capi.ptr(mid), _capi.ptr(b2),
+                                              B, T, K, F, _capi.ptr(gate1 if layer1 else None), _capi.ptr(gate2), _capi.ptr(gcn1), F,
+                                              _capi.ptr(xo), F, _capi.ptr(x1), _capi.ptr(y1), _capi.ptr(out),
+                                              _capi.ptr(part), st), "ggcn_block_fused_bf16")
+        if part is not None and not defer_xy:
+            _capi.check(lib.ggcn_overlap_reduce(_capi.ptr(part), B, F, _capi.ptr(xy), st), "ggcn_overlap_reduce")
+    r = pick({"gcn1": None if gcn1 is None else gcn1.view(B, T, F), "x1": x1, "y1": y1, "xy": xy,
+              "x": None if xo is None else xo.view(B, T, F), "out": out})
+    if defer_xy and part is not None:
+        r["_xy_partials"] = part
+    return r
+
+
 def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch=True, want=None, _defer_xy=False):
     """gated_gcn_block proper.  _defer_xy: on the one-launch path leave the regulariser's partial sums under "_xy_partials"
     instead of launching ggcn_overlap_reduce (the caller's dense head finishes them)."""
@@ -189,9 +270,10 @@ def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch
         gc1._check(x)
         B, T, F = 0, x.shape[1], gc2.out_features
         z2 = x.new_zeros((0, F), dtype=torch.float32)
-        return {"gcn1": x.new_zeros((0, T, gc1.out_features)), "x1": x.new_zeros((0, gc1.out_features)),
-                "y1": x.new_zeros((0, gc1.out_features)), "xy": x.new_full((), float("nan")),
-                "x": x.new_zeros((0, T, F)), "out": z2}
+        dt = torch.float32 if _bf16_block_on(x, gc1) else x.dtype   # (the bf16 block's outputs are all float32)
+        return {"gcn1": x.new_zeros((0, T, gc1.out_features), dtype=dt), "x1": x.new_zeros((0, gc1.out_features), dtype=dt),
+                "y1": x.new_zeros((0, gc1.out_features), dtype=dt), "xy": x.new_full((), float("nan"), dtype=dt),
+                "x": x.new_zeros((0, T, F), dtype=dt), "out": z2}
     csr = adj if isinstance(adj, BatchedCSR) else gc1._as_csr(adj, x)
     training = torch.is_grad_enabled() and (gc1._needs_grad(x, gate1, gate2) or gc2._needs_grad(x, gate2))
     if training and set(want) != set(BLOCK_OUTPUTS):
@@ -248,6 +330,11 @@ def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch
         if _defer_xy and part is not None:
             r["_xy_partials"] = part
         return r
+    if not training and one_launch and takes_bf16_block_path(x, csr, gc1, gc2):
+        return _bf16_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, pick, _defer_xy)
+    if not training and one_launch and not w_l1 and not want_gcn1 and takes_bf16_folded_eval_path(x, csr, gc1, gc2):
+        x2, out = _folded_eval(x, csr, gate2, gc1, gc2, w_x)   # bf16 features of 33..256-node graphs: no product with W1
+        return pick({"gcn1": None, "x1": None, "y1": None, "xy": None, "x": x2, "out": out})
     if (not training and _layer1_takes_fused(x, csr, gc1) and gc2.takes_fused_path(_layer2_input(x, gc1), csr)
             and gc1.out_features == gc2.out_features):
         # two launches in all: layer 1 leaves its share of sum_f x1*y1 per (graph, 64 columns), layer 2's

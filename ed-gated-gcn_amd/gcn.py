@@ -222,6 +222,10 @@ class GraphConvolution(nn.Module):
         # form on their own (takes_fused_path); set 256 to send graphs of 129..192 nodes there as well.
         self.fused = bool(getattr(opt, "ggcn_fused", True)) and os.environ.get("GGCN_FUSED", "1") != "0"
         self.fused_max_t = int(getattr(opt, "ggcn_fused_max_t", None) or os.environ.get("GGCN_FUSED_MAX_T", "128"))
+        # bfloat16 features, inference: the whole gated block as one launch for graphs of <= 32 nodes (ggcn_block_fused_bf16) and
+        # the folded evaluation of 33..256-node graphs (gated_block.takes_bf16_block_path / takes_bf16_folded_eval_path).  Off by
+        # default: the fold sums in another order than the two layer launches (both inside the parity gate).
+        self.bf16_block = bool(getattr(opt, "ggcn_bf16_block", False)) or os.environ.get("GGCN_BF16_BLOCK", "0") == "1"
         # dense adjacency handed to forward(): None = let the device detect edge weights (one 4-byte
         # read-back per conversion), True = promise 0/1 entries like the reference's (graph.py:66-74)
         # and stay sync-free, False = always keep the values

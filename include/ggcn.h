@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 /* Bumped when a prototype, struct or enum CHANGES.  Added functions alone do not bump it: a binding that declares a function
- * an older library lacks fails at load time on the missing symbol (14 also covers ggcn_layer_fused_bf16_drop / _wide). */
+ * an older library lacks fails at load time on the missing symbol (14 also covers ggcn_layer_fused_bf16_drop / _wide, ggcn_block_fused_bf16 and ggcn_aggregate_bf16). */
 #define GGCN_ABI_VERSION 14
 #define GGCN_MASK_MAX_T 256   /* largest graph the row-mask (one-launch) path takes */
 
@@ -559,6 +559,16 @@ int ggcn_subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t s
  *                         reduction as ggcn_layer_fused; p = 0: no dropout, else as ggcn_layer_fused_bf16_drop
  *                         A T outside an entry's range returns GGCN_EUNSUPPORTED and names the entry to use; dropout needs
  *                         B*T*F < 2^32; overlap_in and overlap_out go together.
+ *   ggcn_block_fused_bf16 ggcn_block_fused on bf16 X (graphs of <= 32 nodes): its argument list without `precision` -- always
+ *                         the GGCN_PREC_BF16X3 images of W1 and W12 and the plane-0 blocks of ggcn_graph_operands2.  Same
+ *                         contract: layer 1's outputs (gate1, x1, y1; gcn1 and overlap_partial optional) all together or none
+ *                         (none = the eval form: only the W12 tiles are launched, graph_ops may be NULL), bias_mid required
+ *                         (zeros when gc1 has no bias), all outputs float32.  T > 32: GGCN_EUNSUPPORTED (one
+ *                         ggcn_layer_fused_bf16_wide per layer)
+ *   ggcn_aggregate_bf16   Z [B*T,K] float32 (row stride ldz) = D.A.X for bf16 X (row stride ldx): ggcn_aggregate's sums over a
+ *                         node's neighbours in CSR order, fp32 accumulation, divided by rowsum + 1; no bias, gates or pools.
+ *                         Z equals ggcn_aggregate on the float32 copy of X bit for bit.  vals = NULL: 0/1 adjacency.  The
+ *                         input of ggcn_layer_fused_prebias for the folded evaluation of graphs of 33..256 nodes
  *   ggcn_dweight_bf16     dW [K,F] float32 = X^T . dH with bf16 X, float32 dH: X is transposed in bf16 and dH packed,
  *                         then the split-K form of ggcn_dweight(GGCN_PREC_BF16X3); deterministic; workspace of
  *                         ggcn_dweight_bf16_workspace_bytes(n_rows, K, F) bytes, 16-byte aligned
@@ -585,6 +595,16 @@ int ggcn_layer_fused_bf16_wide(const void *X, int64_t ldx, const void *wpack, co
                                float *out, int64_t ldo, float *pool_a, float *pool_b,
                                float *overlap_partial, const float *overlap_in, float *overlap_out,
                                float p, uint64_t seed, int stream_store, int stream_a, int stream_b, ggcn_stream_t stream);
+int ggcn_block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const void *wpack12,
+                          const void *graph_ops, const void *graph_ops2,
+                          const float *bias1, const float *bias_mid, const float *bias2,
+                          int B, int T, int K, int F, const float *gate1, const float *gate2,
+                          float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
+                          float *x1, float *y1, float *pool_out, float *overlap_partial,
+                          ggcn_stream_t stream);
+int ggcn_aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx,
+                        const float *vals, int B, int T, int K, float *Z, int64_t ldz,
+                        ggcn_stream_t stream);
 size_t ggcn_dweight_bf16_workspace_bytes(int64_t n_rows, int K, int F);
 int ggcn_dweight_bf16(const void *X, int64_t ldx, const float *dH, int64_t ldg, int64_t n_rows, int K, int F,
                       float *dW, int64_t lddw, void *workspace, ggcn_stream_t stream);
