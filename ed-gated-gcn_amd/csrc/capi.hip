@@ -163,6 +163,12 @@ int ggcn_inv_denominators(const int32_t *rowptr, const float *vals, int64_t n_ro
     return inv_denominators(rowptr, vals, n_rows, inv, as_stream(stream));
 }
 
+int ggcn_adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64_t ldh, const float *inv, const int32_t *rowptr,
+                        const int32_t *colidx, const float *vals, int B, int T, int F, float *d_adj, ggcn_stream_t stream)
+{
+    return adjacency_grad(dY, ldy, hidden, ldh, inv, rowptr, colidx, vals, B, T, F, d_adj, as_stream(stream));
+}
+
 int ggcn_linear(const float *X, int64_t ldx, const float *W, int64_t ldw, const void *wpack, float *Y,
                 int64_t ldy, int64_t M, int K, int F, int precision, ggcn_stream_t stream)
 {

@@ -57,6 +57,8 @@ int aggregate_t(const float *G, int64_t ldg, const int32_t *rowptr_t, const int3
                 const float *vals_t, const float *src_scale, int B, int T, int F, float *out, int64_t ldo,
                 hipStream_t st);
 int inv_denominators(const int32_t *rowptr, const float *vals, int64_t n, float *inv, hipStream_t st);
+int adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64_t ldh, const float *inv, const int32_t *rowptr,
+                   const int32_t *colidx, const float *vals, int B, int T, int F, float *d_adj, hipStream_t st);   // adjacency_grad.hip
 int aggregate_h(const void *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx, const float *vals,
                 const float *bias, int B, int T, int F, const float *store_gate, const float *pool_gate_a,
                 const float *pool_gate_b, void *out, int64_t ldo, float *pool_a, float *pool_b, hipStream_t st);

@@ -192,7 +192,7 @@ def gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch=
     launch that finishes ``xy`` (``ggcn_dense_head``), so the block + head are two launches in all."""
     if dense_head is not None:
         from .heads import dense_head as _dense_head
-        if torch.is_grad_enabled() and (gc1._needs_grad(x, gate1, gate2) or gc2._needs_grad(x, gate2)):
+        if torch.is_grad_enabled() and (gc1._needs_grad(x, gate1, gate2, adj=adj) or gc2._needs_grad(x, gate2, adj=adj)):
             raise RuntimeError("dense_head= is an inference feature; under autograd apply the classifier's own dense layer")
         r = _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1, one_launch, want, _defer_xy=True)
         part = r.pop("_xy_partials", None)
@@ -275,7 +275,7 @@ def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch
                 "y1": x.new_zeros((0, gc1.out_features), dtype=dt), "xy": x.new_full((), float("nan"), dtype=dt),
                 "x": x.new_zeros((0, T, F), dtype=dt), "out": z2}
     csr = adj if isinstance(adj, BatchedCSR) else gc1._as_csr(adj, x)
-    training = torch.is_grad_enabled() and (gc1._needs_grad(x, gate1, gate2) or gc2._needs_grad(x, gate2))
+    training = torch.is_grad_enabled() and (gc1._needs_grad(x, gate1, gate2, adj=adj) or gc2._needs_grad(x, gate2, adj=adj))
     if training and set(want) != set(BLOCK_OUTPUTS):
         raise RuntimeError("want= selects outputs of the inference block; under autograd every output is produced")
 
@@ -358,12 +358,15 @@ def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch
         gcn1, _, _ = gc1.forward_gated(x, csr)
         x2, out, _ = gc2.forward_gated(gcn1, csr, store_gate=gate2, pool_gate_a=gate2, want_out=w_x, want_pool_a=True)
         return pick({"gcn1": gcn1 if want_gcn1 else None, "x1": None, "y1": None, "xy": None, "x": x2, "out": out})
-    gcn1, x1, y1 = gc1.forward_gated(x, csr, store_gate=None, pool_gate_a=gate1, pool_gate_b=gate2,
+    # a dense adj that wants its gradient goes to the layers as the tensor (autograd adds their two contributions); its
+    # conversion is the cached one
+    graph = adj if gc1._differentiable_adj(adj) is not None else csr
+    gcn1, x1, y1 = gc1.forward_gated(x, graph, store_gate=None, pool_gate_a=gate1, pool_gate_b=gate2,
                                      want_pool_a=True, want_pool_b=True)           # :626-636
     if torch.is_grad_enabled() and (x1.requires_grad or y1.requires_grad):
         xy = (x1 * y1).sum(1).mean()   # differentiable form of :638 (the regulariser is trained on)
     else:
         xy = gate_overlap(x1, y1) if "xy" in want else None                        # :638
-    x2, out, _ = gc2.forward_gated(gcn1, csr, store_gate=gate2, pool_gate_a=gate2,
+    x2, out, _ = gc2.forward_gated(gcn1, graph, store_gate=gate2, pool_gate_a=gate2,
                                    want_out=training or w_x, want_pool_a=True)   # :639-640
     return pick({"gcn1": gcn1, "x1": x1, "y1": y1, "xy": xy, "x": x2, "out": out})

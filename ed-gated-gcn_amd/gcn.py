@@ -48,10 +48,13 @@ class _GatedLayerFunction(torch.autograd.Function):
         dW = X^T.dH            HIP split-K: bf16x3 main loop on X^T and packed dH (dweight_bx3.hip; bfloat16 features:
                                X^T in bf16, ggcn_dweight_bf16), or the exact-fp32 MFMA form for precision 'fp32' (dweight_fp32.hip)
         db = sum_rows dY       HIP: per-graph sums from the gate/pool pass + ggcn_colsum
+        dA = D.dY.H^T - c      HIP, only for a differentiable dense `adj` (``adj_t``; gcn.py:33-45 is differentiable in it): the
+                               two-call form so that dY exists in memory, `hidden` H recomputed by the layer's linear, then
+                               ggcn_adjacency_grad (bf16x3 MFMA; dense [B,T,T], zero entries and padding rows included)
     """
 
     @staticmethod
-    def forward(ctx, text, weight, bias, store_gate, gate_a, gate_b, layer, csr, want_pa, want_pb, dropout=None):
+    def forward(ctx, text, weight, bias, store_gate, gate_a, gate_b, layer, csr, want_pa, want_pb, dropout=None, adj_t=None):
         with torch.no_grad():
             out, pa, pb = layer.forward_gated(text, csr, store_gate=store_gate, pool_gate_a=gate_a,
                                               pool_gate_b=gate_b, want_out=True, want_pool_a=want_pa,
@@ -59,6 +62,7 @@ class _GatedLayerFunction(torch.autograd.Function):
         ctx.layer, ctx.csr, ctx.dropout = layer, csr, dropout
         ctx.save_for_backward(text, weight, out, store_gate, gate_a, gate_b)
         ctx.has_bias = bias is not None
+        ctx.adj_dtype = None if adj_t is None else adj_t.dtype
         # an output the loss does not use arrives as None, not as a tensor of zeros: the [B,T,F] `out` of a layer whose pools alone
         # are used would otherwise cost a 400 MB fill AND a 400 MB read per step (every backward kernel takes d_out = NULL)
         ctx.set_materialize_grads(False)
@@ -69,7 +73,7 @@ class _GatedLayerFunction(torch.autograd.Function):
         text, weight, out, store_gate, gate_a, gate_b = ctx.saved_tensors
         layer, csr = ctx.layer, ctx.csr
         if d_out is None and d_pa is None and d_pb is None:
-            return (None,) * 11
+            return (None,) * 12
         lib = _capi.load_library()
         B, T, K = text.shape
         F = layer.out_features
@@ -94,7 +98,9 @@ class _GatedLayerFunction(torch.autograd.Function):
             # graphs of up to 32 nodes with a 0/1 adjacency: gate / pool backward AND the transposed aggregation in one launch
             # (dY is consumed by nothing else: it never reaches memory)
             # (its 16-byte accesses need every operand 16-byte aligned: a contiguous view at an odd storage offset takes the two calls)
-            one_pass = (T <= 32 and F % 4 == 0 and csr.is_binary and csr.rowmask is not None and csr.rowmask.is_cuda
+            # (a differentiable adjacency reads dY: the two calls)
+            need_adj = ctx.adj_dtype is not None and need[11]
+            one_pass = (not need_adj and T <= 32 and F % 4 == 0 and csr.is_binary and csr.rowmask is not None and csr.rowmask.is_cuda
                         and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1"
                         and all(t is None or t.data_ptr() % 16 == 0
                                 for t in (out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum)))
@@ -143,6 +149,18 @@ class _GatedLayerFunction(torch.autograd.Function):
                 _capi.check(lib.ggcn_aggregate_t(_capi.ptr(dy), F, _capi.ptr(csr_t.rowptr), _capi.ptr(csr_t.colidx),
                                                  _capi.ptr(csr_t.vals), _capi.ptr(inv), B, T, F, _capi.ptr(dh), F, st),
                             "ggcn_aggregate_t")
+            d_adj = None
+            if need_adj:   # dA = D.dY.H^T - c on `hidden` as the forward computed it (float32 for bfloat16 features too)
+                x2d = text.reshape(B * T, K)
+                if x2d.stride(1) != 1:
+                    x2d = x2d.contiguous()
+                hidden = layer.linear(x2d)
+                d_adj = torch.empty(B, T, T, dtype=torch.float32, device=dev)
+                _capi.check(lib.ggcn_adjacency_grad(_capi.ptr(dy), F, _capi.ptr(hidden), hidden.stride(0), _capi.ptr(csr.inv_denominators()),
+                                                    _capi.ptr(csr.rowptr), _capi.ptr(csr.colidx), _capi.ptr(csr.vals), B, T, F,
+                                                    _capi.ptr(d_adj), st), "ggcn_adjacency_grad")
+                if ctx.adj_dtype != torch.float32:
+                    d_adj = d_adj.to(ctx.adj_dtype)
             dw = db = None
             if need[0] and bf16:   # bfloat16 features: dX in bf16 (the reference's gradient dtype under autocast), rounded in the store
                 dx = torch.empty(B * T, K, dtype=torch.bfloat16, device=dev)
@@ -194,7 +212,7 @@ class _GatedLayerFunction(torch.autograd.Function):
                 db = torch.empty(F, dtype=torch.float32, device=dev)
                 ws = torch.empty(lib.ggcn_colsum_workspace_bytes(F), dtype=torch.uint8, device=dev)
                 _capi.check(lib.ggcn_colsum(_capi.ptr(d_bsum), F, B, F, _capi.ptr(db), _capi.ptr(ws), st), "ggcn_colsum")
-        return dx, dw, db, d_sg, d_ga, d_gb, None, None, None, None, None
+        return dx, dw, db, d_sg, d_ga, d_gb, None, None, None, None, None, d_adj
 
 
 class GraphConvolution(nn.Module):
@@ -376,10 +394,19 @@ class GraphConvolution(nn.Module):
                         "ggcn_linear")
         return y
 
-    def _needs_grad(self, text, *gates):
+    @staticmethod
+    def _differentiable_adj(adj):
+        """``adj`` itself when it is a dense floating-point tensor that wants a gradient under grad mode (a soft or learned graph:
+        ``gcn.py:33-45`` is differentiable in it), else None.  A ``BatchedCSR`` has no tensor to differentiate."""
+        if isinstance(adj, torch.Tensor) and adj.is_floating_point() and adj.requires_grad and torch.is_grad_enabled():
+            return adj
+        return None
+
+    def _needs_grad(self, text, *gates, adj=None):
         return torch.is_grad_enabled() and (text.requires_grad or self.weight.requires_grad
                                             or (self.bias is not None and self.bias.requires_grad)
-                                            or any(g is not None and g.requires_grad for g in gates))
+                                            or any(g is not None and g.requires_grad for g in gates)
+                                            or self._differentiable_adj(adj) is not None)
 
     WIDE_AUTO_MIN_T = 193     # graphs of 193..256 nodes fill >= 75 % of the 256-row slot of the eight-wavefront kernel
     WIDE_AUTO_MIN_T_FULL = {"f16mx8": 129, "bf16x3": 161}   # shorter graphs: only batches that fill whole rounds of workgroups (one per CU)
@@ -537,7 +564,7 @@ class GraphConvolution(nn.Module):
             return ((z if want_out else None), (text.new_zeros((0, F), dtype=torch.float32) if want_pool_a else None),
                     (text.new_zeros((0, F), dtype=torch.float32) if want_pool_b else None))
         csr = self._as_csr(adj, text)
-        if not _internal and self._needs_grad(text, store_gate, pool_gate_a, pool_gate_b):
+        if not _internal and self._needs_grad(text, store_gate, pool_gate_a, pool_gate_b, adj=adj):
             # training: the same kernels, wrapped in an autograd Function with a HIP backward
             if text.dtype not in (torch.float32, torch.bfloat16):
                 raise RuntimeError("training through the HIP layer needs float32 features (or bfloat16 ones)")
@@ -551,8 +578,12 @@ class GraphConvolution(nn.Module):
                     raise RuntimeError("dropout streams %r: under autograd a pool must share the store gate's keep stream (or the "
                                        "store gate stay undropped, stream 0) -- the backward reads y back from the stored output, "
                                        "which a dropped store gate zeroes" % ((ss, sa, sb),))
+            adj_t = self._differentiable_adj(adj)   # a dense `adj` that wants its gradient: one more input, so autograd links it
+            if adj_t is not None and csr.T > self.LONG_MAX_T:
+                raise RuntimeError("adj.requires_grad with graphs of %d nodes: the adjacency gradient (ggcn_adjacency_grad) takes "
+                                   "graphs of up to %d nodes; detach adj or shorten the graphs" % (csr.T, self.LONG_MAX_T))
             out, pa, pb = _GatedLayerFunction.apply(text, self.weight, self.bias, store_gate, pool_gate_a,
-                                                    pool_gate_b, self, csr, want_pool_a, want_pool_b, dropout)
+                                                    pool_gate_b, self, csr, want_pool_a, want_pool_b, dropout, adj_t)
             return (out if want_out else None), pa, pb
         lib = _capi.load_library()
         B, T, _ = text.shape
@@ -660,6 +691,8 @@ class GraphConvolution(nn.Module):
         return (None if out is None else out.view(B, T, F)), pa, pb
 
     def forward(self, text, adj):
-        """``models/gcn.py:30-45``; ``adj`` is the reference's dense [B,T,T] (or a BatchedCSR)."""
+        """``models/gcn.py:30-45``; ``adj`` is the reference's dense [B,T,T] (or a BatchedCSR).  A dense floating-point ``adj``
+        with ``requires_grad`` receives its gradient, dense like the reference's (graphs of up to ``LONG_MAX_T`` nodes; longer
+        ones raise); a ``BatchedCSR`` has no tensor to differentiate."""
         out, _, _ = self.forward_gated(text, adj)
         return out

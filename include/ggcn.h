@@ -268,6 +268,21 @@ int ggcn_aggregate_t(const float *G, int64_t ldg,
                      const int32_t *rowptr_t, const int32_t *colidx_t, const float *vals_t,
                      const float *src_scale, int B, int T, int F,
                      float *out, int64_t ldo, ggcn_stream_t stream);
+/* Gradient with respect to a REAL-VALUED adjacency (models/gcn.py:33-45 is differentiable in `adj`: a soft or learned graph).
+ * Per graph, with H = X.W the layer's `hidden`, inv_i = 1/(sum_k A_ik + 1) (ggcn_inv_denominators) and dY the gradient at the
+ * plain layer output y = D.A.H + b (what ggcn_gate_pool_backward[_drop] writes):
+ *   G_ij  = inv_i * (dY_i . H_j)          reduction over F
+ *   c_i   = inv_i * sum_k A_ik * G_ik     over the row's non-zeros (rowptr / colidx with global node ids / vals, NULL = 0/1)
+ *   dA_ij = G_ij - c_i                    for EVERY (i, j): the gradient is dense, zero entries and padding rows included
+ * d_adj is [B,T,T] contiguous.  One launch: float32 operands split into bf16 hi / lo in the kernel, three bf16 MFMAs per product
+ * with fp32 accumulation (the fp32 exponent range: gradients have no range contract), no atomics, a fixed summation order --
+ * results are bit-identical from run to run.  Any T in 1..GGCN_LONG_MAX_T (beyond: GGCN_EUNSUPPORTED), any F >= 1, ldy, ldh >= F;
+ * rows that are not 16-byte aligned take element loads.  NULL pointers (vals excepted), ldy or ldh < F, pointers off 4 bytes and
+ * negative sizes return GGCN_EINVAL with a message that names the argument, before any launch; B = 0 succeeds without one. */
+int ggcn_adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64_t ldh,
+                        const float *inv,
+                        const int32_t *rowptr, const int32_t *colidx, const float *vals,
+                        int B, int T, int F, float *d_adj, ggcn_stream_t stream);
 
 /* ---- fp16 features (BASELINE configs[3]: 512-token graphs, hidden 1024) ------------------
  * Same operations with X / hidden / out stored as IEEE half and fp32 accumulation; weights
