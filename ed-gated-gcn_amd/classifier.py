@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from .csr import tensor_version
-from .gated_block import _layer2_input, gated_gcn_block, takes_block_path
+from . import dispatch
+from .gated_block import gated_gcn_block, takes_block_path
 from .gcn import GraphConvolution
 from .heads import gate_mlps, scores_and_kl
 from .pooling import subword_pool
@@ -135,7 +136,7 @@ class GatedGCNEventDetector(nn.Module):
         """Both layers draw the gates' dropout inside their own launches: gc1 on x (float32, or bfloat16 under autocast), gc2 on
         its real input, the float32 gcn1."""
         return ((self.gc1.takes_dropout_path(x, csr) or self.gc1.takes_bf16_dropout_path(x, csr))
-                and self.gc2.takes_dropout_path(_layer2_input(x, self.gc1), csr))
+                and dispatch.takes_dropout(self.gc2, csr, dispatch.Input.of(x, torch.float32)))
 
     def forward(self, inputs):
         B = inputs["sentence_length"].shape[0]                              # :579-589

@@ -1,0 +1,221 @@
+"""Which launch a layer call, its backward and a block call take: every rule in one place, decided once per call.
+
+Host logic only -- nothing here loads libggcn_hip.so or launches.  ``layer_path``, ``backward_plan`` and ``block_path`` return
+names out of fixed tuples; ``_forward_gated``, ``_GatedLayerFunction.backward`` and ``_gated_gcn_block`` call them once and switch
+on the answer.  The public ``takes_*`` predicates are one-line statements over the functions below (their docstrings keep the
+measurements behind the thresholds); ``tests/golden/dispatch_table.json`` pins every answer.  DESIGN.md "Dispatch"."""
+import collections
+import os
+
+import torch
+
+from . import _capi
+
+# precisions that mean "the bf16 pair form" for bfloat16 features: x is exact in bf16, so every product is hi.Whi + hi.Wlo,
+# two bf16 MFMAs on the bf16x3 image of W (include/ggcn.h ggcn_linear_bf16)
+BF16_PRECISIONS = ("bf16x3", "f16mx8", "f16mx6")
+
+LAYER_PATHS = ("fused", "fused_drop", "bf16", "bf16_drop", "bf16_wide", "bf16_wide_drop", "weighted", "long", "two_launch")
+DROPOUT_PATHS = ("fused_drop", "bf16_drop", "bf16_wide_drop")           # the gates' dropout is drawn inside these launches
+OVERLAP_PATHS = LAYER_PATHS[:6]                                         # launches that take overlap_partial / overlap_reduce
+BACKWARD_PASSES = ("mma", "one_pass", "two_pass", "two_pass_drop")
+DX_FORMS = ("bf16", "scaled", "bf16x3", "fp32")                         # the dW forms are these without "scaled"
+BLOCK_PATHS = ("block", "bf16_block", "folded_eval", "bf16_folded_eval", "two_fused", "layers_eval", "layers")
+
+
+class Input(collections.namedtuple("Input", "dtype B T gpu")):
+    """What the rules read of a layer's features: dtype, batch size, graph length and the GPU they are on (None: not on one).
+    gc2 of a block is judged by ``of(x, torch.float32)``: it reads gcn1, float32 whatever x is, with x's B, T and device."""
+    @classmethod
+    def of(cls, text, dtype=None):
+        return cls(dtype or text.dtype, text.shape[0], text.shape[1], text.device if text.is_cuda else None)
+
+
+def edge_lists(csr):
+    """The graphs' edge lists for the row-mask kernels of > 32 (float32) / > 128 (bfloat16) nodes; GGCN_EDGE_LISTS=0: the masks alone."""
+    return csr.edge_lists if os.environ.get("GGCN_EDGE_LISTS", "1") != "0" else None
+
+
+# ---- one layer --------------------------------------------------------------------------------------------------------------
+def _one_launch_base(layer, csr, precisions):
+    """What every row-mask launch needs: the ``fused`` option, a split precision, a 0/1 adjacency and its row masks."""
+    return bool(layer.fused and layer.precision in precisions and csr.rowmask is not None and csr.is_binary)
+
+
+def _fills_whole_rounds(layer, B, device):
+    """One workgroup per graph x 256 columns: at least two rounds of the GPU's CUs, the last one ``WIDE_AUTO_FILL`` full."""
+    if device is None:
+        return False
+    wgs = B * ((layer.out_features + 255) // 256)
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    rounds = -(-wgs // cus)
+    return rounds >= 2 and wgs >= layer.WIDE_AUTO_FILL * rounds * cus
+
+
+def _index_fits(layer, inp):
+    return inp.B * inp.T * layer.out_features < 2 ** 32   # the dropout hash takes a 32-bit element index
+
+
+def takes_fused(layer, csr, inp):
+    if not (_one_launch_base(layer, csr, _capi.PACKED) and inp.dtype == torch.float32):
+        return False
+    if csr.T <= layer.fused_max_t:
+        return True
+    if layer.fused_max_t < 128 or csr.T > 256:
+        return False
+    if csr.T >= layer.WIDE_AUTO_MIN_T:
+        return True
+    return csr.T >= layer.WIDE_AUTO_MIN_T_FULL.get(layer.precision, 161) and _fills_whole_rounds(layer, inp.B, inp.gpu)
+
+
+def _bf16_base(layer, csr, inp):
+    return _one_launch_base(layer, csr, BF16_PRECISIONS) and inp.dtype == torch.bfloat16 and bool(csr.rowmask.is_cuda)
+
+
+def takes_bf16_fused(layer, csr, inp):
+    return _bf16_base(layer, csr, inp) and csr.T <= 32 and csr.T <= layer.fused_max_t
+
+
+def takes_bf16_wide(layer, csr, inp):
+    if not (_bf16_base(layer, csr, inp) and 32 < csr.T <= 256):
+        return False
+    if layer.fused_max_t >= 256:
+        return True
+    if csr.T <= 128:
+        slot = 64 if csr.T <= 64 else 128
+        return csr.T <= layer.fused_max_t and csr.T >= layer.BF16_WIDE_MIN_FILL * slot
+    return layer.fused_max_t >= 128 and _fills_whole_rounds(layer, inp.B, inp.gpu)
+
+
+def takes_dropout(layer, csr, inp):
+    return takes_fused(layer, csr, inp) and _index_fits(layer, inp)
+
+
+def takes_bf16_dropout(layer, csr, inp):
+    return (takes_bf16_fused(layer, csr, inp) or takes_bf16_wide(layer, csr, inp)) and _index_fits(layer, inp)
+
+
+def takes_weighted(layer, csr, inp):
+    return bool(layer.fused and layer.precision in _capi.PACKED and not csr.is_binary and csr.T <= 32 and layer.fused_max_t >= 32
+                and inp.dtype == torch.float32 and inp.gpu is not None
+                and csr.graph_ops_weighted(0 if layer.precision == "bf16x3" else 1) is not None)
+
+
+def takes_long(layer, csr, inp):
+    return bool(layer.fused and layer.precision == "f16" and inp.dtype == torch.float16
+                and 128 < csr.T <= layer.LONG_MAX_T and layer.in_features % 64 == 0 and layer.out_features % 8 == 0)
+
+
+def layer_path(layer, text, csr, dropout=False, rows=None):
+    """The launch ``forward_gated`` takes, one of ``LAYER_PATHS``.  Precedence: fused, bf16 (33..256 nodes: bf16_wide), weighted,
+    long, two launches (linear + aggregate).  ``dropout``: the caller hands gate dropout in -- a ``DROPOUT_PATHS`` name comes back
+    exactly where ``takes_dropout_path`` / ``takes_bf16_dropout_path`` hold, and any other name means the request is refused;
+    the weighted launch has no dropout epilogue.  ``rows``: the features as [B*T,K] rows (``ggcn_layer_fused_h`` wants them
+    16-byte aligned; other views take linear_h + aggregate_h); None: not looked at."""
+    inp = Input.of(text)
+    drop = "_drop" if dropout and _index_fits(layer, inp) else ""
+    if takes_fused(layer, csr, inp):
+        return "fused" + drop
+    if takes_bf16_wide(layer, csr, inp):
+        return "bf16_wide" + drop
+    if takes_bf16_fused(layer, csr, inp):
+        return "bf16" + drop
+    if not dropout and takes_weighted(layer, csr, inp):
+        return "weighted"
+    if takes_long(layer, csr, inp) and (rows is None or (rows.data_ptr() % 16 == 0 and rows.stride(0) % 8 == 0)):
+        return "long"
+    return "two_launch"
+
+
+def backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands):
+    """``(passes, dx, dw)`` of the layer's backward: ``passes`` out of ``BACKWARD_PASSES``, ``dx`` out of ``DX_FORMS`` (None: no dX
+    wanted), ``dw`` likewise.  The three environment switches are read here, at call time.
+    * one pass -- gate / pool backward AND the transposed aggregation in one launch, dY never reaches memory: graphs of up to 32
+      nodes, 0/1 adjacency, row masks, F % 4 == 0, every operand 16-byte aligned (a contiguous view at an odd storage offset takes
+      the two calls), no adjacency gradient (it reads dY); "mma": that pass on the matrix cores, dH_g = A_g^T . (D.dY_g) as an MFMA
+      chain, without gate dropout; two passes under gate dropout draw the forward's keep factors again ("two_pass_drop");
+    * dX "scaled": the two-unit f16mx8 product (ggcn_linear_scaled) -- the launch that makes dH also leaves max |dH|, from which
+      the linear derives a power-of-two scale on the device.  It wants F % 32 == 0 and 16-byte rows, and the scalar launch hands
+      max |dH| over for whole wavefronts of columns only.  Otherwise split precisions take bf16x3 (gradients can be far below
+      fp16's range), precision "fp32" the exact form, bfloat16 features the bf16 forms."""
+    env = os.environ.get
+    one_pass = (not need_adj and csr.T <= 32 and F % 4 == 0 and csr.is_binary and csr.rowmask is not None and csr.rowmask.is_cuda
+                and env("GGCN_BACKWARD_TWO_PASS", "0") != "1" and all(t is None or t.data_ptr() % 16 == 0 for t in operands))
+    mma = (one_pass and dropout is None and env("GGCN_BACKWARD_SCALAR", "0") != "1"
+           and csr.graph_ops is not None and csr.graph_ops_t is not None)
+    passes = "mma" if mma else "one_pass" if one_pass else "two_pass" if dropout is None else "two_pass_drop"
+    if dtype == torch.bfloat16:
+        return passes, ("bf16" if need_x else None), "bf16"
+    dw = "bf16x3" if layer.precision in _capi.PACKED else "fp32"
+    scaled = (one_pass and need_x and layer.precision == "f16mx8" and K % 4 == 0 and F % 32 == 0 and (mma or F % 256 == 0)
+              and env("GGCN_DX_PRECISION", "f16mx8") == "f16mx8")
+    return passes, ("scaled" if scaled else dw if need_x else None), dw
+
+
+# ---- the block of two layers (the four predicates are gated_block's public ones) -------------------------------------------------
+def bf16_block_on(x, gc1):
+    """The opt-in of the bf16 block forms (``GraphConvolution.bf16_block``) on bfloat16 GPU features."""
+    return bool(getattr(gc1, "bf16_block", False)) and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.bfloat16
+
+
+def _square(gc1, gc2):
+    return gc1.out_features == gc2.in_features and gc1.out_features == gc2.out_features
+
+
+def takes_block_path(x, csr, gc1, gc2):
+    """True when the inference block runs as ONE launch: both layers on the one-launch layer path with the
+    same arithmetic, and gc1's output width = gc2's (the reference's blocks are square, bert_amir5.py:559-560)."""
+    inp = Input.of(x)
+    return (csr.T <= 32 and takes_fused(gc1, csr, inp) and takes_fused(gc2, csr, inp) and gc1.precision == gc2.precision
+            and _square(gc1, gc2))
+
+
+def takes_folded_eval_path(x, csr, gc1, gc2):
+    """True when an evaluation that needs only ``out`` / ``x`` of graphs of 33..256 nodes runs WITHOUT the W1 product:
+    ``Z = D.A.X`` (the aggregation kernel on the features), then ONE one-launch layer on Z with the folded weight
+    ``W12 = W1.W2`` and ``mid = W2^T.b1`` added before its aggregation (``ggcn_layer_fused_prebias``):
+    ``gc2(gc1(X)) = D.A.(Z.W12 + 1.mid^T) + b2`` (``bert_amir5.py:626,639``: no non-linearity between the layers)."""
+    inp = Input.of(x)
+    return (32 < csr.T <= 256 and takes_fused(gc1, csr, inp) and takes_fused(gc2, csr, inp) and gc1.precision == gc2.precision
+            and gc1.precision in ("f16mx8", "bf16x3") and _square(gc1, gc2) and gc1.in_features == gc1.out_features)
+
+
+def takes_bf16_block_path(x, csr, gc1, gc2):
+    """True when inference on bfloat16 features runs the block as ONE launch (``ggcn_block_fused_bf16``): the option
+    ``gc1.bf16_block`` (``opt.ggcn_bf16_block`` / ``GGCN_BF16_BLOCK=1``; off by default), graphs of <= 32 nodes that gc1 would run
+    as one bf16 layer launch, gc2 on the one-launch path, split precisions on both layers (all of them mean the bf16 pair form on
+    the ``bf16x3`` images) and square widths."""
+    return (bf16_block_on(x, gc1) and csr.T <= 32 and takes_bf16_fused(gc1, csr, Input.of(x)) and bool(gc2.fused)
+            and gc1.precision in BF16_PRECISIONS and gc2.precision in BF16_PRECISIONS and _square(gc1, gc2))
+
+
+def takes_bf16_folded_eval_path(x, csr, gc1, gc2):
+    """``takes_folded_eval_path`` for bfloat16 features (same option as ``takes_bf16_block_path``): graphs of 33..256 nodes with a
+    0/1 adjacency and row masks on the device, gc2 on the float32 one-launch path for its float32 input, square widths.
+    ``Z = D.A.X`` by ``ggcn_aggregate_bf16``, then one ``ggcn_layer_fused_prebias`` launch in ``bf16x3``."""
+    return (bf16_block_on(x, gc1) and 32 < csr.T <= 256 and bool(csr.is_binary) and csr.rowmask is not None
+            and bool(csr.rowmask.is_cuda) and gc1.precision in BF16_PRECISIONS and takes_fused(gc2, csr, Input.of(x, torch.float32))
+            and _square(gc1, gc2) and gc1.in_features == gc1.out_features)
+
+
+def block_path(x, csr, gc1, gc2, want, want_gcn1, one_launch, training):
+    """What ``gated_gcn_block`` runs, one of ``BLOCK_PATHS``.  Under autograd "layers" (each layer through its own
+    ``forward_gated``).  Inference, in this order: with ``one_launch``, "block" / "bf16_block" (<= 32 nodes, the whole block as one
+    launch), then -- nothing of layer 1 wanted (no x1, y1, xy, gcn1) -- "bf16_folded_eval" / "folded_eval" (33..256 nodes, no
+    product with W1); no x1, y1, xy wanted: "layers_eval" (gc1 plain, gc2 with its gate and pool); both layers one launch each
+    and equal widths: "two_fused" (the regulariser's sums ride in the two launches); else "layers"."""
+    if training:
+        return "layers"
+    layer1 = any(k in want for k in ("x1", "y1", "xy"))   # anything of bert_amir5.py:627-638
+    eval_only = not layer1 and not want_gcn1
+    for name, takes, allowed in (("block", takes_block_path, True), ("bf16_block", takes_bf16_block_path, True),
+                                 ("bf16_folded_eval", takes_bf16_folded_eval_path, eval_only), ("folded_eval", takes_folded_eval_path, eval_only)):
+        if one_launch and allowed and takes(x, csr, gc1, gc2):
+            return name
+    if not layer1:
+        return "layers_eval"
+    inp = Input.of(x)
+    if ((takes_fused(gc1, csr, inp) or takes_bf16_fused(gc1, csr, inp) or takes_bf16_wide(gc1, csr, inp))
+            and takes_fused(gc2, csr, Input.of(x, torch.float32)) and gc1.out_features == gc2.out_features):
+        return "two_fused"
+    return "layers"

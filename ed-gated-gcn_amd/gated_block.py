@@ -17,9 +17,12 @@ also applies the gate and the max over tokens.
 """
 import torch
 
-from . import _capi, range_guard
+from . import _capi, dispatch, range_guard
 from .csr import BatchedCSR, tensor_version
-from .gcn import BF16_PRECISIONS
+from .dispatch import takes_bf16_block_path, takes_bf16_folded_eval_path, takes_block_path, takes_folded_eval_path  # noqa: F401
+from .gcn import _require_gate, _rows2d
+
+GATE_WORDING = "%(name)s must be a contiguous float32 [B,F]=[%(B)d,%(F)d] GPU tensor"
 
 
 def gate_overlap(x1, y1):
@@ -72,16 +75,6 @@ def _block_operands(gc1, gc2, lib, st, precision=None):
     return gc1._packed_weight(lib, st, precision=precision), cached[1], cached[2]
 
 
-def takes_folded_eval_path(x, csr, gc1, gc2):
-    """True when an evaluation that needs only ``out`` / ``x`` of graphs of 33..256 nodes runs WITHOUT the W1 product:
-    ``Z = D.A.X`` (the aggregation kernel on the features), then ONE one-launch layer on Z with the folded weight
-    ``W12 = W1.W2`` and ``mid = W2^T.b1`` added before its aggregation (``ggcn_layer_fused_prebias``):
-    ``gc2(gc1(X)) = D.A.(Z.W12 + 1.mid^T) + b2`` (``bert_amir5.py:626,639``: no non-linearity between the layers)."""
-    return (32 < csr.T <= 256 and gc1.takes_fused_path(x, csr) and gc2.takes_fused_path(x, csr) and gc1.precision == gc2.precision
-            and gc1.precision in ("f16mx8", "bf16x3") and gc1.out_features == gc2.in_features
-            and gc1.in_features == gc1.out_features == gc2.out_features)
-
-
 def _folded_eval(x, csr, gate2, gc1, gc2, want_x):
     """``(x or None, out)`` of ``bert_amir5.py:639-640`` through the folded weight, two launches, no product with W1.
     bfloat16 features (``takes_bf16_folded_eval_path``): ``Z`` comes from ``ggcn_aggregate_bf16`` (float32, the sums of
@@ -92,15 +85,9 @@ def _folded_eval(x, csr, gate2, gc1, gc2, want_x):
     if not bf16:
         range_guard.before(x.device)
     lib = _capi.load_library()
-    B, T, K = x.shape
-    F = gc2.out_features
-    dev = x.device
-    x2d = x.reshape(B * T, K)
-    if x2d.stride(1) != 1:
-        x2d = x2d.contiguous()
-    if not (isinstance(gate2, torch.Tensor) and gate2.is_cuda and gate2.dtype == torch.float32 and tuple(gate2.shape) == (B, F)
-            and gate2.is_contiguous()):
-        raise RuntimeError("gate2 must be a contiguous float32 [B,F]=[%d,%d] GPU tensor" % (B, F))
+    (B, T, K), F, dev = x.shape, gc2.out_features, x.device
+    x2d = _rows2d(x)
+    _require_gate("gate2", gate2, B, F, GATE_WORDING)
     with torch.cuda.device(dev):
         st = _capi.stream_of(dev)
         prec = "bf16x3" if bf16 else gc1.precision
@@ -122,51 +109,6 @@ def _folded_eval(x, csr, gate2, gc1, gc2, want_x):
     if prec == "f16mx8":
         range_guard.after(x.device)
     return (None if xo is None else xo.view(B, T, F)), out
-
-
-def _bf16_block_on(x, gc1):
-    """The opt-in of the bf16 block forms (``GraphConvolution.bf16_block``) on bfloat16 GPU features."""
-    return bool(getattr(gc1, "bf16_block", False)) and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.bfloat16
-
-
-def takes_bf16_block_path(x, csr, gc1, gc2):
-    """True when inference on bfloat16 features runs the block as ONE launch (``ggcn_block_fused_bf16``): the option
-    ``gc1.bf16_block`` (``opt.ggcn_bf16_block`` / ``GGCN_BF16_BLOCK=1``; off by default), graphs of <= 32 nodes that gc1 would run
-    as one bf16 layer launch, gc2 on the one-launch path, split precisions on both layers (all of them mean the bf16 pair form on
-    the ``bf16x3`` images) and square widths."""
-    return (_bf16_block_on(x, gc1) and csr.T <= 32 and gc1.takes_bf16_fused_path(x, csr) and bool(gc2.fused)
-            and gc1.precision in BF16_PRECISIONS and gc2.precision in BF16_PRECISIONS
-            and gc1.out_features == gc2.in_features and gc1.out_features == gc2.out_features)
-
-
-def takes_bf16_folded_eval_path(x, csr, gc1, gc2):
-    """``takes_folded_eval_path`` for bfloat16 features (same option as ``takes_bf16_block_path``): graphs of 33..256 nodes with a
-    0/1 adjacency and row masks on the device, gc2 on the float32 one-launch path for its float32 input, square widths.
-    ``Z = D.A.X`` by ``ggcn_aggregate_bf16``, then one ``ggcn_layer_fused_prebias`` launch in ``bf16x3``."""
-    return (_bf16_block_on(x, gc1) and 32 < csr.T <= 256 and bool(csr.is_binary) and csr.rowmask is not None and csr.rowmask.is_cuda
-            and gc1.precision in BF16_PRECISIONS and gc2.takes_fused_path(_layer2_input(x, gc1), csr)
-            and gc1.out_features == gc2.in_features and gc1.in_features == gc1.out_features == gc2.out_features)
-
-
-def takes_block_path(x, csr, gc1, gc2):
-    """True when the inference block runs as ONE launch: both layers on the one-launch layer path with the
-    same arithmetic, and gc1's output width = gc2's (the reference's blocks are square, bert_amir5.py:559-560)."""
-    return (csr.T <= 32 and gc1.takes_fused_path(x, csr) and gc2.takes_fused_path(x, csr) and gc1.precision == gc2.precision
-            and gc1.out_features == gc2.in_features and gc1.out_features == gc2.out_features)
-
-
-def _layer2_input(x, gc1):
-    """What gc2's dispatch is judged by: gc2 reads gcn1, which is float32 whatever x is (bfloat16 features give a float32
-    layer output).  For float32 x that is x itself -- every float32 decision stays as it was; for bf16 x a float32
-    stand-in of gcn1's shape (an expanded single element: nothing of [B,T,H] is allocated)."""
-    if x.dtype == torch.float32:
-        return x
-    return torch.zeros(1, dtype=torch.float32, device=x.device).expand(x.shape[0], x.shape[1], gc1.out_features)
-
-
-def _layer1_takes_fused(x, csr, gc1):
-    """gc1 runs as one launch: the float32 one-launch layer, or a bf16 one (graphs of <= 32 nodes, or 33..256 on the row masks)."""
-    return gc1.takes_fused_path(x, csr) or gc1.takes_bf16_fused_path(x, csr) or gc1.takes_bf16_wide_path(x, csr)
 
 
 BLOCK_OUTPUTS = ("x1", "y1", "xy", "x", "out")
@@ -210,48 +152,45 @@ def gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch=
     return _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1, one_launch, want)
 
 
-def _bf16_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, pick, defer_xy):
-    """``bert_amir5.py:626-640`` on bfloat16 features of graphs of <= 32 nodes as ONE launch (``ggcn_block_fused_bf16``; + the
-    1-block launch that finishes ``:638`` unless the caller's dense head does).  The float32 block's outputs and options, all
-    float32; no range report -- bf16 features run no fp16 arithmetic."""
+def _one_launch_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, defer_xy, bf16):
+    """``bert_amir5.py:626-640`` on graphs of <= 32 nodes as ONE launch (+ the 1-block launch that finishes ``:638`` unless the
+    caller's dense head does): ``ggcn_block_fused`` in the layers' arithmetic between the two halves of the lazy range report,
+    or (``bf16``) ``ggcn_block_fused_bf16`` on the ``bf16x3`` images -- same outputs and options, all float32, no range
+    report: bf16 features run no fp16 arithmetic."""
     gc1._check(x)
-    w_l1 = any(k in want for k in ("x1", "y1", "xy"))
+    if not bf16:
+        range_guard.before(x.device)   # the lazy f16mx8 range report (a violation of an EARLIER launch raises here)
     lib = _capi.load_library()
-    B, T, K = x.shape
-    F = gc2.out_features
-    dev = x.device
-    x2d = x.reshape(B * T, K)
-    if x2d.stride(1) != 1:
-        x2d = x2d.contiguous()
-    layer1 = w_l1 or want_gcn1   # False: the eval form -- only the W12 column tiles are launched
-    for name, g in (("gate1", gate1), ("gate2", gate2)):
-        if g is None and name == "gate1" and not layer1:
-            continue   # the eval form never reads gate1
-        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float32
-                and tuple(g.shape) == (B, F) and g.is_contiguous()):
-            raise RuntimeError("%s must be a contiguous float32 [B,F]=[%d,%d] GPU tensor" % (name, B, F))
+    (B, T, K), F, dev = x.shape, gc2.out_features, x.device
+    x2d = _rows2d(x)
+    layer1 = want_gcn1 or any(k in want for k in ("x1", "y1", "xy"))   # False: the eval form -- only the W12 column tiles are launched
+    if gate1 is not None or layer1:   # (the eval form never reads gate1)
+        _require_gate("gate1", gate1, B, F, GATE_WORDING)
+    _require_gate("gate2", gate2, B, F, GATE_WORDING)
+    ptr, f32 = _capi.ptr, dict(dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         st = _capi.stream_of(dev)
-        pack1, pack12, mid = _block_operands(gc1, gc2, lib, st, precision="bf16x3")
-        gcn1 = torch.empty(B * T, F, dtype=torch.float32, device=dev) if want_gcn1 else None
-        xo = torch.empty(B * T, F, dtype=torch.float32, device=dev) if "x" in want else None
-        x1 = torch.empty(B, F, dtype=torch.float32, device=dev) if layer1 else None
-        y1 = torch.empty(B, F, dtype=torch.float32, device=dev) if layer1 else None
-        out = torch.empty(B, F, dtype=torch.float32, device=dev)
-        part = torch.empty(B, (F + 63) // 64, dtype=torch.float32, device=dev) if "xy" in want else None
-        xy = torch.empty((), dtype=torch.float32, device=dev) if "xy" in want else None
+        kprec = "bf16x3" if bf16 else gc1.kernel_precision(x2d, csr)   # "f16mx6" where the fp6 kernel takes the shape, else "f16mx8"
+        pack1, pack12, mid = _block_operands(gc1, gc2, lib, st, precision=kprec)
+        gcn1 = torch.empty(B * T, F, **f32) if want_gcn1 else None
+        xo = torch.empty(B * T, F, **f32) if "x" in want else None
+        x1, y1 = (torch.empty(B, F, **f32), torch.empty(B, F, **f32)) if layer1 else (None, None)
+        out = torch.empty(B, F, **f32)
+        part = torch.empty(B, (F + 63) // 64, **f32) if "xy" in want else None
+        xy = torch.empty((), **f32) if "xy" in want else None
         b1 = None if gc1.bias is None else gc1.bias.detach()
         b2 = None if gc2.bias is None else gc2.bias.detach()
-        _capi.check(lib.ggcn_block_fused_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack1 if layer1 else None), _capi.ptr(pack12),
-                                              _capi.ptr(csr.graph_ops), _capi.ptr(csr.graph_ops2(0)),
-                                              _capi.ptr(b1), _capi.ptr(mid), _capi.ptr(b2),
-                                              B, T, K, F, _capi.ptr(gate1 if layer1 else None), _capi.ptr(gate2), _capi.ptr(gcn1), F,
-                                              _capi.ptr(xo), F, _capi.ptr(x1), _capi.ptr(y1), _capi.ptr(out),
-                                              _capi.ptr(part), st), "ggcn_block_fused_bf16")
+        entry = "ggcn_block_fused_bf16" if bf16 else "ggcn_block_fused"   # (bf16: layer 1's image only where layer 1 runs, no precision)
+        _capi.check(getattr(lib, entry)(ptr(x2d), x2d.stride(0), ptr(pack1 if (layer1 or not bf16) else None), ptr(pack12),
+                                        ptr(csr.graph_ops), ptr(csr.graph_ops2(0 if kprec == "bf16x3" else 1)), ptr(b1), ptr(mid), ptr(b2),
+                                        B, T, K, F, ptr(gate1 if layer1 else None), ptr(gate2), ptr(gcn1), F, ptr(xo), F,
+                                        ptr(x1), ptr(y1), ptr(out), ptr(part), *(() if bf16 else (_capi.PREC[kprec],)), st), entry)
         if part is not None and not defer_xy:
-            _capi.check(lib.ggcn_overlap_reduce(_capi.ptr(part), B, F, _capi.ptr(xy), st), "ggcn_overlap_reduce")
-    r = pick({"gcn1": None if gcn1 is None else gcn1.view(B, T, F), "x1": x1, "y1": y1, "xy": xy,
-              "x": None if xo is None else xo.view(B, T, F), "out": out})
+            _capi.check(lib.ggcn_overlap_reduce(ptr(part), B, F, ptr(xy), st), "ggcn_overlap_reduce")
+    if kprec in ("f16mx8", "f16mx6"):
+        range_guard.after(x.device)
+    r = {"gcn1": None if gcn1 is None else gcn1.view(B, T, F), "x1": x1, "y1": y1, "xy": xy,
+         "x": None if xo is None else xo.view(B, T, F), "out": out}
     if defer_xy and part is not None:
         r["_xy_partials"] = part
     return r
@@ -264,13 +203,12 @@ def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch
     bad = [k for k in want if k not in BLOCK_OUTPUTS]
     if bad:
         raise ValueError("want: unknown output(s) %s (choose from %s; gcn1 has its own flag want_gcn1)" % (bad, list(BLOCK_OUTPUTS)))
-    w_l1 = any(k in want for k in ("x1", "y1", "xy"))   # anything of bert_amir5.py:627-638
     w_x = "x" in want
     if x.shape[0] == 0:   # empty batch: what the reference's ops give on empty tensors (the mean of nothing is nan)
         gc1._check(x)
         B, T, F = 0, x.shape[1], gc2.out_features
         z2 = x.new_zeros((0, F), dtype=torch.float32)
-        dt = torch.float32 if _bf16_block_on(x, gc1) else x.dtype   # (the bf16 block's outputs are all float32)
+        dt = torch.float32 if dispatch.bf16_block_on(x, gc1) else x.dtype   # (the bf16 block's outputs are all float32)
         return {"gcn1": x.new_zeros((0, T, gc1.out_features), dtype=dt), "x1": x.new_zeros((0, gc1.out_features), dtype=dt),
                 "y1": x.new_zeros((0, gc1.out_features), dtype=dt), "xy": x.new_full((), float("nan"), dtype=dt),
                 "x": x.new_zeros((0, T, F), dtype=dt), "out": z2}
@@ -278,95 +216,41 @@ def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch
     training = torch.is_grad_enabled() and (gc1._needs_grad(x, gate1, gate2, adj=adj) or gc2._needs_grad(x, gate2, adj=adj))
     if training and set(want) != set(BLOCK_OUTPUTS):
         raise RuntimeError("want= selects outputs of the inference block; under autograd every output is produced")
-
-    def pick(r):   # outputs the caller did not ask for are not handed out (whether or not a path had to compute them)
-        for k in BLOCK_OUTPUTS:
-            if k not in want:
-                r[k] = None
-        return r
-    if not training and one_launch and takes_block_path(x, csr, gc1, gc2):
+    path = dispatch.block_path(x, csr, gc1, gc2, want, want_gcn1, one_launch, training)
+    r = dict.fromkeys(("gcn1",) + BLOCK_OUTPUTS)
+    if path in ("block", "bf16_block"):
         # ---- ONE launch for :626-640 (+ one 1-block launch that finishes :638) ----
-        gc1._check(x)
-        range_guard.before(x.device)   # the lazy f16mx8 range report (a violation of an EARLIER launch raises here)
-        lib = _capi.load_library()
-        B, T, K = x.shape
-        F = gc2.out_features
-        dev = x.device
-        x2d = x.reshape(B * T, K)
-        if x2d.stride(1) != 1:
-            x2d = x2d.contiguous()
-        for name, g in (("gate1", gate1), ("gate2", gate2)):
-            if g is None and name == "gate1" and not (w_l1 or want_gcn1):
-                continue   # the eval form never reads gate1
-            if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float32
-                    and tuple(g.shape) == (B, F) and g.is_contiguous()):
-                raise RuntimeError("%s must be a contiguous float32 [B,F]=[%d,%d] GPU tensor" % (name, B, F))
-        with torch.cuda.device(dev):
-            st = _capi.stream_of(dev)
-            kprec = gc1.kernel_precision(x2d, csr)   # "f16mx6" where the fp6 kernel takes the shape, else "f16mx8"
-            pack1, pack12, mid = _block_operands(gc1, gc2, lib, st, precision=kprec)
-            layer1 = w_l1 or want_gcn1   # False: the eval form -- only the W12 column tiles are launched
-            gcn1 = torch.empty(B * T, F, dtype=torch.float32, device=dev) if want_gcn1 else None
-            xo = torch.empty(B * T, F, dtype=torch.float32, device=dev) if w_x else None
-            x1 = torch.empty(B, F, dtype=torch.float32, device=dev) if layer1 else None
-            y1 = torch.empty(B, F, dtype=torch.float32, device=dev) if layer1 else None
-            out = torch.empty(B, F, dtype=torch.float32, device=dev)
-            part = torch.empty(B, (F + 63) // 64, dtype=torch.float32, device=dev) if "xy" in want else None
-            xy = torch.empty((), dtype=torch.float32, device=dev) if "xy" in want else None
-            b1 = None if gc1.bias is None else gc1.bias.detach()
-            b2 = None if gc2.bias is None else gc2.bias.detach()
-            _capi.check(lib.ggcn_block_fused(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack1), _capi.ptr(pack12),
-                                             _capi.ptr(csr.graph_ops), _capi.ptr(csr.graph_ops2(0 if kprec == "bf16x3" else 1)),
-                                             _capi.ptr(b1), _capi.ptr(mid), _capi.ptr(b2),
-                                             B, T, K, F, _capi.ptr(gate1 if layer1 else None), _capi.ptr(gate2), _capi.ptr(gcn1), F,
-                                             _capi.ptr(xo), F, _capi.ptr(x1), _capi.ptr(y1), _capi.ptr(out),
-                                             _capi.ptr(part), _capi.PREC[kprec], st), "ggcn_block_fused")
-            if part is not None and not _defer_xy:
-                _capi.check(lib.ggcn_overlap_reduce(_capi.ptr(part), B, F, _capi.ptr(xy), st), "ggcn_overlap_reduce")
-        if kprec in ("f16mx8", "f16mx6"):
-            range_guard.after(x.device)
-        r = pick({"gcn1": None if gcn1 is None else gcn1.view(B, T, F), "x1": x1, "y1": y1, "xy": xy,
-                  "x": None if xo is None else xo.view(B, T, F), "out": out})
-        if _defer_xy and part is not None:
-            r["_xy_partials"] = part
-        return r
-    if not training and one_launch and takes_bf16_block_path(x, csr, gc1, gc2):
-        return _bf16_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, pick, _defer_xy)
-    if not training and one_launch and not w_l1 and not want_gcn1 and takes_bf16_folded_eval_path(x, csr, gc1, gc2):
-        x2, out = _folded_eval(x, csr, gate2, gc1, gc2, w_x)   # bf16 features of 33..256-node graphs: no product with W1
-        return pick({"gcn1": None, "x1": None, "y1": None, "xy": None, "x": x2, "out": out})
-    if (not training and _layer1_takes_fused(x, csr, gc1) and gc2.takes_fused_path(_layer2_input(x, gc1), csr)
-            and gc1.out_features == gc2.out_features):
+        r = _one_launch_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, _defer_xy, bf16=path == "bf16_block")
+    elif path in ("folded_eval", "bf16_folded_eval"):   # the eval form of 33..256-node graphs: no product with W1
+        r["x"], r["out"] = _folded_eval(x, csr, gate2, gc1, gc2, w_x)
+    elif path == "layers_eval":   # gc2 needs gcn1 itself, nothing else of layer 1: no pools, no regulariser
+        gcn1, _, _ = gc1.forward_gated(x, csr)
+        r["x"], r["out"], _ = gc2.forward_gated(gcn1, csr, store_gate=gate2, pool_gate_a=gate2, want_out=w_x, want_pool_a=True)
+        r["gcn1"] = gcn1 if want_gcn1 else None
+    elif path == "two_fused":
         # two launches in all: layer 1 leaves its share of sum_f x1*y1 per (graph, 64 columns), layer 2's
         # launch adds them up before it starts on its own tiles (:638 costs no launch of its own)
         B, F = x.shape[0], gc1.out_features
-        if not w_l1 and not want_gcn1 and one_launch and takes_folded_eval_path(x, csr, gc1, gc2):
-            x2, out = _folded_eval(x, csr, gate2, gc1, gc2, w_x)      # the eval form of 33..256-node graphs: no product with W1
-            return pick({"gcn1": None, "x1": None, "y1": None, "xy": None, "x": x2, "out": out})
-        if not w_l1:   # gc2 needs gcn1 itself, nothing else of layer 1: no pools, no regulariser
-            gcn1, _, _ = gc1.forward_gated(x, csr)
-            x2, out, _ = gc2.forward_gated(gcn1, csr, store_gate=gate2, pool_gate_a=gate2, want_out=w_x, want_pool_a=True)
-            return pick({"gcn1": gcn1 if want_gcn1 else None, "x1": None, "y1": None, "xy": None, "x": x2, "out": out})
         part = torch.empty(B, (F + 63) // 64, dtype=torch.float32, device=x.device)
-        xy = torch.empty((), dtype=torch.float32, device=x.device)
-        gcn1, x1, y1 = gc1.forward_gated(x, csr, store_gate=None, pool_gate_a=gate1, pool_gate_b=gate2,
-                                         want_pool_a=True, want_pool_b=True, overlap_partial=part)   # :626-636
-        x2, out, _ = gc2.forward_gated(gcn1, csr, store_gate=gate2, pool_gate_a=gate2, want_pool_a=True,
-                                       want_out=w_x, overlap_reduce=(part, xy))        # :638-640
-        return pick({"gcn1": gcn1, "x1": x1, "y1": y1, "xy": xy, "x": x2, "out": out})
-    if not training and not w_l1:
-        gcn1, _, _ = gc1.forward_gated(x, csr)
-        x2, out, _ = gc2.forward_gated(gcn1, csr, store_gate=gate2, pool_gate_a=gate2, want_out=w_x, want_pool_a=True)
-        return pick({"gcn1": gcn1 if want_gcn1 else None, "x1": None, "y1": None, "xy": None, "x": x2, "out": out})
-    # a dense adj that wants its gradient goes to the layers as the tensor (autograd adds their two contributions); its
-    # conversion is the cached one
-    graph = adj if gc1._differentiable_adj(adj) is not None else csr
-    gcn1, x1, y1 = gc1.forward_gated(x, graph, store_gate=None, pool_gate_a=gate1, pool_gate_b=gate2,
-                                     want_pool_a=True, want_pool_b=True)           # :626-636
-    if torch.is_grad_enabled() and (x1.requires_grad or y1.requires_grad):
-        xy = (x1 * y1).sum(1).mean()   # differentiable form of :638 (the regulariser is trained on)
-    else:
-        xy = gate_overlap(x1, y1) if "xy" in want else None                        # :638
-    x2, out, _ = gc2.forward_gated(gcn1, graph, store_gate=gate2, pool_gate_a=gate2,
-                                   want_out=training or w_x, want_pool_a=True)   # :639-640
-    return pick({"gcn1": gcn1, "x1": x1, "y1": y1, "xy": xy, "x": x2, "out": out})
+        r["xy"] = torch.empty((), dtype=torch.float32, device=x.device)
+        r["gcn1"], r["x1"], r["y1"] = gc1.forward_gated(x, csr, store_gate=None, pool_gate_a=gate1, pool_gate_b=gate2,
+                                                        want_pool_a=True, want_pool_b=True, overlap_partial=part)   # :626-636
+        r["x"], r["out"], _ = gc2.forward_gated(r["gcn1"], csr, store_gate=gate2, pool_gate_a=gate2, want_pool_a=True,
+                                                want_out=w_x, overlap_reduce=(part, r["xy"]))        # :638-640
+    else:   # "layers"
+        # a dense adj that wants its gradient goes to the layers as the tensor (autograd adds their two contributions); its
+        # conversion is the cached one
+        graph = adj if gc1._differentiable_adj(adj) is not None else csr
+        r["gcn1"], x1, y1 = gc1.forward_gated(x, graph, store_gate=None, pool_gate_a=gate1, pool_gate_b=gate2,
+                                              want_pool_a=True, want_pool_b=True)           # :626-636
+        if torch.is_grad_enabled() and (x1.requires_grad or y1.requires_grad):
+            r["xy"] = (x1 * y1).sum(1).mean()   # differentiable form of :638 (the regulariser is trained on)
+        else:
+            r["xy"] = gate_overlap(x1, y1) if "xy" in want else None                        # :638
+        r["x1"], r["y1"] = x1, y1
+        r["x"], r["out"], _ = gc2.forward_gated(r["gcn1"], graph, store_gate=gate2, pool_gate_a=gate2,
+                                                want_out=training or w_x, want_pool_a=True)   # :639-640
+    for k in BLOCK_OUTPUTS:   # outputs the caller did not ask for are not handed out (whether or not a path had to compute them)
+        if k not in want:
+            r[k] = None
+    return r

@@ -16,8 +16,9 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _capi, range_guard
+from . import _capi, dispatch, range_guard
 from .csr import BatchedCSR, cached_from_dense, tensor_version
+from .dispatch import BF16_PRECISIONS  # noqa: F401  (its home is dispatch.py; imported from here too)
 
 
 def _require_gpu_f32(name, t, allow_half=False, allow_bf16=False):
@@ -31,9 +32,30 @@ def _require_gpu_f32(name, t, allow_half=False, allow_bf16=False):
                                                                " or bfloat16" if allow_bf16 else "", t.dtype))
 
 
-# precisions that mean "the bf16 pair form" for bfloat16 features: x is exact in bf16, so every product is hi.Whi + hi.Wlo,
-# two bf16 MFMAs on the bf16x3 image of W (include/ggcn.h ggcn_linear_bf16)
-BF16_PRECISIONS = ("bf16x3", "f16mx8", "f16mx6")
+def _rows2d(text):
+    """[B,T,K] features as [B*T,K] rows with unit column stride (a view where the layout allows it)."""
+    B, T, K = text.shape
+    x2d = text.reshape(B * T, K)
+    return x2d if x2d.stride(1) == 1 else x2d.contiguous()
+
+
+def _require_gate(name, g, B, F, wording):
+    """A gate is a contiguous float32 [B,F] GPU tensor; else RuntimeError in the caller's ``wording`` (name, B, F, shape)."""
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float32 and tuple(g.shape) == (B, F) and g.is_contiguous()):
+        raise RuntimeError(wording % {"name": name, "B": B, "F": F, "shape": tuple(getattr(g, "shape", ()))})
+
+
+def _drop_args(dropout):
+    """``(p, seed, stream_store, stream_a, stream_b)`` as the entries take them; no dropout: p = 0, every stream 0."""
+    return (0.0, 0, 0, 0, 0) if dropout is None else (float(dropout[0]), int(dropout[1])) + tuple(dropout[2])
+
+
+def _admit(path, dropout, overlap):
+    """Gate dropout and the overlap operands exist in the one-launch layers only: decided from the name of the path the call takes."""
+    if dropout is not None and path not in dispatch.DROPOUT_PATHS:
+        raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
+    if overlap and path not in dispatch.OVERLAP_PATHS:
+        raise RuntimeError("overlap_partial / overlap_reduce need the one-launch layer (takes_fused_path)")
 
 
 class _GatedLayerFunction(torch.autograd.Function):
@@ -75,9 +97,7 @@ class _GatedLayerFunction(torch.autograd.Function):
         if d_out is None and d_pa is None and d_pb is None:
             return (None,) * 12
         lib = _capi.load_library()
-        B, T, K = text.shape
-        F = layer.out_features
-        dev = text.device
+        (B, T, K), F, dev = text.shape, layer.out_features, text.device
 
         def f32c(t, shape):
             if t is None:
@@ -86,132 +106,84 @@ class _GatedLayerFunction(torch.autograd.Function):
             return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
         d_out2, d_pa, d_pb = f32c(d_out, (B * T, F)), f32c(d_pa, (B, F)), f32c(d_pb, (B, F))
-        out2 = out.reshape(B * T, F)
+        out2 = out.reshape(-1, F)
+        ptr = _capi.ptr
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
             need = ctx.needs_input_grad
-            d_sg = torch.empty(B, F, dtype=torch.float32, device=dev) if (store_gate is not None and need[3]) else None
-            d_ga = torch.empty(B, F, dtype=torch.float32, device=dev) if (gate_a is not None and need[4] and d_pa is not None) else None
-            d_gb = torch.empty(B, F, dtype=torch.float32, device=dev) if (gate_b is not None and need[5] and d_pb is not None) else None
-            d_bsum = torch.empty(B, F, dtype=torch.float32, device=dev) if (ctx.has_bias and need[2]) else None
-            dh = torch.empty(B * T, F, dtype=torch.float32, device=dev)
-            # graphs of up to 32 nodes with a 0/1 adjacency: gate / pool backward AND the transposed aggregation in one launch
-            # (dY is consumed by nothing else: it never reaches memory)
-            # (its 16-byte accesses need every operand 16-byte aligned: a contiguous view at an odd storage offset takes the two calls)
-            # (a differentiable adjacency reads dY: the two calls)
+            f32 = dict(dtype=torch.float32, device=dev)
+            d_sg = torch.empty(B, F, **f32) if (store_gate is not None and need[3]) else None
+            d_ga = torch.empty(B, F, **f32) if (gate_a is not None and need[4] and d_pa is not None) else None
+            d_gb = torch.empty(B, F, **f32) if (gate_b is not None and need[5] and d_pb is not None) else None
+            d_bsum = torch.empty(B, F, **f32) if (ctx.has_bias and need[2]) else None
+            dh = torch.empty(B * T, F, **f32)
             need_adj = ctx.adj_dtype is not None and need[11]
-            one_pass = (not need_adj and T <= 32 and F % 4 == 0 and csr.is_binary and csr.rowmask is not None and csr.rowmask.is_cuda
-                        and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1"
-                        and all(t is None or t.data_ptr() % 16 == 0
-                                for t in (out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum)))
-            # dX on the two-unit f16mx8 product (ggcn_linear_scaled): the launch that makes dH also leaves max |dH|, from which the
-            # linear derives a power-of-two scale on the device -- gradients have no range contract of their own
-            dx = None
-            # without gate dropout the backward runs on the matrix cores: dH_g = A_g^T . (D.dY_g) as an MFMA chain (ggcn_gate_pool_backward_mma)
-            mma = (one_pass and ctx.dropout is None and os.environ.get("GGCN_BACKWARD_SCALAR", "0") != "1"
-                   and csr.graph_ops is not None and csr.graph_ops_t is not None)
-            # (the scaled linear wants its reduction length F % 32 == 0 and 16-byte rows; the scalar launch hands max |dH| over for
-            # whole wavefronts of columns only)
-            bf16 = text.dtype == torch.bfloat16
-            scaled_dx = (one_pass and need[0] and not bf16 and layer.precision == "f16mx8" and K % 4 == 0 and F % 32 == 0 and (mma or F % 256 == 0)
-                         and os.environ.get("GGCN_DX_PRECISION", "f16mx8") == "f16mx8")
-            dh_amax = torch.zeros(1, dtype=torch.float32, device=dev) if scaled_dx else None
-            if mma:
-                _capi.check(lib.ggcn_gate_pool_backward_mma(
-                    _capi.ptr(out2), F, _capi.ptr(store_gate), _capi.ptr(gate_a), _capi.ptr(gate_b),
-                    _capi.ptr(d_out2), F, _capi.ptr(d_pa), _capi.ptr(d_pb), _capi.ptr(csr.graph_ops), _capi.ptr(csr.graph_ops_t), B, T, F,
-                    _capi.ptr(dh), F, _capi.ptr(d_sg), _capi.ptr(d_ga), _capi.ptr(d_gb), _capi.ptr(d_bsum), _capi.ptr(dh_amax), st),
-                    "ggcn_gate_pool_backward_mma")
-            elif one_pass:
-                dp, dseed, (ss, sa, sb) = ctx.dropout if ctx.dropout is not None else (0.0, 0, (0, 0, 0))
-                _capi.check(lib.ggcn_gate_pool_backward_agg(
-                    _capi.ptr(out2), F, _capi.ptr(store_gate), _capi.ptr(gate_a), _capi.ptr(gate_b),
-                    _capi.ptr(d_out2), F, _capi.ptr(d_pa), _capi.ptr(d_pb), _capi.ptr(csr.rowmask), B, T, F, _capi.ptr(dh), F,
-                    _capi.ptr(d_sg), _capi.ptr(d_ga), _capi.ptr(d_gb), _capi.ptr(d_bsum), float(dp), int(dseed), ss, sa, sb,
-                    _capi.ptr(dh_amax), st), "ggcn_gate_pool_backward_agg")
-            elif ctx.dropout is None:
-                dy = torch.empty(B * T, F, dtype=torch.float32, device=dev)
-                _capi.check(lib.ggcn_gate_pool_backward(
-                    _capi.ptr(out2), F, _capi.ptr(store_gate), _capi.ptr(gate_a), _capi.ptr(gate_b),
-                    _capi.ptr(d_out2), F, _capi.ptr(d_pa), _capi.ptr(d_pb), B, T, F, _capi.ptr(dy), F,
-                    _capi.ptr(d_sg), _capi.ptr(d_ga), _capi.ptr(d_gb), _capi.ptr(d_bsum), st), "ggcn_gate_pool_backward")
-            else:   # the keep factors of the forward launch, drawn again from (seed, element)
-                dy = torch.empty(B * T, F, dtype=torch.float32, device=dev)
-                dp, dseed, (ss, sa, sb) = ctx.dropout
-                _capi.check(lib.ggcn_gate_pool_backward_drop(
-                    _capi.ptr(out2), F, _capi.ptr(store_gate), _capi.ptr(gate_a), _capi.ptr(gate_b),
-                    _capi.ptr(d_out2), F, _capi.ptr(d_pa), _capi.ptr(d_pb), B, T, F, _capi.ptr(dy), F,
-                    _capi.ptr(d_sg), _capi.ptr(d_ga), _capi.ptr(d_gb), _capi.ptr(d_bsum), float(dp), int(dseed), ss, sa, sb, st),
-                    "ggcn_gate_pool_backward_drop")
-            if not one_pass:
+            passes, dx_form, dw_form = dispatch.backward_plan(layer, csr, text.dtype, K, F, need[0], need_adj, ctx.dropout, (
+                out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum))
+            two_pass = passes in ("two_pass", "two_pass_drop")   # dY to memory, then dH = A^T.(D.dY) on the transposed CSR
+            dh_amax = torch.zeros(1, **f32) if dx_form == "scaled" else None
+            dy = torch.empty(B * T, F, **f32) if two_pass else None
+            drop = _drop_args(ctx.dropout)   # the keep factors of the forward launch, drawn again from (seed, element)
+            entry, graph, tail = {"mma": ("ggcn_gate_pool_backward_mma", ("graph_ops", "graph_ops_t"), (ptr(dh_amax),)),
+                                  "one_pass": ("ggcn_gate_pool_backward_agg", ("rowmask",), drop + (ptr(dh_amax),)),
+                                  "two_pass": ("ggcn_gate_pool_backward", (), ()),
+                                  "two_pass_drop": ("ggcn_gate_pool_backward_drop", (), drop)}[passes]
+            _capi.check(getattr(lib, entry)(
+                ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
+                *(ptr(getattr(csr, name)) for name in graph), B, T, F, ptr(dy if two_pass else dh), F,
+                ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), *tail, st), entry)
+            if two_pass:
                 csr_t = csr.transposed()
-                inv = csr.inv_denominators()
-                _capi.check(lib.ggcn_aggregate_t(_capi.ptr(dy), F, _capi.ptr(csr_t.rowptr), _capi.ptr(csr_t.colidx),
-                                                 _capi.ptr(csr_t.vals), _capi.ptr(inv), B, T, F, _capi.ptr(dh), F, st),
-                            "ggcn_aggregate_t")
+                _capi.check(lib.ggcn_aggregate_t(ptr(dy), F, ptr(csr_t.rowptr), ptr(csr_t.colidx), ptr(csr_t.vals),
+                                                 ptr(csr.inv_denominators()), B, T, F, ptr(dh), F, st), "ggcn_aggregate_t")
             d_adj = None
             if need_adj:   # dA = D.dY.H^T - c on `hidden` as the forward computed it (float32 for bfloat16 features too)
-                x2d = text.reshape(B * T, K)
-                if x2d.stride(1) != 1:
-                    x2d = x2d.contiguous()
-                hidden = layer.linear(x2d)
-                d_adj = torch.empty(B, T, T, dtype=torch.float32, device=dev)
-                _capi.check(lib.ggcn_adjacency_grad(_capi.ptr(dy), F, _capi.ptr(hidden), hidden.stride(0), _capi.ptr(csr.inv_denominators()),
-                                                    _capi.ptr(csr.rowptr), _capi.ptr(csr.colidx), _capi.ptr(csr.vals), B, T, F,
-                                                    _capi.ptr(d_adj), st), "ggcn_adjacency_grad")
+                hidden = layer.linear(_rows2d(text))
+                d_adj = torch.empty(B, T, T, **f32)
+                _capi.check(lib.ggcn_adjacency_grad(ptr(dy), F, ptr(hidden), hidden.stride(0), ptr(csr.inv_denominators()), ptr(csr.rowptr),
+                                                    ptr(csr.colidx), ptr(csr.vals), B, T, F, ptr(d_adj), st), "ggcn_adjacency_grad")
                 if ctx.adj_dtype != torch.float32:
                     d_adj = d_adj.to(ctx.adj_dtype)
-            dw = db = None
-            if need[0] and bf16:   # bfloat16 features: dX in bf16 (the reference's gradient dtype under autocast), rounded in the store
-                dx = torch.empty(B * T, K, dtype=torch.bfloat16, device=dev)
-                pack_t = layer._packed_weight(lib, st, transposed=True)
-                _capi.check(lib.ggcn_linear_out_bf16(_capi.ptr(dh), F, _capi.ptr(pack_t), _capi.ptr(dx), K, B * T, F, K, st),
-                            "ggcn_linear_out_bf16(dX)")
-                dx = dx.view(B, T, K)
-            elif need[0]:
-                dx = torch.empty(B * T, K, dtype=torch.float32, device=dev)
-                if scaled_dx:
+            dx = dw = db = None
+            if dx_form is not None:
+                dx = torch.empty(B * T, K, dtype=torch.bfloat16 if dx_form == "bf16" else torch.float32, device=dev)
+                if dx_form == "bf16":   # bfloat16 features: dX in bf16 (the reference's gradient dtype under autocast), rounded in the store
+                    pack_t = layer._packed_weight(lib, st, transposed=True)
+                    _capi.check(lib.ggcn_linear_out_bf16(ptr(dh), F, ptr(pack_t), ptr(dx), K, B * T, F, K, st), "ggcn_linear_out_bf16(dX)")
+                elif dx_form == "scaled":
                     pack_t = layer._packed_weight(lib, st, transposed=True, precision="f16mx8")
-                    _capi.check(lib.ggcn_linear_scaled(_capi.ptr(dh), F, _capi.ptr(pack_t), _capi.ptr(dx), K, B * T, F, K,
-                                                       _capi.ptr(dh_amax), st), "ggcn_linear_scaled(dX)")
-                elif layer.precision in _capi.PACKED:
+                    _capi.check(lib.ggcn_linear_scaled(ptr(dh), F, ptr(pack_t), ptr(dx), K, B * T, F, K, ptr(dh_amax), st),
+                                "ggcn_linear_scaled(dX)")
+                elif dx_form == "bf16x3":
                     # gradients can be far below fp16's range (f16mx8 would flush them): dX always takes
                     # the bf16x3 linear, which keeps the fp32 exponent range
                     pack_t = layer._packed_weight(lib, st, transposed=True)
-                    _capi.check(lib.ggcn_linear(_capi.ptr(dh), F, None, 0, _capi.ptr(pack_t), _capi.ptr(dx), K,
-                                                B * T, F, K, _capi.PREC["bf16x3"], st), "ggcn_linear(dX)")
+                    _capi.check(lib.ggcn_linear(ptr(dh), F, None, 0, ptr(pack_t), ptr(dx), K, B * T, F, K, _capi.PREC["bf16x3"], st),
+                                "ggcn_linear(dX)")
                 else:   # exact-fp32 mode: W^T as a plain matrix, transposed once per weight update
                     key = (weight.data_ptr(), tensor_version(weight), weight.device)
                     if getattr(layer, "_wt_key", None) != key:
                         layer._wt, layer._wt_key = weight.detach().t().contiguous(), key
-                    wt = layer._wt
-                    _capi.check(lib.ggcn_linear(_capi.ptr(dh), F, _capi.ptr(wt), K, None, _capi.ptr(dx), K,
-                                                B * T, F, K, _capi.PREC["fp32"], st), "ggcn_linear(dX)")
+                    _capi.check(lib.ggcn_linear(ptr(dh), F, ptr(layer._wt), K, None, ptr(dx), K, B * T, F, K, _capi.PREC["fp32"], st),
+                                "ggcn_linear(dX)")
                 dx = dx.view(B, T, K)
-            if need[1] and bf16:
-                x2d = text.reshape(B * T, K)
-                if x2d.stride(1) != 1:
-                    x2d = x2d.contiguous()
-                dw = torch.empty(K, F, dtype=torch.float32, device=dev)
-                ws = torch.empty(lib.ggcn_dweight_bf16_workspace_bytes(B * T, K, F), dtype=torch.uint8, device=dev)
-                _capi.check(lib.ggcn_dweight_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(dh), F, B * T, K, F,
-                                                  _capi.ptr(dw), F, _capi.ptr(ws), st), "ggcn_dweight_bf16")
-            elif need[1]:
-                x2d = text.reshape(B * T, K)
-                if x2d.stride(1) != 1:
-                    x2d = x2d.contiguous()
-                # split-precision layers: bf16x3 on the forward's main loop (fp32 exponent range, ~1e-5);
-                # precision "fp32": the exact fp32 MFMA form, which wants 16-byte aligned rows
-                prec = "bf16x3" if layer.precision in _capi.PACKED else "fp32"
-                dw = torch.empty(K, F, dtype=torch.float32, device=dev)
-                ws = torch.empty(lib.ggcn_dweight_workspace_bytes(B * T, K, F, _capi.PREC[prec]),
-                                 dtype=torch.uint8, device=dev)
-                _capi.check(lib.ggcn_dweight(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(dh), F, B * T, K, F,
-                                             _capi.ptr(dw), F, _capi.PREC[prec], _capi.ptr(ws), st), "ggcn_dweight")
+            if need[1]:
+                x2d = _rows2d(text)
+                dw = torch.empty(K, F, **f32)
+                if dw_form == "bf16":
+                    ws = torch.empty(lib.ggcn_dweight_bf16_workspace_bytes(B * T, K, F), dtype=torch.uint8, device=dev)
+                    _capi.check(lib.ggcn_dweight_bf16(ptr(x2d), x2d.stride(0), ptr(dh), F, B * T, K, F, ptr(dw), F, ptr(ws), st),
+                                "ggcn_dweight_bf16")
+                else:
+                    # split-precision layers: bf16x3 on the forward's main loop (fp32 exponent range, ~1e-5);
+                    # precision "fp32": the exact fp32 MFMA form, which wants 16-byte aligned rows
+                    ws = torch.empty(lib.ggcn_dweight_workspace_bytes(B * T, K, F, _capi.PREC[dw_form]), dtype=torch.uint8, device=dev)
+                    _capi.check(lib.ggcn_dweight(ptr(x2d), x2d.stride(0), ptr(dh), F, B * T, K, F, ptr(dw), F, _capi.PREC[dw_form],
+                                                 ptr(ws), st), "ggcn_dweight")
             if d_bsum is not None:   # db = sum_rows dY: per-graph sums from the pass above, added over the graphs
-                db = torch.empty(F, dtype=torch.float32, device=dev)
+                db = torch.empty(F, **f32)
                 ws = torch.empty(lib.ggcn_colsum_workspace_bytes(F), dtype=torch.uint8, device=dev)
-                _capi.check(lib.ggcn_colsum(_capi.ptr(d_bsum), F, B, F, _capi.ptr(db), _capi.ptr(ws), st), "ggcn_colsum")
+                _capi.check(lib.ggcn_colsum(ptr(d_bsum), F, B, F, ptr(db), ptr(ws), st), "ggcn_colsum")
         return dx, dw, db, d_sg, d_ga, d_gb, None, None, None, None, None, d_adj
 
 
@@ -312,15 +284,10 @@ class GraphConvolution(nn.Module):
         # bfloat16 features: the layer under torch.autocast(dtype=torch.bfloat16) -- float32 out and pools (the reference's
         # `/ denom` promotes), bf16 dX; every split precision runs the bf16 pair form (BF16_PRECISIONS).
         _require_gpu_f32("text", text, allow_half=True, allow_bf16=True)
-        if text.dtype == torch.bfloat16:
-            if self.precision not in BF16_PRECISIONS:
-                raise RuntimeError("bfloat16 features need precision 'bf16x3', 'f16mx8' or 'f16mx6' (all run the bf16 pair form); "
-                                   "precision=%r does not apply to them" % (self.precision,))
-            if text.dim() != 3 or text.shape[2] != self.in_features:
-                raise RuntimeError("text must be [B,T,%d], got %s" % (self.in_features, tuple(text.shape)))
-            if self.weight.device != text.device:
-                raise RuntimeError("weight is on %s but text is on %s" % (self.weight.device, text.device))
-            return
+        bf16 = text.dtype == torch.bfloat16
+        if bf16 and self.precision not in BF16_PRECISIONS:
+            raise RuntimeError("bfloat16 features need precision 'bf16x3', 'f16mx8' or 'f16mx6' (all run the bf16 pair form); "
+                               "precision=%r does not apply to them" % (self.precision,))
         if self.precision == "f16" and text.dtype != torch.float16:
             raise RuntimeError("precision='f16' (plain fp16 MFMA) is for float16 features only; float32 features take "
                                "'bf16x3', 'f16mx8' or 'fp32'")
@@ -331,6 +298,8 @@ class GraphConvolution(nn.Module):
             raise RuntimeError("text must be [B,T,%d], got %s" % (self.in_features, tuple(text.shape)))
         if self.weight.device != text.device:
             raise RuntimeError("weight is on %s but text is on %s" % (self.weight.device, text.device))
+        if bf16:   # every split precision runs the bf16 pair form on the bf16x3 image: nothing below applies
+            return
         if self.precision == "f16mx6" and not _capi.has_f16mx6():
             raise RuntimeError("precision='f16mx6' is an experiment this libggcn_hip.so was built without (make -C "
                                "ed-gated-gcn_amd/csrc F16MX6=1); use 'f16mx8'")
@@ -425,29 +394,14 @@ class GraphConvolution(nn.Module):
         launches (``tools/wide_timing.py``).  The choice depends on the batch size and the device's CU count, and the two
         paths sum in different orders (both inside the parity gate): ``fused_max_t = 256`` (always one launch) or
         ``fused = False`` (never) pin it where bit-reproducibility across batch sizes matters."""
-        if not (self.fused and self.precision in _capi.PACKED and csr.rowmask is not None and csr.is_binary
-                and text.dtype == torch.float32):
-            return False
-        if csr.T <= self.fused_max_t:
-            return True
-        if self.fused_max_t < 128 or csr.T > 256:
-            return False
-        if csr.T >= self.WIDE_AUTO_MIN_T:
-            return True
-        if csr.T < self.WIDE_AUTO_MIN_T_FULL.get(self.precision, 161) or not text.is_cuda:
-            return False
-        wgs = text.shape[0] * ((self.out_features + 255) // 256)
-        cus = torch.cuda.get_device_properties(text.device).multi_processor_count
-        rounds = -(-wgs // cus)
-        return rounds >= 2 and wgs >= self.WIDE_AUTO_FILL * rounds * cus
+        return dispatch.takes_fused(self, csr, dispatch.Input.of(text))
 
     def takes_bf16_fused_path(self, text, csr):
         """True when ``forward_gated`` (inference or the forward of training) runs bfloat16 features as ONE launch
         (``ggcn_layer_fused_bf16``): graphs of <= 32 nodes, 0/1 adjacency, a split precision (``BF16_PRECISIONS``).  Graphs of
         33..256 nodes: ``takes_bf16_wide_path``; gate dropout in either launch: ``takes_bf16_dropout_path``.  Anything else
         (longer graphs, weighted adjacencies) takes ``ggcn_linear_bf16`` + ``ggcn_aggregate``."""
-        return (self.fused and text.dtype == torch.bfloat16 and self.precision in BF16_PRECISIONS and csr.is_binary
-                and csr.T <= 32 and csr.T <= self.fused_max_t and csr.rowmask is not None and csr.rowmask.is_cuda)
+        return dispatch.takes_bf16_fused(self, csr, dispatch.Input.of(text))
 
     BF16_WIDE_MIN_FILL = 0.75   # 33..128 nodes: one launch when the graph fills this share of its 64- or 128-row slot
 
@@ -471,36 +425,19 @@ class GraphConvolution(nn.Module):
 
         The choice depends on the batch size and the device's CU count, and the two paths sum in different orders (both
         inside the parity gate): ``fused_max_t = 256`` or ``fused = False`` pin it."""
-        if not (self.fused and text.dtype == torch.bfloat16 and self.precision in BF16_PRECISIONS and csr.is_binary
-                and csr.rowmask is not None and csr.rowmask.is_cuda and 32 < csr.T <= 256):
-            return False
-        if self.fused_max_t >= 256:
-            return True
-        if csr.T <= 128:
-            slot = 64 if csr.T <= 64 else 128
-            return csr.T <= self.fused_max_t and csr.T >= self.BF16_WIDE_MIN_FILL * slot
-        if self.fused_max_t < 128 or not text.is_cuda:
-            return False
-        wgs = text.shape[0] * ((self.out_features + 255) // 256)
-        cus = torch.cuda.get_device_properties(text.device).multi_processor_count
-        rounds = -(-wgs // cus)
-        return rounds >= 2 and wgs >= self.WIDE_AUTO_FILL * rounds * cus
+        return dispatch.takes_bf16_wide(self, csr, dispatch.Input.of(text))
 
     def takes_bf16_dropout_path(self, text, csr):
         """True when the gates' training-mode dropout (``bert_amir5.py:621-625``) of bfloat16 features is drawn inside the
         layer launch (``ggcn_layer_fused_bf16_drop`` for graphs of <= 32 nodes, ``ggcn_layer_fused_bf16_wide`` up to 256):
         one of the two bf16 one-launch paths and an element index below 2^32."""
-        return ((self.takes_bf16_fused_path(text, csr) or self.takes_bf16_wide_path(text, csr))
-                and text.shape[0] * text.shape[1] * self.out_features < 2 ** 32)
+        return dispatch.takes_bf16_dropout(self, csr, dispatch.Input.of(text))
 
     def takes_weighted_path(self, text, csr):
         """True when ``forward_gated`` (inference) will run a REAL-valued adjacency (``gcn.py:33`` accepts any ``adj``) as ONE
         launch (``ggcn_layer_fused_weighted``): graphs of <= 32 nodes, float32 features, a split-precision linear, every entry
         of D.A_w inside the plane type (``BatchedCSR.graph_ops_weighted``).  Anything else: linear + aggregate."""
-        if not (self.fused and self.precision in _capi.PACKED and not csr.is_binary and csr.T <= 32 and self.fused_max_t >= 32
-                and text.dtype == torch.float32 and text.is_cuda):
-            return False
-        return csr.graph_ops_weighted(0 if self.precision == "bf16x3" else 1) is not None
+        return dispatch.takes_weighted(self, csr, dispatch.Input.of(text))
 
     LONG_MAX_T = 512   # include/ggcn.h GGCN_LONG_MAX_T
 
@@ -508,13 +445,12 @@ class GraphConvolution(nn.Module):
         """True when ``forward_gated`` will run as ONE launch of ``ggcn_layer_fused_h``: half features with
         ``precision="f16"``, graphs of 129..512 nodes (shorter ones leave most of the 512 row slots empty and stay
         with linear + aggregate), K % 64 == 0, F % 8 == 0."""
-        return (self.fused and self.precision == "f16" and text.dtype == torch.float16
-                and 128 < csr.T <= self.LONG_MAX_T and self.in_features % 64 == 0 and self.out_features % 8 == 0)
+        return dispatch.takes_long(self, csr, dispatch.Input.of(text))
 
     def takes_dropout_path(self, text, csr):
         """True when the gates' training-mode dropout (``bert_amir5.py:621-625``) can be drawn inside the layer launch:
         every one-launch form (graphs of <= 256 nodes on the fused path), element index below 2^32."""
-        return self.takes_fused_path(text, csr) and text.shape[0] * text.shape[1] * self.out_features < 2 ** 32
+        return dispatch.takes_dropout(self, csr, dispatch.Input.of(text))
 
     def forward_gated(self, text, adj, store_gate=None, pool_gate_a=None, pool_gate_b=None,
                       want_out=True, want_pool_a=False, want_pool_b=False, _internal=False,
@@ -564,12 +500,13 @@ class GraphConvolution(nn.Module):
             return ((z if want_out else None), (text.new_zeros((0, F), dtype=torch.float32) if want_pool_a else None),
                     (text.new_zeros((0, F), dtype=torch.float32) if want_pool_b else None))
         csr = self._as_csr(adj, text)
-        if not _internal and self._needs_grad(text, store_gate, pool_gate_a, pool_gate_b, adj=adj):
-            # training: the same kernels, wrapped in an autograd Function with a HIP backward
+        training = not _internal and self._needs_grad(text, store_gate, pool_gate_a, pool_gate_b, adj=adj)
+        x2d = None if training else _rows2d(text)
+        path = dispatch.layer_path(self, text, csr, dropout is not None, x2d)
+        if training:   # the same kernels, wrapped in an autograd Function with a HIP backward
             if text.dtype not in (torch.float32, torch.bfloat16):
                 raise RuntimeError("training through the HIP layer needs float32 features (or bfloat16 ones)")
-            if dropout is not None and not (self.takes_dropout_path(text, csr) or self.takes_bf16_dropout_path(text, csr)):
-                raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
+            _admit(path, dropout, False)
             if dropout is not None:
                 # the backward recovers y from the stored out = y*sg*k_store: a token whose store factor is 0 leaves nothing to
                 # recover, which is exact only for pools that drop the same tokens (include/ggcn.h ggcn_gate_pool_backward_drop)
@@ -586,108 +523,62 @@ class GraphConvolution(nn.Module):
                                                     pool_gate_b, self, csr, want_pool_a, want_pool_b, dropout, adj_t)
             return (out if want_out else None), pa, pb
         lib = _capi.load_library()
-        B, T, _ = text.shape
-        F = self.out_features
-        dev = text.device
-        x2d = text.reshape(B * T, self.in_features)
-        if x2d.stride(1) != 1:
-            x2d = x2d.contiguous()
+        (B, T, K), F, dev = text.shape, self.out_features, text.device
         for name, g in (("store_gate", store_gate), ("pool_gate_a", pool_gate_a), ("pool_gate_b", pool_gate_b)):
             if g is not None:
                 _require_gpu_f32(name, g)
-                if tuple(g.shape) != (B, F) or not g.is_contiguous():
-                    raise RuntimeError("%s must be a contiguous [B,F]=[%d,%d] tensor, got %s"
-                                       % (name, B, F, tuple(g.shape)))
-        half = text.dtype == torch.float16
-        bf16 = text.dtype == torch.bfloat16
-        use_fused = self.takes_fused_path(text, csr)
-        use_bf16 = bf16 and self.takes_bf16_fused_path(text, csr)
-        use_bf16_wide = bf16 and self.takes_bf16_wide_path(text, csr)
-        if dropout is not None and not ((use_fused and self.takes_dropout_path(text, csr))
-                                        or ((use_bf16 or use_bf16_wide) and self.takes_bf16_dropout_path(text, csr))):
-            raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
-        if (overlap_partial is not None or overlap_reduce is not None) and not (use_fused or use_bf16 or use_bf16_wide):
-            raise RuntimeError("overlap_partial / overlap_reduce need the one-launch layer (takes_fused_path)")
-        use_long = ((not use_fused) and self.takes_long_path(text, csr) and x2d.data_ptr() % 16 == 0
-                    and x2d.stride(0) % 8 == 0)   # ggcn_layer_fused_h wants 16-byte aligned rows; other views: linear_h + aggregate_h
-        use_weighted = (not use_fused) and dropout is None and self.takes_weighted_path(text, csr)
-        hidden = None if (use_fused or use_long or use_weighted or use_bf16 or use_bf16_wide) else self.linear(x2d)
+                _require_gate(name, g, B, F, "%(name)s must be a contiguous [B,F]=[%(B)d,%(F)d] tensor, got %(shape)s")
+        _admit(path, dropout, overlap_partial is not None or overlap_reduce is not None)
+        hidden = self.linear(x2d) if path == "two_launch" else None
+        ptr = _capi.ptr
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
-            out = torch.empty(B * T, F, dtype=torch.float32 if bf16 else text.dtype, device=dev) if want_out else None
+            out = torch.empty(B * T, F, dtype=torch.float32 if text.dtype == torch.bfloat16 else text.dtype, device=dev) if want_out else None
             pa = torch.empty(B, F, dtype=torch.float32, device=dev) if want_pool_a else None
             pb = torch.empty(B, F, dtype=torch.float32, device=dev) if want_pool_b else None
             bias = None if self.bias is None else self.bias.detach()
-            if use_fused and dropout is not None:
+            # what every entry takes after its operands: the shape, the three gates, the outputs
+            tail = (B, T, K, F, ptr(store_gate), ptr(pool_gate_a), ptr(pool_gate_b), ptr(out), F, ptr(pa), ptr(pb))
+            ov = (ptr(overlap_partial), ptr(overlap_reduce[0]) if overlap_reduce else None, ptr(overlap_reduce[1]) if overlap_reduce else None)
+            drop = _drop_args(dropout)
+            if path == "fused_drop":
                 kprec = "f16mx8" if self.precision == "f16mx6" else self.precision   # the fp6 kernel has no dropout epilogue
                 pack = self._packed_weight(lib, st, precision=kprec)
-                dp, dseed, (ss, sa, sb) = dropout
-                _capi.check(lib.ggcn_layer_fused_drop(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.rowmask), _capi.ptr(csr.graph_ops),
-                                                      _capi.ptr(bias), B, T, self.in_features, F, _capi.ptr(store_gate),
-                                                      _capi.ptr(pool_gate_a), _capi.ptr(pool_gate_b), _capi.ptr(out), F,
-                                                      _capi.ptr(pa), _capi.ptr(pb), _capi.PREC[kprec], float(dp), int(dseed),
-                                                      ss, sa, sb, st), "ggcn_layer_fused_drop")
-                return (None if out is None else out.view(B, T, F)), pa, pb
-            if use_fused:
+                _capi.check(lib.ggcn_layer_fused_drop(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowmask), ptr(csr.graph_ops), ptr(bias),
+                                                      *tail, _capi.PREC[kprec], *drop, st), "ggcn_layer_fused_drop")
+            elif path == "fused":
                 kprec = self.kernel_precision(x2d, csr)
                 pack = self._packed_weight(lib, st, precision=kprec)
-                _capi.check(lib.ggcn_layer_fused(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack),
-                                                 _capi.ptr(csr.rowmask), _capi.ptr(csr.graph_ops if csr.T <= 32 else (csr.edge_lists if os.environ.get("GGCN_EDGE_LISTS", "1") != "0" else None)), _capi.ptr(bias), B, T,
-                                                 self.in_features, F, _capi.ptr(store_gate),
-                                                 _capi.ptr(pool_gate_a), _capi.ptr(pool_gate_b), _capi.ptr(out),
-                                                 F, _capi.ptr(pa), _capi.ptr(pb), _capi.ptr(overlap_partial),
-                                                 _capi.ptr(overlap_reduce[0]) if overlap_reduce else None,
-                                                 _capi.ptr(overlap_reduce[1]) if overlap_reduce else None,
-                                                 _capi.PREC[kprec], st),
-                            "ggcn_layer_fused")
-                return (None if out is None else out.view(B, T, F)), pa, pb
-            if use_bf16 or use_bf16_wide:   # bfloat16 features: one launch on the bf16x3 image (<= 32 nodes; 33..256 on the row masks)
+                _capi.check(lib.ggcn_layer_fused(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowmask),
+                                                 ptr(csr.graph_ops if T <= 32 else dispatch.edge_lists(csr)), ptr(bias),
+                                                 *tail, *ov, _capi.PREC[kprec], st), "ggcn_layer_fused")
+            elif path in ("bf16_wide", "bf16_wide_drop"):   # bfloat16 features, 33..256 nodes: one launch on the bf16x3 image and the row masks
                 pack = self._packed_weight(lib, st, precision="bf16x3")
-                dp, dseed, (ss, sa, sb) = dropout if dropout is not None else (0.0, 0, (0, 0, 0))
-                ov = (_capi.ptr(overlap_partial), _capi.ptr(overlap_reduce[0]) if overlap_reduce else None,
-                      _capi.ptr(overlap_reduce[1]) if overlap_reduce else None)
-                tail = (B, T, self.in_features, F, _capi.ptr(store_gate), _capi.ptr(pool_gate_a), _capi.ptr(pool_gate_b),
-                        _capi.ptr(out), F, _capi.ptr(pa), _capi.ptr(pb)) + ov
-                if use_bf16_wide:
-                    lists = csr.edge_lists if (T > 128 and os.environ.get("GGCN_EDGE_LISTS", "1") != "0") else None
-                    _capi.check(lib.ggcn_layer_fused_bf16_wide(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.rowmask),
-                                                               _capi.ptr(lists), _capi.ptr(bias), *tail, float(dp), int(dseed),
-                                                               ss, sa, sb, st), "ggcn_layer_fused_bf16_wide")
-                elif dropout is not None:
-                    _capi.check(lib.ggcn_layer_fused_bf16_drop(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.graph_ops),
-                                                               _capi.ptr(bias), *tail, float(dp), int(dseed), ss, sa, sb, st),
-                                "ggcn_layer_fused_bf16_drop")
-                else:
-                    _capi.check(lib.ggcn_layer_fused_bf16(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.graph_ops),
-                                                          _capi.ptr(bias), *tail, st), "ggcn_layer_fused_bf16")
-                return (None if out is None else out.view(B, T, F)), pa, pb
-            if use_weighted:   # real-valued adjacency, graphs of <= 32 nodes: one launch on D.A_w operand blocks
+                _capi.check(lib.ggcn_layer_fused_bf16_wide(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowmask),
+                                                           ptr(dispatch.edge_lists(csr) if T > 128 else None), ptr(bias),
+                                                           *tail, *ov, *drop, st), "ggcn_layer_fused_bf16_wide")
+            elif path in ("bf16", "bf16_drop"):   # bfloat16 features, <= 32 nodes: one launch on the bf16x3 image
+                pack = self._packed_weight(lib, st, precision="bf16x3")
+                entry = "ggcn_layer_fused_" + path
+                _capi.check(getattr(lib, entry)(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops), ptr(bias),
+                                                *tail, *ov, *(drop if path == "bf16_drop" else ()), st), entry)
+            elif path == "weighted":   # real-valued adjacency, graphs of <= 32 nodes: one launch on D.A_w operand blocks
                 kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"
                 pack = self._packed_weight(lib, st, precision=kprec)
                 zmid = getattr(self, "_zero_mid", None)
                 if zmid is None or zmid.device != dev or zmid.numel() < F:
                     zmid = self._zero_mid = torch.zeros(F, dtype=torch.float32, device=dev)
-                _capi.check(lib.ggcn_layer_fused_weighted(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack),
-                                                          _capi.ptr(csr.graph_ops_weighted(0 if kprec == "bf16x3" else 1)),
-                                                          _capi.ptr(bias), _capi.ptr(zmid), B, T, self.in_features, F,
-                                                          _capi.ptr(store_gate), _capi.ptr(pool_gate_a), _capi.ptr(pool_gate_b),
-                                                          _capi.ptr(out), F, _capi.ptr(pa), _capi.ptr(pb), None, None, None,
-                                                          _capi.PREC[kprec], st), "ggcn_layer_fused_weighted")
-                return (None if out is None else out.view(B, T, F)), pa, pb
-            if use_long:   # long fp16 graphs (BASELINE configs[3]): linear + aggregation in one launch, hidden stays in LDS
+                _capi.check(lib.ggcn_layer_fused_weighted(ptr(x2d), x2d.stride(0), ptr(pack),
+                                                          ptr(csr.graph_ops_weighted(0 if kprec == "bf16x3" else 1)), ptr(bias), ptr(zmid),
+                                                          *tail, None, None, None, _capi.PREC[kprec], st), "ggcn_layer_fused_weighted")
+            elif path == "long":   # long fp16 graphs (BASELINE configs[3]): linear + aggregation in one launch, hidden stays in LDS
                 pack = self._packed_weight(lib, st)
-                _capi.check(lib.ggcn_layer_fused_h(_capi.ptr(x2d), x2d.stride(0), _capi.ptr(pack), _capi.ptr(csr.rowptr),
-                                                   _capi.ptr(csr.colidx), _capi.ptr(csr.vals), _capi.ptr(bias), B, T,
-                                                   self.in_features, F, _capi.ptr(store_gate), _capi.ptr(pool_gate_a),
-                                                   _capi.ptr(pool_gate_b), _capi.ptr(out), F, _capi.ptr(pa), _capi.ptr(pb), st),
-                            "ggcn_layer_fused_h")
-                return (None if out is None else out.view(B, T, F)), pa, pb
-            agg = lib.ggcn_aggregate_h if half else lib.ggcn_aggregate
-            _capi.check(agg(_capi.ptr(hidden), hidden.stride(0), _capi.ptr(csr.rowptr),
-                                           _capi.ptr(csr.colidx), _capi.ptr(csr.vals), _capi.ptr(bias),
-                                           B, T, F, _capi.ptr(store_gate), _capi.ptr(pool_gate_a),
-                                           _capi.ptr(pool_gate_b), _capi.ptr(out), F, _capi.ptr(pa),
-                                           _capi.ptr(pb), st), "ggcn_aggregate")
+                _capi.check(lib.ggcn_layer_fused_h(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowptr), ptr(csr.colidx), ptr(csr.vals),
+                                                   ptr(bias), *tail, st), "ggcn_layer_fused_h")
+            else:   # "two_launch": the aggregation of `hidden`, gate and pools in its epilogue
+                agg = lib.ggcn_aggregate_h if text.dtype == torch.float16 else lib.ggcn_aggregate
+                _capi.check(agg(ptr(hidden), hidden.stride(0), ptr(csr.rowptr), ptr(csr.colidx), ptr(csr.vals), ptr(bias),
+                                B, T, *tail[3:], st), "ggcn_aggregate")
         return (None if out is None else out.view(B, T, F)), pa, pb
 
     def forward(self, text, adj):

@@ -12,6 +12,7 @@ import torch
 
 from . import _capi
 from .csr import tensor_version
+from .gcn import _rows2d
 
 
 def _transposed(linear, lib, st):
@@ -83,9 +84,7 @@ def scores_and_kl(x, aspect, logits, fc_linear, dist):
     C = logits.shape[1]
     if fc_linear.in_features != 2 * H or fc_linear.out_features != C:
         raise RuntimeError("fc must be Linear(%d, %d)" % (2 * H, C))
-    x2 = x.reshape(B * T, H)
-    if x2.stride(1) != 1:
-        x2 = x2.contiguous()
+    x2 = _rows2d(x)
     a = aspect if aspect.stride(1) == 1 else aspect.contiguous()
     lg = logits if logits.stride(1) == 1 else logits.contiguous()
     d = dist.float()                                   # :648 `dist_to_target.float()`

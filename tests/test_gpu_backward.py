@@ -5,7 +5,8 @@ columns of every strided operand NaN, the workspace pre-filled with 0xFF bytes (
 made twice and compared bit for bit, then against a float64 product of the same operands on the device.
 
 Second half: ``GraphConvolution.forward_gated`` and ``gated_gcn_block`` under autograd against ``oracle/backward_ref.py``
-(float64, torch autograd), one case per branch of ``_GatedLayerFunction.backward``.  Every case counts the library calls its
+(float64, torch autograd), one case per branch of ``_GatedLayerFunction.backward`` -- the pass, dX and dW forms that
+``dispatch.backward_plan`` names.  Every case counts the library calls its
 backward makes and asserts the branch it is named after, so a silent fall-back fails.  Pools whose two largest float64 values
 are closer than 2*TOL/(1-p) get a zero upstream gradient on both sides (``backward_ref.pool_tie_mask``: the reference never sees
 the GPU's picks); at most 3 % of a case's pools may be masked, asserted in every case.
