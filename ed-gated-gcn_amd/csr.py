@@ -61,7 +61,7 @@ class BatchedCSR:
     kernel: all the fused layer needs); the CSR arrays are materialised on first access."""
 
     __slots__ = ("_rowptr", "_colidx", "_vals", "rowmask", "B", "T", "nnz", "is_binary",
-                 "_dense", "_dense_version", "_t", "_inv", "_graph_ops", "_graph_ops2", "_graph_ops_t", "_edge_lists", "_graph_ops_w", "__weakref__")
+                 "_dense", "_dense_version", "_t", "_inv", "_graph_ops", "_graph_ops2", "_graph_ops_t", "_edge_lists", "_graph_ops_w", "_graph_ops_ww", "__weakref__")
 
     def __init__(self, rowptr, colidx, vals, B, T, nnz=None, rowmask=None):
         self._rowptr, self._colidx, self._vals, self.rowmask = rowptr, colidx, vals, rowmask
@@ -76,6 +76,7 @@ class BatchedCSR:
         self._graph_ops_t = None  # cached ggcn_graph_operands blocks of the TRANSPOSED row masks (the MFMA backward)
         self._edge_lists = None   # cached ggcn_graph_edge_lists blocks (graphs of 129..256 nodes: the eight-wavefront layer)
         self._graph_ops_w = None  # cached ggcn_graph_operands_weighted blocks per plane type (real-valued adjacency, <= 32 nodes)
+        self._graph_ops_ww = None  # cached ggcn_graph_operands_weighted_wide blocks (real-valued adjacency, 33..128 nodes); False: refused
 
     @property
     def graph_ops(self):
@@ -161,6 +162,26 @@ class BatchedCSR:
                                                              _capi.stream_of(dev)), "ggcn_graph_operands_weighted")
             store[plane] = None if int(flag.item()) else ops
         return store[plane]
+
+    def graph_ops_weighted_wide(self):
+        """uint8 [``ggcn_graph_operands_weighted_wide_bytes(B, T)``] or None: a REAL-valued adjacency of graphs of 33..128 nodes
+        as the one-launch layer's operand (``ggcn_graph_operands_weighted_wide``: ceil(T/32)^2 blocks of D.A_w per graph as hi /
+        lo bf16 fragments, one form for both split precisions), built from the CSR arrays on first use.  None when an entry is
+        not finite (``rowsum + 1 == 0``; one read-back of the builder's flag per adjacency) or the arrays are not on the GPU:
+        that adjacency keeps linear + aggregate."""
+        if self._graph_ops_ww is None:
+            if not 32 < self.T <= 128 or not self.rowptr.is_cuda:
+                return None
+            lib = _capi.load_library()
+            dev = self.rowptr.device
+            ops = torch.empty(lib.ggcn_graph_operands_weighted_wide_bytes(self.B, self.T), dtype=torch.uint8, device=dev)
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _capi.check(lib.ggcn_graph_operands_weighted_wide(_capi.ptr(self.rowptr), _capi.ptr(self.colidx), _capi.ptr(self.vals),
+                                                                  self.B, self.T, _capi.ptr(ops), _capi.ptr(flag),
+                                                                  _capi.stream_of(dev)), "ggcn_graph_operands_weighted_wide")
+            self._graph_ops_ww = False if int(flag.item()) else ops
+        return None if self._graph_ops_ww is False else self._graph_ops_ww
 
     @property
     def device(self):

@@ -91,6 +91,12 @@ int layer_fused_weighted(const float *X, int64_t ldx, const void *wpack, const v
                          int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
                          float *out, int64_t ldo, float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in,
                          float *overlap_out, int precision, hipStream_t st);
+size_t graph_operands_weighted_wide_bytes(int B, int T);   // fused_wide.hip
+int graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops, int *flag,
+                                 hipStream_t st);
+int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, const void *ops, const float *bias, int B, int T, int K, int F,
+                              const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
+                              float *pool_a, float *pool_b, int precision, hipStream_t st);
 int layer_fused(const float *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops, const float *bias,
                 int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a,
                 const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b,

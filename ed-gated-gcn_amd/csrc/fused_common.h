@@ -28,7 +28,8 @@ struct FusedArgs {
     const float *X;
     int64_t ldx;
     const uint32_t *rowmask;    // graphs of 33..256 nodes (layer_fused_wide_kernel)
-    const char *graph_ops;      // graphs of <= 32 nodes: ggcn_graph_operands blocks (layer_fused_kernel)
+    const char *graph_ops;      // graphs of <= 32 nodes: ggcn_graph_operands blocks (layer_fused_kernel); 129..256: optional edge-list blocks;
+                                // layer_fused_wide_kernel<.., WEIGHTED>: ggcn_graph_operands_weighted_wide blocks (rowmask NULL)
     const char *graph_ops2;     // the block's W12 tiles: ggcn_graph_operands2 blocks ((D.A)^2 in the launch's plane type)
     const float *ov_in;         // partials an EARLIER launch wrote: block 0 reduces them to *ov_out first
     float *ov_out;
@@ -161,6 +162,12 @@ static_assert(kOpsBytes == 2048 + 128, "layout above");
 constexpr int kOps2Bytes = GGCN_GRAPH_OPS2_BYTES;
 static_assert(kOps2Bytes == 4096 + 128, "layout above");
 constexpr float kM2Scale = 1024.0f, kM2InvScale = 1.0f / 1024.0f;
+// ggcn_graph_operands_weighted_wide (graphs of 33..128 nodes, W = ceil(T/32)): per graph W x W blocks, block (io, ii) at
+// (io * W + ii) * GGCN_GRAPH_OPSW_BLOCK_BYTES = rows 32 io .., columns 32 ii .. of M = D.A_w as bf16 A-operand fragments:
+//   [0, 1024) hi part, k-step 0;  [1024, 2048) hi, k-step 1;  [2048, 3072) lo, k-step 0;  [3072, 4096) lo, k-step 1
+//   (lane l at 16 l; element j <-> column 16s + 8(j>>2) + 4h + (j&3) of the block, as expand_mask orders them)
+constexpr int kWOpsBlock = GGCN_GRAPH_OPSW_BLOCK_BYTES;
+static_assert(kWOpsBlock == 4096, "layout above");
 
 
 // acc -> two fp16 planes (hi = RNE fp16(v), lo = fp16(v - hi): residual <= 2^-22 |v| + 2^-25, fp16 subnormals are kept

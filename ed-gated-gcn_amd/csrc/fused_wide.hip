@@ -24,10 +24,21 @@ namespace {
 // pools maximise the gated, kept values themselves (every element has its own factor: no max / min shortcut).
 // XT: element type of the features -- float, or __bf16 (a.Xb; bf16x3 image, two MFMAs per product: bf16x3_core.h); the epilogue
 // works on the float32 accumulators and is the same for both.
-template <int SCH, bool AVEC, bool KFULL, bool VST, int SB, bool DROP = false, typename XT = float>
+// WEIGHTED (ggcn_layer_fused_weighted_wide): a REAL-valued adjacency (gcn.py:33-41 take any `adj`).  No row masks are read: the
+// A operands are the hi / lo bf16 fragments of M = D.A_w that ggcn_graph_operands_weighted_wide left in a.graph_ops (layout:
+// kWOpsBlock in fused_common.h), D already inside, and an output block is
+//     y[io] = sum_ii  Mlo[io][ii].Hhi[ii] + Mhi[io][ii].Hlo[ii] + Mhi[io][ii].Hhi[ii]      (3 x W x 2 MFMAs, small terms first;
+// the lo.lo term is 2^-18 of a term) over the W = ceil(T/32) real blocks only.  Everything after y -- bias, gates, row stores,
+// pools, ov_partial -- is the code of the 0/1 form with the row factor 1.  The fragments of block row io (W x 4 KiB) come from
+// global memory into the registers the 0/1 form spends on masks, expanded fragments and rinv; a load waits 1-2 us in an
+// epilogue (fused_common.h), so the lo fragments of the NEXT block row (the next graph's first one after the last) are
+// requested as soon as the last column tile's lo products have issued and the hi fragments after its hi products: the
+// element-wise work and stores of that tile and the next row's first products run under them.
+template <int SCH, bool AVEC, bool KFULL, bool VST, int SB, bool DROP = false, typename XT = float, bool WEIGHTED = false>
 __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_fused_wide_kernel(const FusedArgs a)
 {
     static_assert(SB == 2 || SB == 4 || SB == 8, "a graph slot is 64, 128 or 256 rows");
+    static_assert(!WEIGHTED || (SB != 8 && !DROP && std::is_same<XT, float>::value), "real-valued adjacency: float32 features, 64- and 128-row slots, no gate dropout");
     static_assert(std::is_same<XT, float>::value || (SCH == 0 && SB != 8), "bf16 features: the bf16x3 main loop, 64- and 128-row slots");
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
@@ -89,7 +100,7 @@ __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_f
         // `pre` (ggcn_layer_fused_prebias): y = D.A.(hidden + 1.pre^T) + bias -- the folded second layer of the eval form, whose
         // input rows are already aggregated once (gated_block.py).  Workgroup-uniform; padding rows are nobody's neighbours.
         // (float32 features only: the bf16 launches refuse `pre`, and without this branch their accumulators are never live twice)
-        if (std::is_same<XT, float>::value && lp.pre) {
+        if (!WEIGHTED && std::is_same<XT, float>::value && lp.pre) {   // (the weighted entry takes no `pre`)
 #pragma unroll
             for (int j = 0; j < RN; ++j) {
                 const int gn = (nt0 + j) * NT + (lane & 31);
@@ -131,6 +142,26 @@ __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_f
     float *stage_lds = reinterpret_cast<float *>(lds) + wave * (32 * 64);
     const int perm_base = 16 * h;
     const int lane_off = 4 * h * ldo + c;
+    // WEIGHTED: the A fragments of one block row, wf[plane][ii][ks] (plane 0 = hi, 1 = lo): 16 bytes per lane and fragment
+    constexpr int WSB = WEIGHTED ? SB : 1;
+    bf16x8 wf[2][WSB][2];
+    // (no branch around a load: a conditional load makes the compiler copy the fragments where the paths meet, and wait for them there)
+    auto fetch_w = [&](int g, int io, int plane) {
+        const char *src = a.graph_ops + ((int64_t)g * W * W + (int64_t)io * W) * kWOpsBlock + plane * 2048 + lane * 16;
+#pragma unroll
+        for (int ii = 0; ii < WSB; ++ii) {
+            const int ic = ii < W ? ii : 0;   // workgroup-uniform: the 128-row slot of a 65..96-node graph has three blocks (the fourth: block 0 again, unused)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) wf[plane][ii][ks] = *reinterpret_cast<const bf16x8 *>(src + ic * kWOpsBlock + ks * 1024);
+        }
+    };
+    // the block row after (graph slot s, block row io) of this workgroup, requested while the current one is finished; after the
+    // last one the current row once more (unused)
+    auto fetch_next_w = [&](int s, int io, int plane) {
+        const int g = g0 + s;
+        const bool row = 32 * (io + 1) < T, graph = s + 1 < GPT && g + 1 < B;
+        fetch_w(row ? g : graph ? g + 1 : g, row ? io + 1 : graph ? 0 : io, plane);
+    };
     auto graphs = [&](auto has_out) {
         constexpr bool vst = VST && decltype(has_out)::value;
         constexpr bool direct_store = !VST && decltype(has_out)::value;
@@ -152,7 +183,9 @@ __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_f
                     m[ii] = okw ? v : 0u;
                 }
             };
-            if constexpr (SB == 8) {
+            if constexpr (WEIGHTED) {
+                if (s == 0) fetch_w(g, 0, 0), fetch_w(g, 0, 1);   // (later graphs: requested under the previous graph's last block row)
+            } else if constexpr (SB == 8) {
                 load_masks(0, mw[0]);
             } else {
 #pragma unroll
@@ -168,33 +201,57 @@ __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_f
                 const int mi = SB == 8 ? (io & 1) : io;
                 if constexpr (SB == 8)
                     if (io + 1 < SB) load_masks(io + 1, mw[(io + 1) & 1]);   // rows past T read as zeros
-                int deg = 0;
-                bf16x8 af[SB][2];
-#pragma unroll
-                for (int ii = 0; ii < SB; ++ii) {
-                    deg += __popc(mw[mi][ii]);
-                    expand_mask(mw[mi][ii] >> (4 * h), af[ii]);
-                }
-                const float inv = 1.0f / (float)(deg + 1);                  // gcn.py:35
+                bf16x8 af[WEIGHTED ? 1 : SB][2];
                 float rinv[16];
+                if constexpr (WEIGHTED) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row0 = (r & 3) + 8 * (r >> 2);
-                    rinv[r] = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_base + 4 * row0, __float_as_int(inv)));
+                    for (int r = 0; r < 16; ++r) rinv[r] = 1.0f;   // D is inside the operand
+                } else {
+                    int deg = 0;
+#pragma unroll
+                    for (int ii = 0; ii < SB; ++ii) {
+                        deg += __popc(mw[mi][ii]);
+                        expand_mask(mw[mi][ii] >> (4 * h), af[ii]);
+                    }
+                    const float inv = 1.0f / (float)(deg + 1);                  // gcn.py:35
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row0 = (r & 3) + 8 * (r >> 2);
+                        rinv[r] = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_base + 4 * row0, __float_as_int(inv)));
+                    }
                 }
 #pragma unroll
                 for (int j = 0; j < RN; ++j) {
-                    if (nt0 + j >= n_tiles_total) break;  // wavefront-uniform: column tile past F
+                    // wavefront-uniform: column tile past F (WEIGHTED: a live wavefront computes it unstored -- the requests for the next
+                    // block row ride in the last tile's products, and a branch around them would stall them: fetch_w)
+                    if (!WEIGHTED && nt0 + j >= n_tiles_total) break;
                     f32x16 y;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) y[r] = 0.0f;
+                    if constexpr (WEIGHTED) {
+                        const bool last_tile = j == RN - 1;   // its products free the fragments for the next block row's
 #pragma unroll
-                    for (int p = 1; p >= 0; --p)  // small plane first
+                        for (int t = 0; t < 3; ++t) {   // Mlo.Hhi, Mhi.Hlo, Mhi.Hhi: small terms first
+                            const int pm = t == 0 ? 1 : 0, ph = t == 1 ? 1 : 0;
 #pragma unroll
-                        for (int ii = 0; ii < SB; ++ii)
+                            for (int ii = 0; ii < SB; ++ii) {
+                                if (ii >= W) break;   // workgroup-uniform
 #pragma unroll
-                            for (int ks = 0; ks < 2; ++ks)
-                                y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ii][ks], hf[s * SB + ii][j][p][ks], y, 0, 0, 0);   // gcn.py:41
+                                for (int ks = 0; ks < 2; ++ks)
+                                    y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[pm][ii][ks], hf[s * SB + ii][j][ph][ks], y, 0, 0, 0);   // gcn.py:41
+                            }
+                            if (last_tile && t == 0) fetch_next_w(s, io, 1);
+                            if (last_tile && t == 2) fetch_next_w(s, io, 0);
+                        }
+                    } else {
+#pragma unroll
+                        for (int p = 1; p >= 0; --p)  // small plane first
+#pragma unroll
+                            for (int ii = 0; ii < SB; ++ii)
+#pragma unroll
+                                for (int ks = 0; ks < 2; ++ks)
+                                    y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ii][ks], hf[s * SB + ii][j][p][ks], y, 0, 0, 0);   // gcn.py:41
+                    }
                     float *tile = decltype(has_out)::value ? out + ((int64_t)g * T + node0) * ldo + (nt0 + j) * NT : nullptr;
                     const float sg = store_gate ? vsg[s][j] : 1.0f;
                     const float bj = bias ? vb[j] : 0.0f;
@@ -269,10 +326,73 @@ __global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_f
             }
         }
     };
+    if (WEIGHTED && nt0 >= n_tiles_total) return;   // wavefront-uniform: both column tiles past F (no barrier follows the main loop)
     if (out) graphs(std::true_type{});
     else graphs(std::false_type{});
 }
 
+
+// ggcn_graph_operands_weighted_wide: a REAL-valued adjacency of graphs of 33..128 nodes as the WEIGHTED kernel's A operands.
+// M = D.A_w with D = diag(1 / (rowsum(A_w) + 1)) (gcn.py:35) folded in; bf16 keeps fp32's exponent, so no power-of-two scale
+// rides along (the <= 32-node form scales by 2^10 for its fp16 planes).  One wavefront per 32 x 32 block (graph, io, ii):
+// lane (r, h) walks row 32 io + r of the CSR -- the whole row, in CSR order, so that its rowsum is the number ggcn_aggregate
+// and ggcn_inv_denominators compute -- and keeps the 16 columns of block column ii its fragments hold.  Rows >= T and columns
+// >= T stay zero.  flag (optional): bit 0 when an entry is not finite (rowsum + 1 == 0 makes every entry of the row inf or NaN).
+__global__ __launch_bounds__(256) void graph_operands_ww_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
+                                                                const float *__restrict__ vals, int B, int T, int W, char *__restrict__ ops,
+                                                                int *__restrict__ flag)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int WW = W * W;
+    if (blk >= (int64_t)B * WW) return;   // wavefront-uniform
+    const int g = (int)(blk / WW), io = (int)(blk % WW) / W, ii = (int)(blk % WW) % W;
+    const int r = lane & 31, h = lane >> 5;
+    const int64_t node0 = (int64_t)g * T;
+    const int row = 32 * io + r;
+    float a[16], wsum = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) a[e] = 0.0f;
+    if (row < T) {
+        auto take = [&](int col, float w) {
+            const int c = col - (int)node0 - 32 * ii;
+            wsum += w;
+            // column c of the block sits in k-step c >> 4 as element 4 ((c >> 3) & 1) + (c & 3) of the lane half (c >> 2) & 1
+            const int idx = ((unsigned)c < 32u && ((c >> 2) & 1) == h) ? (c >> 4) * 8 + ((c >> 3) & 1) * 4 + (c & 3) : -1;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) a[q] += idx == q ? w : 0.0f;
+        };
+        const int e1 = rowptr[node0 + row + 1];
+        int e = rowptr[node0 + row];
+        for (; e + 4 <= e1; e += 4) {   // four edges per trip, their loads in flight together (a dense row is 128 dependent trips otherwise); CSR order kept
+            int cj[4];
+            float wj[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { cj[q] = colidx[e + q]; wj[q] = vals ? vals[e + q] : 1.0f; }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) take(cj[q], wj[q]);
+        }
+        for (; e < e1; ++e) take(colidx[e], vals ? vals[e] : 1.0f);
+    }
+    const float inv = 1.0f / (wsum + 1.0f);   // gcn.py:35
+    char *dst = ops + blk * kWOpsBlock;
+    bool bad = false;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        union { uint4 q; unsigned short u[8]; } hi, lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float v = a[8 * s + e] * inv;
+            bad = bad || !(fabsf(v) < 3.0e38f);
+            const __bf16 vh = (__bf16)v, vl = (__bf16)(v - (float)vh);
+            hi.u[e] = __builtin_bit_cast(unsigned short, vh);
+            lo.u[e] = __builtin_bit_cast(unsigned short, vl);
+        }
+        *reinterpret_cast<uint4 *>(dst + s * 1024 + lane * 16) = hi.q;
+        *reinterpret_cast<uint4 *>(dst + 2048 + s * 1024 + lane * 16) = lo.q;
+    }
+    if (bad && flag) atomicOr(flag, 1);
+}
 
 }  // namespace
 
@@ -315,6 +435,83 @@ int launch_fused_wide(const char *who, const FusedArgs &a, int precision, int sb
 #undef GGCN_PICKW
 #undef GGCN_PICKWD
 #undef GGCN_LAUNCHW
+    return check_launch(who);
+}
+
+size_t graph_operands_weighted_wide_bytes(int B, int T)
+{
+    if (B <= 0 || T <= 32 || T > 128) return 0;
+    const size_t W = (size_t)(T + 31) / 32;
+    return (size_t)B * W * W * kWOpsBlock;
+}
+
+int graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops, int *flag,
+                                 hipStream_t st)
+{
+    const char *who = "ggcn_graph_operands_weighted_wide";
+    if (!rowptr || !colidx || !ops) return fail(GGCN_EINVAL, "%s: null pointer", who);
+    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d must be positive", who, B, T);
+    if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32 (one block per graph: ggcn_graph_operands_weighted)", who, T);
+    if (T > 128) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 128 (weighted graphs of more nodes: ggcn_linear + ggcn_aggregate)", who, T);
+    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: the blocks must be 16-byte aligned", who);
+    if ((int64_t)B * T >= (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: B*T does not fit int32 node ids", who);
+    const int W = (T + 31) >> 5;
+    const int64_t grid = ((int64_t)B * W * W + 3) / 4;
+    if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
+    hipLaunchKernelGGL(graph_operands_ww_kernel, dim3((unsigned)grid), dim3(256), 0, st, rowptr, colidx, vals, B, T, W, static_cast<char *>(ops), flag);
+    return check_launch(who);
+}
+
+// gcn.py:30-45 with a real-valued adjacency for graphs of 33..128 nodes in ONE launch: layer_fused_wide_kernel<.., WEIGHTED> on
+// ggcn_graph_operands_weighted_wide blocks.  The argument checks are launch_fused's (fused_layer.hip) for one part.
+int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, const void *ops, const float *bias, int B, int T, int K, int F,
+                              const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
+                              float *pool_a, float *pool_b, int precision, hipStream_t st)
+{
+    const char *who = "ggcn_layer_fused_weighted_wide";
+    if (precision != GGCN_PREC_BF16X3 && precision != GGCN_PREC_F16MX8)
+        return fail(GGCN_EUNSUPPORTED, "%s: precision %d (bf16x3 or f16mx8)", who, precision);
+    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
+    if (!ops) return fail(GGCN_EINVAL, "%s: the weighted operand blocks are required", who);
+    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: the operand blocks must be 16-byte aligned", who);
+    if (B <= 0 || T <= 0 || K <= 0 || F <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d K=%d F=%d must be positive", who, B, T, K, F);
+    if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32 (ggcn_layer_fused_weighted)", who, T);
+    if (T > 128) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 128 (use ggcn_linear + ggcn_aggregate)", who, T);
+    if (ldx < K) return fail(GGCN_EINVAL, "%s: ldx < K", who);
+    if (!wpack) return fail(GGCN_EINVAL, "%s: null weight image", who);
+    if (!aligned16(wpack)) return fail(GGCN_EINVAL, "%s: wpack must be 16-byte aligned", who);
+    if (!out && !pool_a && !pool_b) return fail(GGCN_EINVAL, "%s: no output requested", who);
+    bool vst = false;
+    if (out) {
+        if (ldo < F) return fail(GGCN_EINVAL, "%s: leading dimension of the output too small", who);
+        if (ldo > (int64_t)INT32_MAX || (int64_t)T * ldo >= (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: T*ldo does not fit 32-bit offsets", who);
+        vst = (F % 4 == 0) && (ldo % 4 == 0) && aligned16(out) && (int64_t)T * ldo * 4 < ((int64_t)1 << 31);
+    }
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.graph_ops = static_cast<const char *>(ops);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, nullptr, nullptr, store_gate, pool_gate_a, pool_gate_b,
+                          out, pool_a, pool_b, nullptr, (int)ldo};
+    const bool fast = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(X) && (int64_t)ldx * 4 * 257 < ((int64_t)1 << 31) && (K % BK == 0);
+    a.k_steps = round_up(K, BK) / KSTEP;
+    a.n_wg = (F + BN - 1) / BN;
+    const int sb = T <= 64 ? 2 : 4;
+    const int64_t gt = sb == 2 ? ((int64_t)B + 1) / 2 : B;   // two graphs per workgroup in the 64-row slot
+    const int64_t gridw = grid_for(gt, a.n_wg);
+    if (gridw > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
+    a.g_tiles = (int)gt;
+#define GGCN_LAUNCHWW(SC, AV, KF, VS, SBV) \
+    hipLaunchKernelGGL((layer_fused_wide_kernel<SC, AV, KF, VS, SBV, false, float, true>), dim3((unsigned)gridw), dim3(kThreads), 0, st, a)
+#define GGCN_PICKWW(SC, SBV)                                                 \
+    do {                                                                     \
+        if (fast && vst) GGCN_LAUNCHWW(SC, true, true, true, SBV);           \
+        else if (fast) GGCN_LAUNCHWW(SC, true, true, false, SBV);            \
+        else GGCN_LAUNCHWW(SC, false, false, false, SBV);                    \
+    } while (0)
+    if (precision == GGCN_PREC_F16MX8) { if (sb == 2) GGCN_PICKWW(1, 2); else GGCN_PICKWW(1, 4); }
+    else { if (sb == 2) GGCN_PICKWW(0, 2); else GGCN_PICKWW(0, 4); }
+#undef GGCN_PICKWW
+#undef GGCN_LAUNCHWW
     return check_launch(who);
 }
 

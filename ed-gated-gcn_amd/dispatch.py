@@ -96,9 +96,12 @@ def takes_bf16_dropout(layer, csr, inp):
 
 
 def takes_weighted(layer, csr, inp):
-    return bool(layer.fused and layer.precision in _capi.PACKED and not csr.is_binary and csr.T <= 32 and layer.fused_max_t >= 32
-                and inp.dtype == torch.float32 and inp.gpu is not None
-                and csr.graph_ops_weighted(0 if layer.precision == "bf16x3" else 1) is not None)
+    if not (layer.fused and layer.precision in _capi.PACKED and not csr.is_binary and inp.dtype == torch.float32 and inp.gpu is not None):
+        return False
+    if csr.T <= 32:
+        return bool(layer.fused_max_t >= 32 and csr.graph_ops_weighted(0 if layer.precision == "bf16x3" else 1) is not None)
+    # 33..128 nodes: the opt-in ``weighted_max_t`` (32 by default) -- looked at BEFORE the graph is asked for its operand blocks
+    return bool(csr.T <= min(getattr(layer, "weighted_max_t", 32), 128) and csr.graph_ops_weighted_wide() is not None)
 
 
 def takes_long(layer, csr, inp):

@@ -216,6 +216,11 @@ class GraphConvolution(nn.Module):
         # the folded evaluation of 33..256-node graphs (gated_block.takes_bf16_block_path / takes_bf16_folded_eval_path).  Off by
         # default: the fold sums in another order than the two layer launches (both inside the parity gate).
         self.bf16_block = bool(getattr(opt, "ggcn_bf16_block", False)) or os.environ.get("GGCN_BF16_BLOCK", "0") == "1"
+        # real-valued adjacency (a soft or learned graph), float32 features: graphs of up to weighted_max_t nodes run as ONE launch.
+        # 32 by default (ggcn_layer_fused_weighted); 128 adds graphs of 33..128 nodes (ggcn_layer_fused_weighted_wide,
+        # takes_weighted_path has the measurements); larger values mean 128.  Off by default: its sums differ from linear +
+        # aggregate's in the last bits (both inside the parity gate).
+        self.weighted_max_t = int(getattr(opt, "ggcn_weighted_max_t", None) or os.environ.get("GGCN_WEIGHTED_MAX_T", "32"))
         # dense adjacency handed to forward(): None = let the device detect edge weights (one 4-byte
         # read-back per conversion), True = promise 0/1 entries like the reference's (graph.py:66-74)
         # and stay sync-free, False = always keep the values
@@ -434,9 +439,23 @@ class GraphConvolution(nn.Module):
         return dispatch.takes_bf16_dropout(self, csr, dispatch.Input.of(text))
 
     def takes_weighted_path(self, text, csr):
-        """True when ``forward_gated`` (inference) will run a REAL-valued adjacency (``gcn.py:33`` accepts any ``adj``) as ONE
-        launch (``ggcn_layer_fused_weighted``): graphs of <= 32 nodes, float32 features, a split-precision linear, every entry
-        of D.A_w inside the plane type (``BatchedCSR.graph_ops_weighted``).  Anything else: linear + aggregate."""
+        """True when ``forward_gated`` (inference, and the forward under autograd) will run a REAL-valued adjacency (``gcn.py:33``
+        accepts any ``adj``) as ONE launch: ``fused``, float32 features on a GPU, a split-precision linear, and
+
+        * graphs of <= 32 nodes (``ggcn_layer_fused_weighted``): every entry of D.A_w inside the plane type
+          (``BatchedCSR.graph_ops_weighted``);
+        * graphs of 33..``min(weighted_max_t, 128)`` nodes (``ggcn_layer_fused_weighted_wide``) -- ``weighted_max_t`` is 32 by
+          default, so this is OPT-IN (``opt.ggcn_weighted_max_t = 128`` / ``GGCN_WEIGHTED_MAX_T=128``): every entry of D.A_w finite
+          (``BatchedCSR.graph_ops_weighted_wide``: ceil(T/32)^2 blocks of hi / lo bf16 fragments per graph, built once per
+          adjacency tensor, one read-back).  The option is looked at before the graph is asked for anything.
+
+        Anything else -- gate dropout included -- takes linear + aggregate.  The 33..128 launch WINS ON SPARSE AND ON DENSE graphs
+        (``tools/weighted_wide_timing.py``, one MI355X, H = 768, f16mx8 / bf16x3, us): 512 x 100 with 3 edges per
+        row 189 / 237 vs 226 / 251 (the 0/1 launch on the same pattern: 180 / 225), 1024 x 64: 195 / 235 vs 286 / 319, 512 x 128:
+        203 / 248 vs 277 / 313; dense softmax rows 512 x 100: 197 / 244 vs 935 / 943, 1024 x 64: 197 / 243 vs 801 / 825, 512 x 128:
+        222 / 268 vs 1389 / 1396.  The operand builder adds 10-15 us (sparse) or 62-229 us (dense) per NEW adjacency tensor -- a
+        learned graph pays it every step and still wins (512 x 128 dense: 451 vs 1389).  It stays an option because the two
+        paths sum in different orders (2.7e-6..1.2e-5 of the output scale apart, both inside the parity gate)."""
         return dispatch.takes_weighted(self, csr, dispatch.Input.of(text))
 
     LONG_MAX_T = 512   # include/ggcn.h GGCN_LONG_MAX_T
@@ -562,6 +581,11 @@ class GraphConvolution(nn.Module):
                 entry = "ggcn_layer_fused_" + path
                 _capi.check(getattr(lib, entry)(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops), ptr(bias),
                                                 *tail, *ov, *(drop if path == "bf16_drop" else ()), st), entry)
+            elif path == "weighted" and T > 32:   # real-valued adjacency, 33..128 nodes (weighted_max_t): one launch on ceil(T/32)^2 blocks of D.A_w
+                kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"
+                pack = self._packed_weight(lib, st, precision=kprec)
+                _capi.check(lib.ggcn_layer_fused_weighted_wide(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops_weighted_wide()), ptr(bias),
+                                                               *tail, _capi.PREC[kprec], st), "ggcn_layer_fused_weighted_wide")
             elif path == "weighted":   # real-valued adjacency, graphs of <= 32 nodes: one launch on D.A_w operand blocks
                 kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"
                 pack = self._packed_weight(lib, st, precision=kprec)

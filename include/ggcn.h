@@ -370,6 +370,39 @@ int ggcn_layer_fused_weighted(const float *X, int64_t ldx, const void *wpack, co
                               float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out, int precision,
                               ggcn_stream_t stream);
 
+/* The same for graphs of 33..128 nodes (LitBank: ORI_ML = 100, constant.py:227 -- a learned or soft adjacency at the lengths
+ * the reference trains on), float32 features.
+ * ggcn_graph_operands_weighted_wide turns the batched CSR with its weights (vals; NULL = all ones) into W x W blocks per
+ * graph, W = ceil(T/32): block (io, ii) -- rows 32 io .. 32 io + 31, columns 32 ii .. 32 ii + 31 of M = D.A_w,
+ * D = diag(1 / (rowsum(A_w) + 1)) (gcn.py:35) -- lies at ((g * W + io) * W + ii) * GGCN_GRAPH_OPSW_BLOCK_BYTES and holds
+ *     [0, 1024) hi = bf16(M), k-step 0;  [1024, 2048) hi, k-step 1;  [2048, 3072) lo = bf16(M - hi), k-step 0;  [3072, 4096) lo, k-step 1
+ * each as 64 lanes x 16 bytes in the A-operand order of v_mfma_f32_32x32x16_bf16 (lane l: row l & 31, h = l >> 5; element j of
+ * k-step s = column 16 s + 8 (j >> 2) + 4 h + (j & 3) of the block).  Rows and columns >= T are zero.  The planes are bf16 for
+ * both precisions: the 33..128-node kernel holds `hidden` as bf16 planes whatever its main loop is.
+ * D IS FOLDED INTO THE OPERAND, without a power-of-two scale: bf16 has fp32's exponent range, so D.A_w needs none (the <= 32
+ * form scales by 2^10 for its fp16 planes), the kernel then applies no row factor at all -- the 16 registers and 16 cross-lane
+ * moves per block row the 0/1 form spends on 1 / (deg + 1) carry operand fragments instead -- and no second array travels
+ * beside the blocks.  A row's weights are summed in CSR order, as ggcn_aggregate and ggcn_inv_denominators sum them: D is the
+ * same number on both paths (the products w * (1 / (rowsum + 1)) round once more than ggcn_aggregate's (sum w.h) * inv).
+ * Size: ggcn_graph_operands_weighted_wide_bytes(B, T) = B * W * W * 4096 (0 for T outside 33..128 or B <= 0); 16-byte aligned.
+ * *flag (optional, device memory, zeroed by the caller) gets bit 0 when an entry is not finite (rowsum + 1 == 0: mixed-sign
+ * weights can do that) -- such an adjacency stays with ggcn_linear + ggcn_aggregate.
+ * Refusals: T <= 32 -> GGCN_EUNSUPPORTED (ggcn_graph_operands_weighted is the one-block form); T > 128 -> GGCN_EUNSUPPORTED;
+ * null rowptr / colidx / blocks, B <= 0 -> GGCN_EINVAL.
+ * ggcn_layer_fused_weighted_wide is ggcn_layer_fused on those blocks: per 32 x 32 output tile 3 x W x 2 bf16 MFMAs
+ * (Mlo.Hhi, Mhi.Hlo, Mhi.Hhi, small terms first; the lo.lo term is 2^-18 of a term) where the 0/1 form needs 2 x SB x 2, then
+ * the 0/1 form's own epilogue (bias, store gate, both pools).  precision GGCN_PREC_BF16X3 or GGCN_PREC_F16MX8; 33 <= T <= 128
+ * (else GGCN_EUNSUPPORTED); ldx >= K, ldo >= F, 16-byte aligned weight image and blocks, at least one output (else
+ * GGCN_EINVAL).  Inference form (no gate dropout, no regulariser partials); other arguments as in ggcn_layer_fused. */
+#define GGCN_GRAPH_OPSW_BLOCK_BYTES 4096
+size_t ggcn_graph_operands_weighted_wide_bytes(int B, int T);
+int ggcn_graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T,
+                                      void *graph_opsww, int32_t *flag, ggcn_stream_t stream);
+int ggcn_layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, const void *graph_opsww, const float *bias,
+                                   int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a,
+                                   const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b, int precision,
+                                   ggcn_stream_t stream);
+
 /* ---- the whole gated block in one launch (graphs of <= 32 nodes, binary adjacency, inference) ----
  * Replaces models/bert_amir5.py:626-640 -- gc1, both gates, both max-pools, gc2, its gate and pool -- with
  * ONE launch that reads X once and never writes gcn1 unless asked to.  The reference feeds gc2 with the

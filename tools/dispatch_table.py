@@ -95,7 +95,7 @@ def pretend_device():
     props, zeros = torch.cuda.get_device_properties, torch.zeros
     torch.cuda.get_device_properties = lambda device=None: types.SimpleNamespace(multi_processor_count=CUS)
     torch.zeros = lambda *a, **k: zeros(*a, **k).as_subclass(GpuMeta)
-    saved = {k: os.environ.pop(k) for k in ("GGCN_PRECISION", "GGCN_FUSED", "GGCN_FUSED_MAX_T", "GGCN_BF16_BLOCK") if k in os.environ}
+    saved = {k: os.environ.pop(k) for k in ("GGCN_PRECISION", "GGCN_FUSED", "GGCN_FUSED_MAX_T", "GGCN_BF16_BLOCK", "GGCN_WEIGHTED_MAX_T") if k in os.environ}
     try:
         yield
     finally:
