@@ -61,7 +61,7 @@ class BatchedCSR:
     kernel: all the fused layer needs); the CSR arrays are materialised on first access."""
 
     __slots__ = ("_rowptr", "_colidx", "_vals", "rowmask", "B", "T", "nnz", "is_binary",
-                 "_dense", "_dense_version", "_t", "_inv", "_graph_ops", "_graph_ops2", "_graph_ops_t", "_edge_lists", "_graph_ops_w", "_graph_ops_ww", "__weakref__")
+                 "_dense", "_dense_version", "_t", "_inv", "_graph_ops", "_graph_ops2", "_graph_ops_t", "_edge_lists", "_graph_ops_w", "_graph_ops_ww", "_graph_ops_wt", "__weakref__")
 
     def __init__(self, rowptr, colidx, vals, B, T, nnz=None, rowmask=None):
         self._rowptr, self._colidx, self._vals, self.rowmask = rowptr, colidx, vals, rowmask
@@ -77,6 +77,7 @@ class BatchedCSR:
         self._edge_lists = None   # cached ggcn_graph_edge_lists blocks (graphs of 129..256 nodes: the eight-wavefront layer)
         self._graph_ops_w = None  # cached ggcn_graph_operands_weighted blocks per plane type (real-valued adjacency, <= 32 nodes)
         self._graph_ops_ww = None  # cached ggcn_graph_operands_weighted_wide blocks (real-valued adjacency, 33..128 nodes); False: refused
+        self._graph_ops_wt = None  # cached ggcn_graph_operands_weighted_t blocks (A_w^T of <= 32 nodes: the weighted backward); False: refused
 
     @property
     def graph_ops(self):
@@ -182,6 +183,26 @@ class BatchedCSR:
                                                                   _capi.stream_of(dev)), "ggcn_graph_operands_weighted_wide")
             self._graph_ops_ww = False if int(flag.item()) else ops
         return None if self._graph_ops_ww is False else self._graph_ops_ww
+
+    def graph_ops_weighted_t(self):
+        """uint8 [``ggcn_graph_operands_weighted_t_bytes(B)``] or None: A_w^T of a REAL-valued adjacency of graphs of <= 32 nodes
+        as three bf16 planes, the A operand of the backward's ``dH = A_w^T . D . dY`` on the matrix cores
+        (``ggcn_gate_pool_backward_weighted``), built from the CSR arrays on first use -- no transposed CSR.  None for graphs of
+        more than 32 nodes, arrays that are not on the GPU, or an entry that is not finite (one read-back of the builder's flag per
+        adjacency): that adjacency keeps ``ggcn_gate_pool_backward`` + ``ggcn_aggregate_t``."""
+        if self._graph_ops_wt is None:
+            if self.T > 32 or not self.rowptr.is_cuda:
+                return None
+            lib = _capi.load_library()
+            dev = self.rowptr.device
+            ops = torch.empty(lib.ggcn_graph_operands_weighted_t_bytes(self.B), dtype=torch.uint8, device=dev)
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _capi.check(lib.ggcn_graph_operands_weighted_t(_capi.ptr(self.rowptr), _capi.ptr(self.colidx), _capi.ptr(self.vals),
+                                                               self.B, self.T, _capi.ptr(ops), _capi.ptr(flag),
+                                                               _capi.stream_of(dev)), "ggcn_graph_operands_weighted_t")
+            self._graph_ops_wt = False if int(flag.item()) else ops
+        return None if self._graph_ops_wt is False else self._graph_ops_wt
 
     @property
     def device(self):

@@ -135,6 +135,13 @@ int gate_pool_backward_mma(const float *out, int64_t ldo, const float *store_gat
                            const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops,
                            const void *graph_ops_t, int B, int T, int F, float *dH, int64_t ldh, float *d_sg, float *d_ga,
                            float *d_gb, float *d_bsum, float *dh_amax, hipStream_t st);
+size_t graph_operands_weighted_t_bytes(int B);   // gate_pool_backward_weighted.hip
+int graph_operands_weighted_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops, int *flag,
+                              hipStream_t st);
+int gate_pool_backward_weighted(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
+                                const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wt,
+                                const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
+                                float *d_ga, float *d_gb, float *d_bsum, hipStream_t st);
 size_t colsum_workspace_bytes(int F);
 int colsum(const float *X, int64_t ld, int64_t M, int F, float *out, void *workspace, hipStream_t st);
 

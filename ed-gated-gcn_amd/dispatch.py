@@ -155,6 +155,24 @@ def backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands):
     return passes, ("scaled" if scaled else dw if need_x else None), dw
 
 
+def takes_weighted_backward(layer, csr, F, dropout, operands):
+    """True when the backward of a layer on a REAL-valued adjacency runs its gate / pool pass AND ``dH = A_w^T . D . dY`` as ONE
+    launch on the matrix cores (``ggcn_gate_pool_backward_weighted``) where ``backward_plan`` says "two_pass": the option
+    ``layer.weighted_backward`` (``opt.ggcn_weighted_backward`` / ``GGCN_WEIGHTED_BACKWARD=1``; OFF by default), a real-valued
+    adjacency of graphs of <= 32 nodes, F % 4 == 0, no gate dropout, every operand 16-byte aligned, ``GGCN_BACKWARD_TWO_PASS``
+    not set, and -- asked last, so that a refused call builds nothing -- the graph's A_w^T operand
+    (``BatchedCSR.graph_ops_weighted_t``: None when an entry is not finite).  It replaces ``ggcn_gate_pool_backward`` +
+    ``BatchedCSR.transposed()`` + ``ggcn_aggregate_t``; dY is written only for an adjacency gradient; the dX / dW forms stay the
+    plan's.  float32 and bfloat16 features alike (``out``, dY and dH are float32 in both).
+    NOT MEASURED yet: ``tools/weighted_backward_timing.py`` (option off against on in one process: the replaced stage with its
+    per-adjacency builders, and the whole layer backward, at 4096 x 32 x 768 sparse / dense softmax and 512 x 24 x 768) has not run
+    on an MI355X, so how much the one launch saves over the two calls is unknown, and the option stays opt-in whatever it shows.
+    The compiler's report: 165 VGPRs, no scratch, three workgroups per CU."""
+    return bool(getattr(layer, "weighted_backward", False) and not csr.is_binary and csr.T <= 32 and F % 4 == 0 and dropout is None
+                and all(t is None or t.data_ptr() % 16 == 0 for t in operands)
+                and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1" and csr.graph_ops_weighted_t() is not None)
+
+
 # ---- the block of two layers (the four predicates are gated_block's public ones) -------------------------------------------------
 def bf16_block_on(x, gc1):
     """The opt-in of the bf16 block forms (``GraphConvolution.bf16_block``) on bfloat16 GPU features."""

@@ -65,7 +65,9 @@ class _GatedLayerFunction(torch.autograd.Function):
     epilogue).  Backward, for y = D.A.(X.W) + b, out = y*sg, pa = max_t y*ga, pb = max_t y*gb:
 
         dY, d_sg, d_ga, d_gb   HIP, one pass over the stored output (gate_pool_backward.hip)
-        dH = A^T.(D.dY)        HIP, one wavefront per SOURCE node on the transposed CSR
+        dH = A^T.(D.dY)        HIP, one wavefront per SOURCE node on the transposed CSR (0/1 graphs of <= 32 nodes: one launch with
+                               the line above, dispatch.backward_plan; real-valued ones with ``weighted_backward``:
+                               ggcn_gate_pool_backward_weighted, dispatch.takes_weighted_backward)
         dX = dH.W^T            HIP bf16x3 MFMA linear on the packed W^T (bfloat16 features: stored as bf16, RNE)
         dW = X^T.dH            HIP split-K: bf16x3 main loop on X^T and packed dH (dweight_bx3.hip; bfloat16 features:
                                X^T in bf16, ggcn_dweight_bf16), or the exact-fp32 MFMA form for precision 'fp32' (dweight_fp32.hip)
@@ -118,20 +120,28 @@ class _GatedLayerFunction(torch.autograd.Function):
             d_bsum = torch.empty(B, F, **f32) if (ctx.has_bias and need[2]) else None
             dh = torch.empty(B * T, F, **f32)
             need_adj = ctx.adj_dtype is not None and need[11]
-            passes, dx_form, dw_form = dispatch.backward_plan(layer, csr, text.dtype, K, F, need[0], need_adj, ctx.dropout, (
-                out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum))
-            two_pass = passes in ("two_pass", "two_pass_drop")   # dY to memory, then dH = A^T.(D.dY) on the transposed CSR
+            operands = (out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum)
+            passes, dx_form, dw_form = dispatch.backward_plan(layer, csr, text.dtype, K, F, need[0], need_adj, ctx.dropout, operands)
+            # a real-valued adjacency of <= 32 nodes, opt-in: the two passes as one launch on the matrix cores (dY only for d_adj)
+            weighted = passes == "two_pass" and dispatch.takes_weighted_backward(layer, csr, F, ctx.dropout, operands)
+            two_pass = passes in ("two_pass", "two_pass_drop") and not weighted   # dY to memory, then dH = A^T.(D.dY) on the transposed CSR
             dh_amax = torch.zeros(1, **f32) if dx_form == "scaled" else None
-            dy = torch.empty(B * T, F, **f32) if two_pass else None
+            dy = torch.empty(B * T, F, **f32) if (two_pass or (weighted and need_adj)) else None
             drop = _drop_args(ctx.dropout)   # the keep factors of the forward launch, drawn again from (seed, element)
             entry, graph, tail = {"mma": ("ggcn_gate_pool_backward_mma", ("graph_ops", "graph_ops_t"), (ptr(dh_amax),)),
                                   "one_pass": ("ggcn_gate_pool_backward_agg", ("rowmask",), drop + (ptr(dh_amax),)),
                                   "two_pass": ("ggcn_gate_pool_backward", (), ()),
                                   "two_pass_drop": ("ggcn_gate_pool_backward_drop", (), drop)}[passes]
-            _capi.check(getattr(lib, entry)(
-                ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
-                *(ptr(getattr(csr, name)) for name in graph), B, T, F, ptr(dy if two_pass else dh), F,
-                ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), *tail, st), entry)
+            if weighted:
+                _capi.check(lib.ggcn_gate_pool_backward_weighted(
+                    ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
+                    ptr(csr.graph_ops_weighted_t()), ptr(csr.inv_denominators()), B, T, F, ptr(dh), F, ptr(dy), F,
+                    ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), st), "ggcn_gate_pool_backward_weighted")
+            else:
+                _capi.check(getattr(lib, entry)(
+                    ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
+                    *(ptr(getattr(csr, name)) for name in graph), B, T, F, ptr(dy if two_pass else dh), F,
+                    ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), *tail, st), entry)
             if two_pass:
                 csr_t = csr.transposed()
                 _capi.check(lib.ggcn_aggregate_t(ptr(dy), F, ptr(csr_t.rowptr), ptr(csr_t.colidx), ptr(csr_t.vals),
@@ -221,6 +231,11 @@ class GraphConvolution(nn.Module):
         # takes_weighted_path has the measurements); larger values mean 128.  Off by default: its sums differ from linear +
         # aggregate's in the last bits (both inside the parity gate).
         self.weighted_max_t = int(getattr(opt, "ggcn_weighted_max_t", None) or os.environ.get("GGCN_WEIGHTED_MAX_T", "32"))
+        # real-valued adjacency of graphs of <= 32 nodes under autograd: gate / pool backward and dH = A_w^T.D.dY as ONE launch on
+        # the matrix cores (ggcn_gate_pool_backward_weighted; dispatch.takes_weighted_backward has the measurements) instead of
+        # ggcn_gate_pool_backward + a transposed CSR + ggcn_aggregate_t.  Off by default: dH's sums differ in the last bits.
+        self.weighted_backward = (bool(getattr(opt, "ggcn_weighted_backward", False))
+                                  or os.environ.get("GGCN_WEIGHTED_BACKWARD", "0") == "1")
         # dense adjacency handed to forward(): None = let the device detect edge weights (one 4-byte
         # read-back per conversion), True = promise 0/1 entries like the reference's (graph.py:66-74)
         # and stay sync-free, False = always keep the values

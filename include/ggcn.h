@@ -283,6 +283,40 @@ int ggcn_adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64
                         const float *inv,
                         const int32_t *rowptr, const int32_t *colidx, const float *vals,
                         int B, int T, int F, float *d_adj, ggcn_stream_t stream);
+/* ggcn_gate_pool_backward_mma for a REAL-valued adjacency (a soft or learned graph), graphs of <= 32 nodes, no gate dropout:
+ * gate / pool backward and dH = A_w^T . D . dY in ONE launch on the matrix cores -- no transposed CSR, no ggcn_aggregate_t, and
+ * dY in memory only when asked for.
+ * ggcn_graph_operands_weighted_t turns the batched CSR with its weights (vals; NULL = all ones) into one block of
+ * GGCN_GRAPH_OPSWT_BYTES per graph holding N = A_w^T (N[s][t] = A_w[t][s]; row s is the SOURCE node) and nothing else:
+ * 1 / (rowsum + 1) stays with dY, as in the 0/1 kernel.  N is stored as three bf16 planes p0 + p1 + p2 (p0 = bf16(N),
+ * p1 = bf16(N - p0), p2 = bf16(N - p0 - p1): the residual is at most 2^-24 of the entry); plane p, k-step s lies at byte
+ * (2 p + s) * 1024 as 64 lanes x 16 bytes in the A-operand order of v_mfma_f32_32x32x16_bf16, the order of
+ * GGCN_GRAPH_OPSW_BLOCK_BYTES blocks (lane l: row l & 31, h = l >> 5; element j of k-step s = column 16 s + 8 (j >> 2) + 4 h +
+ * (j & 3)), which is the consuming kernel's register -> row map.  Rows and columns >= T are zero.  Entries of one (t, s) add up.
+ * Size: ggcn_graph_operands_weighted_t_bytes(B) = B * 6144 (0 for B <= 0); 16-byte aligned.  *flag (optional, device memory,
+ * zeroed by the caller) gets bit 0 when an entry of A_w is not finite -- such an adjacency keeps the two calls.
+ * Refusals, before any launch: T > 32 -> GGCN_EUNSUPPORTED; null rowptr / colidx / graph_ops_wt, T < 1, B < 0, blocks off
+ * 16 bytes -> GGCN_EINVAL; B = 0 succeeds without a launch.
+ * ggcn_gate_pool_backward_weighted: arguments as ggcn_gate_pool_backward_mma, with
+ *   graph_ops_wt  the blocks above;   inv  float[B*T] = 1 / (rowsum(A_w) + 1) (ggcn_inv_denominators);
+ *   dY            NULL, or [B*T, ldy]: receives the UNSCALED dY (what ggcn_gate_pool_backward writes), for ggcn_adjacency_grad.
+ * D.dY is split into three bf16 planes as in the 0/1 kernel and multiplied by the three planes of N; the six products of weight
+ * >= 2^-16 of the leading one are kept (n0.y0, n0.y1, n0.y2, n1.y0, n1.y1, n2.y0) and summed smallest first: 12 MFMAs per
+ * 32-column tile, dH within a few fp32 ulps of its scale.  The gate gradients and bias sums are the 0/1 kernel's (the same
+ * winners: ties go to the smaller row; two partial sums per column).  No atomics, a fixed summation order: bit-identical from run
+ * to run.  No max |dH| (dX takes ggcn_linear).
+ * Needs T <= 32 (GGCN_EUNSUPPORTED: ggcn_gate_pool_backward + ggcn_aggregate_t), F % 4 == 0, ldo, ldd, ldh, ldy % 4 == 0 and
+ * 16-byte aligned dH / dY / blocks (GGCN_EUNSUPPORTED); null out / dH / inv / graph_ops_wt, a leading dimension below F, T or
+ * F < 1 -> GGCN_EINVAL; every check comes before the launch, and B = 0 succeeds without one. */
+#define GGCN_GRAPH_OPSWT_BYTES 6144
+size_t ggcn_graph_operands_weighted_t_bytes(int B);
+int ggcn_graph_operands_weighted_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T,
+                                   void *graph_ops_wt, int32_t *flag, ggcn_stream_t stream);
+int ggcn_gate_pool_backward_weighted(const float *out, int64_t ldo, const float *store_gate, const float *gate_a,
+                                     const float *gate_b, const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb,
+                                     const void *graph_ops_wt, const float *inv, int B, int T, int F, float *dH, int64_t ldh,
+                                     float *dY, int64_t ldy, float *d_sg, float *d_ga, float *d_gb, float *d_bsum,
+                                     ggcn_stream_t stream);
 
 /* ---- fp16 features (BASELINE configs[3]: 512-token graphs, hidden 1024) ------------------
  * Same operations with X / hidden / out stored as IEEE half and fp32 accumulation; weights
