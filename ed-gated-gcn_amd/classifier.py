@@ -134,9 +134,13 @@ class GatedGCNEventDetector(nn.Module):
 
     def _takes_dropout_launches(self, x, csr):
         """Both layers draw the gates' dropout inside their own launches: gc1 on x (float32, or bfloat16 under autocast), gc2 on
-        its real input, the float32 gcn1."""
-        return ((self.gc1.takes_dropout_path(x, csr) or self.gc1.takes_bf16_dropout_path(x, csr))
-                and dispatch.takes_dropout(self.gc2, csr, dispatch.Input.of(x, torch.float32)))
+        its real input, the float32 gcn1 -- on a 0/1 adjacency, or on a real-valued one where both layers have the opt-in
+        ``weighted_dropout`` (``dispatch.takes_weighted_dropout``)."""
+        if ((self.gc1.takes_dropout_path(x, csr) or self.gc1.takes_bf16_dropout_path(x, csr))
+                and dispatch.takes_dropout(self.gc2, csr, dispatch.Input.of(x, torch.float32))):
+            return True
+        return (dispatch.takes_weighted_dropout(self.gc1, csr, dispatch.Input.of(x))
+                and dispatch.takes_weighted_dropout(self.gc2, csr, dispatch.Input.of(x, torch.float32)))
 
     def forward(self, inputs):
         B = inputs["sentence_length"].shape[0]                              # :579-589
@@ -198,7 +202,7 @@ class GatedGCNEventDetector(nn.Module):
             xg, out, _ = self.gc2.forward_gated(gcn1, csr, want_pool_a=True)           # :748-749
             xy = 0.0
         elif dropping and self._takes_dropout_launches(x, csr):
-            # ---- training with dropout on the one-launch path (graphs of <= 256 nodes): the reference drops entries of the REPEATED [B,T,H] gates
+            # ---- training with dropout on the one-launch path (graphs of <= 256 nodes; real-valued adjacency: weighted_dropout): the reference drops entries of the REPEATED [B,T,H] gates
             # (:621-625), one draw per token and feature.  The layers draw those keep factors in their own epilogues from a
             # counter-based hash of (seed, element) -- stream 1 for gate1, stream 2 for gate2 in BOTH layers, as the
             # reference's one dropped copy of gate2 serves :631 and :639 -- and again in the backward pass: nothing of
@@ -215,7 +219,7 @@ class GatedGCNEventDetector(nn.Module):
             if pooled is not None and not v54:
                 self.dropout(pooled)                                                   # :641 (unused; keeps the RNG stream)
         elif dropping:
-            # ---- a layer off the one-launch path (weighted adjacency, > 256 nodes, ...): gating, dropout and the pools as the reference's own
+            # ---- a layer off the one-launch path (weighted adjacency without ``weighted_dropout``, > 256 nodes, ...): gating, dropout and the pools as the reference's own
             # ops around the two HIP layers (three [B,T,H] temporaries) ----
             gate1 = self.dropout(self.gate1(aspect)[:, None, :].expand(-1, T, -1))     # :621-624 (repeat, then dropout)
             gate2 = self.dropout(self.gate2(aspect)[:, None, :].expand(-1, T, -1))

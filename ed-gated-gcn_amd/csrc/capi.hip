@@ -144,6 +144,51 @@ int ggcn_layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpac
                                      pool_a, pool_b, precision, as_stream(stream));
 }
 
+namespace {
+// what the three weighted dropout entries check alike before anything else: p and the gates' keep streams
+int drop_entry_checks(const char *who, float p, int sel_store, int sel_a, int sel_b)
+{
+    if (!(p >= 0.0f && p < 1.0f) || sel_store < 0 || sel_store > 2 || sel_a < 0 || sel_a > 2 || sel_b < 0 || sel_b > 2)
+        return fail(GGCN_EINVAL, "%s: p=%g streams %d %d %d", who, (double)p, sel_store, sel_a, sel_b);
+    return GGCN_OK;
+}
+}  // namespace
+
+int ggcn_layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias,
+                                   const float *zero_mid, int B, int T, int K, int F, const float *store_gate,
+                                   const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo, float *pool_a,
+                                   float *pool_b, int precision, float p, uint64_t seed, int sel_store, int sel_a, int sel_b,
+                                   ggcn_stream_t stream)
+{
+    if (int rc = drop_entry_checks("ggcn_layer_fused_weighted_drop", p, sel_store, sel_a, sel_b)) return rc;
+    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);   // p = 0: thr = 0, nothing is dropped
+    return layer_fused_weighted_drop(X, ldx, wpack, graph_opsw, bias, zero_mid, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo,
+                                     pool_a, pool_b, precision, as_stream(stream), &d);
+}
+
+int ggcn_layer_fused_weighted_wide_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsww, const float *bias,
+                                        int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a,
+                                        const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b, int precision,
+                                        float p, uint64_t seed, int sel_store, int sel_a, int sel_b, ggcn_stream_t stream)
+{
+    if (int rc = drop_entry_checks("ggcn_layer_fused_weighted_wide_drop", p, sel_store, sel_a, sel_b)) return rc;
+    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);   // p = 0: thr = 0, nothing is dropped
+    return layer_fused_weighted_wide(X, ldx, wpack, graph_opsww, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo,
+                                     pool_a, pool_b, precision, as_stream(stream), &d);
+}
+
+int ggcn_gate_pool_backward_weighted_drop(const float *out, int64_t ldo, const float *store_gate, const float *gate_a,
+                                          const float *gate_b, const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb,
+                                          const void *graph_ops_wt, const float *inv, int B, int T, int F, float *dH, int64_t ldh,
+                                          float *dY, int64_t ldy, float *d_sg, float *d_ga, float *d_gb, float *d_bsum, float p,
+                                          uint64_t seed, int sel_store, int sel_a, int sel_b, ggcn_stream_t stream)
+{
+    if (int rc = drop_entry_checks("ggcn_gate_pool_backward_weighted_drop", p, sel_store, sel_a, sel_b)) return rc;
+    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);   // p = 0: thr = 0, the kernel without dropout
+    return gate_pool_backward_weighted(out, ldo, store_gate, gate_a, gate_b, d_out, ldd, d_pa, d_pb, graph_ops_wt, inv, B, T, F, dH, ldh,
+                                       dY, ldy, d_sg, d_ga, d_gb, d_bsum, as_stream(stream), &d);
+}
+
 int ggcn_block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
                      const void *graph_ops2, const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
                      const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
@@ -521,6 +566,7 @@ int ggcn_range_flag(uint32_t *flag, int clear, ggcn_stream_t stream)
     rc = rc ? rc : range_flag_wide(flag, clear, as_stream(stream));
     rc = rc ? rc : range_flag_wide8(flag, clear, as_stream(stream));
     rc = rc ? rc : range_flag_block8(flag, clear, as_stream(stream));
+    rc = rc ? rc : range_flag_weighted_drop(flag, clear, as_stream(stream));
 #ifdef GGCN_WITH_F16MX6
     rc = rc ? rc : range_flag_fused6(flag, clear, as_stream(stream));
 #endif

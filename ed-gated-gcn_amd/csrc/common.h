@@ -96,7 +96,10 @@ int graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, c
                                  hipStream_t st);
 int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, const void *ops, const float *bias, int B, int T, int K, int F,
                               const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-                              float *pool_a, float *pool_b, int precision, hipStream_t st);
+                              float *pool_a, float *pool_b, int precision, hipStream_t st, const struct DropSpec *drop = nullptr);
+int layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias, const float *zero_mid,
+                              int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
+                              float *out, int64_t ldo, float *pool_a, float *pool_b, int precision, hipStream_t st, const struct DropSpec *drop);
 int layer_fused(const float *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops, const float *bias,
                 int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a,
                 const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b,
@@ -141,7 +144,7 @@ int graph_operands_weighted_t(const int32_t *rowptr, const int32_t *colidx, cons
 int gate_pool_backward_weighted(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
                                 const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wt,
                                 const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
-                                float *d_ga, float *d_gb, float *d_bsum, hipStream_t st);
+                                float *d_ga, float *d_gb, float *d_bsum, hipStream_t st, const struct DropSpec *drop = nullptr);
 size_t colsum_workspace_bytes(int F);
 int colsum(const float *X, int64_t ld, int64_t M, int F, float *out, void *workspace, hipStream_t st);
 
@@ -167,6 +170,7 @@ int range_flag_fused(unsigned int *dst, int clear, hipStream_t st);    // fused_
 int range_flag_wide(unsigned int *dst, int clear, hipStream_t st);     // fused_wide.hip
 int range_flag_wide8(unsigned int *dst, int clear, hipStream_t st);    // fused_wide8.hip
 int range_flag_block8(unsigned int *dst, int clear, hipStream_t st);   // fused_block8.hip
+int range_flag_weighted_drop(unsigned int *dst, int clear, hipStream_t st);   // fused_weighted_drop.hip
 int lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,
                      const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F, const float *gate1,
                      const float *gate2, float *x_out, int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial,

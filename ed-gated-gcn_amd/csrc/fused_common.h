@@ -48,6 +48,8 @@ struct FusedArgs {
 int launch_fused_wide(const char *who, const FusedArgs &a, int precision, int sb, bool fast, bool vst, int64_t grid, hipStream_t st);
 int launch_fused_wide8(const char *who, const FusedArgs &a, int precision, bool fast, bool vst, int64_t grid, hipStream_t st);
 int launch_fused6(const char *who, const FusedArgs &a, bool fullt, bool vst, int64_t grid, hipStream_t st);   // GGCN_WITH_F16MX6 builds
+int launch_fused_weighted_drop(const char *who, const FusedArgs &a, int precision, bool avec, bool kfull, bool fullt, bool vst, int64_t grid,
+                               hipStream_t st);   // fused_weighted_drop.hip
 
 namespace {
 

@@ -505,6 +505,10 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
                         who, a.K, (long long)a.ldx);
         return launch_fused6(who, a, fullt, vst, grid, st);
     }
+    if (a.drop.thr != 0 && a.part[0].mid) {   // ggcn_layer_fused_weighted_drop (the only caller with both): kernels of their own
+        if (a.stamps || a.ov_in || a.part[0].ov_partial) return fail(GGCN_EUNSUPPORTED, "%s: no stamps and no overlap operands under gate dropout", who);
+        return launch_fused_weighted_drop(who, a, precision, avec, kfull, fullt, vst, grid, st);
+    }
 #define GGCN_LAUNCH(SC, AV, KF, FT, VS) \
     hipLaunchKernelGGL((layer_fused_kernel<SC, AV, KF, FT, VS>), dim3((unsigned)grid), dim3(kThreads), 0, st, a)
 #define GGCN_PICK(SC)                                                                 \
@@ -621,6 +625,29 @@ int layer_fused_weighted(const float *X, int64_t ldx, const void *wpack, const v
     a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
     a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, zero_mid, nullptr, store_gate, pool_gate_a, pool_gate_b,
                           out, pool_a, pool_b, overlap_partial, (int)ldo};
+    return launch_fused(who, a, precision, st);
+}
+
+// ggcn_layer_fused_weighted under the gates' training-mode dropout: layer_fused_weighted_drop_kernel on the same blocks; thr = 0
+// (p = 0) launches layer_fused_kernel's MID form -- ggcn_layer_fused_weighted's launch, bit for bit
+int layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias, const float *zero_mid,
+                              int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
+                              float *out, int64_t ldo, float *pool_a, float *pool_b, int precision, hipStream_t st, const DropSpec *drop)
+{
+    const char *who = "ggcn_layer_fused_weighted_drop";
+    if (!graph_opsw || !zero_mid) return fail(GGCN_EINVAL, "%s: the weighted operand blocks and the zero row are required", who);
+    if (!drop) return fail(GGCN_EINVAL, "%s: no keep streams", who);
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (33..128 nodes: ggcn_layer_fused_weighted_wide_drop)", who, T);
+    if (precision == GGCN_PREC_F16MX6) return fail(GGCN_EUNSUPPORTED, "%s: bf16x3 or f16mx8", who);
+    if ((int64_t)B * T * F >= ((int64_t)1 << 32))
+        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)B * T * F);
+    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: ldo too large", who);
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.graph_ops = static_cast<const char *>(graph_opsw); a.graph_ops2 = a.graph_ops;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    a.drop = *drop;
+    a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, zero_mid, nullptr, store_gate, pool_gate_a, pool_gate_b,
+                          out, pool_a, pool_b, nullptr, (int)ldo};
     return launch_fused(who, a, precision, st);
 }
 

@@ -34,11 +34,18 @@ namespace {
 // epilogue (fused_common.h), so the lo fragments of the NEXT block row (the next graph's first one after the last) are
 // requested as soon as the last column tile's lo products have issued and the hi fragments after its hi products: the
 // element-wise work and stores of that tile and the next row's first products run under them.
+// WEIGHTED && DROP (ggcn_layer_fused_weighted_wide_drop): both of the above -- the keep factors only touch what follows y.
+// wide_one_wave: the instantiations compiled WITHOUT the two-wavefronts-per-SIMD bound.  SB = 8 (the lab form above), and one more: WEIGHTED && DROP with the general f16mx8 main loop at
+// SB = 4 spills 8 bytes per lane under it -- 64 registers of fragments, 128 of planes and the pools' running maxima leave nothing
+// for the hash; an opaque lane id after the main loop and a 32-bit element index left one register spilled.  Unbound it takes
+// 253 VGPRs + 128 AGPRs and no scratch: ONE wavefront per SIMD, for the slow-shape form (K % 32 != 0 or rows off 16 bytes) of
+// 65..128-node graphs under dropout in f16mx8 alone.  The fast shapes and every bf16x3 form keep two.  Its speed is not measured.
+constexpr bool wide_one_wave(int sch, bool avec, int sb, bool drop, bool weighted) { return sb == 8 || (weighted && drop && sch == 1 && sb == 4 && !avec); }
 template <int SCH, bool AVEC, bool KFULL, bool VST, int SB, bool DROP = false, typename XT = float, bool WEIGHTED = false>
-__global__ __launch_bounds__(kThreads, SB == 8 ? 1 : kWavesPerSimd) void layer_fused_wide_kernel(const FusedArgs a)
+__global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHTED) ? 1 : kWavesPerSimd) void layer_fused_wide_kernel(const FusedArgs a)
 {
     static_assert(SB == 2 || SB == 4 || SB == 8, "a graph slot is 64, 128 or 256 rows");
-    static_assert(!WEIGHTED || (SB != 8 && !DROP && std::is_same<XT, float>::value), "real-valued adjacency: float32 features, 64- and 128-row slots, no gate dropout");
+    static_assert(!WEIGHTED || (SB != 8 && std::is_same<XT, float>::value), "real-valued adjacency: float32 features, 64- and 128-row slots");
     static_assert(std::is_same<XT, float>::value || (SCH == 0 && SB != 8), "bf16 features: the bf16x3 main loop, 64- and 128-row slots");
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
@@ -464,11 +471,12 @@ int graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, c
 
 // gcn.py:30-45 with a real-valued adjacency for graphs of 33..128 nodes in ONE launch: layer_fused_wide_kernel<.., WEIGHTED> on
 // ggcn_graph_operands_weighted_wide blocks.  The argument checks are launch_fused's (fused_layer.hip) for one part.
+// drop: NULL, or the gates' keep streams (ggcn_layer_fused_weighted_wide_drop; thr = 0: the launch without dropout)
 int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, const void *ops, const float *bias, int B, int T, int K, int F,
                               const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-                              float *pool_a, float *pool_b, int precision, hipStream_t st)
+                              float *pool_a, float *pool_b, int precision, hipStream_t st, const DropSpec *drop)
 {
-    const char *who = "ggcn_layer_fused_weighted_wide";
+    const char *who = drop ? "ggcn_layer_fused_weighted_wide_drop" : "ggcn_layer_fused_weighted_wide";
     if (precision != GGCN_PREC_BF16X3 && precision != GGCN_PREC_F16MX8)
         return fail(GGCN_EUNSUPPORTED, "%s: precision %d (bf16x3 or f16mx8)", who, precision);
     if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
@@ -481,6 +489,8 @@ int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, co
     if (!wpack) return fail(GGCN_EINVAL, "%s: null weight image", who);
     if (!aligned16(wpack)) return fail(GGCN_EINVAL, "%s: wpack must be 16-byte aligned", who);
     if (!out && !pool_a && !pool_b) return fail(GGCN_EINVAL, "%s: no output requested", who);
+    if (drop && (int64_t)B * T * F >= ((int64_t)1 << 32))
+        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)B * T * F);
     bool vst = false;
     if (out) {
         if (ldo < F) return fail(GGCN_EINVAL, "%s: leading dimension of the output too small", who);
@@ -490,6 +500,7 @@ int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, co
     FusedArgs a = {};
     a.X = X; a.ldx = ldx; a.graph_ops = static_cast<const char *>(ops);
     a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    if (drop) a.drop = *drop;
     a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, nullptr, nullptr, store_gate, pool_gate_a, pool_gate_b,
                           out, pool_a, pool_b, nullptr, (int)ldo};
     const bool fast = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(X) && (int64_t)ldx * 4 * 257 < ((int64_t)1 << 31) && (K % BK == 0);
@@ -500,17 +511,23 @@ int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, co
     const int64_t gridw = grid_for(gt, a.n_wg);
     if (gridw > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
     a.g_tiles = (int)gt;
-#define GGCN_LAUNCHWW(SC, AV, KF, VS, SBV) \
-    hipLaunchKernelGGL((layer_fused_wide_kernel<SC, AV, KF, VS, SBV, false, float, true>), dim3((unsigned)gridw), dim3(kThreads), 0, st, a)
+#define GGCN_LAUNCHWW(SC, AV, KF, VS, SBV, DR) \
+    hipLaunchKernelGGL((layer_fused_wide_kernel<SC, AV, KF, VS, SBV, DR, float, true>), dim3((unsigned)gridw), dim3(kThreads), 0, st, a)
+#define GGCN_PICKWWD(SC, SBV, DR)                                            \
+    do {                                                                     \
+        if (fast && vst) GGCN_LAUNCHWW(SC, true, true, true, SBV, DR);       \
+        else if (fast) GGCN_LAUNCHWW(SC, true, true, false, SBV, DR);        \
+        else GGCN_LAUNCHWW(SC, false, false, false, SBV, DR);                \
+    } while (0)
 #define GGCN_PICKWW(SC, SBV)                                                 \
     do {                                                                     \
-        if (fast && vst) GGCN_LAUNCHWW(SC, true, true, true, SBV);           \
-        else if (fast) GGCN_LAUNCHWW(SC, true, true, false, SBV);            \
-        else GGCN_LAUNCHWW(SC, false, false, false, SBV);                    \
+        if (a.drop.thr != 0) GGCN_PICKWWD(SC, SBV, true);                    \
+        else GGCN_PICKWWD(SC, SBV, false);                                   \
     } while (0)
     if (precision == GGCN_PREC_F16MX8) { if (sb == 2) GGCN_PICKWW(1, 2); else GGCN_PICKWW(1, 4); }
     else { if (sb == 2) GGCN_PICKWW(0, 2); else GGCN_PICKWW(0, 4); }
 #undef GGCN_PICKWW
+#undef GGCN_PICKWWD
 #undef GGCN_LAUNCHWW
     return check_launch(who);
 }

@@ -1,5 +1,5 @@
 // Backward of the gate / max-pool epilogue AND the transposed aggregation in one launch, on the matrix cores, for a REAL-valued
-// adjacency (a soft or learned graph) of graphs of <= 32 nodes, no gate dropout:
+// adjacency (a soft or learned graph) of graphs of <= 32 nodes, without gate dropout or (DROP) under it:
 //
 //   dY[t] = d_out[t]*sg + [t = argmax_a] d_pa*ga + [t = argmax_b] d_pb*gb         models/bert_amir5.py:627-640 backwards
 //   dH    = A_w^T . D . dY,   D = diag(1 / (rowsum(A_w) + 1))                       models/gcn.py:35,41 backwards (train.py:120)
@@ -19,14 +19,23 @@
 //     folded into N, so the blocks depend on the adjacency's entries alone.
 //   * dY (optional): the UNSCALED dY, stored for ggcn_adjacency_grad, which reads it from memory.  NULL: nothing of size
 //     [B*T,F] but dH is written.
-//   * no gate dropout, no max |dH|.
+//   * no max |dH|.
+//   * DROP (ggcn_gate_pool_backward_weighted_drop; training, bert_amir5.py:621-625): the element math of
+//     gate_pool_backward_agg_kernel<true> (gate_pool_backward.hip) in this kernel's register -> row map.  Element
+//     ((b T + row) F + col) as uint32 gives the hash of dropout_hash.h and from it the keep factors ks, ka, kb of the three gates;
+//     y = out * inv_sg / ks (0 where ks = 0), the pools' candidates are y*ga*ka and y*gb*kb (the winner keeps y*k),
+//     d_sg sums d_out*y*ks and dY = d_out*sg*ks + [row = ia] d_pa*ga*ka + [row = ib] d_pb*gb*kb.  The hash is evaluated again in the
+//     dY loop: 16 hashes (or 48 keep factors) held per lane across the winners' exchange would cost the third workgroup per CU.
 // No atomics, a fixed summation order: bit-identical from run to run.
 // Registers (`make resources`): with the three operand planes held in 24 VGPRs and dY stored through lane pointers the kernel
 // wants 208 VGPRs and spills 92 bytes per lane under __launch_bounds__(256, 3).  So the planes wait in LDS (6 KiB per workgroup,
 // read per tile right before the MFMAs) and dY leaves through a buffer resource (scalar row offsets, no address pairs):
 // 165 VGPRs, no scratch, 38 KiB of LDS -- three workgroups per CU, as the 0/1 form (150 VGPRs).
+// DROP: under that bound the keep factors spill 84 bytes per lane, so the DROP instantiation alone is bound to TWO workgroups per
+// CU: 219 VGPRs, no scratch.  The instantiation without dropout keeps the figures above.
 #include "bf16x3_core.h"
 #include "common.h"
+#include "dropout_hash.h"
 
 namespace ggcn {
 namespace {
@@ -55,12 +64,13 @@ __device__ __forceinline__ void split3(const float (&v)[16], bf16x8 (&f)[3][2])
         }
 }
 
-__global__ __launch_bounds__(256, 3) void gate_pool_backward_weighted_kernel(
+template <bool DROP>
+__global__ __launch_bounds__(256, DROP ? 2 : 3) void gate_pool_backward_weighted_kernel(
     const float *__restrict__ out, int64_t ldo, const float *__restrict__ store_gate, const float *__restrict__ gate_a,
     const float *__restrict__ gate_b, const float *__restrict__ d_out, int64_t ldd, const float *__restrict__ d_pa,
     const float *__restrict__ d_pb, const char *__restrict__ ops_wt, const float *__restrict__ inv, int T, int F,
     float *__restrict__ dH, int64_t ldh, float *__restrict__ dY, int64_t ldy, float *__restrict__ d_sg, float *__restrict__ d_ga,
-    float *__restrict__ d_gb, float *__restrict__ d_bsum)
+    float *__restrict__ d_gb, float *__restrict__ d_bsum, DropSpec drop)
 {
     __shared__ __attribute__((aligned(16))) float stage_all[4][32 * 64];   // per wavefront: 32 rows x 64 columns on their way to 16-byte stores
     const int b = blockIdx.x;          // one workgroup per graph: its rows are ONE contiguous block of `out` / `d_out` / dH / dY
@@ -112,15 +122,29 @@ __global__ __launch_bounds__(256, 3) void gate_pool_backward_weighted_kernel(
         // forward values and the pools' winners (bert_amir5.py:627-640): first maximum in ascending row order
         float best_a = -INFINITY, best_b = -INFINITY, ya = 0.0f, yb = 0.0f, acc_sg = 0.0f;
         int ia = 0, ib = 0;
+        // DROP: the element of this lane's row 4 h (rows add rs * F), as the forward launch and ggcn_dropout_mask count it
+        const uint32_t e0 = DROP ? (uint32_t)(((int64_t)b * T + 4 * h) * F + colc) : 0u;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = row_of(r, h);
             const bool valid = row < T;
-            const float y = ov[r] * inv_sg;          // (rows past T: 0)
-            const float va = y * ga, vb = y * gb;
-            if (valid && va > best_a) { best_a = va; ia = row; ya = y; }
-            if (valid && vb > best_b) { best_b = vb; ib = row; yb = y; }
-            acc_sg = fmaf(dv[r], y, acc_sg);
+            if constexpr (DROP) {
+                const uint32_t hh = drop_hash(e0 + (uint32_t)(((r & 3) + 8 * (r >> 2)) * F), drop.seed_lo, drop.seed_hi);
+                const float ks = drop_keep(hh, drop.sel[0], drop.thr, drop.scale);
+                const float ka = drop_keep(hh, drop.sel[1], drop.thr, drop.scale);
+                const float kb = drop_keep(hh, drop.sel[2], drop.thr, drop.scale);
+                const float y = ks != 0.0f ? ov[r] * inv_sg / ks : 0.0f;   // (rows past T: 0)
+                const float va = y * ga * ka, vb = y * gb * kb;
+                if (valid && va > best_a) { best_a = va; ia = row; ya = y * ka; }
+                if (valid && vb > best_b) { best_b = vb; ib = row; yb = y * kb; }
+                acc_sg = fmaf(dv[r], y * ks, acc_sg);
+            } else {
+                const float y = ov[r] * inv_sg;          // (rows past T: 0)
+                const float va = y * ga, vb = y * gb;
+                if (valid && va > best_a) { best_a = va; ia = row; ya = y; }
+                if (valid && vb > best_b) { best_b = vb; ib = row; yb = y; }
+                acc_sg = fmaf(dv[r], y, acc_sg);
+            }
         }
         {   // the two lane halves hold different rows of the same column: the smaller row wins a tie
             const float oa = __shfl_xor(best_a, 32), oya = __shfl_xor(ya, 32);
@@ -142,9 +166,17 @@ __global__ __launch_bounds__(256, 3) void gate_pool_backward_weighted_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = row_of(r, h);
-            float g = dv[r] * sg;
-            if (d_pa && row == ia && row < T) g += pa_g;
-            if (d_pb && row == ib && row < T) g += pb_g;
+            float g;
+            if constexpr (DROP) {   // the keep factors once more (see the head of the file)
+                const uint32_t hh = drop_hash(e0 + (uint32_t)(((r & 3) + 8 * (r >> 2)) * F), drop.seed_lo, drop.seed_hi);
+                g = dv[r] * sg * drop_keep(hh, drop.sel[0], drop.thr, drop.scale);
+                if (d_pa && row == ia && row < T) g = fmaf(dpa, ga * drop_keep(hh, drop.sel[1], drop.thr, drop.scale), g);
+                if (d_pb && row == ib && row < T) g = fmaf(dpb, gb * drop_keep(hh, drop.sel[2], drop.thr, drop.scale), g);
+            } else {
+                g = dv[r] * sg;
+                if (d_pa && row == ia && row < T) g += pa_g;
+                if (d_pb && row == ib && row < T) g += pb_g;
+            }
             bsum += g;
             if (dY && cok && row < T)
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g), yrsrc, yvoff, (int)(((r & 3) + 8 * (r >> 2)) * ldy * 4), 0);
@@ -278,9 +310,10 @@ int graph_operands_weighted_t(const int32_t *rowptr, const int32_t *colidx, cons
 int gate_pool_backward_weighted(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
                                 const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wt,
                                 const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
-                                float *d_ga, float *d_gb, float *d_bsum, hipStream_t st)
+                                float *d_ga, float *d_gb, float *d_bsum, hipStream_t st, const DropSpec *drop)
 {
-    const char *who = "ggcn_gate_pool_backward_weighted";
+    // drop: NULL, or the keep streams of ggcn_gate_pool_backward_weighted_drop (thr = 0: p = 0, the form without dropout)
+    const char *who = drop ? "ggcn_gate_pool_backward_weighted_drop" : "ggcn_gate_pool_backward_weighted";
     if (!out) return fail(GGCN_EINVAL, "%s: out is null", who);
     if (!dH) return fail(GGCN_EINVAL, "%s: dH is null", who);
     if (!inv) return fail(GGCN_EINVAL, "%s: inv is null", who);
@@ -297,10 +330,17 @@ int gate_pool_backward_weighted(const float *out, int64_t ldo, const float *stor
         (dY && !aligned16(dY)) || !aligned16(graph_ops_wt))
         return fail(GGCN_EUNSUPPORTED, "%s: needs F %% 4 == 0, ldo, ldd, ldh, ldy %% 4 == 0 and 16-byte aligned dH / dY / graph_ops_wt; use "
                                        "ggcn_gate_pool_backward + ggcn_aggregate_t", who);
+    if (drop && (int64_t)B * T * F >= ((int64_t)1 << 32))
+        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)B * T * F);
     if (B == 0) return GGCN_OK;
-    hipLaunchKernelGGL(gate_pool_backward_weighted_kernel, dim3((unsigned)B), dim3(256), 0, st, out, ldo, store_gate, gate_a, gate_b, d_out,
-                       d_out ? ldd : ldo, d_pa, d_pb, static_cast<const char *>(graph_ops_wt), inv, T, F, dH, ldh, dY, ldy, d_sg, d_ga, d_gb,
-                       d_bsum);
+    if (drop && drop->thr != 0)
+        hipLaunchKernelGGL(gate_pool_backward_weighted_kernel<true>, dim3((unsigned)B), dim3(256), 0, st, out, ldo, store_gate, gate_a, gate_b,
+                           d_out, d_out ? ldd : ldo, d_pa, d_pb, static_cast<const char *>(graph_ops_wt), inv, T, F, dH, ldh, dY, ldy, d_sg,
+                           d_ga, d_gb, d_bsum, *drop);
+    else
+        hipLaunchKernelGGL(gate_pool_backward_weighted_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, out, ldo, store_gate, gate_a, gate_b,
+                           d_out, d_out ? ldd : ldo, d_pa, d_pb, static_cast<const char *>(graph_ops_wt), inv, T, F, dH, ldh, dY, ldy, d_sg,
+                           d_ga, d_gb, d_bsum, DropSpec{});
     return check_launch(who);
 }
 

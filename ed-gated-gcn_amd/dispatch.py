@@ -104,6 +104,24 @@ def takes_weighted(layer, csr, inp):
     return bool(csr.T <= min(getattr(layer, "weighted_max_t", 32), 128) and csr.graph_ops_weighted_wide() is not None)
 
 
+def takes_weighted_dropout(layer, csr, inp):
+    """True when the gates' training-mode dropout (``bert_amir5.py:621-625``) on a REAL-valued adjacency is drawn inside the
+    weighted layer launch (``ggcn_layer_fused_weighted_drop`` for graphs of <= 32 nodes, ``ggcn_layer_fused_weighted_wide_drop``
+    for 33..``weighted_max_t``): the option ``layer.weighted_dropout`` (``opt.ggcn_weighted_dropout`` /
+    ``GGCN_WEIGHTED_DROPOUT=1``; OFF by default) -- looked at first, so that a refused call builds no operand block -- an element
+    index below 2^32, and ``takes_weighted``.  ``layer_path`` does not know this path (its answers are pinned):
+    ``_forward_gated`` asks here once where dropout is handed in and ``layer_path`` named no ``DROPOUT_PATHS`` launch.
+    float32 features only; bfloat16 features on a weighted adjacency under dropout keep raising.
+    Measured (``tools/weighted_dropout_timing.py``, one MI355X, one process, H = 768, f16mx8, p = 0.25, us per training step of
+    one gated layer, per-adjacency builders inside; off = the plain weighted launch + the reference's [B,T,H] gate ops under PyTorch
+    autograd, on = these launches, wb = with ``weighted_backward``): 4096 x 32 sparse 5346 / on 2322 / wb 2091 (with adj.grad
+    5898 / 2855 / 2665), dense softmax rows 5754 / 2705 / 2080 (6310 / 3263 / 2697); 512 x 100 sparse 2200 / 1073 (2528 / 1405),
+    dense 2974 / 1864 (3327 / 2221).  It stays opt-in, like the launches it builds on.  Not measured: the
+    one-wavefront form of the 128-row slot (general f16mx8 main loop).
+    The compiler's report: no scratch in any of the 22 new forward kernels."""
+    return bool(getattr(layer, "weighted_dropout", False)) and _index_fits(layer, inp) and takes_weighted(layer, csr, inp)
+
+
 def takes_long(layer, csr, inp):
     return bool(layer.fused and layer.precision == "f16" and inp.dtype == torch.float16
                 and 128 < csr.T <= layer.LONG_MAX_T and layer.in_features % 64 == 0 and layer.out_features % 8 == 0)
@@ -164,11 +182,29 @@ def takes_weighted_backward(layer, csr, F, dropout, operands):
     (``BatchedCSR.graph_ops_weighted_t``: None when an entry is not finite).  It replaces ``ggcn_gate_pool_backward`` +
     ``BatchedCSR.transposed()`` + ``ggcn_aggregate_t``; dY is written only for an adjacency gradient; the dX / dW forms stay the
     plan's.  float32 and bfloat16 features alike (``out``, dY and dH are float32 in both).
-    NOT MEASURED yet: ``tools/weighted_backward_timing.py`` (option off against on in one process: the replaced stage with its
-    per-adjacency builders, and the whole layer backward, at 4096 x 32 x 768 sparse / dense softmax and 512 x 24 x 768) has not run
-    on an MI355X, so how much the one launch saves over the two calls is unknown, and the option stays opt-in whatever it shows.
+    Measured (``tools/weighted_backward_timing.py``, one MI355X, one process, option off against on, H = 768, f16mx8, us, the
+    per-adjacency builders inside): the replaced stage 552 -> 306 (4096 x 32 sparse; 383 with the dY store), 899 -> 337 (dense
+    softmax rows; 416), 68 -> 62 (512 x 24); the whole layer backward 1521 -> 1271, 1881 -> 1295, 230 -> 226, with an adjacency
+    gradient 2016 -> 1859, 2407 -> 1914, 300 -> 300.  It stays opt-in: dH differs in the last bits.
     The compiler's report: 165 VGPRs, no scratch, three workgroups per CU."""
     return bool(getattr(layer, "weighted_backward", False) and not csr.is_binary and csr.T <= 32 and F % 4 == 0 and dropout is None
+                and all(t is None or t.data_ptr() % 16 == 0 for t in operands)
+                and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1" and csr.graph_ops_weighted_t() is not None)
+
+
+def takes_weighted_backward_drop(layer, csr, B, F, dropout, operands):
+    """``takes_weighted_backward`` under gate dropout: True when the backward of a layer on a REAL-valued adjacency runs
+    ``ggcn_gate_pool_backward_weighted_drop`` -- gate / pool pass with the forward's keep factors drawn again AND
+    ``dH = A_w^T . D . dY`` in one launch -- where ``backward_plan`` says "two_pass_drop": the option ``layer.weighted_backward``,
+    ``dropout`` handed in, B*T*F < 2^32 (the hash takes a 32-bit element index), and then ``takes_weighted_backward``'s
+    conditions: a real-valued adjacency of graphs of <= 32 nodes, F % 4 == 0, every operand 16-byte aligned,
+    ``GGCN_BACKWARD_TWO_PASS`` not set, and -- asked last, so that a refused call builds nothing -- the graph's A_w^T operand.
+    It replaces ``ggcn_gate_pool_backward_drop`` + ``BatchedCSR.transposed()`` + ``ggcn_aggregate_t``; dY is written only for an
+    adjacency gradient.  The compiler's report: 219 VGPRs, no scratch, TWO workgroups per CU (under the three-workgroup bound the
+    keep factors spill 84 bytes per lane; the form without dropout keeps 165 VGPRs and three workgroups).
+    Timings: ``takes_weighted_dropout``."""
+    return bool(getattr(layer, "weighted_backward", False) and dropout is not None and B * csr.T * F < 2 ** 32
+                and not csr.is_binary and csr.T <= 32 and F % 4 == 0
                 and all(t is None or t.data_ptr() % 16 == 0 for t in operands)
                 and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1" and csr.graph_ops_weighted_t() is not None)
 

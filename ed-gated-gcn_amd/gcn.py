@@ -50,9 +50,10 @@ def _drop_args(dropout):
     return (0.0, 0, 0, 0, 0) if dropout is None else (float(dropout[0]), int(dropout[1])) + tuple(dropout[2])
 
 
-def _admit(path, dropout, overlap):
-    """Gate dropout and the overlap operands exist in the one-launch layers only: decided from the name of the path the call takes."""
-    if dropout is not None and path not in dispatch.DROPOUT_PATHS:
+def _admit(path, dropout, overlap, weighted_drop=False):
+    """Gate dropout and the overlap operands exist in the one-launch layers only: decided from the name of the path the call takes
+    (``weighted_drop``: ``dispatch.takes_weighted_dropout`` holds -- the opt-in launches that ``layer_path`` has no name for)."""
+    if dropout is not None and path not in dispatch.DROPOUT_PATHS and not weighted_drop:
         raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
     if overlap and path not in dispatch.OVERLAP_PATHS:
         raise RuntimeError("overlap_partial / overlap_reduce need the one-launch layer (takes_fused_path)")
@@ -67,7 +68,7 @@ class _GatedLayerFunction(torch.autograd.Function):
         dY, d_sg, d_ga, d_gb   HIP, one pass over the stored output (gate_pool_backward.hip)
         dH = A^T.(D.dY)        HIP, one wavefront per SOURCE node on the transposed CSR (0/1 graphs of <= 32 nodes: one launch with
                                the line above, dispatch.backward_plan; real-valued ones with ``weighted_backward``:
-                               ggcn_gate_pool_backward_weighted, dispatch.takes_weighted_backward)
+                               ggcn_gate_pool_backward_weighted[_drop], dispatch.takes_weighted_backward[_drop])
         dX = dH.W^T            HIP bf16x3 MFMA linear on the packed W^T (bfloat16 features: stored as bf16, RNE)
         dW = X^T.dH            HIP split-K: bf16x3 main loop on X^T and packed dH (dweight_bx3.hip; bfloat16 features:
                                X^T in bf16, ggcn_dweight_bf16), or the exact-fp32 MFMA form for precision 'fp32' (dweight_fp32.hip)
@@ -123,7 +124,8 @@ class _GatedLayerFunction(torch.autograd.Function):
             operands = (out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum)
             passes, dx_form, dw_form = dispatch.backward_plan(layer, csr, text.dtype, K, F, need[0], need_adj, ctx.dropout, operands)
             # a real-valued adjacency of <= 32 nodes, opt-in: the two passes as one launch on the matrix cores (dY only for d_adj)
-            weighted = passes == "two_pass" and dispatch.takes_weighted_backward(layer, csr, F, ctx.dropout, operands)
+            weighted = ((passes == "two_pass" and dispatch.takes_weighted_backward(layer, csr, F, ctx.dropout, operands))
+                        or (passes == "two_pass_drop" and dispatch.takes_weighted_backward_drop(layer, csr, B, F, ctx.dropout, operands)))
             two_pass = passes in ("two_pass", "two_pass_drop") and not weighted   # dY to memory, then dH = A^T.(D.dY) on the transposed CSR
             dh_amax = torch.zeros(1, **f32) if dx_form == "scaled" else None
             dy = torch.empty(B * T, F, **f32) if (two_pass or (weighted and need_adj)) else None
@@ -132,11 +134,12 @@ class _GatedLayerFunction(torch.autograd.Function):
                                   "one_pass": ("ggcn_gate_pool_backward_agg", ("rowmask",), drop + (ptr(dh_amax),)),
                                   "two_pass": ("ggcn_gate_pool_backward", (), ()),
                                   "two_pass_drop": ("ggcn_gate_pool_backward_drop", (), drop)}[passes]
-            if weighted:
-                _capi.check(lib.ggcn_gate_pool_backward_weighted(
+            if weighted:   # (under gate dropout: the same launch with the forward's keep factors)
+                entry = "ggcn_gate_pool_backward_weighted" + ("_drop" if ctx.dropout is not None else "")
+                _capi.check(getattr(lib, entry)(
                     ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
                     ptr(csr.graph_ops_weighted_t()), ptr(csr.inv_denominators()), B, T, F, ptr(dh), F, ptr(dy), F,
-                    ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), st), "ggcn_gate_pool_backward_weighted")
+                    ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), *(drop if ctx.dropout is not None else ()), st), entry)
             else:
                 _capi.check(getattr(lib, entry)(
                     ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
@@ -236,6 +239,11 @@ class GraphConvolution(nn.Module):
         # ggcn_gate_pool_backward + a transposed CSR + ggcn_aggregate_t.  Off by default: dH's sums differ in the last bits.
         self.weighted_backward = (bool(getattr(opt, "ggcn_weighted_backward", False))
                                   or os.environ.get("GGCN_WEIGHTED_BACKWARD", "0") == "1")
+        # real-valued adjacency under the gates' training-mode dropout: the keep factors are drawn inside the weighted launches
+        # (ggcn_layer_fused_weighted_drop / _wide_drop; with weighted_backward also ggcn_gate_pool_backward_weighted_drop) instead of
+        # the call being refused (dispatch.takes_weighted_dropout).  Off by default, like the launches it builds on.
+        self.weighted_dropout = (bool(getattr(opt, "ggcn_weighted_dropout", False))
+                                 or os.environ.get("GGCN_WEIGHTED_DROPOUT", "0") == "1")
         # dense adjacency handed to forward(): None = let the device detect edge weights (one 4-byte
         # read-back per conversion), True = promise 0/1 entries like the reference's (graph.py:66-74)
         # and stay sync-free, False = always keep the values
@@ -383,6 +391,13 @@ class GraphConvolution(nn.Module):
                         "ggcn_linear")
         return y
 
+    def _zero_row(self, F, dev):
+        """The all-zero ``mid`` row of the weighted launches of <= 32 nodes ([F] floats, made once per device)."""
+        zmid = getattr(self, "_zero_mid", None)
+        if zmid is None or zmid.device != dev or zmid.numel() < F:
+            zmid = self._zero_mid = torch.zeros(F, dtype=torch.float32, device=dev)
+        return zmid
+
     @staticmethod
     def _differentiable_adj(adj):
         """``adj`` itself when it is a dense floating-point tensor that wants a gradient under grad mode (a soft or learned graph:
@@ -420,7 +435,8 @@ class GraphConvolution(nn.Module):
         """True when ``forward_gated`` (inference or the forward of training) runs bfloat16 features as ONE launch
         (``ggcn_layer_fused_bf16``): graphs of <= 32 nodes, 0/1 adjacency, a split precision (``BF16_PRECISIONS``).  Graphs of
         33..256 nodes: ``takes_bf16_wide_path``; gate dropout in either launch: ``takes_bf16_dropout_path``.  Anything else
-        (longer graphs, weighted adjacencies) takes ``ggcn_linear_bf16`` + ``ggcn_aggregate``."""
+        (longer graphs, weighted adjacencies) takes ``ggcn_linear_bf16`` + ``ggcn_aggregate``, which have no gate dropout: on a
+        weighted adjacency ``dropout=`` is refused for bfloat16 features (``takes_weighted_dropout_path`` is float32 only)."""
         return dispatch.takes_bf16_fused(self, csr, dispatch.Input.of(text))
 
     BF16_WIDE_MIN_FILL = 0.75   # 33..128 nodes: one launch when the graph fills this share of its 64- or 128-row slot
@@ -464,7 +480,8 @@ class GraphConvolution(nn.Module):
           (``BatchedCSR.graph_ops_weighted_wide``: ceil(T/32)^2 blocks of hi / lo bf16 fragments per graph, built once per
           adjacency tensor, one read-back).  The option is looked at before the graph is asked for anything.
 
-        Anything else -- gate dropout included -- takes linear + aggregate.  The 33..128 launch WINS ON SPARSE AND ON DENSE graphs
+        Anything else takes linear + aggregate.  Gate dropout (``dropout=``) is refused on a real-valued adjacency unless
+        ``takes_weighted_dropout_path`` holds (the opt-in ``weighted_dropout``).  The 33..128 launch WINS ON SPARSE AND ON DENSE graphs
         (``tools/weighted_wide_timing.py``, one MI355X, H = 768, f16mx8 / bf16x3, us): 512 x 100 with 3 edges per
         row 189 / 237 vs 226 / 251 (the 0/1 launch on the same pattern: 180 / 225), 1024 x 64: 195 / 235 vs 286 / 319, 512 x 128:
         203 / 248 vs 277 / 313; dense softmax rows 512 x 100: 197 / 244 vs 935 / 943, 1024 x 64: 197 / 243 vs 801 / 825, 512 x 128:
@@ -472,6 +489,16 @@ class GraphConvolution(nn.Module):
         learned graph pays it every step and still wins (512 x 128 dense: 451 vs 1389).  It stays an option because the two
         paths sum in different orders (2.7e-6..1.2e-5 of the output scale apart, both inside the parity gate)."""
         return dispatch.takes_weighted(self, csr, dispatch.Input.of(text))
+
+    def takes_weighted_dropout_path(self, text, csr):
+        """True when ``forward_gated(..., dropout=...)`` on a REAL-valued adjacency draws the gates' keep factors inside the weighted
+        launch (``ggcn_layer_fused_weighted_drop`` up to 32 nodes, ``ggcn_layer_fused_weighted_wide_drop`` for
+        33..``weighted_max_t``) instead of raising: the option ``weighted_dropout`` (``opt.ggcn_weighted_dropout`` /
+        ``GGCN_WEIGHTED_DROPOUT=1``; off by default), B*T*F < 2^32 and ``takes_weighted_path``.  Under autograd the backward is
+        ``ggcn_gate_pool_backward_drop`` + ``ggcn_aggregate_t``, or with ``weighted_backward`` one
+        ``ggcn_gate_pool_backward_weighted_drop`` launch (``dispatch.takes_weighted_backward_drop``).  Timings:
+        ``dispatch.takes_weighted_dropout``."""
+        return dispatch.takes_weighted_dropout(self, csr, dispatch.Input.of(text))
 
     LONG_MAX_T = 512   # include/ggcn.h GGCN_LONG_MAX_T
 
@@ -537,10 +564,13 @@ class GraphConvolution(nn.Module):
         training = not _internal and self._needs_grad(text, store_gate, pool_gate_a, pool_gate_b, adj=adj)
         x2d = None if training else _rows2d(text)
         path = dispatch.layer_path(self, text, csr, dropout is not None, x2d)
+        # gate dropout where layer_path names no launch that draws it: the opt-in weighted launches, asked once
+        weighted_drop = (dropout is not None and path not in dispatch.DROPOUT_PATHS
+                         and dispatch.takes_weighted_dropout(self, csr, dispatch.Input.of(text)))
         if training:   # the same kernels, wrapped in an autograd Function with a HIP backward
             if text.dtype not in (torch.float32, torch.bfloat16):
                 raise RuntimeError("training through the HIP layer needs float32 features (or bfloat16 ones)")
-            _admit(path, dropout, False)
+            _admit(path, dropout, False, weighted_drop)
             if dropout is not None:
                 # the backward recovers y from the stored out = y*sg*k_store: a token whose store factor is 0 leaves nothing to
                 # recover, which is exact only for pools that drop the same tokens (include/ggcn.h ggcn_gate_pool_backward_drop)
@@ -562,8 +592,8 @@ class GraphConvolution(nn.Module):
             if g is not None:
                 _require_gpu_f32(name, g)
                 _require_gate(name, g, B, F, "%(name)s must be a contiguous [B,F]=[%(B)d,%(F)d] tensor, got %(shape)s")
-        _admit(path, dropout, overlap_partial is not None or overlap_reduce is not None)
-        hidden = self.linear(x2d) if path == "two_launch" else None
+        _admit(path, dropout, overlap_partial is not None or overlap_reduce is not None, weighted_drop)
+        hidden = self.linear(x2d) if path == "two_launch" and not weighted_drop else None
         ptr = _capi.ptr
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
@@ -575,7 +605,20 @@ class GraphConvolution(nn.Module):
             tail = (B, T, K, F, ptr(store_gate), ptr(pool_gate_a), ptr(pool_gate_b), ptr(out), F, ptr(pa), ptr(pb))
             ov = (ptr(overlap_partial), ptr(overlap_reduce[0]) if overlap_reduce else None, ptr(overlap_reduce[1]) if overlap_reduce else None)
             drop = _drop_args(dropout)
-            if path == "fused_drop":
+            if weighted_drop:   # real-valued adjacency under gate dropout (weighted_dropout): the weighted launches with keep factors
+                if overlap_partial is not None or overlap_reduce is not None:
+                    raise RuntimeError("overlap_partial / overlap_reduce need the one-launch layer (takes_fused_path)")
+                kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"
+                pack = self._packed_weight(lib, st, precision=kprec)
+                if T > 32:
+                    _capi.check(lib.ggcn_layer_fused_weighted_wide_drop(
+                        ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops_weighted_wide()), ptr(bias), *tail, _capi.PREC[kprec], *drop, st),
+                        "ggcn_layer_fused_weighted_wide_drop")
+                else:
+                    _capi.check(lib.ggcn_layer_fused_weighted_drop(
+                        ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops_weighted(0 if kprec == "bf16x3" else 1)), ptr(bias),
+                        ptr(self._zero_row(F, dev)), *tail, _capi.PREC[kprec], *drop, st), "ggcn_layer_fused_weighted_drop")
+            elif path == "fused_drop":
                 kprec = "f16mx8" if self.precision == "f16mx6" else self.precision   # the fp6 kernel has no dropout epilogue
                 pack = self._packed_weight(lib, st, precision=kprec)
                 _capi.check(lib.ggcn_layer_fused_drop(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowmask), ptr(csr.graph_ops), ptr(bias),
@@ -604,11 +647,9 @@ class GraphConvolution(nn.Module):
             elif path == "weighted":   # real-valued adjacency, graphs of <= 32 nodes: one launch on D.A_w operand blocks
                 kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"
                 pack = self._packed_weight(lib, st, precision=kprec)
-                zmid = getattr(self, "_zero_mid", None)
-                if zmid is None or zmid.device != dev or zmid.numel() < F:
-                    zmid = self._zero_mid = torch.zeros(F, dtype=torch.float32, device=dev)
                 _capi.check(lib.ggcn_layer_fused_weighted(ptr(x2d), x2d.stride(0), ptr(pack),
-                                                          ptr(csr.graph_ops_weighted(0 if kprec == "bf16x3" else 1)), ptr(bias), ptr(zmid),
+                                                          ptr(csr.graph_ops_weighted(0 if kprec == "bf16x3" else 1)), ptr(bias),
+                                                          ptr(self._zero_row(F, dev)),
                                                           *tail, None, None, None, _capi.PREC[kprec], st), "ggcn_layer_fused_weighted")
             elif path == "long":   # long fp16 graphs (BASELINE configs[3]): linear + aggregation in one launch, hidden stays in LDS
                 pack = self._packed_weight(lib, st)

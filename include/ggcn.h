@@ -437,6 +437,41 @@ int ggcn_layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpac
                                    const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b, int precision,
                                    ggcn_stream_t stream);
 
+/* ---- gate dropout inside the launches on a REAL-valued adjacency (training a soft or learned graph) ----
+ * The three entries above that serve a real-valued adjacency, with the gates' training-mode keep factors of ggcn_layer_fused_drop
+ * (models/bert_amir5.py:621-625; csrc/dropout_hash.h: element ((b T + t) F + f) as uint32, streams 0 / 1 / 2 per gate slot):
+ *   out = y * store_gate * k_store,   pool_x = max_t (y * pool_gate_x * k_x)        (every element has its own factor: the
+ *   pools maximise the gated, kept values themselves, no max / min shortcut)
+ * ggcn_layer_fused_weighted_drop: ggcn_layer_fused_weighted's operands (ggcn_graph_operands_weighted blocks, the zero `mid` row,
+ *   GGCN_PREC_BF16X3 or GGCN_PREC_F16MX8) without the overlap arguments, graphs of <= 32 nodes; every shape that launch takes.
+ * ggcn_layer_fused_weighted_wide_drop: the same on ggcn_graph_operands_weighted_wide blocks, graphs of 33..128 nodes.
+ * ggcn_gate_pool_backward_weighted_drop: ggcn_gate_pool_backward_weighted with the forward's keep factors drawn again:
+ *   y = k_store != 0 ? out / store_gate / k_store : 0;  the pools' candidates are y*ga*ka and y*gb*kb (ties to the smaller row);
+ *   d_sg = sum_t d_out*y*k_store;   dY = d_out*sg*k_store + [t = ia] d_pa*ga*ka + [t = ib] d_pb*gb*kb  -- the dY that is stored
+ *   for ggcn_adjacency_grad and multiplied by A_w^T . D.  A dropped store gate zeroes what y is read back from: exact where
+ *   every pool in use shares the store gate's stream (ggcn_gate_pool_backward_drop).  No atomics, a fixed summation order:
+ *   bit-identical from run to run.
+ * p = 0 launches the kernels WITHOUT dropout: results are bit-identical to the three entries above.
+ * Refusals, all before any launch: p outside [0, 1) or a stream outside 0..2 -> GGCN_EINVAL; B*T*F >= 2^32 ->
+ * GGCN_EUNSUPPORTED (32-bit element index); forward: T > 32 (wide: outside 33..128) or GGCN_PREC_F16MX6 -> GGCN_EUNSUPPORTED,
+ * null blocks or null zero row -> GGCN_EINVAL; every other refusal is the entry's without dropout.  float32 features only. */
+int ggcn_layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias,
+                                   const float *zero_mid, int B, int T, int K, int F, const float *store_gate,
+                                   const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo, float *pool_a,
+                                   float *pool_b, int precision, float p, uint64_t seed, int stream_store, int stream_a,
+                                   int stream_b, ggcn_stream_t stream);
+int ggcn_layer_fused_weighted_wide_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsww, const float *bias,
+                                        int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a,
+                                        const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b,
+                                        int precision, float p, uint64_t seed, int stream_store, int stream_a, int stream_b,
+                                        ggcn_stream_t stream);
+int ggcn_gate_pool_backward_weighted_drop(const float *out, int64_t ldo, const float *store_gate, const float *gate_a,
+                                          const float *gate_b, const float *d_out, int64_t ldd, const float *d_pa,
+                                          const float *d_pb, const void *graph_ops_wt, const float *inv, int B, int T, int F,
+                                          float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg, float *d_ga, float *d_gb,
+                                          float *d_bsum, float p, uint64_t seed, int stream_store, int stream_a, int stream_b,
+                                          ggcn_stream_t stream);
+
 /* ---- the whole gated block in one launch (graphs of <= 32 nodes, binary adjacency, inference) ----
  * Replaces models/bert_amir5.py:626-640 -- gc1, both gates, both max-pools, gc2, its gate and pool -- with
  * ONE launch that reads X once and never writes gcn1 unless asked to.  The reference feeds gc2 with the
