@@ -79,18 +79,25 @@ class BatchedCSR:
         self._graph_ops_ww = None  # cached ggcn_graph_operands_weighted_wide blocks (real-valued adjacency, 33..128 nodes); False: refused
         self._graph_ops_wt = None  # cached ggcn_graph_operands_weighted_t blocks (A_w^T of <= 32 nodes: the weighted backward); False: refused
 
+    def _build(self, entry, sizer, source, extra=(), by_length=False, flagged=False):
+        """What every cached operand builder does once its precondition holds: ask ``sizer`` for the bytes of B graphs (``by_length``:
+        of T nodes), allocate, launch ``entry(*source, B, T, *extra, block, [flag], stream)`` on ``source``'s device and return the
+        block -- or None where a ``flagged`` builder raised its device flag for an adjacency it refuses (one read-back)."""
+        lib = _capi.load_library()
+        dev = source[0].device
+        ops = torch.empty(getattr(lib, sizer)(*((self.B, self.T) if by_length else (self.B,))), dtype=torch.uint8, device=dev)
+        flag = (torch.zeros(1, dtype=torch.int32, device=dev),) if flagged else ()
+        with torch.cuda.device(dev):
+            _capi.check(getattr(lib, entry)(*map(_capi.ptr, source), self.B, self.T, *extra, _capi.ptr(ops), *map(_capi.ptr, flag),
+                                            _capi.stream_of(dev)), entry)
+        return None if flagged and int(flag[0].item()) else ops
+
     @property
     def graph_ops(self):
         """uint8 [B * GGCN_GRAPH_OPS_BYTES] or None: what the one-launch layer / block reads per graph of <= 32 nodes
         (adjacency in MFMA operand order + reciprocal denominators), built from the row masks on first use."""
         if self._graph_ops is None and self.rowmask is not None and self.T <= 32 and self.rowmask.is_cuda:
-            lib = _capi.load_library()
-            dev = self.rowmask.device
-            ops = torch.empty(lib.ggcn_graph_operands_bytes(self.B), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _capi.check(lib.ggcn_graph_operands(_capi.ptr(self.rowmask), self.B, self.T, _capi.ptr(ops),
-                                                    _capi.stream_of(dev)), "ggcn_graph_operands")
-            self._graph_ops = ops
+            self._graph_ops = self._build("ggcn_graph_operands", "ggcn_graph_operands_bytes", (self.rowmask,))
         return self._graph_ops
 
     @property
@@ -98,13 +105,7 @@ class BatchedCSR:
         """``ggcn_graph_edge_lists`` blocks (graphs of 129..256 nodes with row masks) or None: the per-row edge lists the
         eight-wavefront one-launch layer walks, made once per adjacency tensor instead of by every workgroup of every launch."""
         if self._edge_lists is None and self.rowmask is not None and 128 < self.T <= 256 and self.rowmask.is_cuda:
-            lib = _capi.load_library()
-            dev = self.rowmask.device
-            lists = torch.empty(lib.ggcn_graph_edge_lists_bytes(self.B), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _capi.check(lib.ggcn_graph_edge_lists(_capi.ptr(self.rowmask), self.B, self.T, _capi.ptr(lists), _capi.stream_of(dev)),
-                            "ggcn_graph_edge_lists")
-            self._edge_lists = lists
+            self._edge_lists = self._build("ggcn_graph_edge_lists", "ggcn_graph_edge_lists_bytes", (self.rowmask,))
         return self._edge_lists
 
     @property
@@ -112,15 +113,12 @@ class BatchedCSR:
         """``ggcn_graph_operands`` blocks of the transposed adjacency (graphs of <= 32 nodes): the A^T operand of the backward's
         ``dH = A^T . D . dY`` on the matrix cores (``ggcn_gate_pool_backward_mma``); built from the row masks on first use."""
         if self._graph_ops_t is None and self.rowmask is not None and self.T <= 32 and self.rowmask.is_cuda:
-            lib = _capi.load_library()
             dev = self.rowmask.device
             mt = torch.empty_like(self.rowmask)
-            ops = torch.empty(lib.ggcn_graph_operands_bytes(self.B), dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                st = _capi.stream_of(dev)
-                _capi.check(lib.ggcn_rowmask_transpose(_capi.ptr(self.rowmask), self.B, self.T, _capi.ptr(mt), st), "ggcn_rowmask_transpose")
-                _capi.check(lib.ggcn_graph_operands(_capi.ptr(mt), self.B, self.T, _capi.ptr(ops), st), "ggcn_graph_operands")
-            self._graph_ops_t = ops
+                _capi.check(_capi.load_library().ggcn_rowmask_transpose(_capi.ptr(self.rowmask), self.B, self.T, _capi.ptr(mt),
+                                                                        _capi.stream_of(dev)), "ggcn_rowmask_transpose")
+            self._graph_ops_t = self._build("ggcn_graph_operands", "ggcn_graph_operands_bytes", (mt,))
         return self._graph_ops_t
 
     def graph_ops2(self, plane):
@@ -133,13 +131,7 @@ class BatchedCSR:
         if plane not in store:
             if self.rowmask is None or self.T > 32 or not self.rowmask.is_cuda:
                 return None
-            lib = _capi.load_library()
-            dev = self.rowmask.device
-            ops = torch.empty(lib.ggcn_graph_operands2_bytes(self.B), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _capi.check(lib.ggcn_graph_operands2(_capi.ptr(self.rowmask), self.B, self.T, plane, _capi.ptr(ops),
-                                                     _capi.stream_of(dev)), "ggcn_graph_operands2")
-            store[plane] = ops
+            store[plane] = self._build("ggcn_graph_operands2", "ggcn_graph_operands2_bytes", (self.rowmask,), extra=(plane,))
         return store[plane]
 
     def graph_ops_weighted(self, plane):
@@ -153,15 +145,8 @@ class BatchedCSR:
         if plane not in store:
             if self.T > 32 or not self.rowptr.is_cuda:
                 return None
-            lib = _capi.load_library()
-            dev = self.rowptr.device
-            ops = torch.empty(lib.ggcn_graph_operands2_bytes(self.B), dtype=torch.uint8, device=dev)
-            flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _capi.check(lib.ggcn_graph_operands_weighted(_capi.ptr(self.rowptr), _capi.ptr(self.colidx), _capi.ptr(self.vals),
-                                                             self.B, self.T, plane, _capi.ptr(ops), _capi.ptr(flag),
-                                                             _capi.stream_of(dev)), "ggcn_graph_operands_weighted")
-            store[plane] = None if int(flag.item()) else ops
+            store[plane] = self._build("ggcn_graph_operands_weighted", "ggcn_graph_operands2_bytes", (self.rowptr, self.colidx, self.vals),
+                                       extra=(plane,), flagged=True)
         return store[plane]
 
     def graph_ops_weighted_wide(self):
@@ -173,15 +158,9 @@ class BatchedCSR:
         if self._graph_ops_ww is None:
             if not 32 < self.T <= 128 or not self.rowptr.is_cuda:
                 return None
-            lib = _capi.load_library()
-            dev = self.rowptr.device
-            ops = torch.empty(lib.ggcn_graph_operands_weighted_wide_bytes(self.B, self.T), dtype=torch.uint8, device=dev)
-            flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _capi.check(lib.ggcn_graph_operands_weighted_wide(_capi.ptr(self.rowptr), _capi.ptr(self.colidx), _capi.ptr(self.vals),
-                                                                  self.B, self.T, _capi.ptr(ops), _capi.ptr(flag),
-                                                                  _capi.stream_of(dev)), "ggcn_graph_operands_weighted_wide")
-            self._graph_ops_ww = False if int(flag.item()) else ops
+            ops = self._build("ggcn_graph_operands_weighted_wide", "ggcn_graph_operands_weighted_wide_bytes",
+                              (self.rowptr, self.colidx, self.vals), by_length=True, flagged=True)
+            self._graph_ops_ww = False if ops is None else ops
         return None if self._graph_ops_ww is False else self._graph_ops_ww
 
     def graph_ops_weighted_t(self):
@@ -193,15 +172,9 @@ class BatchedCSR:
         if self._graph_ops_wt is None:
             if self.T > 32 or not self.rowptr.is_cuda:
                 return None
-            lib = _capi.load_library()
-            dev = self.rowptr.device
-            ops = torch.empty(lib.ggcn_graph_operands_weighted_t_bytes(self.B), dtype=torch.uint8, device=dev)
-            flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _capi.check(lib.ggcn_graph_operands_weighted_t(_capi.ptr(self.rowptr), _capi.ptr(self.colidx), _capi.ptr(self.vals),
-                                                               self.B, self.T, _capi.ptr(ops), _capi.ptr(flag),
-                                                               _capi.stream_of(dev)), "ggcn_graph_operands_weighted_t")
-            self._graph_ops_wt = False if int(flag.item()) else ops
+            ops = self._build("ggcn_graph_operands_weighted_t", "ggcn_graph_operands_weighted_t_bytes",
+                              (self.rowptr, self.colidx, self.vals), flagged=True)
+            self._graph_ops_wt = False if ops is None else ops
         return None if self._graph_ops_wt is False else self._graph_ops_wt
 
     @property

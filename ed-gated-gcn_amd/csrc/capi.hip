@@ -28,6 +28,32 @@ int fail(int code, const char *fmt, ...)
 
 using namespace ggcn;
 
+namespace {
+// what every entry with gate dropout checks of p and the gates' keep streams
+int drop_entry_checks(const char *who, float p, int sel_store, int sel_a, int sel_b)
+{
+    if (!(p >= 0.0f && p < 1.0f) || sel_store < 0 || sel_store > 2 || sel_a < 0 || sel_a > 2 || sel_b < 0 || sel_b > 2)
+        return fail(GGCN_EINVAL, "%s: p=%g streams %d %d %d", who, (double)p, sel_store, sel_a, sel_b);
+    return GGCN_OK;
+}
+
+// what the bf16 one-launch entries check alike before anything else: X's alignment, then the dropout arguments
+int bf16_entry_checks(const char *who, const void *X, float p, int sel_store, int sel_a, int sel_b)
+{
+    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
+    return drop_entry_checks(who, p, sel_store, sel_a, sel_b);
+}
+
+// the preamble of the four ggcn_linear* entries (`null_operand`: one of the pointers that entry needs is NULL)
+int linear_entry_checks(const char *who, bool null_operand, int64_t M, int K, int F, int64_t ldx, int64_t ldy)
+{
+    if (null_operand) return fail(GGCN_EINVAL, "%s: null pointer", who);
+    if (M <= 0 || K <= 0 || F <= 0) return fail(GGCN_EINVAL, "%s: M=%lld K=%d F=%d must be positive", who, (long long)M, K, F);
+    if (ldx < K || ldy < F) return fail(GGCN_EINVAL, "%s: leading dimension too small", who);
+    return GGCN_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int ggcn_abi_version(void) { return GGCN_ABI_VERSION; }
@@ -144,16 +170,6 @@ int ggcn_layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpac
                                      pool_a, pool_b, precision, as_stream(stream));
 }
 
-namespace {
-// what the three weighted dropout entries check alike before anything else: p and the gates' keep streams
-int drop_entry_checks(const char *who, float p, int sel_store, int sel_a, int sel_b)
-{
-    if (!(p >= 0.0f && p < 1.0f) || sel_store < 0 || sel_store > 2 || sel_a < 0 || sel_a > 2 || sel_b < 0 || sel_b > 2)
-        return fail(GGCN_EINVAL, "%s: p=%g streams %d %d %d", who, (double)p, sel_store, sel_a, sel_b);
-    return GGCN_OK;
-}
-}  // namespace
-
 int ggcn_layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias,
                                    const float *zero_mid, int B, int T, int K, int F, const float *store_gate,
                                    const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo, float *pool_a,
@@ -234,10 +250,7 @@ int ggcn_adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64
 int ggcn_linear(const float *X, int64_t ldx, const float *W, int64_t ldw, const void *wpack, float *Y,
                 int64_t ldy, int64_t M, int K, int F, int precision, ggcn_stream_t stream)
 {
-    if (!X || !Y) return fail(GGCN_EINVAL, "ggcn_linear: null pointer");
-    if (M <= 0 || K <= 0 || F <= 0)
-        return fail(GGCN_EINVAL, "ggcn_linear: M=%lld K=%d F=%d must be positive", (long long)M, K, F);
-    if (ldx < K || ldy < F) return fail(GGCN_EINVAL, "ggcn_linear: leading dimension too small");
+    if (int rc = linear_entry_checks("ggcn_linear", !X || !Y, M, K, F, ldx, ldy)) return rc;
     switch (precision) {
         case GGCN_PREC_BF16X3:
         case GGCN_PREC_F16MX8:
@@ -254,10 +267,7 @@ int ggcn_linear(const float *X, int64_t ldx, const float *W, int64_t ldw, const 
 int ggcn_linear_bf16(const void *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F,
                      ggcn_stream_t stream)
 {
-    if (!X || !Y || !wpack) return fail(GGCN_EINVAL, "ggcn_linear_bf16: null pointer");
-    if (M <= 0 || K <= 0 || F <= 0)
-        return fail(GGCN_EINVAL, "ggcn_linear_bf16: M=%lld K=%d F=%d must be positive", (long long)M, K, F);
-    if (ldx < K || ldy < F) return fail(GGCN_EINVAL, "ggcn_linear_bf16: leading dimension too small");
+    if (int rc = linear_entry_checks("ggcn_linear_bf16", !X || !Y || !wpack, M, K, F, ldx, ldy)) return rc;
     if (reinterpret_cast<uintptr_t>(X) % 2 || reinterpret_cast<uintptr_t>(Y) % 4)
         return fail(GGCN_EINVAL, "ggcn_linear_bf16: X / Y not aligned to their element size");
     return linear_bf16(X, ldx, wpack, Y, ldy, M, K, F, as_stream(stream));
@@ -266,25 +276,11 @@ int ggcn_linear_bf16(const void *X, int64_t ldx, const void *wpack, float *Y, in
 int ggcn_linear_out_bf16(const float *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy, int64_t M, int K, int F,
                          ggcn_stream_t stream)
 {
-    if (!X || !Y || !wpack) return fail(GGCN_EINVAL, "ggcn_linear_out_bf16: null pointer");
-    if (M <= 0 || K <= 0 || F <= 0)
-        return fail(GGCN_EINVAL, "ggcn_linear_out_bf16: M=%lld K=%d F=%d must be positive", (long long)M, K, F);
-    if (ldx < K || ldy < F) return fail(GGCN_EINVAL, "ggcn_linear_out_bf16: leading dimension too small");
+    if (int rc = linear_entry_checks("ggcn_linear_out_bf16", !X || !Y || !wpack, M, K, F, ldx, ldy)) return rc;
     if (reinterpret_cast<uintptr_t>(X) % 4 || reinterpret_cast<uintptr_t>(Y) % 2)
         return fail(GGCN_EINVAL, "ggcn_linear_out_bf16: X / Y not aligned to their element size");
     return linear_out_bf16(X, ldx, wpack, Y, ldy, M, K, F, as_stream(stream));
 }
-
-namespace {
-// what the three bf16 one-launch entries check alike before anything else: X's alignment, the gates' keep streams
-int bf16_entry_checks(const char *who, const void *X, float p, int sel_store, int sel_a, int sel_b)
-{
-    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
-    if (!(p >= 0.0f && p < 1.0f) || sel_store < 0 || sel_store > 2 || sel_a < 0 || sel_a > 2 || sel_b < 0 || sel_b > 2)
-        return fail(GGCN_EINVAL, "%s: p=%g streams %d %d %d", who, (double)p, sel_store, sel_a, sel_b);
-    return GGCN_OK;
-}
-}  // namespace
 
 int ggcn_layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const void *graph_ops, const float *bias, int B, int T,
                           int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out,
@@ -356,10 +352,7 @@ int ggcn_linear_h(const void *X, int64_t ldx, const void *wpack, void *Y, int64_
 {
     if (precision != GGCN_PREC_BF16X3 && precision != GGCN_PREC_F16MX8 && precision != GGCN_PREC_F16)
         return fail(GGCN_EUNSUPPORTED, "ggcn_linear_h: precision %d (use bf16x3, f16mx8 or f16)", precision);
-    if (!X || !Y) return fail(GGCN_EINVAL, "ggcn_linear_h: null pointer");
-    if (M <= 0 || K <= 0 || F <= 0)
-        return fail(GGCN_EINVAL, "ggcn_linear_h: M=%lld K=%d F=%d must be positive", (long long)M, K, F);
-    if (ldx < K || ldy < F) return fail(GGCN_EINVAL, "ggcn_linear_h: leading dimension too small");
+    if (int rc = linear_entry_checks("ggcn_linear_h", !X || !Y, M, K, F, ldx, ldy)) return rc;
     return linear_packed_h(X, ldx, wpack, Y, ldy, M, K, F, precision, as_stream(stream));
 }
 
@@ -396,8 +389,7 @@ int ggcn_gate_pool_backward_drop(const float *out, int64_t ldo, const float *sto
                                  float *d_ga, float *d_gb, float *d_bsum, float p, uint64_t seed, int sel_store,
                                  int sel_a, int sel_b, ggcn_stream_t stream)
 {
-    if (!(p >= 0.0f && p < 1.0f) || sel_store < 0 || sel_store > 2 || sel_a < 0 || sel_a > 2 || sel_b < 0 || sel_b > 2)
-        return fail(GGCN_EINVAL, "ggcn_gate_pool_backward_drop: p=%g streams %d %d %d", (double)p, sel_store, sel_a, sel_b);
+    if (int rc = drop_entry_checks("ggcn_gate_pool_backward_drop", p, sel_store, sel_a, sel_b)) return rc;
     const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);
     return gate_pool_backward(out, ldo, store_gate, gate_a, gate_b, d_out, ldd, d_pa, d_pb, B, T, F, dY, ldy, d_sg,
                               d_ga, d_gb, d_bsum, as_stream(stream), &d);
@@ -409,8 +401,7 @@ int ggcn_gate_pool_backward_agg(const float *out, int64_t ldo, const float *stor
                                 float *d_sg, float *d_ga, float *d_gb, float *d_bsum, float p, uint64_t seed, int sel_store,
                                 int sel_a, int sel_b, float *dh_amax, ggcn_stream_t stream)
 {
-    if (!(p >= 0.0f && p < 1.0f) || sel_store < 0 || sel_store > 2 || sel_a < 0 || sel_a > 2 || sel_b < 0 || sel_b > 2)
-        return fail(GGCN_EINVAL, "ggcn_gate_pool_backward_agg: p=%g streams %d %d %d", (double)p, sel_store, sel_a, sel_b);
+    if (int rc = drop_entry_checks("ggcn_gate_pool_backward_agg", p, sel_store, sel_a, sel_b)) return rc;
     const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);
     return gate_pool_backward_agg(out, ldo, store_gate, gate_a, gate_b, d_out, ldd, d_pa, d_pb, rowmask, B, T, F, dH, ldh, d_sg,
                                   d_ga, d_gb, d_bsum, as_stream(stream), p > 0.0f ? &d : nullptr, dh_amax);
@@ -476,8 +467,7 @@ int ggcn_layer_fused_drop(const float *X, int64_t ldx, const void *wpack, const 
                           float *pool_a, float *pool_b, int precision, float p, uint64_t seed, int sel_store,
                           int sel_a, int sel_b, ggcn_stream_t stream)
 {
-    if (!(p >= 0.0f && p < 1.0f) || sel_store < 0 || sel_store > 2 || sel_a < 0 || sel_a > 2 || sel_b < 0 || sel_b > 2)
-        return fail(GGCN_EINVAL, "ggcn_layer_fused_drop: p=%g streams %d %d %d", (double)p, sel_store, sel_a, sel_b);
+    if (int rc = drop_entry_checks("ggcn_layer_fused_drop", p, sel_store, sel_a, sel_b)) return rc;
     const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);
     return layer_fused(X, ldx, wpack, rowmask, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out,
                        ldo, pool_a, pool_b, nullptr, nullptr, nullptr, precision, as_stream(stream), &d);

@@ -1,9 +1,10 @@
 """Which launch a layer call, its backward and a block call take: every rule in one place, decided once per call.
 
-Host logic only -- nothing here loads libggcn_hip.so or launches.  ``layer_path``, ``backward_plan`` and ``block_path`` return
-names out of fixed tuples; ``_forward_gated``, ``_GatedLayerFunction.backward`` and ``_gated_gcn_block`` call them once and switch
-on the answer.  The public ``takes_*`` predicates are one-line statements over the functions below (their docstrings keep the
-measurements behind the thresholds); ``tests/golden/dispatch_table.json`` pins every answer.  DESIGN.md "Dispatch"."""
+Host logic only -- nothing here loads libggcn_hip.so or launches.  ``layer_launch``, ``backward_launch`` and ``block_path`` return
+names out of fixed tuples; ``_forward_gated``, ``_GatedLayerFunction.backward`` and ``_gated_gcn_block`` call them once and look
+the answer up.  ``layer_launch`` / ``backward_launch`` are ``layer_path`` / ``backward_plan`` (whose answers
+``tests/golden/dispatch_table.json`` pins) plus the names of the opt-in weighted launches.  The public ``takes_*`` predicates are
+one-line statements over the functions below (their docstrings keep the measurements behind the thresholds).  DESIGN.md "Dispatch"."""
 import collections
 import os
 
@@ -19,6 +20,11 @@ LAYER_PATHS = ("fused", "fused_drop", "bf16", "bf16_drop", "bf16_wide", "bf16_wi
 DROPOUT_PATHS = ("fused_drop", "bf16_drop", "bf16_wide_drop")           # the gates' dropout is drawn inside these launches
 OVERLAP_PATHS = LAYER_PATHS[:6]                                         # launches that take overlap_partial / overlap_reduce
 BACKWARD_PASSES = ("mma", "one_pass", "two_pass", "two_pass_drop")
+# what is launched: the pinned names above plus the opt-in launches on a real-valued adjacency
+LAYER_LAUNCHES = LAYER_PATHS + ("weighted_wide", "weighted_drop", "weighted_wide_drop")
+DROPOUT_LAUNCHES = DROPOUT_PATHS + ("weighted_drop", "weighted_wide_drop")
+OVERLAP_LAUNCHES = OVERLAP_PATHS
+BACKWARD_LAUNCHES = BACKWARD_PASSES + ("weighted", "weighted_drop")
 DX_FORMS = ("bf16", "scaled", "bf16x3", "fp32")                         # the dW forms are these without "scaled"
 BLOCK_PATHS = ("block", "bf16_block", "folded_eval", "bf16_folded_eval", "two_fused", "layers_eval", "layers")
 
@@ -148,6 +154,26 @@ def layer_path(layer, text, csr, dropout=False, rows=None):
     return "two_launch"
 
 
+def layer_launch(layer, text, csr, dropout=False, rows=None):
+    """The launch ``_forward_gated`` runs, one of ``LAYER_LAUNCHES``: ``layer_path``'s name, "weighted" told apart by graph size and,
+    where dropout is handed in and ``layer_path`` named no ``DROPOUT_PATHS`` launch, ``takes_weighted_dropout`` asked once.  Under
+    ``dropout`` any name outside ``DROPOUT_LAUNCHES`` means the request is refused."""
+    path = layer_path(layer, text, csr, dropout, rows)
+    if path == "weighted":
+        return "weighted" if csr.T <= 32 else "weighted_wide"
+    if dropout and path not in DROPOUT_PATHS and takes_weighted_dropout(layer, csr, Input.of(text)):
+        return "weighted_drop" if csr.T <= 32 else "weighted_wide_drop"
+    return path
+
+
+def _aligned16(operands):
+    return all(t is None or t.data_ptr() % 16 == 0 for t in operands)
+
+
+def _two_pass_forced():
+    return os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") == "1"   # (read at call time)
+
+
 def backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands):
     """``(passes, dx, dw)`` of the layer's backward: ``passes`` out of ``BACKWARD_PASSES``, ``dx`` out of ``DX_FORMS`` (None: no dX
     wanted), ``dw`` likewise.  The three environment switches are read here, at call time.
@@ -161,7 +187,7 @@ def backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands):
       fp16's range), precision "fp32" the exact form, bfloat16 features the bf16 forms."""
     env = os.environ.get
     one_pass = (not need_adj and csr.T <= 32 and F % 4 == 0 and csr.is_binary and csr.rowmask is not None and csr.rowmask.is_cuda
-                and env("GGCN_BACKWARD_TWO_PASS", "0") != "1" and all(t is None or t.data_ptr() % 16 == 0 for t in operands))
+                and not _two_pass_forced() and _aligned16(operands))
     mma = (one_pass and dropout is None and env("GGCN_BACKWARD_SCALAR", "0") != "1"
            and csr.graph_ops is not None and csr.graph_ops_t is not None)
     passes = "mma" if mma else "one_pass" if one_pass else "two_pass" if dropout is None else "two_pass_drop"
@@ -171,6 +197,12 @@ def backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands):
     scaled = (one_pass and need_x and layer.precision == "f16mx8" and K % 4 == 0 and F % 32 == 0 and (mma or F % 256 == 0)
               and env("GGCN_DX_PRECISION", "f16mx8") == "f16mx8")
     return passes, ("scaled" if scaled else dw if need_x else None), dw
+
+
+def _weighted_backward_base(layer, csr, F, operands):
+    """What ``takes_weighted_backward`` and ``takes_weighted_backward_drop`` share; the graph's A_w^T operand is asked last."""
+    return bool(getattr(layer, "weighted_backward", False) and not csr.is_binary and csr.T <= 32 and F % 4 == 0
+                and _aligned16(operands) and not _two_pass_forced() and csr.graph_ops_weighted_t() is not None)
 
 
 def takes_weighted_backward(layer, csr, F, dropout, operands):
@@ -187,9 +219,7 @@ def takes_weighted_backward(layer, csr, F, dropout, operands):
     softmax rows; 416), 68 -> 62 (512 x 24); the whole layer backward 1521 -> 1271, 1881 -> 1295, 230 -> 226, with an adjacency
     gradient 2016 -> 1859, 2407 -> 1914, 300 -> 300.  It stays opt-in: dH differs in the last bits.
     The compiler's report: 165 VGPRs, no scratch, three workgroups per CU."""
-    return bool(getattr(layer, "weighted_backward", False) and not csr.is_binary and csr.T <= 32 and F % 4 == 0 and dropout is None
-                and all(t is None or t.data_ptr() % 16 == 0 for t in operands)
-                and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1" and csr.graph_ops_weighted_t() is not None)
+    return dropout is None and _weighted_backward_base(layer, csr, F, operands)
 
 
 def takes_weighted_backward_drop(layer, csr, B, F, dropout, operands):
@@ -203,10 +233,18 @@ def takes_weighted_backward_drop(layer, csr, B, F, dropout, operands):
     adjacency gradient.  The compiler's report: 219 VGPRs, no scratch, TWO workgroups per CU (under the three-workgroup bound the
     keep factors spill 84 bytes per lane; the form without dropout keeps 165 VGPRs and three workgroups).
     Timings: ``takes_weighted_dropout``."""
-    return bool(getattr(layer, "weighted_backward", False) and dropout is not None and B * csr.T * F < 2 ** 32
-                and not csr.is_binary and csr.T <= 32 and F % 4 == 0
-                and all(t is None or t.data_ptr() % 16 == 0 for t in operands)
-                and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1" and csr.graph_ops_weighted_t() is not None)
+    return dropout is not None and B * csr.T * F < 2 ** 32 and _weighted_backward_base(layer, csr, F, operands)
+
+
+def backward_launch(layer, csr, dtype, B, K, F, need_x, need_adj, dropout, operands):
+    """``backward_plan`` with its pass replaced by "weighted" / "weighted_drop" (``BACKWARD_LAUNCHES``) where the two predicates above
+    hold: asked after the plan and only where it says "two_pass" / "two_pass_drop", so the plan's answers stay as pinned."""
+    passes, dx, dw = backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands)
+    if passes == "two_pass" and takes_weighted_backward(layer, csr, F, dropout, operands):
+        passes = "weighted"
+    elif passes == "two_pass_drop" and takes_weighted_backward_drop(layer, csr, B, F, dropout, operands):
+        passes = "weighted_drop"
+    return passes, dx, dw
 
 
 # ---- the block of two layers (the four predicates are gated_block's public ones) -------------------------------------------------

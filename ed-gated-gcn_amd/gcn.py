@@ -11,6 +11,7 @@ Extras that the classifier block uses (``models/bert_amir5.py:621-640``):
 ``forward_gated`` fuses the per-sentence gate and the max-pool over tokens into the
 aggregation pass, taking the gate as ``[B,H]`` instead of a materialised ``[B,T,H]``.
 """
+import collections
 import os
 
 import torch
@@ -50,13 +51,59 @@ def _drop_args(dropout):
     return (0.0, 0, 0, 0, 0) if dropout is None else (float(dropout[0]), int(dropout[1])) + tuple(dropout[2])
 
 
-def _admit(path, dropout, overlap, weighted_drop=False):
-    """Gate dropout and the overlap operands exist in the one-launch layers only: decided from the name of the path the call takes
-    (``weighted_drop``: ``dispatch.takes_weighted_dropout`` holds -- the opt-in launches that ``layer_path`` has no name for)."""
-    if dropout is not None and path not in dispatch.DROPOUT_PATHS and not weighted_drop:
+def _admit(launch, dropout, overlap):
+    """Gate dropout and the overlap operands exist in the one-launch layers only: decided from the name of the launch the call takes."""
+    if dropout is not None and launch not in dispatch.DROPOUT_LAUNCHES:
         raise RuntimeError("dropout= needs the one-launch layer (takes_dropout_path: takes_fused_path and B*T*F < 2^32)")
-    if overlap and path not in dispatch.OVERLAP_PATHS:
+    if overlap and launch not in dispatch.OVERLAP_LAUNCHES:
         raise RuntimeError("overlap_partial / overlap_reduce need the one-launch layer (takes_fused_path)")
+
+
+# One one-launch layer of _forward_gated.  Every entry takes ``X, ldx, weight image, <graph operands>, bias, [zero mid row], B, T, K, F,
+# gates, outputs, [overlap x 3], [precision], [p, seed, keep streams], stream``.  image(layer, x2d, csr): the precision of the weight
+# image (None: the layer's own); graph(csr, precision): the per-graph operands; mid: the zero row follows the bias; overlap: True the
+# three overlap operands, False three NULLs, None no such arguments; precision / drop: the precision code / dropout arguments follow.
+_LayerLaunch = collections.namedtuple("_LayerLaunch", "entry image graph mid overlap precision drop", defaults=(False, None, False, False))
+
+
+def _weighted_image(layer, x2d, csr):
+    return "bf16x3" if layer.precision == "bf16x3" else "f16mx8"
+
+
+_LAYER_LAUNCHES = {   # dispatch.layer_launch's names but "two_launch" (linear + aggregate)
+    "fused": _LayerLaunch("ggcn_layer_fused", lambda m, x2d, c: m.kernel_precision(x2d, c),
+                          lambda c, prec: (c.rowmask, c.graph_ops if c.T <= 32 else dispatch.edge_lists(c)), overlap=True, precision=True),
+    "fused_drop": _LayerLaunch("ggcn_layer_fused_drop", lambda m, x2d, c: "f16mx8" if m.precision == "f16mx6" else m.precision,
+                               lambda c, prec: (c.rowmask, c.graph_ops), precision=True, drop=True),   # (the fp6 kernel has no dropout epilogue)
+    # bfloat16 features, the bf16x3 image: <= 32 nodes on the operand blocks; 33..256 on the row masks, one entry (p = 0 draws nothing)
+    "bf16": _LayerLaunch("ggcn_layer_fused_bf16", lambda m, x2d, c: "bf16x3", lambda c, prec: (c.graph_ops,), overlap=True),
+    "bf16_drop": _LayerLaunch("ggcn_layer_fused_bf16_drop", lambda m, x2d, c: "bf16x3", lambda c, prec: (c.graph_ops,), overlap=True, drop=True),
+    "bf16_wide": _LayerLaunch("ggcn_layer_fused_bf16_wide", lambda m, x2d, c: "bf16x3",
+                              lambda c, prec: (c.rowmask, dispatch.edge_lists(c) if c.T > 128 else None), overlap=True, drop=True),
+    # real-valued adjacency: D.A_w as one operand per graph of <= 32 nodes and plane type, or ceil(T/32)^2 blocks of 33..128 (weighted_max_t)
+    "weighted": _LayerLaunch("ggcn_layer_fused_weighted", _weighted_image, lambda c, prec: (c.graph_ops_weighted(0 if prec == "bf16x3" else 1),),
+                             mid=True, overlap=False, precision=True),
+    "weighted_drop": _LayerLaunch("ggcn_layer_fused_weighted_drop", _weighted_image,
+                                  lambda c, prec: (c.graph_ops_weighted(0 if prec == "bf16x3" else 1),), mid=True, precision=True, drop=True),
+    "weighted_wide": _LayerLaunch("ggcn_layer_fused_weighted_wide", _weighted_image, lambda c, prec: (c.graph_ops_weighted_wide(),), precision=True),
+    "weighted_wide_drop": _LayerLaunch("ggcn_layer_fused_weighted_wide_drop", _weighted_image, lambda c, prec: (c.graph_ops_weighted_wide(),),
+                                       precision=True, drop=True),
+    # long fp16 graphs (BASELINE configs[3]): linear + aggregation in one launch, hidden stays in LDS
+    "long": _LayerLaunch("ggcn_layer_fused_h", lambda m, x2d, c: None, lambda c, prec: (c.rowptr, c.colidx, c.vals)),
+}
+_LAYER_LAUNCHES["bf16_wide_drop"] = _LAYER_LAUNCHES["bf16_wide"]
+
+# dispatch.backward_launch's names: the entry, the graph operands after d_pb, what it writes ("dH"; "dY": to memory, for
+# ggcn_aggregate_t; "both": dH, and dY where an adjacency gradient wants it) and what follows d_bsum
+_weighted_t = lambda c: (c.graph_ops_weighted_t(), c.inv_denominators())   # noqa: E731
+_BACKWARD_LAUNCHES = {
+    "mma": ("ggcn_gate_pool_backward_mma", lambda c: (c.graph_ops, c.graph_ops_t), "dH", ("amax",)),
+    "one_pass": ("ggcn_gate_pool_backward_agg", lambda c: (c.rowmask,), "dH", ("drop", "amax")),
+    "two_pass": ("ggcn_gate_pool_backward", lambda c: (), "dY", ()),
+    "two_pass_drop": ("ggcn_gate_pool_backward_drop", lambda c: (), "dY", ("drop",)),
+    "weighted": ("ggcn_gate_pool_backward_weighted", _weighted_t, "both", ()),
+    "weighted_drop": ("ggcn_gate_pool_backward_weighted_drop", _weighted_t, "both", ("drop",)),
+}
 
 
 class _GatedLayerFunction(torch.autograd.Function):
@@ -67,8 +114,8 @@ class _GatedLayerFunction(torch.autograd.Function):
 
         dY, d_sg, d_ga, d_gb   HIP, one pass over the stored output (gate_pool_backward.hip)
         dH = A^T.(D.dY)        HIP, one wavefront per SOURCE node on the transposed CSR (0/1 graphs of <= 32 nodes: one launch with
-                               the line above, dispatch.backward_plan; real-valued ones with ``weighted_backward``:
-                               ggcn_gate_pool_backward_weighted[_drop], dispatch.takes_weighted_backward[_drop])
+                               the line above; real-valued ones with ``weighted_backward``:
+                               ggcn_gate_pool_backward_weighted[_drop]; dispatch.backward_launch names the launch)
         dX = dH.W^T            HIP bf16x3 MFMA linear on the packed W^T (bfloat16 features: stored as bf16, RNE)
         dW = X^T.dH            HIP split-K: bf16x3 main loop on X^T and packed dH (dweight_bx3.hip; bfloat16 features:
                                X^T in bf16, ggcn_dweight_bf16), or the exact-fp32 MFMA form for precision 'fp32' (dweight_fp32.hip)
@@ -122,30 +169,18 @@ class _GatedLayerFunction(torch.autograd.Function):
             dh = torch.empty(B * T, F, **f32)
             need_adj = ctx.adj_dtype is not None and need[11]
             operands = (out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum)
-            passes, dx_form, dw_form = dispatch.backward_plan(layer, csr, text.dtype, K, F, need[0], need_adj, ctx.dropout, operands)
-            # a real-valued adjacency of <= 32 nodes, opt-in: the two passes as one launch on the matrix cores (dY only for d_adj)
-            weighted = ((passes == "two_pass" and dispatch.takes_weighted_backward(layer, csr, F, ctx.dropout, operands))
-                        or (passes == "two_pass_drop" and dispatch.takes_weighted_backward_drop(layer, csr, B, F, ctx.dropout, operands)))
-            two_pass = passes in ("two_pass", "two_pass_drop") and not weighted   # dY to memory, then dH = A^T.(D.dY) on the transposed CSR
+            launch, dx_form, dw_form = dispatch.backward_launch(layer, csr, text.dtype, B, K, F, need[0], need_adj, ctx.dropout, operands)
+            entry, graph, writes, tail = _BACKWARD_LAUNCHES[launch]
             dh_amax = torch.zeros(1, **f32) if dx_form == "scaled" else None
-            dy = torch.empty(B * T, F, **f32) if (two_pass or (weighted and need_adj)) else None
-            drop = _drop_args(ctx.dropout)   # the keep factors of the forward launch, drawn again from (seed, element)
-            entry, graph, tail = {"mma": ("ggcn_gate_pool_backward_mma", ("graph_ops", "graph_ops_t"), (ptr(dh_amax),)),
-                                  "one_pass": ("ggcn_gate_pool_backward_agg", ("rowmask",), drop + (ptr(dh_amax),)),
-                                  "two_pass": ("ggcn_gate_pool_backward", (), ()),
-                                  "two_pass_drop": ("ggcn_gate_pool_backward_drop", (), drop)}[passes]
-            if weighted:   # (under gate dropout: the same launch with the forward's keep factors)
-                entry = "ggcn_gate_pool_backward_weighted" + ("_drop" if ctx.dropout is not None else "")
-                _capi.check(getattr(lib, entry)(
-                    ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
-                    ptr(csr.graph_ops_weighted_t()), ptr(csr.inv_denominators()), B, T, F, ptr(dh), F, ptr(dy), F,
-                    ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), *(drop if ctx.dropout is not None else ()), st), entry)
-            else:
-                _capi.check(getattr(lib, entry)(
-                    ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
-                    *(ptr(getattr(csr, name)) for name in graph), B, T, F, ptr(dy if two_pass else dh), F,
-                    ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), *tail, st), entry)
-            if two_pass:
+            dy = torch.empty(B * T, F, **f32) if (writes == "dY" or (writes == "both" and need_adj)) else None
+            # "drop": the keep factors of the forward launch, drawn again from (seed, element)
+            after = {"drop": _drop_args(ctx.dropout), "amax": (ptr(dh_amax),)}
+            grads = {"dH": (ptr(dh), F), "dY": (ptr(dy), F), "both": (ptr(dh), F, ptr(dy), F)}[writes]
+            _capi.check(getattr(lib, entry)(
+                ptr(out2), F, ptr(store_gate), ptr(gate_a), ptr(gate_b), ptr(d_out2), F, ptr(d_pa), ptr(d_pb),
+                *(ptr(t) for t in graph(csr)), B, T, F, *grads,
+                ptr(d_sg), ptr(d_ga), ptr(d_gb), ptr(d_bsum), *(a for name in tail for a in after[name]), st), entry)
+            if writes == "dY":   # dY went to memory: dH = A^T.(D.dY) on the transposed CSR
                 csr_t = csr.transposed()
                 _capi.check(lib.ggcn_aggregate_t(ptr(dy), F, ptr(csr_t.rowptr), ptr(csr_t.colidx), ptr(csr_t.vals),
                                                  ptr(csr.inv_denominators()), B, T, F, ptr(dh), F, st), "ggcn_aggregate_t")
@@ -563,14 +598,11 @@ class GraphConvolution(nn.Module):
         csr = self._as_csr(adj, text)
         training = not _internal and self._needs_grad(text, store_gate, pool_gate_a, pool_gate_b, adj=adj)
         x2d = None if training else _rows2d(text)
-        path = dispatch.layer_path(self, text, csr, dropout is not None, x2d)
-        # gate dropout where layer_path names no launch that draws it: the opt-in weighted launches, asked once
-        weighted_drop = (dropout is not None and path not in dispatch.DROPOUT_PATHS
-                         and dispatch.takes_weighted_dropout(self, csr, dispatch.Input.of(text)))
+        launch = dispatch.layer_launch(self, text, csr, dropout is not None, x2d)
         if training:   # the same kernels, wrapped in an autograd Function with a HIP backward
             if text.dtype not in (torch.float32, torch.bfloat16):
                 raise RuntimeError("training through the HIP layer needs float32 features (or bfloat16 ones)")
-            _admit(path, dropout, False, weighted_drop)
+            _admit(launch, dropout, False)
             if dropout is not None:
                 # the backward recovers y from the stored out = y*sg*k_store: a token whose store factor is 0 leaves nothing to
                 # recover, which is exact only for pools that drop the same tokens (include/ggcn.h ggcn_gate_pool_backward_drop)
@@ -592,8 +624,8 @@ class GraphConvolution(nn.Module):
             if g is not None:
                 _require_gpu_f32(name, g)
                 _require_gate(name, g, B, F, "%(name)s must be a contiguous [B,F]=[%(B)d,%(F)d] tensor, got %(shape)s")
-        _admit(path, dropout, overlap_partial is not None or overlap_reduce is not None, weighted_drop)
-        hidden = self.linear(x2d) if path == "two_launch" and not weighted_drop else None
+        _admit(launch, dropout, overlap_partial is not None or overlap_reduce is not None)
+        hidden = self.linear(x2d) if launch == "two_launch" else None
         ptr = _capi.ptr
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
@@ -603,62 +635,26 @@ class GraphConvolution(nn.Module):
             bias = None if self.bias is None else self.bias.detach()
             # what every entry takes after its operands: the shape, the three gates, the outputs
             tail = (B, T, K, F, ptr(store_gate), ptr(pool_gate_a), ptr(pool_gate_b), ptr(out), F, ptr(pa), ptr(pb))
-            ov = (ptr(overlap_partial), ptr(overlap_reduce[0]) if overlap_reduce else None, ptr(overlap_reduce[1]) if overlap_reduce else None)
-            drop = _drop_args(dropout)
-            if weighted_drop:   # real-valued adjacency under gate dropout (weighted_dropout): the weighted launches with keep factors
-                if overlap_partial is not None or overlap_reduce is not None:
-                    raise RuntimeError("overlap_partial / overlap_reduce need the one-launch layer (takes_fused_path)")
-                kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"
-                pack = self._packed_weight(lib, st, precision=kprec)
-                if T > 32:
-                    _capi.check(lib.ggcn_layer_fused_weighted_wide_drop(
-                        ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops_weighted_wide()), ptr(bias), *tail, _capi.PREC[kprec], *drop, st),
-                        "ggcn_layer_fused_weighted_wide_drop")
-                else:
-                    _capi.check(lib.ggcn_layer_fused_weighted_drop(
-                        ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops_weighted(0 if kprec == "bf16x3" else 1)), ptr(bias),
-                        ptr(self._zero_row(F, dev)), *tail, _capi.PREC[kprec], *drop, st), "ggcn_layer_fused_weighted_drop")
-            elif path == "fused_drop":
-                kprec = "f16mx8" if self.precision == "f16mx6" else self.precision   # the fp6 kernel has no dropout epilogue
-                pack = self._packed_weight(lib, st, precision=kprec)
-                _capi.check(lib.ggcn_layer_fused_drop(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowmask), ptr(csr.graph_ops), ptr(bias),
-                                                      *tail, _capi.PREC[kprec], *drop, st), "ggcn_layer_fused_drop")
-            elif path == "fused":
-                kprec = self.kernel_precision(x2d, csr)
-                pack = self._packed_weight(lib, st, precision=kprec)
-                _capi.check(lib.ggcn_layer_fused(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowmask),
-                                                 ptr(csr.graph_ops if T <= 32 else dispatch.edge_lists(csr)), ptr(bias),
-                                                 *tail, *ov, _capi.PREC[kprec], st), "ggcn_layer_fused")
-            elif path in ("bf16_wide", "bf16_wide_drop"):   # bfloat16 features, 33..256 nodes: one launch on the bf16x3 image and the row masks
-                pack = self._packed_weight(lib, st, precision="bf16x3")
-                _capi.check(lib.ggcn_layer_fused_bf16_wide(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowmask),
-                                                           ptr(dispatch.edge_lists(csr) if T > 128 else None), ptr(bias),
-                                                           *tail, *ov, *drop, st), "ggcn_layer_fused_bf16_wide")
-            elif path in ("bf16", "bf16_drop"):   # bfloat16 features, <= 32 nodes: one launch on the bf16x3 image
-                pack = self._packed_weight(lib, st, precision="bf16x3")
-                entry = "ggcn_layer_fused_" + path
-                _capi.check(getattr(lib, entry)(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops), ptr(bias),
-                                                *tail, *ov, *(drop if path == "bf16_drop" else ()), st), entry)
-            elif path == "weighted" and T > 32:   # real-valued adjacency, 33..128 nodes (weighted_max_t): one launch on ceil(T/32)^2 blocks of D.A_w
-                kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"
-                pack = self._packed_weight(lib, st, precision=kprec)
-                _capi.check(lib.ggcn_layer_fused_weighted_wide(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.graph_ops_weighted_wide()), ptr(bias),
-                                                               *tail, _capi.PREC[kprec], st), "ggcn_layer_fused_weighted_wide")
-            elif path == "weighted":   # real-valued adjacency, graphs of <= 32 nodes: one launch on D.A_w operand blocks
-                kprec = "bf16x3" if self.precision == "bf16x3" else "f16mx8"
-                pack = self._packed_weight(lib, st, precision=kprec)
-                _capi.check(lib.ggcn_layer_fused_weighted(ptr(x2d), x2d.stride(0), ptr(pack),
-                                                          ptr(csr.graph_ops_weighted(0 if kprec == "bf16x3" else 1)), ptr(bias),
-                                                          ptr(self._zero_row(F, dev)),
-                                                          *tail, None, None, None, _capi.PREC[kprec], st), "ggcn_layer_fused_weighted")
-            elif path == "long":   # long fp16 graphs (BASELINE configs[3]): linear + aggregation in one launch, hidden stays in LDS
-                pack = self._packed_weight(lib, st)
-                _capi.check(lib.ggcn_layer_fused_h(ptr(x2d), x2d.stride(0), ptr(pack), ptr(csr.rowptr), ptr(csr.colidx), ptr(csr.vals),
-                                                   ptr(bias), *tail, st), "ggcn_layer_fused_h")
-            else:   # "two_launch": the aggregation of `hidden`, gate and pools in its epilogue
+            if launch == "two_launch":   # the aggregation of `hidden`, gate and pools in its epilogue
                 agg = lib.ggcn_aggregate_h if text.dtype == torch.float16 else lib.ggcn_aggregate
                 _capi.check(agg(ptr(hidden), hidden.stride(0), ptr(csr.rowptr), ptr(csr.colidx), ptr(csr.vals), ptr(bias),
                                 B, T, *tail[3:], st), "ggcn_aggregate")
+            else:
+                entry, image, graph, mid, overlap, precision, drop = _LAYER_LAUNCHES[launch]
+                kprec = image(self, x2d, csr)
+                args = [ptr(x2d), x2d.stride(0), ptr(self._packed_weight(lib, st, precision=kprec)), *map(ptr, graph(csr, kprec)), ptr(bias)]
+                if mid:
+                    args.append(ptr(self._zero_row(F, dev)))
+                args += tail
+                if overlap and (overlap_partial is not None or overlap_reduce):
+                    args += (ptr(overlap_partial), ptr(overlap_reduce[0]) if overlap_reduce else None, ptr(overlap_reduce[1]) if overlap_reduce else None)
+                elif overlap is not None:
+                    args += (None, None, None)
+                if precision:
+                    args.append(_capi.PREC[kprec])
+                if drop:
+                    args += _drop_args(dropout)
+                _capi.check(getattr(lib, entry)(*args, st), entry)
         return (None if out is None else out.view(B, T, F)), pa, pb
 
     def forward(self, text, adj):

@@ -1,0 +1,334 @@
+"""What ``forward_gated`` and its backward hand to the library, argument by argument, for every launch name of
+``dispatch.LAYER_LAUNCHES`` / ``dispatch.BACKWARD_LAUNCHES``, and what the cached operand builders of ``BatchedCSR`` launch.
+
+A recorder in the pattern of ``_count_calls`` replaces the entries on the loaded library and logs ``(name, arguments)``, pointers as
+integers (NULL: None).  The expectations are written out from the prototypes of ``include/ggcn.h``, entry by entry -- not from the
+tables in ``gcn.py``.  B = 3, K = F = 64, three gates, every output wanted: what can go wrong is an argument in the wrong place or
+an operand chosen on the wrong side of a size rule, so the graph lengths are the rule edges and nothing needs to be large.  Every
+call runs on a side stream, so that the stream argument is not NULL either."""
+import ctypes
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+B, K, F = 3, 64, 64
+SEED = 2 ** 40 + 99
+DROPOUT = (0.25, SEED, (0, 1, 2))
+DROP_ARGS, NO_DROP = [0.25, SEED, 0, 1, 2], [0.0, 0, 0, 0, 0]
+BF16X3, F16MX8 = 0, 2                     # include/ggcn.h GGCN_PREC_*
+LAUNCHES = ("ggcn_layer_fused", "ggcn_layer_fused_drop", "ggcn_layer_fused_bf16", "ggcn_layer_fused_bf16_drop", "ggcn_layer_fused_bf16_wide",
+            "ggcn_layer_fused_weighted", "ggcn_layer_fused_weighted_wide", "ggcn_layer_fused_weighted_drop",
+            "ggcn_layer_fused_weighted_wide_drop", "ggcn_layer_fused_h", "ggcn_layer_fused_prebias", "ggcn_linear", "ggcn_linear_h",
+            "ggcn_linear_bf16", "ggcn_aggregate", "ggcn_aggregate_h")
+BACKWARD = ("ggcn_gate_pool_backward", "ggcn_gate_pool_backward_drop", "ggcn_gate_pool_backward_agg", "ggcn_gate_pool_backward_mma",
+            "ggcn_gate_pool_backward_weighted", "ggcn_gate_pool_backward_weighted_drop", "ggcn_aggregate_t", "ggcn_adjacency_grad")
+BUILDERS = ("ggcn_graph_operands", "ggcn_graph_edge_lists", "ggcn_rowmask_transpose", "ggcn_graph_operands2", "ggcn_graph_operands_weighted",
+            "ggcn_graph_operands_weighted_wide", "ggcn_graph_operands_weighted_t")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import ed_gated_gcn_amd as p
+    p.load_library()
+    return p
+
+
+@pytest.fixture
+def side_stream(dev):
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(s):
+        yield ctypes.c_void_p(s.cuda_stream).value
+        s.synchronize()
+
+
+@pytest.fixture
+def log(monkeypatch, pkg):
+    """``[(entry, [arguments])]`` of every call of a layer, backward or builder entry from here on."""
+    lib = pkg.load_library()
+    calls = []
+    for n in LAUNCHES + BACKWARD + BUILDERS:
+        fn = getattr(lib, n)
+
+        def wrap(*a, _fn=fn, _n=n):
+            calls.append((_n, [v.value if isinstance(v, ctypes.c_void_p) else v for v in a]))
+            return _fn(*a)
+        monkeypatch.setattr(lib, n, wrap)
+    return calls
+
+
+def _only(log, names):
+    return [c for c in log if c[0] in names]
+
+
+def _adjacency(dev, T, weighted=False, seed=0):
+    g = torch.Generator().manual_seed(100 + seed + T)
+    a = (torch.rand(B, T, T, generator=g) < 3.0 / T).float()
+    a = ((a + a.transpose(1, 2) + torch.eye(T)) > 0).float()
+    if weighted:
+        a = a * (0.25 + 0.5 * torch.rand(B, T, T, generator=g))
+    return a.to(dev)
+
+
+def _case(pkg, dev, T, dtype=torch.float32, weighted=False, **options):
+    """``(layer, features, BatchedCSR, three gates)``; ``options`` are attributes of the layer."""
+    g = torch.Generator().manual_seed(7 + T)
+    m = pkg.GraphConvolution(K, F).to(dev)
+    with torch.no_grad():
+        m.weight.copy_(0.05 * torch.randn(K, F, generator=g))
+        m.bias.copy_(0.1 * torch.randn(F, generator=g))
+    for k, v in options.items():
+        assert hasattr(m, k), k
+        setattr(m, k, v)
+    x = torch.randn(B, T, K, generator=g).to(dev).to(dtype)
+    gates = [torch.rand(B, F, generator=g).to(dev) for _ in range(3)]
+    csr = pkg.BatchedCSR.from_dense(_adjacency(dev, T, weighted))
+    assert csr.is_binary == (not weighted)
+    return m, x, csr, gates
+
+
+def _forward(m, x, csr, gates, **kw):
+    with torch.no_grad():
+        return m.forward_gated(x, csr, store_gate=gates[0], pool_gate_a=gates[1], pool_gate_b=gates[2], want_out=True,
+                               want_pool_a=True, want_pool_b=True, **kw)
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _image(pkg, dev, m, precision):
+    from ed_gated_gcn_amd import _capi
+    return _p(m._packed_weight(pkg.load_library(), _capi.stream_of(dev), precision=precision))
+
+
+def _tail(T, gates, res):
+    """B, T, K, F, the three gates, out, ldo, the two pools: what every layer entry takes after its operands."""
+    out, pa, pb = res
+    assert out.shape == (B, T, F) and pa.shape == pb.shape == (B, F)
+    return [B, T, K, F, _p(gates[0]), _p(gates[1]), _p(gates[2]), _p(out), F, _p(pa), _p(pb)]
+
+
+def _check(log, want):
+    got = _only(log, LAUNCHES + BACKWARD)
+    assert [c[0] for c in got] == [w[0] for w in want]
+    for (name, a), (_, w) in zip(got, want):
+        assert len(a) == len(w), (name, len(a), len(w))
+        for i, (x, y) in enumerate(zip(a, w)):
+            assert x == y and type(x) is type(y), "%s argument %d: got %r, expected %r" % (name, i, x, y)
+
+
+# ---------------------------------------------------------------- float32 features, 0/1 adjacency
+@pytest.mark.parametrize("T,fused_max_t,lists", [(32, 128, "1"), (33, 128, "1"), (129, 256, "1"), (129, 256, "0")])
+def test_fused(pkg, dev, log, side_stream, monkeypatch, T, fused_max_t, lists):
+    monkeypatch.setenv("GGCN_EDGE_LISTS", lists)
+    m, x, csr, gates = _case(pkg, dev, T, fused_max_t=fused_max_t)
+    res = _forward(m, x, csr, gates)
+    block = csr.graph_ops if T <= 32 else csr.edge_lists if (T > 128 and lists == "1") else None
+    assert (block is None) == (T == 33 or lists == "0")
+    # X, ldx, wpack, rowmask, graph_ops, bias | tail | overlap_partial, overlap_in, overlap_out, precision, stream
+    _check(log, [("ggcn_layer_fused", [_p(x), K, _image(pkg, dev, m, "f16mx8"), _p(csr.rowmask), _p(block), _p(m.bias)] + _tail(T, gates, res)
+                  + [None, None, None, F16MX8, side_stream])])
+
+
+def test_fused_overlap_operands(pkg, dev, log, side_stream):
+    m, x, csr, gates = _case(pkg, dev, 32)
+    part = torch.zeros(B, (F + 63) // 64, device=dev)
+    xy = torch.zeros((), device=dev)
+    res1 = _forward(m, x, csr, gates, overlap_partial=part)
+    res2 = _forward(m, x, csr, gates, overlap_reduce=(part, xy))
+    head = [_p(x), K, _image(pkg, dev, m, "f16mx8"), _p(csr.rowmask), _p(csr.graph_ops), _p(m.bias)]
+    _check(log, [("ggcn_layer_fused", head + _tail(32, gates, res1) + [_p(part), None, None, F16MX8, side_stream]),
+                 ("ggcn_layer_fused", head + _tail(32, gates, res2) + [None, _p(part), _p(xy), F16MX8, side_stream])])
+
+
+@pytest.mark.parametrize("T,fused_max_t", [(32, 128), (129, 256)])
+def test_fused_drop(pkg, dev, log, side_stream, T, fused_max_t):
+    m, x, csr, gates = _case(pkg, dev, T, fused_max_t=fused_max_t)
+    res = _forward(m, x, csr, gates, dropout=DROPOUT)
+    assert (csr.graph_ops is None) == (T > 32)                # the operand blocks exist up to 32 nodes: NULL above, never the edge lists
+    # X, ldx, wpack, rowmask, graph_ops, bias | tail | precision, p, seed, three streams, stream
+    _check(log, [("ggcn_layer_fused_drop", [_p(x), K, _image(pkg, dev, m, "f16mx8"), _p(csr.rowmask), _p(csr.graph_ops), _p(m.bias)]
+                  + _tail(T, gates, res) + [F16MX8] + DROP_ARGS + [side_stream])])
+
+
+# ---------------------------------------------------------------- bfloat16 features
+@pytest.mark.parametrize("dropout", [None, DROPOUT])
+def test_bf16(pkg, dev, log, side_stream, dropout):
+    m, x, csr, gates = _case(pkg, dev, 32, dtype=torch.bfloat16)
+    res = _forward(m, x, csr, gates, dropout=dropout)
+    # X, ldx, wpack, graph_ops, bias | tail | overlap x 3, [p, seed, three streams], stream
+    _check(log, [("ggcn_layer_fused_bf16_drop" if dropout else "ggcn_layer_fused_bf16",
+                  [_p(x), K, _image(pkg, dev, m, "bf16x3"), _p(csr.graph_ops), _p(m.bias)] + _tail(32, gates, res) + [None, None, None]
+                  + (DROP_ARGS if dropout else []) + [side_stream])])
+    assert res[0].dtype == torch.float32
+
+
+@pytest.mark.parametrize("dropout", [None, DROPOUT])
+@pytest.mark.parametrize("T", [128, 129])
+def test_bf16_wide(pkg, dev, log, side_stream, T, dropout):
+    m, x, csr, gates = _case(pkg, dev, T, dtype=torch.bfloat16, fused_max_t=256)
+    res = _forward(m, x, csr, gates, dropout=dropout)
+    lists = csr.edge_lists
+    assert (lists is None) == (T <= 128)
+    # X, ldx, wpack, rowmask, edge_lists, bias | tail | overlap x 3, p, seed, three streams, stream
+    _check(log, [("ggcn_layer_fused_bf16_wide", [_p(x), K, _image(pkg, dev, m, "bf16x3"), _p(csr.rowmask), _p(lists), _p(m.bias)]
+                  + _tail(T, gates, res) + [None, None, None] + (DROP_ARGS if dropout else NO_DROP) + [side_stream])])
+
+
+# ---------------------------------------------------------------- real-valued adjacency
+@pytest.mark.parametrize("dropout", [None, DROPOUT])
+@pytest.mark.parametrize("precision,plane,code", [("f16mx8", 1, F16MX8), ("bf16x3", 0, BF16X3)])
+def test_weighted(pkg, dev, log, side_stream, precision, plane, code, dropout):
+    m, x, csr, gates = _case(pkg, dev, 32, weighted=True, precision=precision, weighted_dropout=dropout is not None)
+    res = _forward(m, x, csr, gates, dropout=dropout)
+    head = [_p(x), K, _image(pkg, dev, m, precision), _p(csr.graph_ops_weighted(plane)), _p(m.bias), _p(m._zero_mid)]
+    assert list(csr._graph_ops_w) == [plane] and m._zero_mid.numel() >= F
+    if dropout:   # X, ldx, wpack, graph_opsw, bias, zero_mid | tail | precision, p, seed, three streams, stream
+        _check(log, [("ggcn_layer_fused_weighted_drop", head + _tail(32, gates, res) + [code] + DROP_ARGS + [side_stream])])
+    else:         # X, ldx, wpack, graph_opsw, bias, zero_mid | tail | overlap x 3 (NULL), precision, stream
+        _check(log, [("ggcn_layer_fused_weighted", head + _tail(32, gates, res) + [None, None, None, code, side_stream])])
+
+
+@pytest.mark.parametrize("dropout", [None, DROPOUT])
+def test_weighted_wide(pkg, dev, log, side_stream, dropout):
+    m, x, csr, gates = _case(pkg, dev, 33, weighted=True, weighted_max_t=128, weighted_dropout=dropout is not None)
+    res = _forward(m, x, csr, gates, dropout=dropout)
+    # X, ldx, wpack, graph_opsww, bias | tail | precision, [p, seed, three streams], stream
+    _check(log, [("ggcn_layer_fused_weighted_wide_drop" if dropout else "ggcn_layer_fused_weighted_wide",
+                  [_p(x), K, _image(pkg, dev, m, "f16mx8"), _p(csr.graph_ops_weighted_wide()), _p(m.bias)] + _tail(33, gates, res) + [F16MX8]
+                  + (DROP_ARGS if dropout else []) + [side_stream])])
+    assert csr._graph_ops_w is None                            # nothing of the <= 32 form was asked for
+
+
+# ---------------------------------------------------------------- float16 features: the long launch
+def test_long(pkg, dev, log, side_stream):
+    m, x, csr, gates = _case(pkg, dev, 129, dtype=torch.float16, precision="f16")
+    res = _forward(m, x, csr, gates)
+    # X, ldx, wpack, rowptr, colidx, vals, bias | tail | stream
+    _check(log, [("ggcn_layer_fused_h", [_p(x), K, _image(pkg, dev, m, None), _p(csr.rowptr), _p(csr.colidx), None, _p(m.bias)]
+                  + _tail(129, gates, res) + [side_stream])])
+    assert res[0].dtype == torch.float16 and csr.vals is None
+
+
+# ---------------------------------------------------------------- linear + aggregate
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+def test_two_launch(pkg, dev, log, side_stream, dtype):
+    T = 24
+    m, x, csr, gates = _case(pkg, dev, T, dtype=dtype, fused=False)
+    res = _forward(m, x, csr, gates)
+    got = _only(log, LAUNCHES)
+    assert len(got) == 2
+    hidden = got[0][1][5 if dtype == torch.float32 else 3]     # Y of the linear: made inside the call
+    assert isinstance(hidden, int) and hidden not in (_p(x), _p(res[0]))
+    if dtype == torch.float32:     # X, ldx, W, ldw, wpack, Y, ldy, M, K, F, precision, stream
+        linear = ("ggcn_linear", [_p(x), K, _p(m.weight), F, _image(pkg, dev, m, "f16mx8"), hidden, F, B * T, K, F, F16MX8, side_stream])
+    elif dtype == torch.float16:   # X, ldx, wpack, Y, ldy, M, K, F, precision, stream
+        linear = ("ggcn_linear_h", [_p(x), K, _image(pkg, dev, m, "f16mx8"), hidden, F, B * T, K, F, F16MX8, side_stream])
+    else:                          # X, ldx, wpack, Y, ldy, M, K, F, stream
+        linear = ("ggcn_linear_bf16", [_p(x), K, _image(pkg, dev, m, "bf16x3"), hidden, F, B * T, K, F, side_stream])
+    # H, ldh, rowptr, colidx, vals, bias, B, T, F, the gates, out, ldo, the pools, stream
+    _check(log, [linear, ("ggcn_aggregate_h" if dtype == torch.float16 else "ggcn_aggregate",
+                          [hidden, F, _p(csr.rowptr), _p(csr.colidx), None, _p(m.bias), B, T] + _tail(T, gates, res)[3:] + [side_stream])])
+    assert res[0].dtype == (torch.float16 if dtype == torch.float16 else torch.float32)
+
+
+# ---------------------------------------------------------------- the backward launches
+def _step(m, x, graph, gates, dropout=None):
+    x.requires_grad_(True)
+    out, pa, pb = m.forward_gated(x, graph, store_gate=gates[0], pool_gate_a=gates[1], pool_gate_b=gates[2], want_out=True,
+                                  want_pool_a=True, want_pool_b=True, dropout=dropout)
+    (out.sum() + pa.sum() + pb.sum()).backward()
+    assert x.grad is not None and m.weight.grad is not None and m.bias.grad is not None
+
+
+# the arguments up to d_pb are the same nine in every entry: out, ldo, three gates, d_out, ldd, d_pa, d_pb
+@pytest.mark.parametrize("launch,T,weighted,dropout,forward,backward", [
+    ("mma", 24, False, None, "ggcn_layer_fused", ["ggcn_gate_pool_backward_mma"]),
+    ("one_pass", 24, False, DROPOUT, "ggcn_layer_fused_drop", ["ggcn_gate_pool_backward_agg"]),
+    ("two_pass", 33, False, None, "ggcn_layer_fused", ["ggcn_gate_pool_backward", "ggcn_aggregate_t"]),
+    ("two_pass_drop", 33, False, DROPOUT, "ggcn_layer_fused_drop", ["ggcn_gate_pool_backward_drop", "ggcn_aggregate_t"]),
+    ("weighted", 24, True, None, "ggcn_layer_fused_weighted", ["ggcn_gate_pool_backward_weighted"]),
+    ("weighted_drop", 24, True, DROPOUT, "ggcn_layer_fused_weighted_drop", ["ggcn_gate_pool_backward_weighted_drop"])])
+def test_backward_sequence(pkg, dev, log, side_stream, launch, T, weighted, dropout, forward, backward):
+    m, x, csr, gates = _case(pkg, dev, T, weighted=weighted, weighted_backward=weighted, weighted_dropout=weighted)
+    _step(m, x, csr, gates, dropout)
+    assert [c[0] for c in _only(log, LAUNCHES)][:1] == [forward]
+    got = _only(log, BACKWARD)
+    assert [c[0] for c in got] == backward
+    a = got[0][1]
+    assert a[1] == F and a[6] == F and all(isinstance(v, int) for v in a[:9])
+    if launch == "mma":                       # ..., graph_ops, graph_ops_t, B, T, F, dH, ldh, four gradients, dh_amax, stream
+        assert a[9:14] == [_p(csr.graph_ops), _p(csr.graph_ops_t), B, T, F] and a[15] == F and a[14] and len(a) == 22
+        assert a[21] == side_stream and a[20] is not None     # F % 32 == 0: the scaled dX wants max |dH|
+    elif launch == "one_pass":                # ..., rowmask, B, T, F, dH, ldh, four gradients, p, seed, three streams, dh_amax, stream
+        assert a[9:13] == [_p(csr.rowmask), B, T, F] and a[14] == F and a[13] and a[19:24] == DROP_ARGS and a[25] == side_stream
+        assert a[24] is None and len(a) == 26                 # the scalar launch hands max |dH| over for F % 256 == 0 only
+    elif launch in ("two_pass", "two_pass_drop"):   # ..., B, T, F, dY, ldy, four gradients, [p, seed, three streams], stream
+        assert a[9:12] == [B, T, F] and a[13] == F and a[12] is not None
+        assert a[18:-1] == (DROP_ARGS if dropout else []) and a[-1] == side_stream
+        t = got[1][1]                         # G, ldg, rowptr_t, colidx_t, vals_t, src_scale, B, T, F, out, ldo, stream
+        assert t[0] == a[12] and t[1] == F and t[6:9] == [B, T, F] and t[9] not in (None, t[0]) and t[10:] == [F, side_stream]
+        assert t[4] is None and t[5] == _p(csr.inv_denominators())
+    else:                                     # ..., graph_ops_wt, inv, B, T, F, dH, ldh, dY, ldy, four gradients, [p, ...], stream
+        assert a[9:14] == [_p(csr.graph_ops_weighted_t()), _p(csr.inv_denominators()), B, T, F] and a[14] and a[15] == F
+        assert a[16] is None and a[17] == F   # dY: no second pass, no adjacency gradient
+        assert a[22:-1] == (DROP_ARGS if dropout else []) and a[-1] == side_stream
+
+
+@pytest.mark.parametrize("weighted_backward", [False, True])
+def test_backward_with_an_adjacency_gradient_writes_dy(pkg, dev, log, side_stream, weighted_backward):
+    m, x, _, gates = _case(pkg, dev, 24, weighted=True, weighted_backward=weighted_backward)
+    adj = _adjacency(dev, 24, weighted=True).requires_grad_(True)
+    _step(m, x, adj, gates)
+    got = _only(log, BACKWARD)
+    if weighted_backward:
+        assert [c[0] for c in got] == ["ggcn_gate_pool_backward_weighted", "ggcn_adjacency_grad"]
+        dy = got[0][1][16]
+    else:
+        assert [c[0] for c in got] == ["ggcn_gate_pool_backward", "ggcn_aggregate_t", "ggcn_adjacency_grad"]
+        dy = got[0][1][12]
+        assert got[1][1][0] == dy
+    assert dy is not None and got[-1][1][0] == dy and adj.grad is not None and adj.grad.shape == (B, 24, 24)
+
+
+# ---------------------------------------------------------------- the cached operand builders
+BUILT = [   # (accessor, arguments, entries it launches, T it takes, weighted, slot, T it does not take)
+    ("graph_ops", None, ["ggcn_graph_operands"], 32, False, "_graph_ops", [33]),
+    ("edge_lists", None, ["ggcn_graph_edge_lists"], 129, False, "_edge_lists", [128]),
+    ("graph_ops_t", None, ["ggcn_rowmask_transpose", "ggcn_graph_operands"], 32, False, "_graph_ops_t", [33]),
+    ("graph_ops2", (0,), ["ggcn_graph_operands2"], 32, False, "_graph_ops2", [33]),
+    ("graph_ops_weighted", (1,), ["ggcn_graph_operands_weighted"], 32, True, "_graph_ops_w", [33]),
+    ("graph_ops_weighted_wide", (), ["ggcn_graph_operands_weighted_wide"], 33, True, "_graph_ops_ww", [32, 129]),
+    ("graph_ops_weighted_t", (), ["ggcn_graph_operands_weighted_t"], 32, True, "_graph_ops_wt", [33]),
+]
+
+
+@pytest.mark.parametrize("accessor,args,entries,T,weighted,slot,not_taken", BUILT, ids=[b[0] for b in BUILT])
+def test_builder_launches_once_and_caches(pkg, dev, log, side_stream, accessor, args, entries, T, weighted, slot, not_taken):
+    def get(csr):
+        return getattr(csr, accessor) if args is None else getattr(csr, accessor)(*args)
+
+    csr = pkg.BatchedCSR.from_dense(_adjacency(dev, T, weighted))
+    first, second = get(csr), get(csr)
+    assert isinstance(first, torch.Tensor) and first.dtype == torch.uint8 and second is first
+    assert [c[0] for c in _only(log, BUILDERS)] == entries
+    call = _only(log, BUILDERS)[-1][1]
+    assert B in call and T in call and call[-1] == side_stream and _p(first) in call
+    cached = getattr(csr, slot)
+    assert (cached[args[0]] if isinstance(cached, dict) else cached) is first
+    del log[:]
+    for other in not_taken:
+        idle = pkg.BatchedCSR.from_dense(_adjacency(dev, other, weighted))
+        made = idle._rowptr is not None       # (graphs of > 128 nodes come with their CSR arrays)
+        assert get(idle) is None and get(idle) is None
+        assert getattr(idle, slot) in (None, {}) and (idle._rowptr is not None) == made      # nothing cached, nothing materialised
+    assert _only(log, BUILDERS) == []
