@@ -91,6 +91,20 @@ def check(dev):
     _verdict(st, dev)
 
 
+def reset(dev):
+    """Forget what has been collected for `dev` WITHOUT reporting it: the device word, the host word and a pending snapshot
+    (after a device synchronisation).  The kernels' own copies of the flag are cleared by ``ggcn_range_flag(flag, 1, stream)``;
+    this is the Python half.  For tests that provoke reports on purpose."""
+    dev = torch.device(dev)
+    idx = torch.cuda.current_device() if dev.index is None else dev.index
+    st = _STATE.get(idx)
+    if st is not None:
+        torch.cuda.synchronize(idx)
+        st["flag"].zero_()
+        st["host"].zero_()
+        st["pending"] = False
+
+
 def _at_exit():
     """A process that ends before a polled snapshot was read (fewer forwards than it takes, or none after the violation)
     still gets told: one read-back per device that ran guarded forwards, a line on stderr instead of an exception."""
