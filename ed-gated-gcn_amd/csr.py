@@ -61,7 +61,8 @@ class BatchedCSR:
     kernel: all the fused layer needs); the CSR arrays are materialised on first access."""
 
     __slots__ = ("_rowptr", "_colidx", "_vals", "rowmask", "B", "T", "nnz", "is_binary",
-                 "_dense", "_dense_version", "_t", "_inv", "_graph_ops", "_graph_ops2", "_graph_ops_t", "_edge_lists", "_graph_ops_w", "_graph_ops_ww", "_graph_ops_wt", "__weakref__")
+                 "_dense", "_dense_version", "_t", "_inv", "_graph_ops", "_graph_ops2", "_graph_ops_t", "_edge_lists", "_graph_ops_w", "_graph_ops_ww", "_graph_ops_wt", "_graph_ops2_w",
+                 "__weakref__")
 
     def __init__(self, rowptr, colidx, vals, B, T, nnz=None, rowmask=None):
         self._rowptr, self._colidx, self._vals, self.rowmask = rowptr, colidx, vals, rowmask
@@ -78,6 +79,7 @@ class BatchedCSR:
         self._graph_ops_w = None  # cached ggcn_graph_operands_weighted blocks per plane type (real-valued adjacency, <= 32 nodes)
         self._graph_ops_ww = None  # cached ggcn_graph_operands_weighted_wide blocks (real-valued adjacency, 33..128 nodes); False: refused
         self._graph_ops_wt = None  # cached ggcn_graph_operands_weighted_t blocks (A_w^T of <= 32 nodes: the weighted backward); False: refused
+        self._graph_ops2_w = None  # cached ggcn_graph_operands2_weighted blocks per plane type ((D.A_w)^2: the weighted one-launch block)
 
     def _build(self, entry, sizer, source, extra=(), by_length=False, flagged=False):
         """What every cached operand builder does once its precondition holds: ask ``sizer`` for the bytes of B graphs (``by_length``:
@@ -146,6 +148,22 @@ class BatchedCSR:
             if self.T > 32 or not self.rowptr.is_cuda:
                 return None
             store[plane] = self._build("ggcn_graph_operands_weighted", "ggcn_graph_operands2_bytes", (self.rowptr, self.colidx, self.vals),
+                                       extra=(plane,), flagged=True)
+        return store[plane]
+
+    def graph_ops2_weighted(self, plane):
+        """uint8 [B * GGCN_GRAPH_OPS2_BYTES] or None: layer 2 of the one-launch block on a REAL-valued adjacency of graphs of
+        <= 32 nodes as ONE operand per graph (``ggcn_graph_operands2_weighted``: (D.A_w)^2 as hi / lo parts in the plane type,
+        0 = bf16 pairs, 1 = fp16 pairs, and rowsum(D.A_w)), built from the CSR arrays on first use, one per plane type.  None for
+        graphs of more than 32 nodes, arrays that are not on the GPU, or when an entry does not fit the plane type or is not finite
+        (one read-back of the builder's flag per adjacency and plane type): that adjacency keeps one weighted launch per layer."""
+        store = self._graph_ops2_w
+        if store is None:
+            store = self._graph_ops2_w = {}
+        if plane not in store:
+            if self.T > 32 or not self.rowptr.is_cuda:
+                return None
+            store[plane] = self._build("ggcn_graph_operands2_weighted", "ggcn_graph_operands2_bytes", (self.rowptr, self.colidx, self.vals),
                                        extra=(plane,), flagged=True)
         return store[plane]
 

@@ -215,6 +215,22 @@ int ggcn_block_fused(const float *X, int64_t ldx, const void *wpack1, const void
                        x_out, ld2, x1, y1, pool_out, overlap_partial, precision, as_stream(stream));
 }
 
+int ggcn_graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane,
+                                  void *graph_ops2w, int32_t *flag, ggcn_stream_t stream)
+{
+    return graph_operands2_weighted(rowptr, colidx, vals, B, T, plane, graph_ops2w, flag, as_stream(stream));
+}
+
+int ggcn_block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_opsw,
+                              const void *graph_ops2w, const float *bias1, const float *bias_mid, const float *bias2,
+                              const float *zero_mid, int B, int T, int K, int F, const float *gate1, const float *gate2, float *gcn1,
+                              int64_t ld1, float *x_out, int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial,
+                              int precision, ggcn_stream_t stream)
+{
+    return block_fused_weighted(X, ldx, wpack1, wpack12, graph_opsw, graph_ops2w, bias1, bias_mid, bias2, zero_mid, B, T, K, F, gate1,
+                                gate2, gcn1, ld1, x_out, ld2, x1, y1, pool_out, overlap_partial, precision, as_stream(stream));
+}
+
 int ggcn_overlap_reduce(const float *partials, int B, int F, float *xy, ggcn_stream_t stream)
 {
     return overlap_reduce(partials, B, F, xy, as_stream(stream));

@@ -114,6 +114,12 @@ int block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const void 
                      const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
                      const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
                      float *x1, float *y1, float *pool_out, float *overlap_partial, hipStream_t st);
+int graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane, void *ops2,
+                             int *flag, hipStream_t st);   // fused_weighted_drop.hip
+int block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_opsw,
+                         const void *graph_ops2w, const float *bias1, const float *bias_mid, const float *bias2, const float *zero_mid,
+                         int B, int T, int K, int F, const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out,
+                         int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial, int precision, hipStream_t st);
 int dropout_mask(int64_t rows, int F, float p, uint64_t seed, int sel, float *out, hipStream_t st);
 
 int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,

@@ -50,6 +50,8 @@ int launch_fused_wide8(const char *who, const FusedArgs &a, int precision, bool 
 int launch_fused6(const char *who, const FusedArgs &a, bool fullt, bool vst, int64_t grid, hipStream_t st);   // GGCN_WITH_F16MX6 builds
 int launch_fused_weighted_drop(const char *who, const FusedArgs &a, int precision, bool avec, bool kfull, bool fullt, bool vst, int64_t grid,
                                hipStream_t st);   // fused_weighted_drop.hip
+int launch_fused_block_weighted(const char *who, const FusedArgs &a, int precision, bool avec, bool kfull, bool fullt, bool vst, int64_t grid,
+                                hipStream_t st);   // fused_weighted_drop.hip (ggcn_block_fused_weighted)
 
 namespace {
 
@@ -248,17 +250,20 @@ struct EpiLds {   // byte offsets of the staged operands; the store staging of t
 constexpr int kEpiLdsBytes = EpiLds<0>::kEnd;   // 16896 + 12288 + 2048 + 16 = 31248
 static_assert(WM == 1, "one wavefront row: the workgroup's 4 graphs are every wavefront's 4 graphs");
 
-template <int BASE>
-__device__ __forceinline__ void stage_epilogue_operands(const FusedArgs &a, const LayerPart &lp, int g0, int n_wgi, char *lds, int tid)
+// GIVEN (ggcn_block_fused_weighted, fused_weighted_drop.hip): BOTH parts of that launch read blocks of the (D.A)^2 format, each from
+// an array of its own, so the kernel names the array (`given`) instead of `mid` choosing between a.graph_ops and a.graph_ops2.
+template <int BASE, bool GIVEN = false>
+__device__ __forceinline__ void stage_epilogue_operands(const FusedArgs &a, const LayerPart &lp, int g0, int n_wgi, char *lds, int tid,
+                                                        const char *given = nullptr)
 {
     constexpr int kEpiOps = EpiLds<BASE>::kOps, kEpiGate = EpiLds<BASE>::kGate, kEpiBias = EpiLds<BASE>::kBias;
     const int B = a.B, F = a.F;
     // operand blocks: 544 pieces of 16 B (a layer, layer 1 of the block) or 1056 (the block's W12 tiles: (D.A)^2)
     constexpr int kPieceIts = (4 * kOps2Bytes / 16 + kThreads - 1) / kThreads;   // 5
     uint4 piece[kPieceIts];
-    const bool second = lp.mid != nullptr;   // workgroup-uniform
+    const bool second = GIVEN || lp.mid != nullptr;   // workgroup-uniform
     const int blk_bytes = second ? kOps2Bytes : kOpsBytes;
-    const char *ops_src = second ? a.graph_ops2 : a.graph_ops;
+    const char *ops_src = GIVEN ? given : second ? a.graph_ops2 : a.graph_ops;
     const int n_pieces = 4 * blk_bytes / 16;
 #pragma unroll
     for (int it = 0; it < kPieceIts; ++it) {
@@ -322,15 +327,16 @@ __device__ __forceinline__ void fused_range_verdict(float amax, const char *wpac
 // workgroup alone on its CU 2.6-4.6 us in front of its main loop (tools/block8_timing.py stamps).  The pieces land under the main
 // loop's first stages (its vmcnt waits and barriers cover them long before the epilogue).  Whole tiles only (4 real graphs, 256
 // real columns, 16-byte aligned gate rows): the caller falls back otherwise.  tid: 0..255 inside the group.
-template <int BASE>
-__device__ __forceinline__ void stage_epilogue_operands_dma(const FusedArgs &a, const LayerPart &lp, int g0, int n_wgi, char *lds, int tid)
+template <int BASE, bool GIVEN = false>
+__device__ __forceinline__ void stage_epilogue_operands_dma(const FusedArgs &a, const LayerPart &lp, int g0, int n_wgi, char *lds, int tid,
+                                                            const char *given = nullptr)
 {
     constexpr int kEpiOps = EpiLds<BASE>::kOps, kEpiGate = EpiLds<BASE>::kGate, kEpiBias = EpiLds<BASE>::kBias;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int F = a.F;
-    const bool second = lp.mid != nullptr;
+    const bool second = GIVEN || lp.mid != nullptr;
     const int total = 4 * (second ? kOps2Bytes : kOpsBytes);
-    const char *src = (second ? a.graph_ops2 : a.graph_ops) + (int64_t)g0 * (second ? kOps2Bytes : kOpsBytes);
+    const char *src = (GIVEN ? given : second ? a.graph_ops2 : a.graph_ops) + (int64_t)g0 * (second ? kOps2Bytes : kOpsBytes);
     for (int piece = wave; piece * 1024 < total; piece += 4)
         if (piece * 1024 + lane * 16 < total)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + piece * 1024 + lane * 16),

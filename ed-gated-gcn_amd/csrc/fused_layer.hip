@@ -385,7 +385,8 @@ __global__ __launch_bounds__(256) void rowmask_kernel(const int32_t *__restrict_
 }
 
 // shared argument checks + launch of layer_fused_kernel for 1 or 2 parts
-int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
+// (weighted_block: ggcn_block_fused_weighted -- both parts on hi / lo operand blocks, kernels of their own in fused_weighted_drop.hip)
+int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, bool weighted_block = false)
 {
     if (precision != GGCN_PREC_BF16X3 && precision != GGCN_PREC_F16MX8 && precision != GGCN_PREC_F16MX6)
         return fail(GGCN_EUNSUPPORTED, "%s: precision %d (use bf16x3 or f16mx8)", who, precision);
@@ -509,6 +510,7 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st)
         if (a.stamps || a.ov_in || a.part[0].ov_partial) return fail(GGCN_EUNSUPPORTED, "%s: no stamps and no overlap operands under gate dropout", who);
         return launch_fused_weighted_drop(who, a, precision, avec, kfull, fullt, vst, grid, st);
     }
+    if (weighted_block) return launch_fused_block_weighted(who, a, precision, avec, kfull, fullt, vst, grid, st);
 #define GGCN_LAUNCH(SC, AV, KF, FT, VS) \
     hipLaunchKernelGGL((layer_fused_kernel<SC, AV, KF, FT, VS>), dim3((unsigned)grid), dim3(kThreads), 0, st, a)
 #define GGCN_PICK(SC)                                                                 \
@@ -745,6 +747,49 @@ int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpa
         a.part[0] = second;   // every XCD runs W12 tiles (tile_of_block: the column tiles of a row block share an XCD)
     }
     return launch_fused("ggcn_block_fused", a, precision, st);
+}
+
+// ggcn_block_fused on a REAL-valued adjacency: layer 1's tiles apply M = D.A_w (ggcn_graph_operands_weighted blocks) with the zero
+// `mid` row, layer 2's tiles M2 = (D.A_w)^2 (ggcn_graph_operands2_weighted blocks) with bias_mid, both through the MID epilogue
+// (block_fused_weighted_kernel, fused_weighted_drop.hip).  Never the eight-wavefront kernel: fused_block8.hip reads the 0/1 format.
+// Every refusal comes before the launch and names this entry.
+int block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_opsw,
+                         const void *graph_ops2w, const float *bias1, const float *bias_mid, const float *bias2, const float *zero_mid,
+                         int B, int T, int K, int F, const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out,
+                         int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial, int precision, hipStream_t st)
+{
+    const char *who = "ggcn_block_fused_weighted";
+    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (one weighted layer launch per layer)", who, T);
+    if (precision == GGCN_PREC_F16MX6) return fail(GGCN_EUNSUPPORTED, "%s: bf16x3 or f16mx8", who);
+    if (!gate2) return fail(GGCN_EINVAL, "%s: gate2 is required", who);
+    const bool layer1 = x1 || y1 || gcn1 || overlap_partial;   // none of them: the eval form (only the W12 tiles are launched)
+    if (layer1 && (!x1 || !y1 || !gate1))
+        return fail(GGCN_EINVAL, "%s: layer 1's outputs go together (gate1, x1 and y1; all NULL with gcn1 and overlap_partial = the eval form)", who);
+    if (!x_out && !pool_out) return fail(GGCN_EINVAL, "%s: neither x nor its pool requested", who);
+    if ((gcn1 && ld1 > (int64_t)INT32_MAX) || (x_out && ld2 > (int64_t)INT32_MAX))
+        return fail(GGCN_EUNSUPPORTED, "%s: leading dimension too large", who);
+    if (!wpack12 || (layer1 && !wpack1)) return fail(GGCN_EINVAL, "%s: null weight image", who);
+    if (!graph_ops2w || !aligned16(graph_ops2w))
+        return fail(GGCN_EINVAL, "%s: graph_ops2w (ggcn_graph_operands2_weighted blocks, 16-byte aligned) is required", who);
+    if (layer1 && (!graph_opsw || !aligned16(graph_opsw)))
+        return fail(GGCN_EINVAL, "%s: layer 1 needs graph_opsw (ggcn_graph_operands_weighted blocks, 16-byte aligned)", who);
+    if (!bias_mid) return fail(GGCN_EINVAL, "%s: bias_mid (W2^T.b1, zeros when gc1 has no bias) is required", who);
+    if (layer1 && (!zero_mid || !aligned16(zero_mid))) return fail(GGCN_EINVAL, "%s: zero_mid ([F] zeros, 16-byte aligned) is required", who);
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.graph_ops2 = static_cast<const char *>(graph_ops2w);
+    a.graph_ops = layer1 ? static_cast<const char *>(graph_opsw) : a.graph_ops2;   // (the eval form reads graph_ops2 only; launch_fused insists on a block pointer)
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = layer1 ? 2 : 1;
+    const LayerPart second = LayerPart{static_cast<const char *>(wpack12), bias2, bias_mid, nullptr, gate2, gate2, nullptr,
+                                       x_out, pool_out, nullptr, nullptr, (int)ld2};
+    if (layer1) {
+        a.part[0] = LayerPart{static_cast<const char *>(wpack1), bias1, zero_mid, nullptr, nullptr, gate1, gate2,
+                              gcn1, x1, y1, overlap_partial, (int)ld1};
+        a.part[1] = second;
+    } else {
+        a.part[0] = second;
+    }
+    return launch_fused(who, a, precision, st, true);
 }
 
 // ggcn_block_fused on bf16 features: the bf16 pair main loop on the bf16x3 images of W1 and W12, bf16 planes of (D.A)^2

@@ -1,9 +1,9 @@
 """Which launch a layer call, its backward and a block call take: every rule in one place, decided once per call.
 
-Host logic only -- nothing here loads libggcn_hip.so or launches.  ``layer_launch``, ``backward_launch`` and ``block_path`` return
+Host logic only -- nothing here loads libggcn_hip.so or launches.  ``layer_launch``, ``backward_launch`` and ``block_launch`` return
 names out of fixed tuples; ``_forward_gated``, ``_GatedLayerFunction.backward`` and ``_gated_gcn_block`` call them once and look
-the answer up.  ``layer_launch`` / ``backward_launch`` are ``layer_path`` / ``backward_plan`` (whose answers
-``tests/golden/dispatch_table.json`` pins) plus the names of the opt-in weighted launches.  The public ``takes_*`` predicates are
+the answer up.  ``layer_launch`` / ``backward_launch`` / ``block_launch`` are ``layer_path`` / ``backward_plan`` / ``block_path`` (whose
+answers ``tests/golden/dispatch_table.json`` pins) plus the names of the opt-in weighted launches.  The public ``takes_*`` predicates are
 one-line statements over the functions below (their docstrings keep the measurements behind the thresholds).  DESIGN.md "Dispatch"."""
 import collections
 import os
@@ -27,6 +27,8 @@ OVERLAP_LAUNCHES = OVERLAP_PATHS
 BACKWARD_LAUNCHES = BACKWARD_PASSES + ("weighted", "weighted_drop")
 DX_FORMS = ("bf16", "scaled", "bf16x3", "fp32")                         # the dW forms are these without "scaled"
 BLOCK_PATHS = ("block", "bf16_block", "folded_eval", "bf16_folded_eval", "two_fused", "layers_eval", "layers")
+BLOCK_LAUNCHES = BLOCK_PATHS + ("weighted_block",)                    # the pinned names plus the opt-in block on a real-valued adjacency
+WEIGHTED_BLOCK_PRECISIONS = ("bf16x3", "f16mx8")
 
 
 class Input(collections.namedtuple("Input", "dtype B T gpu")):
@@ -314,3 +316,49 @@ def block_path(x, csr, gc1, gc2, want, want_gcn1, one_launch, training):
             and takes_fused(gc2, csr, Input.of(x, torch.float32)) and gc1.out_features == gc2.out_features):
         return "two_fused"
     return "layers"
+
+
+def takes_weighted_block_path(x, csr, gc1, gc2):
+    """True when the inference block on a REAL-valued adjacency runs as ONE launch (``ggcn_block_fused_weighted``) where
+    ``block_path`` says "layers" / "layers_eval": the option ``gc1.weighted_block`` (``opt.ggcn_weighted_block`` /
+    ``GGCN_WEIGHTED_BLOCK=1``; OFF by default) -- looked at first, so that a refused call builds nothing -- float32 features on a
+    GPU, a real-valued adjacency of graphs of <= 32 nodes, both layers with ``fused`` and the same precision out of "bf16x3" /
+    "f16mx8", square widths, ``takes_weighted`` for gc1 on ``x`` and for gc2 on float32 input (so M = D.A_w fits the plane type)
+    and -- asked last -- the graph's (D.A_w)^2 operand (``BatchedCSR.graph_ops2_weighted``: None when an entry does not fit the
+    plane type or is not finite; one read-back per adjacency and plane type).
+    ``gc2(gc1(X)) = M^2.(X.W12) + rowsum(M).mid + b2`` with M = D.A_w: the W1 column tiles apply M with a zero ``mid`` row, the W12
+    tiles M^2 with ``mid = W2^T.b1``, both through the hi / lo operand epilogue (one split of ``hidden``, 6 MFMAs).  It replaces two
+    ``ggcn_layer_fused_weighted`` launches, the write and re-read of gcn1 and ``ggcn_gate_overlap``; ``want=("out",)`` launches the
+    W12 tiles only.  It stays opt-in: its sums differ from the two layer launches' in the last bits (both inside the parity gate).
+    Measured (``tools/weighted_block_timing.py``, one MI355X, one process, each form alone in steady state, H = 768, us per call,
+    option off / on; "cached" = the graph's operand blocks exist, "built" = the per-adjacency builders and their flag read-backs
+    inside every call).  f16mx8, every output: 4096 x 32 sparse cached 691 / 614, built 723 / 686; dense softmax rows cached
+    696 / 618, built 753 / 753; 512 x 24 cached 110 / 88, built 151 / 171.  f16mx8, ``want=("out",)``: sparse cached 626 / 293, built
+    652 / 374; dense cached 632 / 297, built 684 / 429; 512 x 24 cached 97 / 49, built 133 / 127.  bf16x3, every output: sparse cached
+    963 / 856, built 989 / 913; dense cached 965 / 865, built 1022 / 979; 512 x 24 cached 132 / 109, built 170 / 191; ``want=("out",)``:
+    sparse cached 893 / 432, built 925 / 488; dense cached 916 / 434, built 943 / 545; 512 x 24 cached 122 / 62, built 157 / 137.
+    NEGATIVE: with the builders inside and every output wanted the option does not win on dense rows at 4096 x 32 in f16mx8 (a tie)
+    and LOSES on the small batch (171 vs 151, 191 vs 170 us): the second builder and its read-back cost 40-80 us per adjacency
+    (DESIGN.md 4.12).
+    The compiler's report: ``block_fused_weighted_kernel`` 225-253 VGPRs (f16mx8) / 233-248 (bf16x3) over its twelve forms, no
+    scratch, two workgroups per CU; ``graph_operands2_w_kernel`` 58 VGPRs, no scratch, 18 KiB of LDS."""
+    if not getattr(gc1, "weighted_block", False):
+        return False
+    inp = Input.of(x)
+    if not (inp.gpu is not None and inp.dtype == torch.float32 and not csr.is_binary and csr.T <= 32):
+        return False
+    if not (gc1.fused and gc2.fused and gc1.precision == gc2.precision and gc1.precision in WEIGHTED_BLOCK_PRECISIONS and _square(gc1, gc2)):
+        return False
+    if not (takes_weighted(gc1, csr, inp) and takes_weighted(gc2, csr, Input.of(x, torch.float32))):
+        return False
+    return csr.graph_ops2_weighted(0 if gc1.precision == "bf16x3" else 1) is not None
+
+
+def block_launch(x, csr, gc1, gc2, want, want_gcn1, one_launch, training):
+    """What ``_gated_gcn_block`` runs, one of ``BLOCK_LAUNCHES``: ``block_path``'s name, replaced by "weighted_block" where that name
+    is "layers" / "layers_eval", the call is an inference call (``training`` is False: an ``adj`` that requires grad makes it
+    True), ``one_launch`` is set and ``takes_weighted_block_path`` holds -- asked after ``block_path``, whose answers stay as pinned."""
+    path = block_path(x, csr, gc1, gc2, want, want_gcn1, one_launch, training)
+    if path in ("layers", "layers_eval") and not training and one_launch and takes_weighted_block_path(x, csr, gc1, gc2):
+        return "weighted_block"
+    return path

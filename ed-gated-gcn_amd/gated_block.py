@@ -12,14 +12,16 @@ Reference (BertAmir55; identical in BertAmir54 ``:512-531``)::
 Here the gates stay ``[B,H]`` and the adjacency is converted once for both layers.  Inference on
 graphs of <= 32 tokens runs the WHOLE block as one launch (``ggcn_block_fused``: no non-linearity sits
 between gc1 and gc2, so gc2(gc1(x)) is a product of x with the folded weight W1.W2 and gcn1 never
-touches HBM); otherwise each layer is one fused launch, or one linear + one aggregation launch that
-also applies the gate and the max over tokens.
+touches HBM; on a real-valued adjacency with the opt-in ``GraphConvolution.weighted_block``:
+``ggcn_block_fused_weighted``); otherwise each layer is one fused launch, or one linear + one aggregation
+launch that also applies the gate and the max over tokens.
 """
 import torch
 
 from . import _capi, dispatch, range_guard
 from .csr import BatchedCSR, tensor_version
-from .dispatch import takes_bf16_block_path, takes_bf16_folded_eval_path, takes_block_path, takes_folded_eval_path  # noqa: F401
+from .dispatch import (takes_bf16_block_path, takes_bf16_folded_eval_path, takes_block_path, takes_folded_eval_path,  # noqa: F401
+                       takes_weighted_block_path)
 from .gcn import _require_gate, _rows2d
 
 GATE_WORDING = "%(name)s must be a contiguous float32 [B,F]=[%(B)d,%(F)d] GPU tensor"
@@ -152,11 +154,12 @@ def gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch=
     return _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1, one_launch, want)
 
 
-def _one_launch_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, defer_xy, bf16):
+def _one_launch_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, defer_xy, bf16, weighted=False):
     """``bert_amir5.py:626-640`` on graphs of <= 32 nodes as ONE launch (+ the 1-block launch that finishes ``:638`` unless the
     caller's dense head does): ``ggcn_block_fused`` in the layers' arithmetic between the two halves of the lazy range report,
     or (``bf16``) ``ggcn_block_fused_bf16`` on the ``bf16x3`` images -- same outputs and options, all float32, no range
-    report: bf16 features run no fp16 arithmetic."""
+    report: bf16 features run no fp16 arithmetic -- or (``weighted``: a real-valued adjacency, ``takes_weighted_block_path``)
+    ``ggcn_block_fused_weighted`` on the graph's D.A_w and (D.A_w)^2 operands and the zero ``mid`` row of layer 1's tiles."""
     gc1._check(x)
     if not bf16:
         range_guard.before(x.device)   # the lazy f16mx8 range report (a violation of an EARLIER launch raises here)
@@ -180,9 +183,16 @@ def _one_launch_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, defer_xy,
         xy = torch.empty((), **f32) if "xy" in want else None
         b1 = None if gc1.bias is None else gc1.bias.detach()
         b2 = None if gc2.bias is None else gc2.bias.detach()
-        entry = "ggcn_block_fused_bf16" if bf16 else "ggcn_block_fused"   # (bf16: layer 1's image only where layer 1 runs, no precision)
+        entry = "ggcn_block_fused_bf16" if bf16 else "ggcn_block_fused_weighted" if weighted else "ggcn_block_fused"
+        plane = 0 if kprec == "bf16x3" else 1
+        if weighted:   # layer 1: M = D.A_w (only where layer 1 runs), layer 2: M^2, and the W1 tiles' zero `mid` row after b2
+            ops1, ops2 = (csr.graph_ops_weighted(plane) if layer1 else None), csr.graph_ops2_weighted(plane)
+            zero = (ptr(gc1._zero_row(F, dev)),)
+        else:
+            ops1, ops2, zero = csr.graph_ops, csr.graph_ops2(plane), ()
+        # (bf16: layer 1's image only where layer 1 runs, no precision)
         _capi.check(getattr(lib, entry)(ptr(x2d), x2d.stride(0), ptr(pack1 if (layer1 or not bf16) else None), ptr(pack12),
-                                        ptr(csr.graph_ops), ptr(csr.graph_ops2(0 if kprec == "bf16x3" else 1)), ptr(b1), ptr(mid), ptr(b2),
+                                        ptr(ops1), ptr(ops2), ptr(b1), ptr(mid), ptr(b2), *zero,
                                         B, T, K, F, ptr(gate1 if layer1 else None), ptr(gate2), ptr(gcn1), F, ptr(xo), F,
                                         ptr(x1), ptr(y1), ptr(out), ptr(part), *(() if bf16 else (_capi.PREC[kprec],)), st), entry)
         if part is not None and not defer_xy:
@@ -216,11 +226,12 @@ def _gated_gcn_block(x, adj, gate1, gate2, gc1, gc2, want_gcn1=False, one_launch
     training = torch.is_grad_enabled() and (gc1._needs_grad(x, gate1, gate2, adj=adj) or gc2._needs_grad(x, gate2, adj=adj))
     if training and set(want) != set(BLOCK_OUTPUTS):
         raise RuntimeError("want= selects outputs of the inference block; under autograd every output is produced")
-    path = dispatch.block_path(x, csr, gc1, gc2, want, want_gcn1, one_launch, training)
+    path = dispatch.block_launch(x, csr, gc1, gc2, want, want_gcn1, one_launch, training)
     r = dict.fromkeys(("gcn1",) + BLOCK_OUTPUTS)
-    if path in ("block", "bf16_block"):
+    if path in ("block", "bf16_block", "weighted_block"):
         # ---- ONE launch for :626-640 (+ one 1-block launch that finishes :638) ----
-        r = _one_launch_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, _defer_xy, bf16=path == "bf16_block")
+        r = _one_launch_block(x, csr, gate1, gate2, gc1, gc2, want, want_gcn1, _defer_xy, bf16=path == "bf16_block",
+                              weighted=path == "weighted_block")
     elif path in ("folded_eval", "bf16_folded_eval"):   # the eval form of 33..256-node graphs: no product with W1
         r["x"], r["out"] = _folded_eval(x, csr, gate2, gc1, gc2, w_x)
     elif path == "layers_eval":   # gc2 needs gcn1 itself, nothing else of layer 1: no pools, no regulariser

@@ -279,6 +279,12 @@ class GraphConvolution(nn.Module):
         # the call being refused (dispatch.takes_weighted_dropout).  Off by default, like the launches it builds on.
         self.weighted_dropout = (bool(getattr(opt, "ggcn_weighted_dropout", False))
                                  or os.environ.get("GGCN_WEIGHTED_DROPOUT", "0") == "1")
+        # real-valued adjacency of graphs of <= 32 nodes, float32 features, inference: the whole gated block as ONE launch
+        # (ggcn_block_fused_weighted; gated_block.takes_weighted_block_path has the measurements) instead of two weighted layer
+        # launches + the regulariser's.  Off by default: the fold's sums differ from the two layer launches' in the last bits (both
+        # inside the parity gate).
+        self.weighted_block = (bool(getattr(opt, "ggcn_weighted_block", False))
+                               or os.environ.get("GGCN_WEIGHTED_BLOCK", "0") == "1")
         # dense adjacency handed to forward(): None = let the device detect edge weights (one 4-byte
         # read-back per conversion), True = promise 0/1 entries like the reference's (graph.py:66-74)
         # and stay sync-free, False = always keep the values

@@ -495,6 +495,40 @@ int ggcn_block_fused(const float *X, int64_t ldx, const void *wpack1, const void
                      float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
                      float *x1, float *y1, float *pool_out, float *overlap_partial,
                      int precision, ggcn_stream_t stream);
+/* ---- the gated block in one launch on a REAL-valued adjacency (graphs of <= 32 nodes, float32 features, inference) ----
+ * The fold above holds for any `adj` (gcn.py:33-41): with M = D.A_w, D = diag(1 / (rowsum(A_w) + 1)),
+ *     gc2(gc1(X)) = M^2.(X.W12) + rowsum(M).bias_mid^T + 1.b2^T
+ * ggcn_graph_operands2_weighted turns the batched CSR with its weights (vals; NULL = all ones) into the blocks of
+ * ggcn_graph_operands2 (GGCN_GRAPH_OPS2_BYTES per graph, size ggcn_graph_operands2_bytes(B), 16-byte aligned):
+ *     [0, 4096)    M2 = M^2 * 2^10 as hi / lo fragments of the plane type (`plane` 0 = bf16 pairs, 1 = fp16 pairs), two k-steps
+ *                  each, in the A-operand order documented at ggcn_graph_operands_weighted_wide; rows and columns >= T are zero
+ *     [4096, 4224) rowsum(M) per row in accumulator order (float [h][16], entry r = row (r & 3) + 8 (r >> 2) + 4 h): the factor
+ *                  of the `mid` bias; unlike deg / (deg + 1) it is real-valued and may be negative
+ * A row's weights are summed in CSR order (as ggcn_aggregate, ggcn_inv_denominators and ggcn_graph_operands_weighted sum them),
+ * M[r][j] = w * inv_r in fp32, M2[r][c] = sum_j M[r][j] * M[j][c] in fp32 with j ascending over 0..T-1, rowsum(M)[r] likewise: a
+ * fixed order, no atomics, bit-identical from run to run.  One wavefront per graph.
+ * *flag (optional, device memory, zeroed by the caller) gets bit 0 when an entry of M2 * 2^10 does not fit the plane type
+ * (>= 60000 in fp16 planes, >= 3e38 in bf16 planes) or is not finite -- such an adjacency keeps one weighted launch per layer.
+ * Refusals, all before any launch: T > 32 -> GGCN_EUNSUPPORTED; null rowptr / colidx / blocks, B <= 0, T <= 0, blocks not
+ * 16-byte aligned, plane outside 0..1 -> GGCN_EINVAL.
+ * ggcn_block_fused_weighted is ggcn_block_fused on those operands.  Its argument list is ggcn_block_fused's with graph_opsw
+ * (ggcn_graph_operands_weighted blocks: layer 1) and graph_ops2w (the blocks above: layer 2) in place of graph_ops / graph_ops2,
+ * and zero_mid after bias2: [F] zeros, 16-byte aligned, the `mid` row of the W1 tiles (as in ggcn_layer_fused_weighted).  Both
+ * groups of column tiles end in the same epilogue: one split of `hidden`, 6 MFMAs (hi.hi, hi.lo, lo.hi), times 2^-10 -- the W1
+ * tiles on M with the zero row, the W12 tiles on M2 with bias_mid.  Outputs and forms are ggcn_block_fused's: x1, y1, optional
+ * gcn1, x_out, pool_out, overlap_partial; x1 = y1 = gcn1 = overlap_partial = NULL is the eval form (W12 tiles only; graph_opsw,
+ * wpack1, gate1 and zero_mid may then be NULL).  precision GGCN_PREC_BF16X3 (plane 0 blocks) or GGCN_PREC_F16MX8 (plane 1 blocks,
+ * the range flag of ggcn_range_flag as in ggcn_block_fused); GGCN_PREC_F16MX6 and T > 32 -> GGCN_EUNSUPPORTED.  Every other
+ * refusal is ggcn_block_fused's, worded with this entry's name.  It never runs the eight-wavefront kernel of ggcn_block_fused. */
+int ggcn_graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane,
+                                  void *graph_ops2w, int32_t *flag, ggcn_stream_t stream);
+int ggcn_block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, const void *wpack12,
+                              const void *graph_opsw, const void *graph_ops2w, const float *bias1, const float *bias_mid,
+                              const float *bias2, const float *zero_mid, int B, int T, int K, int F, const float *gate1,
+                              const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
+                              float *x1, float *y1, float *pool_out, float *overlap_partial,
+                              int precision, ggcn_stream_t stream);
+
 /* ---- training-mode dropout of the gates inside the one-launch layer (graphs of <= 256 nodes) ------------------
  * models/bert_amir5.py:621-625 repeats each gate to [B,T,H] and THEN applies F.dropout: one Bernoulli draw per (token,
  * feature) and gate.  Here the keep factors k[t,f] in {0, 1/(1-p)} come from a counter-based hash of (seed, element)
