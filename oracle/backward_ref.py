@@ -17,7 +17,7 @@ import torch
 from oracle import ref_dense
 
 MAX_MASKED = 0.03
-# tests/test_gpu_parity.py TOL: the forward parity gate per arithmetic (bfloat16 features run the bf16x3 class)
+# the forward parity gate per arithmetic, the one dict every test imports (bfloat16 features run the bf16x3 class)
 TOL = {"fp32": 2e-5, "bf16x3": 1e-4, "f16mx8": 1e-4, "f16mx6": 1e-4}
 
 

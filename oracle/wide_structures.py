@@ -113,5 +113,5 @@ def with_prebias(x, w, pre):
 
 
 def gate_of(ref, tol):
-    """The project's parity gate on one graph's reference values: tol * max(1, max|ref|) (``_gate`` of tests/test_gpu_backward.py)."""
+    """The project's parity gate on one graph's reference values: tol * max(1, max|ref|) (the bound of ``oracle/gates.py`` ``gate``)."""
     return tol * max(1.0, float(ref.abs().max())) if ref.numel() else 0.0

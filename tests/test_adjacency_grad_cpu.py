@@ -10,7 +10,6 @@ names the argument BEFORE any launch (the pointers handed in are never dereferen
 differentiable ``adj`` to the autograd path.
 """
 import ctypes
-import os
 import re
 
 import pytest
@@ -20,8 +19,8 @@ import ed_gated_gcn_amd as pkg
 from ed_gated_gcn_amd import _capi
 from ed_gated_gcn_amd.gcn import GraphConvolution
 from oracle import backward_ref as br
+from oracle.host_support import header as _header, msg as _msg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = 1, 3
 NAME = "ggcn_adjacency_grad"
 P = ctypes.c_void_p(1 << 20)   # a non-null, 16-byte aligned address: never dereferenced (the checks come first)
@@ -104,10 +103,6 @@ def test_closed_form_in_float32_is_close_to_float64():
     assert float((got.double() - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
 
 
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ggcn.h")).read(), flags=re.S)
-
-
 def test_symbol_declared_bound_and_exported():
     assert re.search(r"\b%s\s*\(" % NAME, _header())
     assert NAME in _capi.PROTOTYPES
@@ -126,11 +121,6 @@ def test_abi_version_stays_14_on_all_three_sides():
 
 def _call(lib, dy=P, ldy=64, hidden=P, ldh=64, inv=P, rowptr=P, colidx=P, vals=None, B=4, T=40, F=64, d_adj=P):
     return lib.ggcn_adjacency_grad(dy, ldy, hidden, ldh, inv, rowptr, colidx, vals, B, T, F, d_adj, None)
-
-
-def _msg(lib, rc, code):
-    assert rc == code, (rc, lib.ggcn_last_error().decode())
-    return lib.ggcn_last_error().decode()
 
 
 def test_refuses_bad_arguments_before_any_launch():

@@ -3,7 +3,6 @@ declared, bound and exported with the ABI still 14 (functions were added, nothin
 a message that names the argument BEFORE any launch (the pointers handed in are never dereferenced), and the new predicates of
 gated_block saying no to CPU tensors, to float32 text and to layers whose ``bf16_block`` option is off (the default)."""
 import ctypes
-import os
 import re
 import types
 
@@ -12,18 +11,14 @@ import torch
 import ed_gated_gcn_amd as pkg
 from ed_gated_gcn_amd import _capi, gated_block
 from ed_gated_gcn_amd.gcn import GraphConvolution
+from oracle.host_support import header as _header, msg as _msg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = 1, 3
 NEW = ("ggcn_block_fused_bf16", "ggcn_aggregate_bf16")
 P = ctypes.c_void_p(1 << 20)   # a non-null, 16-byte aligned address: never dereferenced (the checks come first)
 ODD = ctypes.c_void_p((1 << 20) + 1)
 OFF2 = ctypes.c_void_p((1 << 20) + 2)
 OFF8 = ctypes.c_void_p((1 << 20) + 8)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ggcn.h")).read(), flags=re.S)
 
 
 def test_new_symbols_declared_bound_and_exported():
@@ -43,11 +38,6 @@ def test_abi_version_stays_14_on_all_three_sides():
     assert int(m.group(1)) == 14
     assert _capi.ABI_VERSION == 14
     assert pkg.load_library().ggcn_abi_version() == 14
-
-
-def _msg(lib, rc, code):
-    assert rc == code, (rc, lib.ggcn_last_error().decode())
-    return lib.ggcn_last_error().decode()
 
 
 def _block(lib, x=P, ldx=64, w1=P, w12=P, ops=P, ops2=P, mid=P, T=31, gate1=P, gate2=P, gcn1=None, ld1=64, xo=P, ld2=64, x1=P, y1=P,

@@ -2,7 +2,6 @@
 the ABI version bumped on both sides, every new entry refusing bad arguments with GGCN_EINVAL before any launch, and
 the Python layer's dtype contract for bf16 features (no GPU needed: the checks run before anything touches a device)."""
 import ctypes
-import os
 import re
 
 import pytest
@@ -11,16 +10,12 @@ import torch
 import ed_gated_gcn_amd as pkg
 from ed_gated_gcn_amd import _capi
 from ed_gated_gcn_amd.gcn import BF16_PRECISIONS, GraphConvolution
+from oracle.host_support import header as _header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = 1
 NEW = ("ggcn_linear_bf16", "ggcn_linear_out_bf16", "ggcn_layer_fused_bf16", "ggcn_dweight_bf16",
        "ggcn_dweight_bf16_workspace_bytes", "ggcn_subword_pool_bf16")
 P = ctypes.c_void_p(1 << 20)   # a non-null, 16-byte aligned address: never dereferenced (the checks come first)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ggcn.h")).read(), flags=re.S)
 
 
 def test_new_symbols_declared_bound_and_exported():

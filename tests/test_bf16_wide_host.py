@@ -3,7 +3,6 @@ features": ggcn_layer_fused_bf16_drop, ggcn_layer_fused_bf16_wide): declared, bo
 were added, nothing changed), every refusal returning its code and a message that names the argument BEFORE any launch (the
 pointers handed in are never dereferenced), and the new predicates of GraphConvolution saying no to CPU and float32 text."""
 import ctypes
-import os
 import re
 import types
 
@@ -12,17 +11,13 @@ import torch
 import ed_gated_gcn_amd as pkg
 from ed_gated_gcn_amd import _capi
 from ed_gated_gcn_amd.gcn import GraphConvolution
+from oracle.host_support import header as _header, msg as _msg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = 1, 3
 NEW = ("ggcn_layer_fused_bf16_drop", "ggcn_layer_fused_bf16_wide")
 P = ctypes.c_void_p(1 << 20)   # a non-null, 16-byte aligned address: never dereferenced (the checks come first)
 ODD = ctypes.c_void_p((1 << 20) + 1)
 OFF8 = ctypes.c_void_p((1 << 20) + 8)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ggcn.h")).read(), flags=re.S)
 
 
 def test_new_symbols_declared_bound_and_exported():
@@ -39,11 +34,6 @@ def test_abi_version_stays_14_on_all_three_sides():
     assert int(m.group(1)) == 14
     assert _capi.ABI_VERSION == 14
     assert pkg.load_library().ggcn_abi_version() == 14
-
-
-def _msg(lib, rc, code):
-    assert rc == code, (rc, lib.ggcn_last_error().decode())
-    return lib.ggcn_last_error().decode()
 
 
 def _drop(lib, x=P, ldx=64, wpack=P, ops=P, out=P, ldo=64, B=4, T=31, F=64, ov_in=None, ov_out=None, p=0.25, streams=(0, 1, 2)):

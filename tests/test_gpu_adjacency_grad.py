@@ -18,10 +18,13 @@ import pytest
 import torch
 
 from oracle import backward_ref as br
+from oracle import gates
+from oracle.gpu_support import count_calls, dev, drop_mask as _drop_mask, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
+_hostile, _close32, _gate, _gate_dx = gates.hostile, gates.close32, gates.gate, gates.gate_dx
 ADJ_GRAD = "ggcn_adjacency_grad"
 MMA, AGG, GPB, GPB_DROP, AGG_T = ("ggcn_gate_pool_backward_mma", "ggcn_gate_pool_backward_agg", "ggcn_gate_pool_backward",
                                    "ggcn_gate_pool_backward_drop", "ggcn_aggregate_t")
@@ -30,32 +33,12 @@ COUNTED = (ADJ_GRAD, MMA, AGG, GPB, GPB_DROP, AGG_T, "ggcn_linear_scaled", "ggcn
            "ggcn_layer_fused_bf16_drop", "ggcn_layer_fused_bf16_wide", "ggcn_layer_fused_weighted", "ggcn_linear_bf16", "ggcn_aggregate")
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
-
-
 def closed_form64(dy, hidden, adj):
     """dA [B,T,T] in float64 from float32 dY, H [B,T,F] and A [B,T,T]."""
     dy, hidden, adj = dy.double(), hidden.double(), adj.double()
     inv = 1.0 / (adj.sum(2) + 1.0)
     g = inv[:, :, None] * torch.einsum("bif,bjf->bij", dy, hidden)
     return g - (inv * (adj * g).sum(2))[:, :, None]
-
-
-def _hostile(t, pad):
-    """t [N,F] as the first N rows of a [N + 1, F + pad] buffer of NaN: pad columns and the row after the last one are NaN."""
-    buf = torch.full((t.shape[0] + 1, t.shape[1] + pad), NAN, dtype=t.dtype, device=t.device)
-    buf[:t.shape[0], :t.shape[1]] = t
-    return buf
 
 
 # ================================================================ 1. the kernel through the C ABI
@@ -125,67 +108,8 @@ def test_adjacency_grad_keeps_the_float32_exponent_range(pkg, dev):
 
 
 # ================================================================ 2. through the module under autograd
-def _count_calls(monkeypatch):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = {k: 0 for k in COUNTED}
-    for n in COUNTED:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
-
-
-def _close32(got, ref, what, rel):
-    """float32 gradient: |got - ref| <= rel * max|ref| (tests/test_gpu_backward.py _close32)."""
-    ref = ref.double()
-    scale = float(ref.abs().max()) + 1e-12
-    err = float((got.double() - ref).abs().max())
-    print("  %s: max|diff| %.3g vs scale %.3g (gate %.3g)" % (what, err, scale, rel * scale))
-    assert got.dtype == torch.float32 and err == err and err <= rel * scale, "%s: max|diff| %.3g vs scale %.3g" % (what, err, scale)
-
-
-def _gate(got, ref, what, tol=1e-4):
-    """float32 result of bf16 features: |got - ref| <= tol * max(1, max|ref|) (tests/test_gpu_backward.py _gate)."""
-    ref = ref.double()
-    gate = tol * max(1.0, float(ref.abs().max()))
-    err = float((got.double() - ref).abs().max())
-    print("  %s: max|diff| %.3g (gate %.3g)" % (what, err, gate))
-    assert got.dtype == torch.float32 and err == err and err <= gate, "%s: max|diff| %.3g > %.3g" % (what, err, gate)
-
-
-def _gate_dx(dx, ref, what="dX"):
-    """bfloat16 dX: |dx - ref| <= 2^-8 |ref| + 1e-4 max|ref|, every element (tests/test_gpu_backward.py _gate_dx)."""
-    assert dx.dtype == torch.bfloat16
-    ref = ref.double()
-    bound = 2.0 ** -8 * ref.abs() + 1e-4 * float(ref.abs().max())
-    diff = (dx.double() - ref).abs()
-    print("  %s (bf16): max |diff| / gate %.3f" % (what, float((diff / (bound + 1e-300)).max())))
-    assert not bool(torch.isnan(diff).any()) and not bool((diff > bound).any()), "%s: %d elements outside the gate" % (
-        what, int((diff > bound).sum()))
-
-
 def _layer(pkg, dev, w, b, precision, fused_max_t=None):
-    m = pkg.GraphConvolution(w.shape[0], w.shape[1], bias=b is not None).to(dev)
-    m.precision = precision
-    if fused_max_t is not None:
-        m.fused_max_t = fused_max_t
-    with torch.no_grad():
-        m.weight.copy_(w)
-        if b is not None:
-            m.bias.copy_(b)
-    return m
-
-
-def _drop_mask(pkg, dev, rows, F, p, seed, stream):
-    from ed_gated_gcn_amd import _capi
-    lib = pkg.load_library()
-    m = torch.empty(rows, F, dtype=torch.float32, device=dev)
-    _capi.check(lib.ggcn_dropout_mask(rows, F, float(p), int(seed), stream, _capi.ptr(m), _capi.stream_of(dev)), "ggcn_dropout_mask")
-    return m
+    return make_layer(pkg, dev, w, b, precision=precision, fused_max_t=fused_max_t)
 
 
 STREAMS = (0, 1, 2)      # the block's layer-1 streams: all three gates, the store gate undropped
@@ -234,7 +158,7 @@ def _module_case(pkg, dev, monkeypatch, name, precision="f16mx8", bf16=False):
     what = "%s/%s" % (name, "bf16" if bf16 else precision)
     c, rs, dropout, ref = _reference(pkg, dev, name, bf16, precision)
     fused_max_t = 256 if T > 32 else None      # (as tests/test_gpu_backward.py: one-launch forward up to 256 nodes; dropout needs it)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     adj = c["adj"].clone().requires_grad_()
     got = _run(pkg, dev, c, rs, dropout, precision, fused_max_t, adj)
     assert calls[ADJ_GRAD] == 1 and calls[MMA] == 0 and calls[AGG] == 0 and calls[AGG_T] == 1, "%s: %s" % (what, calls)
@@ -329,7 +253,7 @@ def test_gated_block(pkg, dev, monkeypatch, name, batch):
 
     gc1, gc2 = _layer(pkg, dev, c["w1"], c["b1"], precision, 256), _layer(pkg, dev, c["w2"], c["b2"], precision, 256)
     xg, g1g, g2g, adj = (c[k].clone().requires_grad_() for k in ("x", "g1", "g2", "adj"))
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     r = pkg.gated_gcn_block(xg, adj, g1g, g2g, gc1, gc2)
     loss_of(r).backward()
     torch.cuda.synchronize()
@@ -347,7 +271,7 @@ def test_without_an_adjacency_gradient_nothing_changes(pkg, dev, monkeypatch):
     tests/test_gpu_backward.py, and ggcn_adjacency_grad is never called.  Under no_grad a differentiable adj runs the inference
     launch alone."""
     c, rs, dropout, ref = _reference(pkg, dev, "square", False, "f16mx8")
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     _run(pkg, dev, c, rs, None, "f16mx8", None, c["adj"])
     want = {k: 0 for k in COUNTED}
     want.update({"ggcn_layer_fused": 1, MMA: 1, "ggcn_linear_scaled": 1, "ggcn_dweight": 1, "ggcn_colsum": 1})

@@ -20,27 +20,13 @@ import pytest
 import torch
 
 from oracle import backward_ref as br
+from oracle import gates
+from oracle.gpu_support import count_calls, dev, drop_mask as _drop_mask, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
-
-
-def _poisoned(nbytes, dev):
-    return torch.full((max(256, int(nbytes)),), 0xFF, dtype=torch.uint8, device=dev)
+_poisoned, _close32, _gate, _gate_dx = gates.poisoned, gates.close32, gates.gate, gates.gate_dx
 
 
 def _padded(t, pad):
@@ -280,26 +266,6 @@ DW = {"bf16x3": ("ggcn_dweight", "ggcn_dweight/bf16x3"), "fp32": ("ggcn_dweight"
 KEYS = BWD + FWD + ("ggcn_linear/bf16x3", "ggcn_linear/fp32", "ggcn_linear/f16mx8", "ggcn_dweight/bf16x3", "ggcn_dweight/fp32")
 
 
-def _count_calls(monkeypatch):
-    """The _count_calls pattern of tests/test_gpu_bf16_wide.py on every entry of the backward (and the forward launches), with the
-    precision argument of ggcn_linear / ggcn_dweight counted under its own key."""
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    names = {v: k for k, v in _capi.PREC.items()}
-    calls = {k: 0 for k in KEYS}
-    for n in BWD + FWD:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            if _n in PREC_ARG:
-                key = "%s/%s" % (_n, names.get(int(a[PREC_ARG[_n]]), "?"))
-                calls[key] = calls.get(key, 0) + 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
-
-
 def _expected(passes, dx, dw, db, times=1):
     e = {k: 0 for k in KEYS if k not in FWD}
     for k in PASSES[passes] + DX[dx] + DW[dw] + (("ggcn_colsum",) if db else ()):
@@ -313,53 +279,8 @@ def _assert_calls(calls, before, expect, what):
         what, {k: v for k, v in got.items() if v}, {k: v for k, v in expect.items() if v})
 
 
-def _close32(got, ref, what, rel):
-    """float32 gradient: |got - ref| <= rel * max|ref| (_grad_close of tests/test_gpu_parity.py)."""
-    ref = ref.double()
-    scale = float(ref.abs().max()) + 1e-12
-    err = float((got.double() - ref).abs().max())
-    print("  %s: max|diff| %.3g vs scale %.3g (gate %.3g)" % (what, err, scale, rel * scale))
-    assert got.dtype == torch.float32 and err == err and err <= rel * scale, "%s: max|diff| %.3g vs scale %.3g" % (what, err, scale)
-
-
-def _gate(got, ref, what, tol=1e-4):
-    """float32 result of bf16 features / forward value: |got - ref| <= tol * max(1, max|ref|) (_gate of tests/test_gpu_bf16.py)."""
-    ref = ref.double()
-    gate = tol * max(1.0, float(ref.abs().max())) if ref.numel() else 0.0
-    err = float((got.double() - ref).abs().max()) if ref.numel() else 0.0
-    print("  %s: max|diff| %.3g (gate %.3g)" % (what, err, gate))
-    assert got.dtype == torch.float32 and err == err and err <= gate, "%s: max|diff| %.3g > %.3g" % (what, err, gate)
-
-
-def _gate_dx(dx, ref, what="dX"):
-    """bfloat16 dX: |dx - ref| <= 2^-8 |ref| + 1e-4 max|ref|, every element (_gate_dx of tests/test_gpu_bf16.py)."""
-    assert dx.dtype == torch.bfloat16
-    ref = ref.double()
-    bound = 2.0 ** -8 * ref.abs() + 1e-4 * float(ref.abs().max())
-    diff = (dx.double() - ref).abs()
-    print("  %s (bf16): max |diff| / gate %.3f" % (what, float((diff / (bound + 1e-300)).max())))
-    assert not bool(torch.isnan(diff).any()) and not bool((diff > bound).any()), "%s: %d elements outside 2^-8|ref| + 1e-4 max|ref|" % (
-        what, int((diff > bound).sum()))
-
-
 def _layer(pkg, dev, w, b, precision, fused_max_t=None):
-    m = pkg.GraphConvolution(w.shape[0], w.shape[1], bias=b is not None).to(dev)
-    m.precision = precision
-    if fused_max_t is not None:
-        m.fused_max_t = fused_max_t
-    with torch.no_grad():
-        m.weight.copy_(w)
-        if b is not None:
-            m.bias.copy_(b)
-    return m
-
-
-def _drop_mask(pkg, dev, rows, F, p, seed, stream):
-    from ed_gated_gcn_amd import _capi
-    lib = pkg.load_library()
-    m = torch.empty(rows, F, dtype=torch.float32, device=dev)
-    _capi.check(lib.ggcn_dropout_mask(rows, F, float(p), int(seed), stream, _capi.ptr(m), _capi.stream_of(dev)), "ggcn_dropout_mask")
-    return m
+    return make_layer(pkg, dev, w, b, precision=precision, fused_max_t=fused_max_t)
 
 
 def _offset_leaf(t):
@@ -400,7 +321,7 @@ def _run_layer(pkg, dev, monkeypatch, name, precision, bf16, expect, fwd=None, e
     terms = {"out": (o64 * r1).sum(), "pa": (a64 * r2).sum(), "pb": (b64 * r3).sum()}
     sum(terms[k] for k in loss).backward()
     # ---- the layer under autograd
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, BWD + FWD, PREC_ARG)
     if x_pad:   # x as a view with row stride K + x_pad of a leaf whose spare columns are NaN
         xbuf = torch.full((B, T, K + x_pad), NAN, dtype=c["x"].dtype, device=dev)
         with torch.no_grad():
@@ -671,7 +592,7 @@ def test_gated_block_under_autograd(pkg, dev, monkeypatch, name, precision, bf16
 
     gc1, gc2 = _layer(pkg, dev, c["w1"], c["b1"], precision, 256), _layer(pkg, dev, c["w2"], c["b2"], precision, 256)
     xg, g1g, g2g = (c[k].clone().requires_grad_() for k in ("x", "g1", "g2"))
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, BWD + FWD, PREC_ARG)
     r = pkg.gated_gcn_block(xg, c["adj"], g1g, g2g, gc1, gc2)
     before = dict(calls)
     loss_of(r).backward()

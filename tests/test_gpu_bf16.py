@@ -11,35 +11,10 @@ import pytest
 import torch
 
 from oracle import ref_dense
+from oracle.gates import gate as _gate, gate_dx as _gate_dx
+from oracle.gpu_support import classifier_batch as _classifier_batch, count_calls, dev, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    return p
-
-
-def _gate(got, ref, what=""):
-    ref = ref.double()
-    tol = 1e-4 * max(1.0, float(ref.abs().max())) if ref.numel() else 0.0
-    err = float((got.double() - ref).abs().max()) if ref.numel() else 0.0
-    assert err <= tol, "%s: max|diff| %.3g > %.3g" % (what, err, tol)
-
-
-def _gate_dx(dx, ref):
-    assert dx.dtype == torch.bfloat16
-    ref = ref.double()
-    bound = 2.0 ** -8 * ref.abs() + 1e-4 * float(ref.abs().max())
-    bad = (dx.double() - ref).abs() > bound
-    assert not bool(bad.any()), "dX: %d elements outside 2^-8|ref| + 1e-4 max|ref|" % int(bad.sum())
 
 
 def _adj(B, T, seed, weighted=False, directed=False):
@@ -56,13 +31,7 @@ def _adj(B, T, seed, weighted=False, directed=False):
 def _layer(pkg, dev, K, F, seed, precision="bf16x3", bias=True):
     from ed_gated_gcn_amd import synth
     w, b = synth.layer_params(K, F, seed=seed)
-    m = pkg.GraphConvolution(K, F, bias=bias).to(dev)
-    m.precision = precision
-    with torch.no_grad():
-        m.weight.copy_(torch.from_numpy(w))
-        if bias:
-            m.bias.copy_(torch.from_numpy(b))
-    return m
+    return make_layer(pkg, dev, w, b if bias else None, precision=precision)
 
 
 def _x(B, T, K, dev, seed, pad=0):
@@ -249,44 +218,6 @@ def test_gated_block_bf16_inference_and_training(pkg, dev):
 
 
 # ---------------------------------------------------------------- 5. the classifier under bf16 autocast
-def _classifier_batch(dev):
-    from ed_gated_gcn_amd import synth
-    B, ORI_ML, BERT_ML, NCLS = 8, 31, 65, 34
-    rng = np.random.default_rng(3)
-    sent_len = rng.integers(5, ORI_ML + 1, size=B)
-    sent_len[0] = ORI_ML
-    bert_len = np.minimum(sent_len + rng.integers(2, 10, size=B), BERT_ML)
-    adj = synth.dependency_batch(B, ORI_ML, 3.5, seed=12, lengths=sent_len).astype(np.float32)
-    transform = np.zeros((B, ORI_ML, BERT_ML), dtype=np.float32)
-    for b in range(B):
-        for tkn in range(int(sent_len[b])):
-            transform[b, tkn, 1 + min(tkn, BERT_ML - 2)] = 1.0
-    inputs = {
-        "sentence_length": torch.from_numpy(sent_len), "cls_text_sep_length": torch.from_numpy(bert_len),
-        "cls_text_sep_indices": torch.from_numpy(rng.integers(0, 30522, size=(B, BERT_ML))),
-        "cls_text_sep_segments_ids": torch.zeros(B, BERT_ML, dtype=torch.long),
-        "transform": torch.from_numpy(transform),
-        "anchor_index": torch.from_numpy(np.array([int(rng.integers(0, n)) for n in sent_len])),
-        "dist_to_target": torch.from_numpy(rng.integers(0, 6, size=(B, ORI_ML))),
-        "dependency_graph": torch.from_numpy(adj),
-    }
-    return {k: v.to(dev) for k, v in inputs.items()}, NCLS
-
-
-def _count_calls(monkeypatch, names):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = {n: 0 for n in names}
-    for n in names:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
-
-
 @pytest.mark.parametrize("cls_name", ["GatedGCNEventDetector", "GatedGCNEventDetector54", "GCNEventDetectorNoGate"])
 def test_classifier_under_bf16_autocast(pkg, dev, cls_name, monkeypatch):
     transformers = pytest.importorskip("transformers")
@@ -305,7 +236,7 @@ def test_classifier_under_bf16_autocast(pkg, dev, cls_name, monkeypatch):
         seen.append(text.dtype)
         return orig(text, *a, **k)
     monkeypatch.setattr(model.gc1, "forward_gated", spy)
-    calls = _count_calls(monkeypatch, ["ggcn_layer_fused_bf16", "ggcn_dweight_bf16", "ggcn_linear_out_bf16"])
+    calls = count_calls(monkeypatch, ["ggcn_layer_fused_bf16", "ggcn_dweight_bf16", "ggcn_linear_out_bf16"])
     # eval: the full forward and the logits-only form
     model.eval()
     for logits_only in (False, True):

@@ -3,7 +3,7 @@ the whole gated block as ONE launch for graphs of <= 32 nodes (ggcn_block_fused_
 of graphs of 33..256 nodes (ggcn_aggregate_bf16 + one ggcn_layer_fused_prebias launch, W1 never multiplied).
 
 Oracle: oracle/ref_dense.gated_block in float64 on x.double() (exact: a bf16 value is a float64 value).  Gate: the project's own
-1e-4 * max(1, max|ref|) (tests/test_gpu_bf16.py::_gate) for every output."""
+1e-4 * max(1, max|ref|) (``gate`` of oracle/gates.py) for every output."""
 import types
 
 import numpy as np
@@ -11,32 +11,14 @@ import pytest
 import torch
 
 from oracle import ref_dense
+from oracle.gates import gate as _gate
+from oracle.gpu_support import classifier_batch as _classifier_batch, count_calls, dev, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LAYER_ENTRIES = ("ggcn_layer_fused_bf16", "ggcn_layer_fused_bf16_drop", "ggcn_layer_fused_bf16_wide", "ggcn_layer_fused",
                  "ggcn_layer_fused_prebias", "ggcn_linear_bf16", "ggcn_aggregate", "ggcn_block_fused")
 COUNTED = LAYER_ENTRIES + ("ggcn_block_fused_bf16", "ggcn_aggregate_bf16", "ggcn_overlap_reduce", "ggcn_dense_head")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    return p
-
-
-def _gate(got, ref, what=""):
-    ref = ref.double()
-    tol = 1e-4 * max(1.0, float(ref.abs().max())) if ref.numel() else 0.0
-    err = float((got.double() - ref).abs().max()) if ref.numel() else 0.0
-    print("%s: max|diff| %.3g (gate %.3g)" % (what, err, tol))
-    assert err <= tol, "%s: max|diff| %.3g > %.3g" % (what, err, tol)
 
 
 def _adj(B, T, seed, weighted=False, directed=False):
@@ -53,14 +35,7 @@ def _adj(B, T, seed, weighted=False, directed=False):
 def _layer(pkg, dev, K, F, seed, precision="bf16x3", bias=True, block=True):
     from ed_gated_gcn_amd import synth
     w, b = synth.layer_params(K, F, seed=seed)
-    m = pkg.GraphConvolution(K, F, bias=bias).to(dev)
-    m.precision = precision
-    m.bf16_block = block
-    with torch.no_grad():
-        m.weight.copy_(torch.from_numpy(w))
-        if bias:
-            m.bias.copy_(torch.from_numpy(b))
-    return m
+    return make_layer(pkg, dev, w, b if bias else None, precision=precision, bf16_block=block)
 
 
 def _x(B, T, K, dev, seed, pad=0):
@@ -78,20 +53,6 @@ def _ref(x, adj, g1, g2, gc1, gc2):
     d = lambda t: None if t is None else t.detach().double()   # noqa: E731
     return ref_dense.gated_block(x.double(), adj.to(x.device).double(), d(g1), d(g2), d(gc1.weight), d(gc1.bias), d(gc2.weight),
                                  d(gc2.bias), dtype=torch.float64)
-
-
-def _count_calls(monkeypatch, names=COUNTED):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = {n: 0 for n in names}
-    for n in names:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
 
 
 def _setup(pkg, dev, B, T, H, seed=31, precision="bf16x3", bias1=True, bias2=True, pad=0, directed=False, block=True):
@@ -124,7 +85,7 @@ def test_block_all_outputs_vs_float64(pkg, dev, case, monkeypatch):
     if CASES[case].get("pad"):
         assert not x.is_contiguous()
     assert takes_bf16_block_path(x, csr, gc1, gc2)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         r = pkg.gated_gcn_block(x, csr, g1, g2, gc1, gc2, want_gcn1=True)
     assert calls["ggcn_block_fused_bf16"] == 1 and calls["ggcn_overlap_reduce"] == 1
@@ -164,7 +125,7 @@ def test_every_split_precision_is_the_bf16x3_block(pkg, dev, precision):
 @pytest.mark.parametrize("B,T,H", [(64, 31, 256), (4096, 32, 768), (13, 32, 256), (7, 17, 300)])
 def test_eval_form_is_the_full_blocks_bit_for_bit(pkg, dev, B, T, H, monkeypatch):
     gc1, gc2, x, adj, csr, g1, g2 = _setup(pkg, dev, B, T, H)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         full = pkg.gated_gcn_block(x, csr, g1, g2, gc1, gc2)
         ev = pkg.gated_gcn_block(x, csr, g1, g2, gc1, gc2, want=("out",))
@@ -186,7 +147,7 @@ def test_dense_head_two_launches(pkg, dev, monkeypatch):
     gc1, gc2, x, adj, csr, g1, g2 = _setup(pkg, dev, B, T, H)
     wt = (torch.randn(H, C, generator=torch.Generator().manual_seed(7)) / H ** 0.5).to(dev)
     bias = torch.randn(C, generator=torch.Generator().manual_seed(8)).to(dev)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         r = pkg.gated_gcn_block(x, csr, g1, g2, gc1, gc2, dense_head=(wt, bias))
     assert calls["ggcn_block_fused_bf16"] == 1 and calls["ggcn_dense_head"] == 1 and calls["ggcn_overlap_reduce"] == 0
@@ -223,7 +184,7 @@ def test_option_off_and_one_launch_false_keep_todays_launches(pkg, dev, monkeypa
     gc1, gc2, x, adj, csr, g1, g2 = _setup(pkg, dev, 64, 31, 256)
     fresh = pkg.GraphConvolution(256, 256)
     assert fresh.bf16_block is False                       # the default
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         on = pkg.gated_gcn_block(x, csr, g1, g2, gc1, gc2)
         two = pkg.gated_gcn_block(x, csr, g1, g2, gc1, gc2, one_launch=False)
@@ -249,7 +210,7 @@ def test_option_off_and_one_launch_false_keep_todays_launches(pkg, dev, monkeypa
 # ---------------------------------------------------------------- 7. autograd keeps the two layer launches
 def test_training_with_the_option_on_takes_two_layer_launches(pkg, dev, monkeypatch):
     gc1, gc2, x, adj, csr, g1, g2 = _setup(pkg, dev, 64, 31, 256)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     g1r, g2r = g1.clone().requires_grad_(), g2.clone().requires_grad_()
     rt = pkg.gated_gcn_block(x, csr, g1r, g2r, gc1, gc2)
     assert calls["ggcn_block_fused_bf16"] == 0 and calls["ggcn_layer_fused_bf16"] == 1 and calls["ggcn_layer_fused"] >= 1
@@ -290,7 +251,7 @@ def test_folded_eval_of_longer_graphs(pkg, dev, B, T, H, want, monkeypatch):
     zb, zf = _aggregate_pair(dev, x, csr)
     assert torch.equal(zb, zf)
     _gate(zb.view(B, T, H), torch.bmm(adj.to(dev).double(), x.double()) / (adj.to(dev).double().sum(2, keepdim=True) + 1), "Z")
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         r = pkg.gated_gcn_block(x, csr, g1, g2, gc1, gc2, want=want)
     assert calls["ggcn_aggregate_bf16"] == 1 and calls["ggcn_layer_fused_prebias"] == 1
@@ -335,7 +296,7 @@ def test_aggregate_bf16_equals_aggregate_on_the_float32_copy(pkg, dev, B, T, K, 
 
 def test_folded_eval_off_by_default(pkg, dev, monkeypatch):
     gc1, gc2, x, adj, csr, g1, g2 = _setup(pkg, dev, 8, 100, 256, block=False)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         pkg.gated_gcn_block(x, csr, g1, g2, gc1, gc2, want=("out",))
     assert calls["ggcn_aggregate_bf16"] == 0 and calls["ggcn_layer_fused_prebias"] == 0
@@ -343,30 +304,6 @@ def test_folded_eval_off_by_default(pkg, dev, monkeypatch):
 
 
 # ---------------------------------------------------------------- 9. the classifiers under bf16 autocast
-def _classifier_batch(dev):
-    from ed_gated_gcn_amd import synth
-    B, ORI_ML, BERT_ML, NCLS = 8, 31, 65, 34
-    rng = np.random.default_rng(3)
-    sent_len = rng.integers(5, ORI_ML + 1, size=B)
-    sent_len[0] = ORI_ML
-    bert_len = np.minimum(sent_len + rng.integers(2, 10, size=B), BERT_ML)
-    adj = synth.dependency_batch(B, ORI_ML, 3.5, seed=12, lengths=sent_len).astype(np.float32)
-    transform = np.zeros((B, ORI_ML, BERT_ML), dtype=np.float32)
-    for b in range(B):
-        for tkn in range(int(sent_len[b])):
-            transform[b, tkn, 1 + min(tkn, BERT_ML - 2)] = 1.0
-    inputs = {
-        "sentence_length": torch.from_numpy(sent_len), "cls_text_sep_length": torch.from_numpy(bert_len),
-        "cls_text_sep_indices": torch.from_numpy(rng.integers(0, 30522, size=(B, BERT_ML))),
-        "cls_text_sep_segments_ids": torch.zeros(B, BERT_ML, dtype=torch.long),
-        "transform": torch.from_numpy(transform),
-        "anchor_index": torch.from_numpy(np.array([int(rng.integers(0, n)) for n in sent_len])),
-        "dist_to_target": torch.from_numpy(rng.integers(0, 6, size=(B, ORI_ML))),
-        "dependency_graph": torch.from_numpy(adj),
-    }
-    return {k: v.to(dev) for k, v in inputs.items()}, NCLS
-
-
 @pytest.mark.parametrize("cls_name", ["GatedGCNEventDetector", "GatedGCNEventDetector54", "GCNEventDetectorNoGate"])
 def test_classifier_under_bf16_autocast_with_the_block(pkg, dev, cls_name, monkeypatch):
     """Logits within 2^-6 * max(1, max|logits|) of the same model with the option off: the autocast `dense` rounds its input and
@@ -381,7 +318,7 @@ def test_classifier_under_bf16_autocast_with_the_block(pkg, dev, cls_name, monke
                                       torch.Generator().manual_seed(9))
     model = model.to(dev).eval()
     assert model.gc1.bf16_block and model.gc2.bf16_block
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     for logits_only in (False, True):
         model.eval_logits_only = logits_only
         res = {}

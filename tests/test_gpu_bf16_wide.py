@@ -2,7 +2,7 @@
 launches (ggcn_layer_fused_bf16_drop for <= 32 nodes), against the float64 oracle (oracle/ref_dense) on text_bf16.double(), which
 is exact: a bf16 value is a float64 value.
 
-Gates (the project's own, tests/test_gpu_bf16.py and tests/test_gpu_parity.py): 1e-4 * max(1, max|ref|) for float32 results;
+Gates (the project's own, oracle/gates.py): 1e-4 * max(1, max|ref|) for float32 results;
 |dx - ref| <= 2^-8 |ref| + 1e-4 max|ref| for the bf16 dX; for the dropout cases the gates of
 test_block_layers_with_gate_dropout_vs_oracle_on_the_exported_masks with TOL["bf16x3"] = 1e-4 (forward: 2 * TOL absolute;
 float32 gradients: 5e-4 of the reference's largest entry; xy: 1e-3 relative), the bf16 dX by its own gate above.
@@ -15,42 +15,16 @@ import pytest
 import torch
 
 from oracle import ref_dense
+from oracle.backward_ref import TOL
+from oracle.gates import close32, gate as _gate, gate_dx as _gate_dx
+from oracle.gpu_support import classifier_batch as _classifier_batch, count_calls, dev, drop_mask as _drop_mask, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-TOL_BF16X3 = 1e-4    # tests/test_gpu_parity.py TOL["bf16x3"]
+TOL_BF16X3 = TOL["bf16x3"]
 WIDE, DROP, NARROW, LINEAR = "ggcn_layer_fused_bf16_wide", "ggcn_layer_fused_bf16_drop", "ggcn_layer_fused_bf16", "ggcn_linear_bf16"
+COUNTED = (WIDE, DROP, NARROW, LINEAR)
 ALL_T = [33, 64, 65, 100, 128, 129, 160, 192, 193, 231, 256]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    return p
-
-
-def _gate(got, ref, what=""):
-    ref = ref.double()
-    tol = 1e-4 * max(1.0, float(ref.abs().max())) if ref.numel() else 0.0
-    err = float((got.double() - ref).abs().max()) if ref.numel() else 0.0
-    print("%s: max|diff| %.3g (gate %.3g)" % (what, err, tol))
-    assert err <= tol, "%s: max|diff| %.3g > %.3g" % (what, err, tol)
-
-
-def _gate_dx(dx, ref):
-    assert dx.dtype == torch.bfloat16
-    ref = ref.double().to(dx.device)
-    bound = 2.0 ** -8 * ref.abs() + 1e-4 * float(ref.abs().max())
-    excess = ((dx.double() - ref).abs() - bound).max()
-    print("dX: max(|diff| - bound) %.3g" % float(excess))
-    bad = (dx.double() - ref).abs() > bound
-    assert not bool(bad.any()), "dX: %d elements outside 2^-8|ref| + 1e-4 max|ref|" % int(bad.sum())
 
 
 def _adj(B, T, seed, directed=False):
@@ -67,13 +41,7 @@ def _adj(B, T, seed, directed=False):
 def _layer(pkg, dev, K, F, seed, precision="bf16x3", bias=True):
     from ed_gated_gcn_amd import synth
     w, b = synth.layer_params(K, F, seed=seed)
-    m = pkg.GraphConvolution(K, F, bias=bias).to(dev)
-    m.precision = precision
-    with torch.no_grad():
-        m.weight.copy_(torch.from_numpy(w))
-        if bias:
-            m.bias.copy_(torch.from_numpy(b))
-    return m
+    return make_layer(pkg, dev, w, b if bias else None, precision=precision)
 
 
 def _x(B, T, K, dev, seed, pad=0):
@@ -85,20 +53,6 @@ def _x(B, T, K, dev, seed, pad=0):
 def _ref_layer(x, adj, m):
     b = None if m.bias is None else m.bias.detach().double()
     return ref_dense.graph_convolution(x.double(), adj.to(x.device).double(), m.weight.detach().double(), b, dtype=torch.float64)
-
-
-def _count_calls(monkeypatch, names=(WIDE, DROP, NARROW, LINEAR)):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = {n: 0 for n in names}
-    for n in names:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
 
 
 def _forward_on_announced_path(m, x, adj_d, calls):
@@ -120,7 +74,7 @@ def test_layer_forward_vs_float64_every_slot(pkg, dev, T, monkeypatch):
     """H = 256, B = 5: the last workgroup of the 64-row slot kernel holds one graph of its two.  Run on the default rule (whatever
     it says for this shape), then with fused_max_t = 256 (always one launch), then with fused = False (never)."""
     B, K, F = 5, 256, 256
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     m = _layer(pkg, dev, K, F, seed=1)
     x, adj = _x(B, T, K, dev, seed=2), _adj(B, T, seed=3)
     ref = _ref_layer(x, adj, m)
@@ -153,7 +107,7 @@ def test_layer_forward_vs_float64_every_slot(pkg, dev, T, monkeypatch):
 ], ids=["H768-T100", "H768-T231", "K300-T100", "K300-T200", "view-T60", "view-nobias-T100", "view-nobias-T231", "directed-T100",
         "directed-T231"])
 def test_layer_forward_shapes(pkg, dev, B, T, K, F, pad, bias, directed, monkeypatch):
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     m = _layer(pkg, dev, K, F, seed=4, bias=bias)
     m.fused_max_t = 256                               # the kernels are under test here, not the default rule
     x, adj = _x(B, T, K, dev, seed=5, pad=pad), _adj(B, T, seed=6, directed=directed)
@@ -168,7 +122,7 @@ def test_every_split_precision_means_the_bf16_pair_form(pkg, dev, precision, mon
     from ed_gated_gcn_amd import _capi
     if precision == "f16mx6" and not _capi.has_f16mx6():
         precision = "f16mx8"
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     B, T, K, F = 6, 100, 256, 256
     x, adj = _x(B, T, K, dev, seed=2), _adj(B, T, seed=3).to(dev)
     ref = _layer(pkg, dev, K, F, seed=1, precision="bf16x3")
@@ -181,7 +135,7 @@ def test_every_split_precision_means_the_bf16_pair_form(pkg, dev, precision, mon
 # ---------------------------------------------------------------- 2. one launch vs linear + aggregate
 @pytest.mark.parametrize("T", [64, 100, 160, 231])
 def test_one_launch_agrees_with_linear_plus_aggregate(pkg, dev, T, monkeypatch):
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     B, K, F = 6, 256, 256
     m = _layer(pkg, dev, K, F, seed=1)
     m.fused_max_t = 256
@@ -197,7 +151,7 @@ def test_one_launch_agrees_with_linear_plus_aggregate(pkg, dev, T, monkeypatch):
 # ---------------------------------------------------------------- 3. forward_gated: gates, pools, overlap
 @pytest.mark.parametrize("T", [60, 100, 231])
 def test_forward_gated_gates_pools_and_overlap(pkg, dev, T, monkeypatch):
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     B, K, F = 6, 256, 256
     m = _layer(pkg, dev, K, F, seed=11)
     m.fused_max_t = 256
@@ -234,27 +188,12 @@ def test_overlap_and_dropout_refused_off_the_one_launch_path(pkg, dev):
 
 
 # ---------------------------------------------------------------- 4. gate dropout inside the launches
-def _drop_mask(pkg, dev, rows, F, p, seed, stream):
-    from ed_gated_gcn_amd import _capi
-    lib = pkg.load_library()
-    m = torch.empty(rows, F, dtype=torch.float32, device=dev)
-    _capi.check(lib.ggcn_dropout_mask(rows, F, float(p), int(seed), stream, _capi.ptr(m), _capi.stream_of(dev)), "ggcn_dropout_mask")
-    return m
-
-
-def _grad_close(got, want, name, rel):
-    scale = float(want.abs().max()) + 1e-12
-    err = float((got.double().cpu() - want).abs().max())
-    print("%s: max|diff| %.3g vs scale %.3g (gate %.3g)" % (name, err, scale, rel * scale))
-    assert err <= rel * scale, "%s: max|diff| %.3g vs scale %.3g" % (name, err, scale)
-
-
 @pytest.mark.parametrize("T", [31, 60, 100, 200], ids=["T31", "T60-64row", "T100-128row", "T200-eight-wavefronts"])
 def test_block_layers_with_gate_dropout_bf16_vs_oracle_on_the_exported_masks(pkg, dev, T, monkeypatch):
     """bert_amir5.py:621-640 in training mode on bf16 features: the two layer launches draw the keep factors themselves (stream 1 =
     gate1, stream 2 = gate2 in both layers); the float64 oracle gets the same factors from ggcn_dropout_mask -- forward and, through
     torch autograd, backward.  gc1 reads the bf16 x (the new launches), gc2 the float32 gcn1 (ggcn_layer_fused_drop)."""
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     B, H, p, seed = 12, 128, 0.5, 2 ** 40 + 99
     rng = np.random.default_rng(5)
     from ed_gated_gcn_amd import synth
@@ -316,8 +255,7 @@ def test_block_layers_with_gate_dropout_bf16_vs_oracle_on_the_exported_masks(pkg
     for name, got, want in (("d gate1", g1g.grad, g1r.grad), ("d gate2", g2g.grad, g2r.grad),
                             ("d W1", gc1.weight.grad, w1r.grad), ("d b1", gc1.bias.grad, b1r.grad),
                             ("d W2", gc2.weight.grad, w2r.grad), ("d b2", gc2.bias.grad, b2r.grad)):
-        assert got.dtype == torch.float32, name
-        _grad_close(got, want, name, rel=5e-4)
+        close32(got, want, name, rel=5e-4)
     assert 0.45 < float((k1 == 0).double().mean()) < 0.55
 
 
@@ -344,7 +282,7 @@ def test_forward_and_backward_are_deterministic(pkg, dev, T, dropout):
 # ---------------------------------------------------------------- 6. the block and the classifier under bf16 autocast
 @pytest.mark.parametrize("T", [100, 231])
 def test_gated_block_inference_under_autocast(pkg, dev, T, monkeypatch):
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     B, H = 6, 256
     gc1, gc2 = _layer(pkg, dev, H, H, seed=31), _layer(pkg, dev, H, H, seed=32)
     gc1.fused_max_t = gc2.fused_max_t = 256           # (6 graphs of 231 nodes: one launch on request)
@@ -363,30 +301,6 @@ def test_gated_block_inference_under_autocast(pkg, dev, T, monkeypatch):
         assert r[k].dtype == torch.float32, k
         _gate(r[k], ref[k], k)
     _gate(r_out["out"], ref["out"], "want=out")
-
-
-def _classifier_batch(dev, ORI_ML, BERT_ML):
-    from ed_gated_gcn_amd import synth
-    B, NCLS = 8, 34
-    rng = np.random.default_rng(3)
-    sent_len = rng.integers(5, ORI_ML + 1, size=B)
-    sent_len[0] = ORI_ML
-    bert_len = np.minimum(sent_len + rng.integers(2, 10, size=B), BERT_ML)
-    adj = synth.dependency_batch(B, ORI_ML, 3.5, seed=12, lengths=sent_len).astype(np.float32)
-    transform = np.zeros((B, ORI_ML, BERT_ML), dtype=np.float32)
-    for b in range(B):
-        for tkn in range(int(sent_len[b])):
-            transform[b, tkn, 1 + min(tkn, BERT_ML - 2)] = 1.0
-    inputs = {
-        "sentence_length": torch.from_numpy(sent_len), "cls_text_sep_length": torch.from_numpy(bert_len),
-        "cls_text_sep_indices": torch.from_numpy(rng.integers(0, 30522, size=(B, BERT_ML))),
-        "cls_text_sep_segments_ids": torch.zeros(B, BERT_ML, dtype=torch.long),
-        "transform": torch.from_numpy(transform),
-        "anchor_index": torch.from_numpy(np.array([int(rng.integers(0, n)) for n in sent_len])),
-        "dist_to_target": torch.from_numpy(rng.integers(0, 6, size=(B, ORI_ML))),
-        "dependency_graph": torch.from_numpy(adj),
-    }
-    return {k: v.to(dev) for k, v in inputs.items()}, NCLS
 
 
 @pytest.mark.parametrize("ORI_ML,BERT_ML", [(31, 65), (100, 128)], ids=["T31", "T100"])
@@ -409,7 +323,7 @@ def test_classifier_trains_with_dropout_under_bf16_autocast(pkg, dev, ORI_ML, BE
     monkeypatch.setattr(model.gc1, "forward_gated", spy)
     dims = []
     model.dropout.register_forward_hook(lambda mod, inp, out: dims.append(inp[0].dim()))   # the classifier's own dropout module
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     model.train()
     assert model.dropout.p == 0.25
     with torch.autocast("cuda", dtype=torch.bfloat16):

@@ -16,32 +16,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import ref_dense  # noqa: E402  (tests may use the oracle)
+from oracle.gpu_support import dev, make_layer, pkg  # noqa: E402,F401
 
 TOL = 1e-4
 OUTS = ("x1", "y1", "x", "out")
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()  # fails loudly if the HIP library was not built
-    return p
-
-
 def _layer(pkg, dev, w, b):
-    m = pkg.GraphConvolution(w.shape[0], w.shape[1], opt=None, bias=b is not None).to(dev)
-    m.precision = "f16mx8"
-    with torch.no_grad():
-        m.weight.copy_(torch.from_numpy(w))
-        if b is not None:
-            m.bias.copy_(torch.from_numpy(b))
-    return m.eval()
+    return make_layer(pkg, dev, w, b, precision="f16mx8").eval()
 
 
 def _graphs(kind, B, T, rng):

@@ -1,7 +1,7 @@
 """What ``forward_gated`` and its backward hand to the library, argument by argument, for every launch name of
 ``dispatch.LAYER_LAUNCHES`` / ``dispatch.BACKWARD_LAUNCHES``, and what the cached operand builders of ``BatchedCSR`` launch.
 
-A recorder in the pattern of ``_count_calls`` replaces the entries on the loaded library and logs ``(name, arguments)``, pointers as
+A recorder (``call_log`` of oracle/gpu_support.py) replaces the entries on the loaded library and logs ``(name, arguments)``, pointers as
 integers (NULL: None).  The expectations are written out from the prototypes of ``include/ggcn.h``, entry by entry -- not from the
 tables in ``gcn.py``.  B = 3, K = F = 64, three gates, every output wanted: what can go wrong is an argument in the wrong place or
 an operand chosen on the wrong side of a size rule, so the graph lengths are the rule edges and nothing needs to be large.  Every
@@ -10,6 +10,8 @@ import ctypes
 
 import pytest
 import torch
+
+from oracle.gpu_support import call_log, dev, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,19 +30,6 @@ BUILDERS = ("ggcn_graph_operands", "ggcn_graph_edge_lists", "ggcn_rowmask_transp
             "ggcn_graph_operands_weighted_wide", "ggcn_graph_operands_weighted_t")
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
-
-
 @pytest.fixture
 def side_stream(dev):
     torch.cuda.synchronize()
@@ -53,16 +42,7 @@ def side_stream(dev):
 @pytest.fixture
 def log(monkeypatch, pkg):
     """``[(entry, [arguments])]`` of every call of a layer, backward or builder entry from here on."""
-    lib = pkg.load_library()
-    calls = []
-    for n in LAUNCHES + BACKWARD + BUILDERS:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls.append((_n, [v.value if isinstance(v, ctypes.c_void_p) else v for v in a]))
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
+    return call_log(monkeypatch, LAUNCHES + BACKWARD + BUILDERS)
 
 
 def _only(log, names):
@@ -81,13 +61,7 @@ def _adjacency(dev, T, weighted=False, seed=0):
 def _case(pkg, dev, T, dtype=torch.float32, weighted=False, **options):
     """``(layer, features, BatchedCSR, three gates)``; ``options`` are attributes of the layer."""
     g = torch.Generator().manual_seed(7 + T)
-    m = pkg.GraphConvolution(K, F).to(dev)
-    with torch.no_grad():
-        m.weight.copy_(0.05 * torch.randn(K, F, generator=g))
-        m.bias.copy_(0.1 * torch.randn(F, generator=g))
-    for k, v in options.items():
-        assert hasattr(m, k), k
-        setattr(m, k, v)
+    m = make_layer(pkg, dev, 0.05 * torch.randn(K, F, generator=g), 0.1 * torch.randn(F, generator=g), **options)
     x = torch.randn(B, T, K, generator=g).to(dev).to(dtype)
     gates = [torch.rand(B, F, generator=g).to(dev) for _ in range(3)]
     csr = pkg.BatchedCSR.from_dense(_adjacency(dev, T, weighted))

@@ -17,21 +17,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import csr_ref, ref_dense  # noqa: E402  (tests may use the oracle)
-
-TOL = {"fp32": 2e-5, "bf16x3": 1e-4, "f16mx8": 1e-4, "f16mx6": 1e-4}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()  # fails loudly if the HIP library was not built
-    return p
+from oracle.backward_ref import TOL  # noqa: E402  (the forward parity gate per arithmetic)
+from oracle.gates import close32  # noqa: E402
+from oracle.gpu_support import ace_batch as _ace_batch, dev, drop_mask as _drop_mask, make_layer, pkg  # noqa: E402,F401
 
 
 # (precision, fused): the one-launch layer kernel exists for the two split-precision linears
@@ -51,15 +39,8 @@ def _block(pkg, x, adj, g1, g2, gc1, gc2, fused, want_gcn1=True):
 def _layer(pkg, dev, w, b, precision, fused=True):
     if precision == "f16mx6" and not pkg._capi.has_f16mx6():
         pytest.skip("f16mx6 is an experiment: libggcn_hip.so is built without it (make -C ed-gated-gcn_amd/csrc F16MX6=1)")
-    m = pkg.GraphConvolution(w.shape[0], w.shape[1], opt=None, bias=b is not None).to(dev)
-    m.precision = precision
-    m.fused = bool(fused)
-    m.fused_max_t = 256          # the tests exercise the 256-row graph slot too (the product default is 128)
-    with torch.no_grad():
-        m.weight.copy_(torch.from_numpy(w))
-        if b is not None:
-            m.bias.copy_(torch.from_numpy(b))
-    return m.eval()
+    # the tests exercise the 256-row graph slot too (the product default is 128)
+    return make_layer(pkg, dev, w, b, precision=precision, fused=bool(fused), fused_max_t=256).eval()
 
 
 # ---------------------------------------------------------------- CSR builder: bit exact
@@ -438,12 +419,6 @@ def test_fp16_features_config4(pkg, dev, B, T, H, precision):
 
 
 # ---------------------------------------------------------------- backward
-def _grad_close(got, want, name, rel=2e-4):
-    scale = float(want.abs().max()) + 1e-12
-    err = float((got.cpu() - want).abs().max())
-    assert err <= rel * scale, "%s: max|diff| %.3g vs scale %.3g" % (name, err, scale)
-
-
 @pytest.mark.parametrize("precision,fused", MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("B,T,K,F,weighted", [(8, 32, 256, 256, False), (3, 100, 64, 48, True), (5, 17, 34, 20, False), (6, 20, 64, 96, False)])
 def test_layer_backward_vs_oracle_autograd(pkg, dev, precision, fused, B, T, K, F, weighted):
@@ -463,9 +438,9 @@ def test_layer_backward_vs_oracle_autograd(pkg, dev, precision, fused, B, T, K, 
     xg = x.to(dev).requires_grad_()
     out = m(xg, torch.from_numpy(adj).to(dev))
     (out * R.to(dev)).sum().backward()
-    _grad_close(xg.grad, xr.grad, "d text")
-    _grad_close(m.weight.grad, wr.grad, "d weight")
-    _grad_close(m.bias.grad, br.grad, "d bias")
+    close32(xg.grad, xr.grad, "d text", rel=2e-4)
+    close32(m.weight.grad, wr.grad, "d weight", rel=2e-4)
+    close32(m.bias.grad, br.grad, "d bias", rel=2e-4)
 
 
 @pytest.mark.parametrize("B,T,F,drop", [(7, 32, 256, 0.0), (5, 17, 20, 0.0), (3, 31, 1028, 0.0), (6, 32, 64, 0.3), (1, 1, 8, 0.0)])
@@ -709,7 +684,7 @@ def test_gated_block_backward_vs_oracle_autograd(pkg, dev, precision, fused):
     loss_of(rr, R1, R2).backward()
     got = [xg.grad, g1g.grad, g2g.grad, gc1.weight.grad, gc1.bias.grad, gc2.weight.grad, gc2.bias.grad]
     for name, gv, lv in zip(("x", "gate1", "gate2", "w1", "b1", "w2", "b2"), got, leaves):
-        _grad_close(gv, lv.grad, name, rel=5e-4)
+        close32(gv, lv.grad, name, rel=5e-4)
     # forward values under autograd equal the inference path
     with torch.no_grad():
         ri = pkg.gated_gcn_block(xg.detach(), t(adj).to(dev), g1g.detach(), g2g.detach(), gc1, gc2, want_gcn1=True,
@@ -719,28 +694,6 @@ def test_gated_block_backward_vs_oracle_autograd(pkg, dev, precision, fused):
 
 
 # ---------------------------------------------------------------- config 5: the classifier end to end
-def _ace_batch(rng, B, ORI_ML, BERT_ML, vocab=None):
-    from ed_gated_gcn_amd import synth
-    sent_len = rng.integers(5, ORI_ML + 1, size=B)
-    sent_len[0] = ORI_ML
-    bert_len = np.minimum(sent_len + rng.integers(2, 10, size=B), BERT_ML)
-    adj = synth.dependency_batch(B, ORI_ML, 3.5, seed=12, lengths=sent_len).astype(np.float32)
-    transform = np.zeros((B, ORI_ML, BERT_ML), dtype=np.float32)
-    for b in range(B):                                   # word <- word pieces (data_utils.py:749-766 shape)
-        for tkn in range(int(sent_len[b])):
-            transform[b, tkn, 1 + min(tkn, BERT_ML - 2)] = 1.0
-    ids = np.zeros((B, BERT_ML), dtype=np.int64) if vocab is None else rng.integers(0, vocab, size=(B, BERT_ML))
-    return {
-        "sentence_length": torch.from_numpy(sent_len), "cls_text_sep_length": torch.from_numpy(bert_len),
-        "cls_text_sep_indices": torch.from_numpy(ids),
-        "cls_text_sep_segments_ids": torch.zeros(B, BERT_ML, dtype=torch.long),
-        "transform": torch.from_numpy(transform),
-        "anchor_index": torch.from_numpy(np.array([int(rng.integers(0, n)) for n in sent_len])),
-        "dist_to_target": torch.from_numpy(rng.integers(0, 6, size=(B, ORI_ML))),
-        "dependency_graph": torch.from_numpy(adj),
-    }
-
-
 def test_config5_classifier_golden_reference_logits(pkg, dev, golden_dir):
     """G4: the HIP-backed classifier with the reference's seeded parameters and encoder stand-in
     against the logits the REFERENCE BertAmir55 produced (BASELINE configs[4], 1e-3)."""
@@ -2243,9 +2196,9 @@ def test_backward_through_a_collated_batch_uses_no_host_transpose(pkg, dev):
         wr, br = torch.from_numpy(w).requires_grad_(), torch.from_numpy(b).requires_grad_()
         yr = ref_dense.graph_convolution(xr, torch.from_numpy(adj.astype(np.float32)), wr, br)
         (yr * yr).sum().backward()
-        _grad_close(xg.grad, xr.grad, "x")
-        _grad_close(m.weight.grad, wr.grad, "w")
-        _grad_close(m.bias.grad, br.grad, "b")
+        close32(xg.grad, xr.grad, "x", rel=2e-4)
+        close32(m.weight.grad, wr.grad, "w", rel=2e-4)
+        close32(m.bias.grad, br.grad, "b", rel=2e-4)
 
 
 # ---------------------------------------------------------------- gate MLPs, scores/kl head, collated batches
@@ -2392,14 +2345,6 @@ def test_training_dropout_masks_the_gates_per_token(pkg, dev):
 
 
 # ---------------------------------------------------------------- training-mode dropout of the gates inside the layer launches
-def _drop_mask(pkg, dev, rows, F, p, seed, stream):
-    from ed_gated_gcn_amd import _capi
-    lib = pkg.load_library()
-    m = torch.empty(rows, F, dtype=torch.float32, device=dev)
-    _capi.check(lib.ggcn_dropout_mask(rows, F, float(p), int(seed), stream, _capi.ptr(m), _capi.stream_of(dev)), "ggcn_dropout_mask")
-    return m
-
-
 def test_gate_dropout_masks_are_bernoulli_independent_and_reproducible(pkg, dev):
     """ggcn_dropout_mask = the keep factors the layer epilogue and the backward pass draw (csrc/dropout_hash.h): values in
     {0, 1/(1-p)}, dropped fraction p, two independent streams per seed, the same numbers for the same (seed, element)."""
@@ -2479,7 +2424,7 @@ def test_block_layers_with_gate_dropout_vs_oracle_on_the_exported_masks(pkg, dev
     for name, got, want in (("d x", xg.grad, xr.grad), ("d gate1", g1g.grad, g1r.grad), ("d gate2", g2g.grad, g2r.grad),
                             ("d W1", gc1.weight.grad, w1r.grad), ("d b1", gc1.bias.grad, b1r.grad),
                             ("d W2", gc2.weight.grad, w2r.grad), ("d b2", gc2.bias.grad, b2r.grad)):
-        _grad_close(got, want, name, rel=5e-4)
+        close32(got, want, name, rel=5e-4)
     # half of the gate entries really were dropped, per token: a pooled feature of an all-positive gcn1 would vanish only
     # when all T tokens lose it
     assert 0.45 < float((k1 == 0).float().mean()) < 0.55
@@ -2655,9 +2600,9 @@ def test_wide_graph_block_litbank_shape(pkg, dev, precision, T):
     rr = ref_dense.gated_block(xr, torch.from_numpy(adj.astype(np.float32)), torch.from_numpy(g1), torch.from_numpy(g2),
                                w1r, b1r, torch.from_numpy(w2), torch.from_numpy(b2))
     (rr["x"] * rr["x"]).sum().backward()
-    _grad_close(xg.grad, xr.grad, "x", rel=5e-4)
-    _grad_close(gc1.weight.grad, w1r.grad, "w1", rel=5e-4)
-    _grad_close(gc1.bias.grad, b1r.grad, "b1", rel=5e-4)
+    close32(xg.grad, xr.grad, "x", rel=5e-4)
+    close32(gc1.weight.grad, w1r.grad, "w1", rel=5e-4)
+    close32(gc1.bias.grad, b1r.grad, "b1", rel=5e-4)
 
 
 # ---------------------------------------------------------------- fp16 features: the plain fp16 MFMA linear (config 4)

@@ -19,12 +19,13 @@ The expected bits are ``range_verdict``'s three comparisons, written out in ``_v
 and -- on the launches that bound their fp16 hidden planes -- ``amax * c (+ max|mid|) >= 65504`` HIDDEN, c = max_f sum_k |w[k,f]|.
 The value table runs with c = 0.5, so that no finite probe reaches the hidden bound; an INFINITE activation has an infinite bound
 (inf * c), so on those launches ``inf`` sets HIDDEN next to OVERFLOW and WINDOW -- "NaN outputs are possible" is true of it."""
-import ctypes
 import types
 
 import numpy as np
 import pytest
 import torch
+
+from oracle.gpu_support import call_log, clean_range_flag, dev, make_layer, pkg, range_bits as _bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -65,41 +66,10 @@ def _slot_rows(T):
 
 
 # ---------------------------------------------------------------- fixtures
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
-
-
-def _bits(pkg, dev):
-    """The raw flag bits of every translation unit, read into a zeroed word and cleared."""
-    from ed_gated_gcn_amd import _capi
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    _capi.check(pkg.load_library().ggcn_range_flag(_capi.ptr(flag), 1, _capi.stream_of(dev)), "ggcn_range_flag")
-    return int(flag.item())
-
-
-def _reset_guard(dev):
-    """Forget what range_guard has seen, so that neither a later forward nor the interpreter's exit reports this file's probes."""
-    from ed_gated_gcn_amd import range_guard
-    range_guard.reset(dev)
-
-
 @pytest.fixture(autouse=True)
 def clean_flag(pkg, dev):
     """Every test starts and ends with the flag clear, whatever ran before: the order does not matter."""
-    _bits(pkg, dev)
-    _reset_guard(dev)
-    yield
-    _bits(pkg, dev)
-    _reset_guard(dev)
+    yield from clean_range_flag(pkg, dev)
 
 
 @pytest.fixture
@@ -116,16 +86,7 @@ def guard(monkeypatch):
 @pytest.fixture
 def log(monkeypatch, pkg):
     """``[(entry, [arguments])]`` of every layer, block, linear and aggregate entry called from here on."""
-    lib = pkg.load_library()
-    calls = []
-    for n in ENTRIES:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls.append((_n, [v.value if isinstance(v, ctypes.c_void_p) else v for v in a]))
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
+    return call_log(monkeypatch, ENTRIES)
 
 
 # ---------------------------------------------------------------- the cases
@@ -268,14 +229,7 @@ class Case:
         self.gates_d = [g.to(dev) for g in self.gates]
 
     def _layer(self, w, b, precision):
-        m = self.pkg.GraphConvolution(w.shape[0], w.shape[1]).to(self.dev)
-        with torch.no_grad():
-            m.weight.copy_(w)
-            m.bias.copy_(b)
-        m.precision = precision
-        for k, v in self.s.options.items():
-            assert hasattr(m, k), k
-            setattr(m, k, v)
+        m = make_layer(self.pkg, self.dev, w, b, precision=precision, **self.s.options)
         if self.s.path not in DROPS:
             m.requires_grad_(False)
         return m

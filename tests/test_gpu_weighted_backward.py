@@ -3,7 +3,7 @@
 the figures.
 
 1. The builder: the blocks decoded on the host, p0 + p1 + p2 = A_w^T within 2^-24 |a| per entry, rows and columns >= T exactly 0.
-2. The kernel through the C ABI against a float64 statement of the formulas in csrc/gate_pool_backward_mma.hip's header
+2. The kernel through the C ABI against the float64 statement (oracle/gates.py) of the formulas in csrc/gate_pool_backward_mma.hip's header
    (dY, then dH = A_w^T . (inv . dY)); the pools' winners are taken from the float32 values the kernel itself compares (the first
    maximum in ascending row order), everything else is float64.  Outputs pre-filled with NaN, pad columns and the row after the
    last one checked untouched, each call made twice and compared bit for bit.  Gates: dH and dY 2e-6 * max|ref|; d_sg, d_ga,
@@ -22,29 +22,20 @@ import pytest
 import torch
 
 from oracle import backward_ref as br
+from oracle import gates
+from oracle.gpu_support import count_calls, dev, drop_mask as _drop_mask, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
+_hostile, _close32, _gate, _gate_dx = gates.hostile, gates.close32, gates.gate, gates.gate_dx
+_statement64 = gates.gate_pool_backward_statement64      # keep=None: the kernel without dropout
 BUILD, WEIGHTED, ADJ_GRAD, TRANSPOSE = ("ggcn_graph_operands_weighted_t", "ggcn_gate_pool_backward_weighted", "ggcn_adjacency_grad",
                                         "ggcn_csr_transpose")
 MMA, AGG, GPB, GPB_DROP, AGG_T = ("ggcn_gate_pool_backward_mma", "ggcn_gate_pool_backward_agg", "ggcn_gate_pool_backward",
                                    "ggcn_gate_pool_backward_drop", "ggcn_aggregate_t")
 COUNTED = (BUILD, WEIGHTED, ADJ_GRAD, TRANSPOSE, MMA, AGG, GPB, GPB_DROP, AGG_T)
 BLOCK_BYTES = 6144
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
 
 
 # ================================================================ 1. the builder
@@ -123,43 +114,6 @@ def test_builder_flags_an_entry_that_is_not_finite(pkg, dev):
 
 
 # ================================================================ 2. the kernel through the C ABI
-def _hostile(t, pad, fill=NAN):
-    """t [N,F] as the first N rows of a [N + 1, F + pad] buffer: pad columns and the row after the last one are `fill`."""
-    buf = torch.full((t.shape[0] + 1, t.shape[1] + pad), fill, dtype=t.dtype, device=t.device)
-    buf[:t.shape[0], :t.shape[1]] = t
-    return buf
-
-
-def _first_argmax(v):
-    """[B,T,F] float32 -> one-hot [B,T,F] bool of the first maximum over t (ties: the smaller row)."""
-    m = v == v.max(dim=1, keepdim=True)[0]
-    return m & (m.cumsum(1) == 1)
-
-
-def _statement64(out, sg, ga, gb, d_out, d_pa, d_pb, adj, inv):
-    """float64 statement of gate_pool_backward_mma.hip's header on float32 inputs ([B,T,F] / [B,F]; None = absent)."""
-    B, T, F = out.shape
-    y32 = out if sg is None else out * torch.where(sg != 0, 1.0 / sg, torch.zeros_like(sg))[:, None, :]
-    y = out.double() if sg is None else out.double() * torch.where(sg != 0, 1.0 / sg.double(), torch.zeros_like(sg).double())[:, None, :]
-    dy = torch.zeros(B, T, F, dtype=torch.float64, device=out.device)
-    r = {}
-    if d_out is not None:
-        dy = dy + d_out.double() * (1.0 if sg is None else sg.double()[:, None, :])
-        r["d_sg"] = (d_out.double() * y).sum(1)
-    else:
-        r["d_sg"] = torch.zeros(B, F, dtype=torch.float64, device=out.device)
-    for key, gate, dp in (("d_ga", ga, d_pa), ("d_gb", gb, d_pb)):
-        if dp is None:
-            continue
-        g32 = torch.ones(B, F, device=out.device) if gate is None else gate
-        hot = _first_argmax(y32 * g32[:, None, :]).double()
-        dy = dy + hot * (dp.double() * g32.double())[:, None, :]
-        r[key] = dp.double() * (hot * y).sum(1)
-    r["dY"], r["d_bsum"] = dy, dy.sum(1)
-    r["dH"] = torch.einsum("bts,btf->bsf", adj.double(), inv.double().view(B, T, 1) * dy)
-    return r
-
-
 VARIANTS = ("full", "no-store-gate", "no-pool-a", "no-pool-b", "no-d_out", "no-dY")
 
 
@@ -257,68 +211,9 @@ def test_kernel_more_graphs_than_compute_units(pkg, dev):
 
 
 # ================================================================ 3. under autograd
-def _count_calls(monkeypatch):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = {k: 0 for k in COUNTED}
-    for n in COUNTED:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
-
-
-def _close32(got, ref, what, rel):
-    """float32 gradient: |got - ref| <= rel * max|ref| (tests/test_gpu_backward.py _close32)."""
-    ref = ref.double()
-    scale = float(ref.abs().max()) + 1e-12
-    err = float((got.double() - ref).abs().max())
-    print("  %s: max|diff| %.3g vs scale %.3g (gate %.3g)" % (what, err, scale, rel * scale))
-    assert got.dtype == torch.float32 and err == err and err <= rel * scale, "%s: max|diff| %.3g vs scale %.3g" % (what, err, scale)
-
-
-def _gate(got, ref, what, tol=1e-4):
-    """float32 result of bf16 features: |got - ref| <= tol * max(1, max|ref|) (tests/test_gpu_backward.py _gate)."""
-    ref = ref.double()
-    gate = tol * max(1.0, float(ref.abs().max()))
-    err = float((got.double() - ref).abs().max())
-    print("  %s: max|diff| %.3g (gate %.3g)" % (what, err, gate))
-    assert got.dtype == torch.float32 and err == err and err <= gate, "%s: max|diff| %.3g > %.3g" % (what, err, gate)
-
-
-def _gate_dx(dx, ref, what="dX"):
-    """bfloat16 dX: |dx - ref| <= 2^-8 |ref| + 1e-4 max|ref|, every element (tests/test_gpu_backward.py _gate_dx)."""
-    assert dx.dtype == torch.bfloat16
-    ref = ref.double()
-    bound = 2.0 ** -8 * ref.abs() + 1e-4 * float(ref.abs().max())
-    diff = (dx.double() - ref).abs()
-    print("  %s (bf16): max |diff| / gate %.3f" % (what, float((diff / (bound + 1e-300)).max())))
-    assert not bool(torch.isnan(diff).any()) and not bool((diff > bound).any()), "%s: %d elements outside the gate" % (
-        what, int((diff > bound).sum()))
-
-
 def _layer(pkg, dev, w, b, option, precision="f16mx8", fused_max_t=None):
-    m = pkg.GraphConvolution(w.shape[0], w.shape[1], bias=b is not None).to(dev)
-    assert m.weighted_backward is False                        # off by default
-    m.precision, m.weighted_backward = precision, option
-    if fused_max_t is not None:
-        m.fused_max_t = fused_max_t
-    with torch.no_grad():
-        m.weight.copy_(w)
-        if b is not None:
-            m.bias.copy_(b)
-    return m
-
-
-def _drop_mask(pkg, dev, rows, F, p, seed, stream):
-    from ed_gated_gcn_amd import _capi
-    lib = pkg.load_library()
-    m = torch.empty(rows, F, dtype=torch.float32, device=dev)
-    _capi.check(lib.ggcn_dropout_mask(rows, F, float(p), int(seed), stream, _capi.ptr(m), _capi.stream_of(dev)), "ggcn_dropout_mask")
-    return m
+    return make_layer(pkg, dev, w, b, expect_defaults={"weighted_backward": False}, precision=precision, weighted_backward=option,
+                      fused_max_t=fused_max_t)
 
 
 STREAMS = (0, 1, 2)
@@ -390,7 +285,7 @@ SHAPES = [(5, 17, 34, 20, "u01"), (7, 30, 300, 200, "u01"), (3, 1, 8, 8, "u01"),
 def test_under_autograd_the_new_entry_replaces_the_two_calls(pkg, dev, monkeypatch, B, T, K, F, gates, bf16):
     what = "%dx%dx%dx%d%s" % (B, T, K, F, " bf16" if bf16 else "")
     c, rs, _, ref = _reference(pkg, dev, (B, T, K, F), _weighted_inputs(B, T, K, F, gates, bf16), bf16)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     for adj_grad in (False, True):
         before = dict(calls)
         got, d_adj, csr = _run(pkg, dev, c, rs, None, adj_grad, option=True)
@@ -406,7 +301,7 @@ def test_under_autograd_the_new_entry_replaces_the_two_calls(pkg, dev, monkeypat
 # ================================================================ 4. where it steps aside
 def _steps_aside(pkg, dev, monkeypatch, key, make, expect, option=True, p=0.0, adj_grad=False, bf16=False):
     c, rs, dropout, ref = _reference(pkg, dev, key, make, bf16, p=p)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     got, d_adj, csr = _run(pkg, dev, c, rs, dropout, adj_grad, option, fused_max_t=256 if c["x"].shape[1] > 32 else None)
     want = {k: 0 for k in COUNTED}
     want.update(expect)
@@ -477,7 +372,7 @@ def test_gated_block_on_a_weighted_graph(pkg, dev, monkeypatch):
 
     gc1, gc2 = _layer(pkg, dev, c["w1"], c["b1"], True, precision), _layer(pkg, dev, c["w2"], c["b2"], True, precision)
     xg, g1g, g2g = (c[k].clone().requires_grad_() for k in ("x", "g1", "g2"))
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     r = pkg.gated_gcn_block(xg, c["adj"], g1g, g2g, gc1, gc2)
     loss_of(r).backward()
     torch.cuda.synchronize()

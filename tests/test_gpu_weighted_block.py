@@ -22,10 +22,12 @@ import pytest
 import torch
 
 from oracle import ref_dense
+from oracle.gates import poisoned_rows
+from oracle.gpu_support import clean_range_flag, count_calls, dev, make_layer, pkg, range_bits as _bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GATE = 1e-4                      # tests/test_gpu_parity.py, tests/test_gpu_weighted_wide.py:23,131: the same for both precisions
+GATE = 1e-4                      # oracle/backward_ref.py TOL: the same for both precisions
 OPS2_BYTES = 4224                # include/ggcn.h GGCN_GRAPH_OPS2_BYTES
 BLOCK, LAYER_W, BUILD_M, BUILD_M2 = ("ggcn_block_fused_weighted", "ggcn_layer_fused_weighted", "ggcn_graph_operands_weighted",
                                      "ggcn_graph_operands2_weighted")
@@ -35,50 +37,10 @@ OUTPUTS = ("x1", "y1", "xy", "x", "out")
 GUARD = 4096                     # floats of poison on either side of every output of the direct calls
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
-
-
-def _bits(pkg, dev):
-    """The raw f16mx8 range bits of every translation unit, read into a zeroed word and cleared."""
-    from ed_gated_gcn_amd import _capi
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    _capi.check(pkg.load_library().ggcn_range_flag(_capi.ptr(flag), 1, _capi.stream_of(dev)), "ggcn_range_flag")
-    return int(flag.item())
-
-
 @pytest.fixture(autouse=True)
 def clean_flag(pkg, dev):
     """Every test starts and ends with the range flag clear (some of the inputs below leave the fp16 window on purpose)."""
-    from ed_gated_gcn_amd import range_guard
-    _bits(pkg, dev)
-    range_guard.reset(dev)
-    yield
-    _bits(pkg, dev)
-    range_guard.reset(dev)
-
-
-def _count_calls(monkeypatch):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = {k: 0 for k in COUNTED}
-    for n in COUNTED:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
+    yield from clean_range_flag(pkg, dev)
 
 
 def _adjacency(B, T, kind, rng, lens):
@@ -106,16 +68,7 @@ def _lengths(rng, B, T):
 
 
 def _layers(pkg, dev, params, precision, block=True):
-    out = []
-    for w, b in params:
-        opt = types.SimpleNamespace(ggcn_precision=precision, ggcn_weighted_block=block)
-        m = pkg.GraphConvolution(w.shape[0], w.shape[1], opt=opt, bias=b is not None).to(dev)
-        with torch.no_grad():
-            m.weight.copy_(torch.as_tensor(w))
-            if b is not None:
-                m.bias.copy_(torch.as_tensor(b))
-        out.append(m)
-    return out
+    return [make_layer(pkg, dev, w, b, opt=types.SimpleNamespace(ggcn_precision=precision, ggcn_weighted_block=block)) for w, b in params]
 
 
 # ================================================================ 1. the builder
@@ -256,7 +209,7 @@ def test_m_fits_fp16_planes_and_its_square_does_not(pkg, dev, monkeypatch):
     x, g1, g2, params = _block_inputs(np.random.default_rng(2), B, T, K, F)
     xd, ad, g1d, g2d = torch.from_numpy(x).to(dev), torch.from_numpy(adj).to(dev), g1.to(dev), g2.to(dev)
     ref = _oracle(x, adj, g1, g2, params)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     # fp16 planes: M has its operand, M^2 has none -> today's two weighted layer launches, today's bits
     on, off = _layers(pkg, dev, params, "f16mx8"), _layers(pkg, dev, params, "f16mx8", block=False)
     csr = pkg.BatchedCSR.from_dense(ad)
@@ -317,12 +270,6 @@ def _case(B, T, K, F, kind, bias):
     return _CASE[key]
 
 
-def _poisoned(dev, rows, ld):
-    """``rows`` x ``ld`` floats of NaN between two guard bands of NaN: ``(whole buffer, the view handed to the library)``."""
-    buf = torch.full((rows * ld + 2 * GUARD,), float("nan"), dtype=torch.float32, device=dev)
-    return buf, buf[GUARD:GUARD + rows * ld].view(rows, ld)
-
-
 def _direct(pkg, dev, c, layers, xd, csr, g1d, g2d, outputs=("x1", "y1", "xy", "x", "out", "gcn1"), ld1=None, ld2=None, eval_operands=True):
     """``ggcn_block_fused_weighted`` called directly on NaN-filled outputs between poisoned guard bands.  ``outputs`` names what is
     handed in (the rest is NULL); ``eval_operands=False`` (the eval form) passes NULL for graph_opsw, wpack1, gate1 and zero_mid.
@@ -335,8 +282,8 @@ def _direct(pkg, dev, c, layers, xd, csr, g1d, g2d, outputs=("x1", "y1", "xy", "
     ld1, ld2 = ld1 or F, ld2 or F
     plane = 0 if gc1.precision == "bf16x3" else 1
     layer1 = any(k in outputs for k in ("x1", "y1", "xy", "gcn1"))
-    bufs = {"gcn1": _poisoned(dev, B * T, ld1), "x": _poisoned(dev, B * T, ld2), "x1": _poisoned(dev, B, F), "y1": _poisoned(dev, B, F),
-            "out": _poisoned(dev, B, F), "xy": _poisoned(dev, B, (F + 63) // 64)}
+    shapes = {"gcn1": (B * T, ld1), "x": (B * T, ld2), "x1": (B, F), "y1": (B, F), "out": (B, F), "xy": (B, (F + 63) // 64)}
+    bufs = {k: poisoned_rows(dev, rows, ld, GUARD) for k, (rows, ld) in shapes.items()}
     arg = {k: (bufs[k][1] if k in outputs else None) for k in bufs}
     x2d = xd.view(B * T, K)
     with torch.cuda.device(dev):
@@ -383,7 +330,7 @@ def test_block_vs_float64_oracle(pkg, dev, monkeypatch, B, T, K, F, kind, precis
     csr = pkg.BatchedCSR.from_dense(ad)
     assert not csr.is_binary and pkg.gated_block.takes_weighted_block_path(xd, csr, *on)
     assert not pkg.gated_block.takes_weighted_block_path(xd, csr, *off)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         r = pkg.gated_gcn_block(xd, csr, g1d, g2d, *on, want_gcn1=True)
         assert calls[BLOCK] == 1 and calls[LAYER_W] == 0 and calls["ggcn_block_fused"] == 0, calls
@@ -417,7 +364,7 @@ def test_block_on_large_batches_never_takes_the_eight_wavefront_kernel(pkg, dev,
     x, g1, g2, params = _block_inputs(rng, B, T, K, F)
     xd, ad, g1d, g2d = torch.from_numpy(x).to(dev), torch.from_numpy(adj).to(dev), g1.to(dev), g2.to(dev)
     on = _layers(pkg, dev, params, "f16mx8")
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         r = pkg.gated_gcn_block(xd, ad, g1d, g2d, *on)
     torch.cuda.synchronize()
@@ -439,7 +386,7 @@ def test_forms_and_which_launches_ran(pkg, dev, monkeypatch, precision):
     c = _case(9, 32, 64, 256, "sparse", True)
     xd, ad, g1d, g2d = torch.from_numpy(c.x).to(dev), torch.from_numpy(c.adj).to(dev), c.g1.to(dev), c.g2.to(dev)
     on = _layers(pkg, dev, c.params, precision)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         full = pkg.gated_gcn_block(xd, ad, g1d, g2d, *on)
         assert calls[BLOCK] == 1 and calls[LAYER_W] == 0 and calls["ggcn_gate_overlap"] == 0 and calls["ggcn_overlap_reduce"] == 1, calls
@@ -476,7 +423,7 @@ def test_dense_head_finishes_xy_two_launches_in_all(pkg, dev, monkeypatch, preci
     head = (wt.to(dev), hb.to(dev))
     with torch.no_grad():
         pkg.gated_gcn_block(xd, csr, g1d, g2d, *on, dense_head=head)     # folds W12 and builds the graph's operands: once per weights / adjacency
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         r = pkg.gated_gcn_block(xd, csr, g1d, g2d, *on, dense_head=head)
     torch.cuda.synchronize()
@@ -490,7 +437,7 @@ def test_what_keeps_todays_launches_and_todays_bits(pkg, dev, monkeypatch, preci
     c = _case(5, 17, 34, 100, "signed", True)
     xd, ad, g1d, g2d = torch.from_numpy(c.x).to(dev), torch.from_numpy(c.adj).to(dev), c.g1.to(dev), c.g2.to(dev)
     on, off = _layers(pkg, dev, c.params, precision), _layers(pkg, dev, c.params, precision, block=False)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         base = pkg.gated_gcn_block(xd, ad, g1d, g2d, *off, want_gcn1=True)
         base_eval = pkg.gated_gcn_block(xd, ad, g1d, g2d, *off, want=("x", "out"))
@@ -577,7 +524,7 @@ def test_range_report_on_the_new_launch(pkg, dev, monkeypatch):
     adj = _adjacency(B, T, "sparse", rng, lens)
     x, g1, g2, params = _block_inputs(rng, B, T, K, F)
     ad, g1d, g2d = torch.from_numpy(adj).to(dev), g1.to(dev), g2.to(dev)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     for precision in ("f16mx8", "bf16x3"):
         on = _layers(pkg, dev, params, precision)
         for value, word in ((None, None), (450.0, "window"), (65504.0, "65504 or infinite")):
@@ -633,7 +580,7 @@ def test_classifier_in_eval_on_a_signed_graph(pkg, dev, monkeypatch):
         else:
             torch.nn.init.uniform_(p, -0.05, 0.05, generator=gen)
     m = m.to(dev).eval()
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         logits, xy, kl, scores = m(inputs)
         assert calls[BLOCK] == 1 and calls[LAYER_W] == 0, calls

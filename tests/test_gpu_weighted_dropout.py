@@ -12,8 +12,8 @@ every stream triple, so that the shapes serve the gradient cases as well.
    exactly one call of the new entry, none of ``ggcn_linear`` / ``ggcn_aggregate``; through the C ABI with ``ldo = F + 4`` and NaN
    padding.
 2. p = 0 is bit-identical to the launch without dropout; the same seed twice is bit-identical; another seed differs.
-3. ``ggcn_gate_pool_backward_weighted_drop`` through the C ABI against a float64 statement of its formulas (section 2 of
-   tests/test_gpu_weighted_backward.py with keep factors): dH, dY, gate gradients and bias sums 2e-6 of their scale, dY = NULL
+3. ``ggcn_gate_pool_backward_weighted_drop`` through the C ABI against a float64 statement of its formulas
+   (``gate_pool_backward_statement64`` of oracle/gates.py with keep factors): dH, dY, gate gradients and bias sums 2e-6 of their scale, dY = NULL
    writes nothing but dH, two runs bit-identical, 4e-6 against ``ggcn_gate_pool_backward_drop`` + ``ggcn_aggregate_t``.
 4. ``forward_gated`` under autograd, float32: every gradient (and ``adj.grad``) within 5e-4 of its scale, with call counts, for
    ``adj.requires_grad`` off / on and ``weighted_backward`` off / on; two of the 33..128 shapes with the two-call backward.
@@ -25,10 +25,13 @@ import pytest
 import torch
 
 from oracle import backward_ref as br
+from oracle import gates
+from oracle.gpu_support import ace_batch, count_calls, dev, drop_mask, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
+_gate, _close32, _hostile, _statement64 = gates.gate, gates.close32, gates.hostile, gates.gate_pool_backward_statement64
 P_DROP, SEED = 0.25, 2 ** 40 + 99
 TRIPLES = ((0, 1, 2), (2, 2, 0), (1, 1, 1))
 FWD, WIDE, BWD = "ggcn_layer_fused_weighted_drop", "ggcn_layer_fused_weighted_wide_drop", "ggcn_gate_pool_backward_weighted_drop"
@@ -43,48 +46,14 @@ SHAPES_WIDE = [(3, 33, 64, 64, "u01"), (4, 64, 96, 72, "sym"), (2, 65, 40, 36, "
                (2, 128, 64, 260, "sym")]
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
-
-
-def _count_calls(monkeypatch):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = {k: 0 for k in COUNTED}
-    for n in COUNTED:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
+def _layer(pkg, dev, w, b, precision="f16mx8", dropout=True, backward=False, max_t=None):
+    off = {"weighted_dropout": False, "weighted_backward": False, "weighted_max_t": 32}                 # all off by default
+    return make_layer(pkg, dev, w, b, expect_defaults=off, precision=precision, weighted_dropout=dropout, weighted_backward=backward,
+                      weighted_max_t=max_t)
 
 
 def _made(calls, before=None):
     return {k: v - (before or {}).get(k, 0) for k, v in calls.items() if v - (before or {}).get(k, 0)}
-
-
-def _layer(pkg, dev, w, b, precision="f16mx8", dropout=True, backward=False, max_t=None):
-    m = pkg.GraphConvolution(w.shape[0], w.shape[1], bias=b is not None).to(dev)
-    assert m.weighted_dropout is False and m.weighted_backward is False and m.weighted_max_t == 32      # all off by default
-    m.precision, m.weighted_dropout, m.weighted_backward = precision, dropout, backward
-    if max_t is not None:
-        m.weighted_max_t = max_t
-    with torch.no_grad():
-        m.weight.copy_(w)
-        if b is not None:
-            m.bias.copy_(b)
-    return m
 
 
 _INPUTS, _MASKS, _Y64 = {}, {}, {}
@@ -98,39 +67,26 @@ def _inputs(dev, B, T, K, F, gates):
     return _INPUTS[key]
 
 
-def _drop_mask(pkg, dev, B, T, F, stream, p=P_DROP, seed=SEED):
+def _keep_factors(pkg, dev, B, T, F, stream, p=P_DROP, seed=SEED):
     """Keep factors [B,T,F] of one stream as ``ggcn_dropout_mask`` writes them (float64); stream 0: None."""
     if stream == 0:
         return None
     key = (B, T, F, stream, p, seed)
     if key not in _MASKS:
-        from ed_gated_gcn_amd import _capi
-        lib = pkg.load_library()
-        m = torch.empty(B * T, F, dtype=torch.float32, device=dev)
-        _capi.check(lib.ggcn_dropout_mask(B * T, F, float(p), int(seed), stream, _capi.ptr(m), _capi.stream_of(dev)), "ggcn_dropout_mask")
+        m = drop_mask(pkg, dev, B * T, F, p, seed, stream)
         assert set(m.unique().tolist()) <= {0.0, float(np.float32(1.0) / np.float32(1.0 - p))}
         _MASKS[key] = m.view(B, T, F).double()
     return _MASKS[key]
 
 
 def _keep(pkg, dev, B, T, F, triple):
-    return tuple(_drop_mask(pkg, dev, B, T, F, s) for s in triple)
+    return tuple(_keep_factors(pkg, dev, B, T, F, s) for s in triple)
 
 
 def _y64(dev, c, key):
     if key not in _Y64:
         _Y64[key] = br.layer_output(c["x"], c["adj"], c["w"], c["b"])
     return _Y64[key]
-
-
-def _gate(got, ref, what, tol):
-    """|got - ref| <= tol * max(1, max|ref|) (tests/test_gpu_backward.py _gate); returns err / gate."""
-    ref = ref.double()
-    gate = tol * max(1.0, float(ref.abs().max()))
-    err = float((got.double() - ref).abs().max())
-    print("  %s: max|diff| %.3g (gate %.3g)" % (what, err, gate))
-    assert got.dtype == torch.float32 and err == err and err <= gate, "%s: max|diff| %.3g > %.3g" % (what, err, gate)
-    return err / gate
 
 
 # ================================================================ 1. forward against float64
@@ -144,7 +100,7 @@ def test_forward_vs_float64(pkg, dev, monkeypatch, B, T, K, F, gates, precision)
     y = _y64(dev, c, (B, T, K, F))
     tol = br.TOL[precision] / (1.0 - P_DROP)
     entry, other = (WIDE, FWD) if T > 32 else (FWD, WIDE)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     worst = 0.0
     for triple in TRIPLES:
         ks, ka, kb = _keep(pkg, dev, B, T, F, triple)
@@ -209,7 +165,7 @@ def test_p0_is_the_launch_without_dropout_and_a_seed_is_a_seed(pkg, dev, monkeyp
     c = _inputs(dev, B, T, K, F, gates)
     m = _layer(pkg, dev, c["w"], c["b"], precision, max_t=128)
     csr = pkg.BatchedCSR.from_dense(c["adj"], binary=False)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
 
     def run(dropout):
         with torch.no_grad():
@@ -232,51 +188,6 @@ def test_p0_is_the_launch_without_dropout_and_a_seed_is_a_seed(pkg, dev, monkeyp
 
 
 # ================================================================ 3. the backward kernel through the C ABI
-def _hostile(t, pad, fill=NAN):
-    """t [N,F] as the first N rows of a [N + 1, F + pad] buffer: pad columns and the row after the last one are `fill`."""
-    buf = torch.full((t.shape[0] + 1, t.shape[1] + pad), fill, dtype=t.dtype, device=t.device)
-    buf[:t.shape[0], :t.shape[1]] = t
-    return buf
-
-
-def _first_argmax(v, valid=None):
-    """[B,T,F] float32 -> one-hot [B,T,F] bool of the first maximum over t (ties: the smaller row)."""
-    m = v == v.max(dim=1, keepdim=True)[0]
-    return m & (m.cumsum(1) == 1)
-
-
-def _statement64(out, sg, ga, gb, d_out, d_pa, d_pb, adj, inv, keep):
-    """float64 statement of the DROP formulas in csrc/gate_pool_backward_weighted.hip's header on float32 inputs ([B,T,F] / [B,F];
-    None = absent; keep = (ks, ka, kb) float64 [B,T,F] or None).  The pools' winners are taken from the float32 values the kernel
-    itself compares: y32 = out * inv_sg / ks (0 where ks = 0), candidates y32 * g * k."""
-    B, T, F = out.shape
-    ks, ka, kb = keep
-    one32, one64 = torch.ones(B, T, F, device=out.device), torch.ones(B, T, F, dtype=torch.float64, device=out.device)
-    ks32, ks64 = (one32, one64) if ks is None else (ks.float(), ks)
-    inv_sg32 = torch.ones(B, F, device=out.device) if sg is None else torch.where(sg != 0, 1.0 / sg, torch.zeros_like(sg))
-    inv_sg64 = one64[:, 0] if sg is None else torch.where(sg != 0, 1.0 / sg.double(), torch.zeros_like(sg).double())
-    y32 = torch.where(ks32 != 0, out * inv_sg32[:, None, :] / ks32, torch.zeros_like(out))
-    y = torch.where(ks64 != 0, out.double() * inv_sg64[:, None, :] / ks64, torch.zeros_like(one64))
-    dy = torch.zeros(B, T, F, dtype=torch.float64, device=out.device)
-    r = {}
-    if d_out is not None:
-        dy = dy + d_out.double() * (1.0 if sg is None else sg.double()[:, None, :]) * ks64
-        r["d_sg"] = (d_out.double() * y * ks64).sum(1)
-    else:
-        r["d_sg"] = torch.zeros(B, F, dtype=torch.float64, device=out.device)
-    for key, gate, dp, k in (("d_ga", ga, d_pa, ka), ("d_gb", gb, d_pb, kb)):
-        if dp is None:
-            continue
-        g32 = torch.ones(B, F, device=out.device) if gate is None else gate
-        k32, k64 = (one32, one64) if k is None else (k.float(), k)
-        hot = _first_argmax(y32 * g32[:, None, :] * k32).double()
-        dy = dy + hot * (dp.double() * g32.double())[:, None, :] * k64
-        r[key] = dp.double() * (hot * y * k64).sum(1)
-    r["dY"], r["d_bsum"] = dy, dy.sum(1)
-    r["dH"] = torch.einsum("bts,btf->bsf", adj.double(), inv.double().view(B, T, 1) * dy)
-    return r
-
-
 VARIANTS = ("full", "no-store-gate", "no-pool-a", "no-pool-b", "no-d_out", "no-dY")
 
 
@@ -401,16 +312,6 @@ STREAMS = (0, 1, 2)
 _REF = {}      # case -> the float64 reference, computed once and left unchanged
 
 
-def _close32(got, ref, what, rel):
-    """float32 gradient: |got - ref| <= rel * max|ref| (tests/test_gpu_backward.py _close32)."""
-    ref = ref.double()
-    scale = float(ref.abs().max()) + 1e-12
-    err = float((got.double() - ref).abs().max())
-    print("  %s: max|diff| %.3g vs scale %.3g (gate %.3g)" % (what, err, scale, rel * scale))
-    assert got.dtype == torch.float32 and err == err and err <= rel * scale, "%s: max|diff| %.3g vs scale %.3g" % (what, err, scale)
-    return err / scale
-
-
 def _reference(pkg, dev, B, T, K, F, gates, precision="f16mx8"):
     key = (B, T, K, F)
     if key in _REF:
@@ -461,7 +362,7 @@ def _check_grads(got, d_adj, ref, what, rel=5e-4):
 def test_under_autograd(pkg, dev, monkeypatch, B, T, K, F, gates):
     what = "%dx%dx%dx%d" % (B, T, K, F)
     c, rs, ref = _reference(pkg, dev, B, T, K, F, gates)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     worst = 0.0
     for backward in (True, False):
         for adj_grad in (False, True):
@@ -485,7 +386,7 @@ def test_under_autograd(pkg, dev, monkeypatch, B, T, K, F, gates):
 def test_under_autograd_33_to_128_nodes_keep_the_two_call_backward(pkg, dev, monkeypatch, B, T, K, F, gates):
     what = "%dx%dx%dx%d" % (B, T, K, F)
     c, rs, ref = _reference(pkg, dev, B, T, K, F, gates)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     for adj_grad in (False, True):
         before = dict(calls)
         got, d_adj, csr = _run(pkg, dev, c, rs, adj_grad, True, max_t=128)
@@ -524,7 +425,7 @@ def test_where_it_steps_aside(pkg, dev, monkeypatch):
     with pytest.raises(RuntimeError, match="dropout streams"):
         on.forward_gated(c["x"].clone().requires_grad_(), c["adj"], dropout=(P_DROP, SEED, (1, 2, 0)), **kw)
     # a 0/1 adjacency takes ggcn_layer_fused_drop as ever
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     binary = (c["adj"] != 0).float()
     with torch.no_grad():
         on.forward_gated(c["x"], binary, dropout=dropout, **kw)
@@ -533,29 +434,6 @@ def test_where_it_steps_aside(pkg, dev, monkeypatch):
 
 
 # ================================================================ 6. the classifier
-def _ace_batch(rng, B, ORI_ML, BERT_ML):
-    """``_ace_batch`` of tests/test_gpu_parity.py with real-valued edge weights in [0.25, 2)."""
-    from ed_gated_gcn_amd import synth
-    sent_len = rng.integers(5, ORI_ML + 1, size=B)
-    sent_len[0] = ORI_ML
-    bert_len = np.minimum(sent_len + rng.integers(2, 10, size=B), BERT_ML)
-    adj = synth.dependency_batch(B, ORI_ML, 3.5, seed=12, lengths=sent_len).astype(np.float32)
-    adj = adj * rng.uniform(0.25, 2.0, size=adj.shape).astype(np.float32)
-    transform = np.zeros((B, ORI_ML, BERT_ML), dtype=np.float32)
-    for b in range(B):
-        for tkn in range(int(sent_len[b])):
-            transform[b, tkn, 1 + min(tkn, BERT_ML - 2)] = 1.0
-    return {
-        "sentence_length": torch.from_numpy(sent_len), "cls_text_sep_length": torch.from_numpy(bert_len),
-        "cls_text_sep_indices": torch.zeros(B, BERT_ML, dtype=torch.long),
-        "cls_text_sep_segments_ids": torch.zeros(B, BERT_ML, dtype=torch.long),
-        "transform": torch.from_numpy(transform),
-        "anchor_index": torch.from_numpy(np.array([int(rng.integers(0, n)) for n in sent_len])),
-        "dist_to_target": torch.from_numpy(rng.integers(0, 6, size=(B, ORI_ML))),
-        "dependency_graph": torch.from_numpy(adj),
-    }
-
-
 def test_classifier_trains_a_weighted_graph_inside_the_launches(pkg, dev, monkeypatch):
     import types
 
@@ -576,7 +454,7 @@ def test_classifier_trains_a_weighted_graph_inside_the_launches(pkg, dev, monkey
     m = m.to(dev)
     with torch.no_grad():
         m.gc1.bias.fill_(5.0)                              # gcn1 > 0 everywhere: x1 = 0 iff every token's gate entry was dropped
-    inputs = {k: v.to(dev) for k, v in _ace_batch(np.random.default_rng(0), 32, 31, 60).items()}
+    inputs = {k: v.to(dev) for k, v in ace_batch(np.random.default_rng(0), 32, 31, 60, weights=(0.25, 2.0)).items()}
     seen = {}
     orig = m.gc1.forward_gated
 
@@ -587,7 +465,7 @@ def test_classifier_trains_a_weighted_graph_inside_the_launches(pkg, dev, monkey
         return r
     m.train()
     m.gc1.forward_gated = spy
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     try:
         for on in (True, False):
             for layer in (m.gc1, m.gc2):

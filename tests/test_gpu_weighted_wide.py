@@ -17,53 +17,20 @@ import torch
 
 from oracle import backward_ref as br
 from oracle import ref_dense
+from oracle.gates import close32 as _close32
+from oracle.gpu_support import count_calls, dev, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-TOL = {"bf16x3": 1e-4, "f16mx8": 1e-4}          # the parity gate of tests/test_gpu_parity.py
+TOL = br.TOL                                    # the forward parity gate per arithmetic
 NAN = float("nan")
 WIDE, NARROW, LINEAR, AGGREGATE = "ggcn_layer_fused_weighted_wide", "ggcn_layer_fused_weighted", "ggcn_linear", "ggcn_aggregate"
 COUNTED = (WIDE, NARROW, LINEAR, AGGREGATE, "ggcn_layer_fused", "ggcn_graph_operands_weighted_wide", "ggcn_adjacency_grad",
            "ggcn_aggregate_t", "ggcn_gate_pool_backward")
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
-
-
 def _layer(pkg, dev, w, b, precision, weighted_max_t=128):
-    w, b = torch.as_tensor(w), (None if b is None else torch.as_tensor(b))
-    m = pkg.GraphConvolution(w.shape[0], w.shape[1], bias=b is not None).to(dev)
-    m.precision = precision
-    m.weighted_max_t = weighted_max_t
-    with torch.no_grad():
-        m.weight.copy_(w)
-        if b is not None:
-            m.bias.copy_(b)
-    return m
-
-
-def _count_calls(monkeypatch):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = {k: 0 for k in COUNTED}
-    for n in COUNTED:
-        fn = getattr(lib, n)
-
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
+    return make_layer(pkg, dev, w, b, precision=precision, weighted_max_t=weighted_max_t)
 
 
 def _adjacency(B, T, kind, rng, lens):
@@ -150,7 +117,7 @@ def test_which_launches_ran(pkg, dev, monkeypatch, precision):
     gs, ga, gb = (g.to(dev) for g in gates)
     xd, ad = torch.from_numpy(x).to(dev), torch.from_numpy(adj).to(dev)
     kw = dict(store_gate=gs, pool_gate_a=ga, pool_gate_b=gb, want_pool_a=True, want_pool_b=True)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     on = _layer(pkg, dev, w, b, precision)
     with torch.no_grad():
         on.forward_gated(xd, ad, **kw)
@@ -311,7 +278,7 @@ def test_non_finite_operand_keeps_two_launches(pkg, dev, monkeypatch):
     w, b = synth.layer_params(H, H, seed=8)
     on, parent = _layer(pkg, dev, w, b, "f16mx8"), _layer(pkg, dev, w, b, "f16mx8", weighted_max_t=32)
     assert not on.takes_weighted_path(x, csr)
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     with torch.no_grad():
         got = on.forward_gated(x, csr, want_pool_a=True)
         assert calls[WIDE] == 0 and calls[LINEAR] == 1 and calls[AGGREGATE] == 1, calls
@@ -324,15 +291,6 @@ def test_non_finite_operand_keeps_two_launches(pkg, dev, monkeypatch):
 
 
 # ================================================================ 5. under autograd
-def _close32(got, ref, what, rel=2e-4):
-    """float32 gradient: |got - ref| <= rel * max|ref| (tests/test_gpu_adjacency_grad.py _close32)."""
-    ref = ref.double()
-    scale = float(ref.abs().max()) + 1e-12
-    err = float((got.double() - ref).abs().max())
-    print("  %s: max|diff| %.3g vs scale %.3g (gate %.3g)" % (what, err, scale, rel * scale))
-    assert got.dtype == torch.float32 and err == err and err <= rel * scale, "%s: max|diff| %.3g vs scale %.3g" % (what, err, scale)
-
-
 _REF = {}
 
 
@@ -360,7 +318,7 @@ def test_under_autograd(pkg, dev, monkeypatch, T, precision):
     c, rs, ref = _reference(dev, T)
     m = _layer(pkg, dev, c["w"], c["b"], precision)
     leaves = {k: c[k].clone().requires_grad_() for k in ("x", "sg", "ga", "gb", "adj")}
-    calls = _count_calls(monkeypatch)
+    calls = count_calls(monkeypatch, COUNTED)
     out, pa, pb = m.forward_gated(leaves["x"], leaves["adj"], store_gate=leaves["sg"], pool_gate_a=leaves["ga"], pool_gate_b=leaves["gb"],
                                   want_pool_a=True, want_pool_b=True)
     assert calls[WIDE] == 1 and calls[LINEAR] == 0 and calls[AGGREGATE] == 0, calls
@@ -372,7 +330,7 @@ def test_under_autograd(pkg, dev, monkeypatch, T, precision):
     got["w"], got["b"] = m.weight.grad, m.bias.grad
     assert got["adj"].shape == c["adj"].shape and not bool(torch.isnan(got["adj"]).any())
     for k, label in (("adj", "d adj"), ("x", "dX"), ("w", "dW"), ("b", "db"), ("sg", "d store gate"), ("ga", "d gate a"), ("gb", "d gate b")):
-        _close32(got[k], ref[k], what + " " + label)
+        _close32(got[k], ref[k], what + " " + label, 2e-4)
 
 
 # ================================================================ 6. the gated block
@@ -392,7 +350,7 @@ def test_gated_block_on_a_weighted_adjacency(pkg, dev, monkeypatch):
                                 t(b2).double(), dtype=torch.float64)
     for precision in ("f16mx8", "bf16x3"):
         l1, l2 = _layer(pkg, dev, w1, b1, precision), _layer(pkg, dev, w2, b2, precision)
-        calls = _count_calls(monkeypatch)
+        calls = count_calls(monkeypatch, COUNTED)
         with torch.no_grad():
             r = pkg.gated_gcn_block(t(x).to(dev), t(adj).to(dev), g1.to(dev), g2.to(dev), l1, l2)
         torch.cuda.synchronize()

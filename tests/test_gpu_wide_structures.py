@@ -27,6 +27,7 @@ import torch
 
 from oracle import backward_ref as br
 from oracle import wide_structures as ws
+from oracle.gpu_support import call_log, count_calls, dev, drop_mask as _drop_mask, make_layer, pkg  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -37,52 +38,23 @@ FUSED, PREBIAS, DROP, LINEAR, AGGREGATE, LISTS = ("ggcn_layer_fused", "ggcn_laye
 COUNTED = (FUSED, PREBIAS, DROP, LINEAR, AGGREGATE, LISTS)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "the gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import ed_gated_gcn_amd as p
-    p.load_library()
-    return p
-
-
 def _layer(pkg, dev, w, b, precision, fused=True):
-    """tests/test_gpu_parity.py ``_layer``: fused_max_t = 256 sends every graph of <= 256 nodes to the one launch, whatever the batch."""
-    m = pkg.GraphConvolution(w.shape[0], w.shape[1], opt=None, bias=b is not None).to(dev)
-    m.precision = precision
-    m.fused = bool(fused)
-    m.fused_max_t = 256
-    with torch.no_grad():
-        m.weight.copy_(w)
-        if b is not None:
-            m.bias.copy_(b)
-    return m.eval()
+    """fused_max_t = 256 sends every graph of <= 256 nodes to the one launch, whatever the batch (as tests/test_gpu_parity.py)."""
+    return make_layer(pkg, dev, w, b, precision=precision, fused=bool(fused), fused_max_t=256).eval()
 
 
-class _Calls(dict):
-    """Entry calls counted the way tests/test_gpu_backward.py ``_count_calls`` does; ``args`` keeps the last call's arguments."""
-    def since(self, before):
-        return {k: self[k] - before[k] for k in COUNTED if self[k] != before[k]}
+def _watch(monkeypatch):
+    """``(calls, log)``: the counter and the recorder of ``oracle/gpu_support.py`` on the entries of COUNTED."""
+    return count_calls(monkeypatch, COUNTED), call_log(monkeypatch, COUNTED)
 
 
-def _count_calls(monkeypatch):
-    from ed_gated_gcn_amd import _capi
-    lib = _capi.load_library()
-    calls = _Calls({k: 0 for k in COUNTED})
-    calls.args = {}
-    for n in COUNTED:
-        fn = getattr(lib, n)
+def _since(calls, before):
+    return {k: calls[k] - before[k] for k in COUNTED if calls[k] != before[k]}
 
-        def wrap(*a, _fn=fn, _n=n):
-            calls[_n] += 1
-            calls.args[_n] = a
-            return _fn(*a)
-        monkeypatch.setattr(lib, n, wrap)
-    return calls
+
+def _last(log, entry):
+    """The arguments of the last call of ``entry`` (pointers as integers, NULL: None)."""
+    return [a for n, a in log if n == entry][-1]
 
 
 def _kernel_adj(c):
@@ -159,35 +131,35 @@ def test_layer_on_directed_and_extreme_graphs(pkg, dev, monkeypatch, T, K, F, pr
     csr = pkg.BatchedCSR.from_dense(ad)
     assert csr.is_binary and csr.rowmask is not None and fused.takes_fused_path(c["x"], csr) and not unfused.takes_fused_path(c["x"], csr)
     kw = dict(store_gate=c["sg"], pool_gate_a=c["ga"], pool_gate_b=c["gb"], want_pool_a=True, want_pool_b=True)
-    calls = _count_calls(monkeypatch)
+    calls, log = _watch(monkeypatch)
     with torch.no_grad():
         # ---- the one launch, on the edge lists made once per adjacency (129..256 nodes)
         before = dict(calls)
         got = fused.forward_gated(c["x"], csr, **kw)
-        assert calls.since(before) == ({FUSED: 1, LISTS: 1} if T > 128 else {FUSED: 1}), (what, calls.since(before))
-        assert (calls.args[FUSED][4] is not None) == (T > 128), "%s: edge lists handed over: %r" % (what, calls.args[FUSED][4])
+        assert _since(calls, before) == ({FUSED: 1, LISTS: 1} if T > 128 else {FUSED: 1}), (what, _since(calls, before))
+        assert (_last(log, FUSED)[4] is not None) == (T > 128), "%s: edge lists handed over: %r" % (what, _last(log, FUSED)[4])
         # ---- pools only
         before = dict(calls)
         pools_only = fused.forward_gated(c["x"], csr, pool_gate_a=c["ga"], pool_gate_b=c["gb"], want_out=False, want_pool_a=True, want_pool_b=True)
-        assert calls.since(before) == {FUSED: 1} and calls.args[FUSED][13] is None, (what, calls.since(before))
+        assert _since(calls, before) == {FUSED: 1} and _last(log, FUSED)[13] is None, (what, _since(calls, before))
         # ---- a host-collated CSR of the same graphs
         rp, ci, _ = synth.csr_from_dense_host(ad.cpu().numpy())
         host = pkg.BatchedCSR.from_arrays(rp, ci, G, T, dev)
         before = dict(calls)
         via_host = fused.forward_gated(c["x"], host, **kw)
-        assert calls.since(before) == ({FUSED: 1, LISTS: 1} if T > 128 else {FUSED: 1}), (what, calls.since(before))
+        assert _since(calls, before) == ({FUSED: 1, LISTS: 1} if T > 128 else {FUSED: 1}), (what, _since(calls, before))
         # ---- 129..256 nodes: the lists built inside the workgroup from the row masks
         inside = None
         if T > 128:
             monkeypatch.setenv("GGCN_EDGE_LISTS", "0")
             before = dict(calls)
             inside = fused.forward_gated(c["x"], csr, **kw)
-            assert calls.since(before) == {FUSED: 1} and calls.args[FUSED][4] is None, (what, calls.since(before))
+            assert _since(calls, before) == {FUSED: 1} and _last(log, FUSED)[4] is None, (what, _since(calls, before))
             monkeypatch.delenv("GGCN_EDGE_LISTS")
         # ---- linear + aggregate (the general CSR kernel) on the same batch
         before = dict(calls)
         two = unfused.forward_gated(c["x"], csr, **kw)
-        assert calls.since(before) == {LINEAR: 1, AGGREGATE: 1}, (what, calls.since(before))
+        assert _since(calls, before) == {LINEAR: 1, AGGREGATE: 1}, (what, _since(calls, before))
     torch.cuda.synchronize()
     rep = _Report("a", what, names, br.TOL[precision])
     for label, gv, rv in zip(("out", "pool a", "pool b"), got, c["ref"]):
@@ -216,20 +188,20 @@ def test_folded_evaluation_and_two_launch_block(pkg, dev, monkeypatch, T, precis
     what = "block T=%d H=%d %s" % (T, ws.BLOCK_H, precision)
     l1, l2 = _layer(pkg, dev, c["w1"], c["b1"], precision), _layer(pkg, dev, c["w2"], c["b2"], precision)
     csr = pkg.BatchedCSR.from_dense(_kernel_adj(c).contiguous())
-    calls = _count_calls(monkeypatch)
+    calls, log = _watch(monkeypatch)
     with torch.no_grad():
         before = dict(calls)
         ev = pkg.gated_gcn_block(c["x"], csr, c["g1"], c["g2"], l1, l2, want=("out",))
-        made = calls.since(before)
+        made = _since(calls, before)
         made.pop(LINEAR, None)      # (W12 = W1.W2 and mid = W2^T.b1 are folded once per weight, by the exact fp32 linear)
         assert made == {AGGREGATE: 1, PREBIAS: 1}, (what, made)
-        assert calls.args[PREBIAS][13] is None          # no [B,T,H] store was asked for
+        assert _last(log, PREBIAS)[13] is None          # no [B,T,H] store was asked for
         before = dict(calls)
         evx = pkg.gated_gcn_block(c["x"], csr, c["g1"], c["g2"], l1, l2, want=("x", "out"))
-        assert calls.since(before) == {AGGREGATE: 1, PREBIAS: 1}, (what, calls.since(before))
+        assert _since(calls, before) == {AGGREGATE: 1, PREBIAS: 1}, (what, _since(calls, before))
         before = dict(calls)
         full = pkg.gated_gcn_block(c["x"], csr, c["g1"], c["g2"], l1, l2, want_gcn1=True)
-        assert calls.since(before) == ({FUSED: 2, LISTS: 1} if T > 128 else {FUSED: 2}), (what, calls.since(before))
+        assert _since(calls, before) == ({FUSED: 2, LISTS: 1} if T > 128 else {FUSED: 2}), (what, _since(calls, before))
     torch.cuda.synchronize()
     assert all(ev[k] is None for k in ("gcn1", "x1", "y1", "xy", "x"))
     rep = _Report("b", what, names, br.TOL[precision])
@@ -246,14 +218,6 @@ def test_folded_evaluation_and_two_launch_block(pkg, dev, monkeypatch, T, precis
 
 
 # ================================================================ (c) gate dropout inside the launch
-def _drop_mask(pkg, dev, rows, F, p, seed, stream):
-    from ed_gated_gcn_amd import _capi
-    lib = pkg.load_library()
-    m = torch.empty(rows, F, dtype=torch.float32, device=dev)
-    _capi.check(lib.ggcn_dropout_mask(rows, F, float(p), int(seed), stream, _capi.ptr(m), _capi.stream_of(dev)), "ggcn_dropout_mask")
-    return m
-
-
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("T,K,F", ws.DROP_CASES)
 def test_gate_dropout_inside_the_launch(pkg, dev, monkeypatch, T, K, F, precision):
@@ -267,11 +231,11 @@ def test_gate_dropout_inside_the_launch(pkg, dev, monkeypatch, T, K, F, precisio
     assert 0.2 < float((keep[1] == 0).double().mean()) < 0.3 and not torch.equal(keep[1], keep[2])
     with torch.no_grad():
         ref = br.gated_layer_ref(c["x"], c["adj"], c["w"], c["b"], c["sg"], c["ga"], c["gb"], keep=keep)
-    calls = _count_calls(monkeypatch)
+    calls, log = _watch(monkeypatch)
     with torch.no_grad():
         got = m.forward_gated(c["x"], csr, store_gate=c["sg"], pool_gate_a=c["ga"], pool_gate_b=c["gb"], want_pool_a=True, want_pool_b=True,
                               dropout=(p, seed, streams))
-    assert calls.since({k: 0 for k in COUNTED}) == {DROP: 1}, (what, dict(calls))
+    assert _since(calls, {k: 0 for k in COUNTED}) == {DROP: 1}, (what, dict(calls))
     torch.cuda.synchronize()
     rep = _Report("c", what, names, br.TOL[precision] / (1.0 - p))
     for label, gv, rv in zip(("out", "pool a", "pool b"), got, ref):

@@ -11,6 +11,7 @@ import pytest
 import ed_gated_gcn_amd as pkg
 from ed_gated_gcn_amd import _capi, dispatch
 from ed_gated_gcn_amd.gcn import GraphConvolution
+from oracle.host_support import msg as _msg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = 1, 3
@@ -24,11 +25,6 @@ NAMES = ("ggcn_graph_operands_weighted_t_bytes", "ggcn_graph_operands_weighted_t
 def _no_env(monkeypatch):
     monkeypatch.delenv("GGCN_WEIGHTED_BACKWARD", raising=False)
     monkeypatch.delenv("GGCN_BACKWARD_TWO_PASS", raising=False)
-
-
-def _msg(lib, rc, code):
-    assert rc == code, (rc, lib.ggcn_last_error().decode())
-    return lib.ggcn_last_error().decode()
 
 
 def test_declared_bound_exported_and_abi_stays_14():

@@ -15,6 +15,7 @@ import torch
 import ed_gated_gcn_amd as pkg
 from ed_gated_gcn_amd import _capi, dispatch, gated_block
 from ed_gated_gcn_amd.gcn import GraphConvolution
+from oracle.host_support import msg as _msg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = 1, 3
@@ -30,13 +31,6 @@ ENV = ("GGCN_WEIGHTED_BLOCK", "GGCN_WEIGHTED_MAX_T", "GGCN_FUSED", "GGCN_FUSED_M
 def _no_env(monkeypatch):
     for k in ENV:
         monkeypatch.delenv(k, raising=False)
-
-
-def _msg(lib, rc, code, who):
-    text = lib.ggcn_last_error().decode()
-    assert rc == code, (rc, text)
-    assert text.startswith(who + ":"), text
-    return text
 
 
 # ---------------------------------------------------------------- the ABI

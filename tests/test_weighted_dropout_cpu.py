@@ -14,6 +14,7 @@ import torch
 import ed_gated_gcn_amd as pkg
 from ed_gated_gcn_amd import _capi, dispatch
 from ed_gated_gcn_amd.gcn import GraphConvolution
+from oracle.host_support import msg as _msg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = 1, 3
@@ -30,11 +31,6 @@ ENV = ("GGCN_WEIGHTED_DROPOUT", "GGCN_WEIGHTED_BACKWARD", "GGCN_WEIGHTED_MAX_T",
 def _no_env(monkeypatch):
     for k in ENV:
         monkeypatch.delenv(k, raising=False)
-
-
-def _msg(lib, rc, code):
-    assert rc == code, (rc, lib.ggcn_last_error().decode())
-    return lib.ggcn_last_error().decode()
 
 
 # ---------------------------------------------------------------- the ABI

@@ -14,6 +14,7 @@ import torch
 import ed_gated_gcn_amd as pkg
 from ed_gated_gcn_amd import _capi, dispatch
 from ed_gated_gcn_amd.gcn import GraphConvolution
+from oracle.host_support import msg as _msg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _spec = importlib.util.spec_from_file_location("dispatch_table_tool", os.path.join(ROOT, "tools", "dispatch_table.py"))
@@ -123,11 +124,6 @@ def test_bytes_outside_the_range():
     lib = pkg.load_library()
     for B, T in ((4, 32), (4, 129), (0, 64), (-1, 64), (4, 0)):
         assert lib.ggcn_graph_operands_weighted_wide_bytes(B, T) == 0
-
-
-def _msg(lib, rc, code):
-    assert rc == code, (rc, lib.ggcn_last_error().decode())
-    return lib.ggcn_last_error().decode()
 
 
 def test_builder_refusals():
