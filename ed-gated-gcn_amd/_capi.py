@@ -55,6 +55,11 @@ PROTOTYPES = {
     "ggcn_gate_mlp": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ggcn_scores_head": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32,
                                  c_i32, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    "ggcn_scores_head_backward": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                          c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                          c_vp, c_i64, c_vp, c_vp]),
+    "ggcn_scores_head_dweight_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "ggcn_scores_head_dweight": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "ggcn_absmax": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "ggcn_range_flag": (c_i32, [c_vp, c_i32, c_vp]),
     "ggcn_debug_poison_lds": (c_i32, [ctypes.c_uint32, c_vp]),

@@ -7,7 +7,8 @@ Sub-module names, shapes and construction order follow the reference, so a refer
 way.  ``forward(inputs) -> (logits, gate_reg, kl_reg, scores)`` like every live model of
 ``train.py:109``.  The sub-word pooling (``:600``), the gate MLPs (``:562-571``), the block (``:621-640``) and the
 ``scores`` / ``kl`` head (``:645-648``) run on the HIP path in inference; under autograd the gate MLPs and the
-head keep the reference's PyTorch ops (they are trained), and with dropout active the gates are dropped per
+head keep the reference's PyTorch ops (they are trained; ``opt.ggcn_head_backward`` puts the head on its HIP forward and
+one-launch backward), and with dropout active the gates are dropped per
 token like the reference's (``:621-625``).  BERT, the BiLSTM and ``dense`` stay PyTorch-ROCm.
 """
 import os
@@ -77,6 +78,11 @@ class GatedGCNEventDetector(nn.Module):
         # inference forward computes only what they need -- `out` (bert_amir5.py:640,643): the W12 tiles of the block, no
         # [B,T,H] store of x, no regulariser, no scores / kl head -- and returns (logits, None, None, None)
         self.eval_logits_only = bool(getattr(opt, "ggcn_eval_logits_only", False))
+        # training: the scores / kl head (:645-648) as the differentiable ``scores_and_kl`` (one forward launch pair, one backward
+        # launch + the weight product) instead of the reference's PyTorch ops.  Off by default: its sums differ from those ops'
+        # in the last bits (both inside the gradient gate).
+        self.head_backward = (bool(getattr(opt, "ggcn_head_backward", False))
+                              or os.environ.get("GGCN_HEAD_BACKWARD", "0") == "1")
 
     F16_RANGE_MARGIN = 32752.0   # half of fp16's largest finite value
     F16MX8_WINDOW = 448.0        # include/ggcn.h GGCN_RANGE_WINDOW: beyond it an activation's fp8 correction saturates
@@ -244,6 +250,12 @@ class GatedGCNEventDetector(nn.Module):
         else:
             out = self.dropout(out)                                         # :642
             logits = self.dense(torch.cat([anchor_rep, aspect, out], dim=1))    # :643
+        if self.head_backward:   # :645-648 on the HIP path, forward and backward (sigmoid(cat) = cat(sigmoid), as in inference)
+            if v54:
+                scores, kl = scores_and_kl(torch.sigmoid(xg), torch.sigmoid(aspect), logits, self.fc[1], dist)
+            else:
+                scores, kl = scores_and_kl(xg, aspect, logits, self.fc[0], dist)
+            return logits, xy, kl, scores
         output_w = self.fc(torch.cat([xg, aspect[:, None, :].expand(-1, T, -1)], dim=2))   # :645
         scores = (logits[:, None, :] * output_w).sum(2)                     # :646
         kl = (torch.softmax(scores, 1) * torch.softmax(dist.float(), 1)).sum(1).mean()          # :648

@@ -599,6 +599,25 @@ int ggcn_scores_head(const float *X, int64_t ldx, const float *aspect, int64_t l
                        kl_part, as_stream(stream));
 }
 
+int ggcn_scores_head_backward(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
+                              const float *fc_weight, int64_t ldw, const float *fc_bias, const float *dist, int64_t ldd,
+                              const float *scores, int64_t ld_scores, const float *kl_part, const float *g_scores, int64_t ld_gs,
+                              const float *g_kl, int B, int T, int H, int C, float *dX, int64_t lddx, float *d_aspect, int64_t ldda,
+                              float *d_logits, int64_t lddl, float *G, int64_t ldg, float *dc0, ggcn_stream_t stream)
+{
+    return scores_head_backward(X, ldx, aspect, lda, logits, ldl, fc_weight, ldw, fc_bias, dist, ldd, scores, ld_scores, kl_part,
+                                g_scores, ld_gs, g_kl, B, T, H, C, dX, lddx, d_aspect, ldda, d_logits, lddl, G, ldg, dc0,
+                                as_stream(stream));
+}
+
+size_t ggcn_scores_head_dweight_workspace_bytes(int B, int H, int C) { return scores_head_dweight_workspace_bytes(B, H, C); }
+
+int ggcn_scores_head_dweight(const float *logits, int64_t ldl, const float *G, int64_t ldg, const float *dc0, int B, int H, int C,
+                             float *dW, int64_t lddw, float *d_bias, void *workspace, ggcn_stream_t stream)
+{
+    return scores_head_dweight(logits, ldl, G, ldg, dc0, B, H, C, dW, lddw, d_bias, workspace, as_stream(stream));
+}
+
 int ggcn_dense_head(const float *pooled, int64_t ldp, const float *Wt, int64_t ldw, const float *bias, int B, int H, int C,
                     float *logits, int64_t ldl, const float *overlap_partials, int F_block, float *xy, ggcn_stream_t stream)
 {

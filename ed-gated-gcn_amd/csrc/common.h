@@ -195,6 +195,14 @@ int gate_mlp(const float *aspect, int64_t lda, int B, int H, const float *w1t_a,
 int scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
                 const float *fcw, int64_t ldw, const float *fcb, const float *dist, int64_t ldd, int B, int T, int H,
                 int C, float *scores, int64_t lds_, float *kl_part, hipStream_t st);
+int scores_head_backward(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
+                         const float *fcw, int64_t ldw, const float *fcb, const float *dist, int64_t ldd, const float *scores,
+                         int64_t lds_, const float *kl_part, const float *g_scores, int64_t ldgs, const float *g_kl, int B, int T,
+                         int H, int C, float *dX, int64_t lddx, float *d_aspect, int64_t ldda, float *d_logits, int64_t lddl, float *G,
+                         int64_t ldg, float *dc0, hipStream_t st);
+size_t scores_head_dweight_workspace_bytes(int B, int H, int C);
+int scores_head_dweight(const float *logits, int64_t ldl, const float *G, int64_t ldg, const float *dc0, int B, int H, int C, float *dW,
+                        int64_t lddw, float *d_bias, void *workspace, hipStream_t st);
 
 int dense_head(const float *pooled, int64_t ldp, const float *Wt, int64_t ldw, const float *bias, int B, int H, int C,
                float *logits, int64_t ldl, const float *partials, int F_block, float *xy, hipStream_t st, unsigned *signal = nullptr);

@@ -11,7 +11,8 @@
 //     scores[b,t] = logits_b . (Wx.x_t + Wa.a_b + b) = (Wx^T.logits_b) . x_t + logits_b . (Wa.a_b + b)
 // -- one H-vector and one scalar per sentence, then one dot product per token: x is read once (HBM-bound).
 // Both kernels use plain fp32 FMA chains (exact fp32, no matrix cores: 0.1-0.3 GFLOP at the reference's
-// batch of 256 sentences).
+// batch of 256 sentences).  The scores / kl head also has its backward here, for training through it: one launch per call
+// (scores_head_backward_kernel) and a fixed-order weight product (head_dweight_*_kernel).
 #include "common.h"
 
 namespace ggcn {
@@ -141,6 +142,179 @@ __global__ __launch_bounds__(256) void scores_head_kernel(const float *__restric
         if (lane == 0) kl_part[b] = cross / (zs * zd);
     }
     (void)red;
+}
+
+// ---- backward of the scores / kl head (training through bert_amir5.py:645-648) -------------------------------------------
+// With v = Wx^T.lg, u = Wa.a + fb, c0 = lg.u, scores[t] = v.x_t + c0, p = softmax_t(scores), q = softmax_t(dist),
+// kl_b = sum_t p_t q_t and the incoming g_s [B,T] (d scores) and g_k (d kl, one device float), per sentence:
+//     ds[t]  = g_s[t] + (g_k / B) p_t (q_t - kl_b)
+//     dX[t]  = ds[t] v            dv = sum_t ds[t] x_t          dc0 = sum_t g_s[t]
+//     d lg   = Wx.dv + dc0 u      d a = dc0 (Wa^T.lg)           G = [dv | dc0 a]   (dW = lg^T.G and dfb = lg^T.dc0: below)
+// dc0 is the sum of ds over t; the kl term's share of that sum is sum_t p_t (q_t - kl_b) = 0 identically (a softmax does not
+// see a shift of its scores), so it is left out instead of being summed to rounding noise: a loss that uses kl alone gives
+// exact zeros for d a, dWa and dfb, as the mathematics does.
+// One workgroup per sentence, like the forward.  v, u and the two softmaxes are recomputed (the forward's own loops, on the
+// saved scores and kl_b); then ONE pass over the sentence's x rows: wavefront w takes the tokens t = w, w + 4, ..., lanes over
+// h; per 256-column (scalar form: 64-column) chunk a lane keeps its piece of v and of the wavefront's dv in registers, reads
+// x[t] once, stores dX[t] once.  The four wavefronts' dv meet in LDS in the order 0, 1, 2, 3.  Every sum has a fixed order
+// (t ascending per wavefront, xor butterflies, wavefronts ascending): no atomics, the same bits on every call.
+// Dynamic LDS: v [Hp] | dv of the 4 wavefronts [4][Hp] | Wa^T.lg [Hp] | u [C] | ds [T] | 8 floats, Hp = H rounded up to 4 (16-byte carves).
+// sum_c lg[c] * W[c][col], c ascending (one FMA chain, as the forward's v), the loads of eight classes in flight at a time
+__device__ __forceinline__ float column_dot(const float *__restrict__ lg, const float *__restrict__ wcol, int64_t ldw, int C)
+{
+    float acc = 0.0f;
+    int c = 0;
+    for (; c + 8 <= C; c += 8) {
+        float w[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) w[q] = wcol[(int64_t)(c + q) * ldw];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc = fmaf(lg[c + q], w[q], acc);
+    }
+    for (; c < C; ++c) acc = fmaf(lg[c], wcol[(int64_t)c * ldw], acc);
+    return acc;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void scores_head_backward_kernel(
+    const float *__restrict__ X, int64_t ldx, const float *__restrict__ aspect, int64_t lda, const float *__restrict__ logits,
+    int64_t ldl, const float *__restrict__ fcw, int64_t ldw, const float *__restrict__ fcb, const float *__restrict__ dist,
+    int64_t ldd, const float *__restrict__ scores, int64_t lds_, const float *__restrict__ kl_part,
+    const float *__restrict__ g_scores, int64_t ldgs, const float *__restrict__ g_kl, int B, int T, int H, int C,
+    float *__restrict__ dX, int64_t lddx, float *__restrict__ d_aspect, int64_t ldda, float *__restrict__ d_logits, int64_t lddl,
+    float *__restrict__ G, int64_t ldg, float *__restrict__ dc0_out)
+{
+    extern __shared__ __attribute__((aligned(16))) float bwd_lds[];
+    const int Hp = (H + 3) & ~3;
+    float *v = bwd_lds, *dvp = v + Hp, *wal = dvp + 4 * Hp, *u = wal + Hp, *ds = u + C, *red = ds + T;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const float *lg = logits + (int64_t)b * ldl, *a = aspect + (int64_t)b * lda;
+    // v = Wx^T.lg (the forward's sums, class by class) and, for d a, Wa^T.lg: one loop over fc.weight's 2H columns
+    for (int col = tid; col < (d_aspect ? 2 * H : H); col += 256) {
+        const float s = column_dot(lg, fcw + col, ldw, C);
+        if (col < H) v[col] = s;
+        else wal[col - H] = s;
+    }
+    for (int c = wave; c < C; c += 4) {                           // u: the forward's loop
+        float acc = 0.0f;
+#pragma unroll 4
+        for (int hh = lane; hh < H; hh += 64) acc = fmaf(fcw[(int64_t)c * ldw + H + hh], a[hh], acc);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+        if (lane == 0) u[c] = acc + (fcb ? fcb[c] : 0.0f);
+    }
+    if (wave == 0) {                                              // ds [T] and dc0: one wavefront, lanes loop over t
+        const float *gs = g_scores ? g_scores + (int64_t)b * ldgs : nullptr;
+        float sum_gs = 0.0f;
+        for (int t = lane; t < T; t += 64) {
+            const float g = gs ? gs[t] : 0.0f;
+            ds[t] = g;
+            sum_gs += g;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum_gs += __shfl_xor(sum_gs, d);
+        if (lane == 0) red[0] = sum_gs;
+        if (g_kl) {
+            const float *sr = scores + (int64_t)b * lds_, *dr = dist + (int64_t)b * ldd;
+            float ms = -INFINITY, md = -INFINITY;
+            for (int t = lane; t < T; t += 64) { ms = fmaxf(ms, sr[t]); md = fmaxf(md, dr[t]); }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) { ms = fmaxf(ms, __shfl_xor(ms, d)); md = fmaxf(md, __shfl_xor(md, d)); }
+            float zs = 0.0f, zd = 0.0f;
+            for (int t = lane; t < T; t += 64) { zs += expf(sr[t] - ms); zd += expf(dr[t] - md); }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) { zs += __shfl_xor(zs, d); zd += __shfl_xor(zd, d); }
+            const float gk = *g_kl / (float)B, klb = kl_part[b];
+            for (int t = lane; t < T; t += 64)                     // (each lane re-reads the ds[t] it wrote itself)
+                ds[t] = fmaf(gk * (expf(sr[t] - ms) / zs), expf(dr[t] - md) / zd - klb, ds[t]);
+        }
+    }
+    __syncthreads();
+    const float dc0 = red[0];
+    const int64_t row0 = (int64_t)b * T;
+    if (VEC) {      // H % 4 == 0, 16-byte-aligned rows of X and dX: a lane takes 4 columns of every 256
+        for (int h0 = 4 * lane; h0 < H; h0 += 256) {
+            const float4 vv = *reinterpret_cast<const float4 *>(v + h0);
+            float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll 4
+            for (int t = wave; t < T; t += 4) {
+                const float d = ds[t];
+                const float4 xv = *reinterpret_cast<const float4 *>(X + (row0 + t) * ldx + h0);
+                acc.x = fmaf(d, xv.x, acc.x); acc.y = fmaf(d, xv.y, acc.y);
+                acc.z = fmaf(d, xv.z, acc.z); acc.w = fmaf(d, xv.w, acc.w);
+                if (dX) *reinterpret_cast<float4 *>(dX + (row0 + t) * lddx + h0) = make_float4(d * vv.x, d * vv.y, d * vv.z, d * vv.w);
+            }
+            *reinterpret_cast<float4 *>(dvp + wave * Hp + h0) = acc;
+        }
+    } else {        // any H, any alignment: a lane takes 1 column of every 64
+        for (int hh = lane; hh < H; hh += 64) {
+            const float vh = v[hh];
+            float acc = 0.0f;
+#pragma unroll 4
+            for (int t = wave; t < T; t += 4) {
+                const float d = ds[t];
+                acc = fmaf(d, X[(row0 + t) * ldx + hh], acc);
+                if (dX) dX[(row0 + t) * lddx + hh] = d * vh;
+            }
+            dvp[wave * Hp + hh] = acc;
+        }
+    }
+    __syncthreads();
+    for (int hh = tid; hh < H; hh += 256) {
+        const float dv = ((dvp[hh] + dvp[Hp + hh]) + dvp[2 * Hp + hh]) + dvp[3 * Hp + hh];   // wavefronts 0, 1, 2, 3
+        dvp[hh] = dv;                                              // (this thread's own column: read again after the barrier)
+        if (G) {
+            G[(int64_t)b * ldg + hh] = dv;
+            G[(int64_t)b * ldg + H + hh] = dc0 * a[hh];
+        }
+        if (d_aspect) d_aspect[(int64_t)b * ldda + hh] = dc0 * wal[hh];   // d a = dc0 * (Wa^T . lg)
+    }
+    __syncthreads();
+    if (d_logits)
+        for (int c = wave; c < C; c += 4) {                        // d lg[c] = Wx[c,:] . dv + dc0 u[c]: u's loop on the first half
+            float acc = 0.0f;
+#pragma unroll 4
+            for (int hh = lane; hh < H; hh += 64) acc = fmaf(fcw[(int64_t)c * ldw + hh], dvp[hh], acc);
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+            if (lane == 0) d_logits[(int64_t)b * lddl + c] = fmaf(dc0, u[c], acc);
+        }
+    if (dc0_out && tid == 0) dc0_out[b] = dc0;
+}
+
+// dW = lg^T . G  ([C,B] x [B,2H]) and dfb = lg^T . dc0 of the head, in a fixed order: G's columns and dc0 as column 2H; the
+// launch's z slices take kDwRows sentences each (b ascending) into part [slices][C][2H + 1], a second launch adds the slices in
+// ascending order.  0.4 GFLOP at 4096 x 768 x 34: exact fp32 FMA chains, lg read through scalar loads (uniform per workgroup).
+constexpr int kDwRows = 128, kDwClasses = 8;
+__global__ __launch_bounds__(256) void head_dweight_partial_kernel(const float *__restrict__ logits, int64_t ldl, const float *__restrict__ G,
+                                                                   int64_t ldg, const float *__restrict__ dc0, int B, int W2, int C,
+                                                                   float *__restrict__ part)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x, c0 = blockIdx.y * kDwClasses, b0 = blockIdx.z * kDwRows;
+    const int b1 = b0 + kDwRows < B ? b0 + kDwRows : B;
+    if (j > W2) return;
+    float acc[kDwClasses] = {};
+    for (int b = b0; b < b1; ++b) {
+        const float g = j < W2 ? G[(int64_t)b * ldg + j] : dc0[b];
+#pragma unroll
+        for (int q = 0; q < kDwClasses; ++q) acc[q] = fmaf(c0 + q < C ? logits[(int64_t)b * ldl + c0 + q] : 0.0f, g, acc[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < kDwClasses; ++q)
+        if (c0 + q < C) part[((int64_t)blockIdx.z * C + c0 + q) * (W2 + 1) + j] = acc[q];
+}
+
+__global__ __launch_bounds__(256) void head_dweight_finish_kernel(const float *__restrict__ part, int slices, int W2, int C, float *__restrict__ dW,
+                                                                  int64_t lddw, float *__restrict__ dfb)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, n = (int64_t)C * (W2 + 1);
+    if (idx >= n) return;
+    const int c = (int)(idx / (W2 + 1)), j = (int)(idx - (int64_t)c * (W2 + 1));
+    float t = 0.0f;
+    for (int s = 0; s < slices; ++s) t += part[(int64_t)s * n + idx];
+    if (j < W2) dW[(int64_t)c * lddw + j] = t;
+    else if (dfb) dfb[c] = t;
 }
 
 
@@ -289,6 +463,54 @@ int scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, c
     hipLaunchKernelGGL(scores_head_kernel, dim3((unsigned)B), dim3(256), lds, st, X, ldx, aspect, lda, logits, ldl, fcw, ldw,
                        fcb, dist, ldd, T, H, C, scores, lds_, kl_part);
     return check_launch("ggcn_scores_head");
+}
+
+int scores_head_backward(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
+                         const float *fcw, int64_t ldw, const float *fcb, const float *dist, int64_t ldd, const float *scores,
+                         int64_t lds_, const float *kl_part, const float *g_scores, int64_t ldgs, const float *g_kl, int B, int T,
+                         int H, int C, float *dX, int64_t lddx, float *d_aspect, int64_t ldda, float *d_logits, int64_t lddl, float *G,
+                         int64_t ldg, float *dc0, hipStream_t st)
+{
+    if (!X || !aspect || !logits || !fcw) return fail(GGCN_EINVAL, "ggcn_scores_head_backward: null pointer");
+    if (g_kl && (!dist || !scores || !kl_part))
+        return fail(GGCN_EINVAL, "ggcn_scores_head_backward: a gradient of kl needs dist, the saved scores and the saved kl_part");
+    if ((G != nullptr) != (dc0 != nullptr)) return fail(GGCN_EINVAL, "ggcn_scores_head_backward: G and dc0 go together");
+    if (B <= 0 || T <= 0 || H <= 0 || C <= 0) return fail(GGCN_EINVAL, "ggcn_scores_head_backward: B=%d T=%d H=%d C=%d", B, T, H, C);
+    if (ldx < H || lda < H || ldl < C || ldw < 2 * H || (g_kl && (ldd < T || lds_ < T)) || (g_scores && ldgs < T) || (dX && lddx < H) ||
+        (d_aspect && ldda < H) || (d_logits && lddl < C) || (G && ldg < 2 * H))
+        return fail(GGCN_EINVAL, "ggcn_scores_head_backward: leading dimension too small");
+    const size_t lds = ((size_t)6 * ((H + 3) & ~3) + C + T + 8) * sizeof(float);
+    if (lds > 64 * 1024)
+        return fail(GGCN_EUNSUPPORTED, "ggcn_scores_head_backward: 6 H + C + T = %lld floats need more than 64 KiB of LDS",
+                    6LL * H + C + T);
+    const auto aligned16 = [](const void *p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && (ld & 3) == 0; };
+    const bool vec = (H & 3) == 0 && aligned16(X, ldx) && (!dX || aligned16(dX, lddx));
+    hipLaunchKernelGGL(vec ? scores_head_backward_kernel<true> : scores_head_backward_kernel<false>, dim3((unsigned)B), dim3(256), lds, st,
+                       X, ldx, aspect, lda, logits, ldl, fcw, ldw, fcb, dist, ldd, scores, lds_, kl_part, g_scores, ldgs, g_kl, B, T, H, C,
+                       dX, lddx, d_aspect, ldda, d_logits, lddl, G, ldg, dc0);
+    return check_launch("ggcn_scores_head_backward");
+}
+
+size_t scores_head_dweight_workspace_bytes(int B, int H, int C)
+{
+    if (B <= 0 || H <= 0 || C <= 0) return sizeof(float);
+    return (size_t)((B + kDwRows - 1) / kDwRows) * (size_t)C * (size_t)(2 * H + 1) * sizeof(float);
+}
+
+int scores_head_dweight(const float *logits, int64_t ldl, const float *G, int64_t ldg, const float *dc0, int B, int H, int C, float *dW,
+                        int64_t lddw, float *d_bias, void *workspace, hipStream_t st)
+{
+    if (!logits || !G || !dc0 || !dW || !workspace) return fail(GGCN_EINVAL, "ggcn_scores_head_dweight: null pointer");
+    if (B <= 0 || H <= 0 || C <= 0) return fail(GGCN_EINVAL, "ggcn_scores_head_dweight: B=%d H=%d C=%d", B, H, C);
+    if (ldl < C || ldg < 2 * H || lddw < 2 * H) return fail(GGCN_EINVAL, "ggcn_scores_head_dweight: leading dimension too small");
+    const int W2 = 2 * H, slices = (B + kDwRows - 1) / kDwRows;
+    if (slices > 65535) return fail(GGCN_EUNSUPPORTED, "ggcn_scores_head_dweight: B=%d (at most %d sentences)", B, 65535 * kDwRows);
+    float *part = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(head_dweight_partial_kernel, dim3((unsigned)((W2 + 1 + 255) / 256), (unsigned)((C + kDwClasses - 1) / kDwClasses), (unsigned)slices),
+                       dim3(256), 0, st, logits, ldl, G, ldg, dc0, B, W2, C, part);
+    const int64_t n = (int64_t)C * (W2 + 1);
+    hipLaunchKernelGGL(head_dweight_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, slices, W2, C, dW, lddw, d_bias);
+    return check_launch("ggcn_scores_head_dweight");
 }
 
 int dense_head(const float *pooled, int64_t ldp, const float *Wt, int64_t ldw, const float *bias, int B, int H, int C,

@@ -5,8 +5,11 @@
 * ``scores_and_kl`` -- ``models/bert_amir5.py:645-648``: the ``fc`` / ``scores`` / ``kl`` head without its
   ``[B,T,2H]`` concat and ``[B,T,C]`` product.
 
-Inference only (``torch.no_grad`` or no parameter needing a gradient): under autograd the classifier keeps the
-reference's PyTorch ops for these ~0.1 GFLOP pieces, so ``train.py:115-121`` trains them unchanged.
+``gate_mlps`` is inference only (``torch.no_grad`` or no parameter needing a gradient): under autograd the classifier
+keeps the reference's PyTorch ops for the ``[B,H]`` gate MLPs.  ``scores_and_kl`` is differentiable: when a gradient is wanted
+it runs as ``_ScoresAndKl``, whose backward is one launch (``ggcn_scores_head_backward``) plus a fixed-order weight product
+(``ggcn_scores_head_dweight``).  The classifier takes it in training with ``opt.ggcn_head_backward`` / ``GGCN_HEAD_BACKWARD=1``
+(off by default: the fused sums differ from the PyTorch ops' in the last bits).
 """
 import torch
 
@@ -72,28 +75,20 @@ def gate_mlps(aspect, gate1_seq, gate2_seq):
     return g1, g2
 
 
-def scores_and_kl(x, aspect, logits, fc_linear, dist):
-    """``models/bert_amir5.py:645-648``: ``(scores [B,T], kl scalar)`` from the block's gated output ``x [B,T,H]``.
-    bfloat16 operands (``aspect`` and ``logits`` under bf16 autocast) are taken as float32 here."""
-    x, aspect, logits = (t.float() if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 else t for t in (x, aspect, logits))
-    for name, t in (("x", x), ("aspect", aspect), ("logits", logits)):
-        if not (t.is_cuda and t.dtype == torch.float32):
-            raise RuntimeError("%s must be a float32 GPU tensor (no CPU path exists)" % name)
+def _head_forward(x, aspect, logits, w, fb, dist):
+    """The ``ggcn_scores_head`` + ``ggcn_overlap_reduce`` pair on detached float32 operands: ``(scores, kl, what the backward
+    needs)``."""
     lib = _capi.load_library()
     B, T, H = x.shape
     C = logits.shape[1]
-    if fc_linear.in_features != 2 * H or fc_linear.out_features != C:
-        raise RuntimeError("fc must be Linear(%d, %d)" % (2 * H, C))
     x2 = _rows2d(x)
     a = aspect if aspect.stride(1) == 1 else aspect.contiguous()
     lg = logits if logits.stride(1) == 1 else logits.contiguous()
     d = dist.float()                                   # :648 `dist_to_target.float()`
     if d.stride(1) != 1:
         d = d.contiguous()
-    w = fc_linear.weight.detach()
     if not w.is_contiguous():
         w = w.contiguous()
-    fb = None if fc_linear.bias is None else fc_linear.bias.detach()
     dev = x.device
     with torch.cuda.device(dev):
         st = _capi.stream_of(dev)
@@ -105,6 +100,81 @@ def scores_and_kl(x, aspect, logits, fc_linear, dist):
                                          d.stride(0), B, T, H, C, _capi.ptr(scores), T, _capi.ptr(part), st),
                     "ggcn_scores_head")
         _capi.check(lib.ggcn_overlap_reduce(_capi.ptr(part), B, 1, _capi.ptr(kl), st), "ggcn_overlap_reduce")
+    return scores, kl, (x2, a, lg, w, d, part)
+
+
+class _ScoresAndKl(torch.autograd.Function):
+    """``scores_and_kl`` under autograd: the forward is ``_head_forward`` (the bits of a ``no_grad`` call), the backward one
+    ``ggcn_scores_head_backward`` launch and, when ``fc`` trains, the fixed-order weight product ``ggcn_scores_head_dweight``."""
+
+    @staticmethod
+    def forward(ctx, x, aspect, logits, weight, bias, dist):
+        ctx.set_materialize_grads(False)     # a loss on kl alone (or on scores alone) hands the launch a NULL, not zeros
+        scores, kl, (x2, a, lg, w, d, part) = _head_forward(x.detach(), aspect.detach(), logits.detach(), weight.detach(),
+                                                            None if bias is None else bias.detach(), dist)
+        ctx.save_for_backward(x2, a, lg, w, bias, d, scores, part)
+        ctx.dims = tuple(x.shape) + (logits.shape[1],)
+        return scores, kl
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_scores, g_kl):
+        x2, a, lg, w, bias, d, scores, part = ctx.saved_tensors
+        B, T, H, C = ctx.dims
+        need_x, need_a, need_lg, need_w, need_b = ctx.needs_input_grad[:5]
+        need_b = need_b and bias is not None
+        if g_scores is None and g_kl is None:
+            return None, None, None, None, None, None
+        g_scores = None if g_scores is None else g_scores.float().contiguous()
+        g_kl = None if g_kl is None else g_kl.float().contiguous()
+        lib = _capi.load_library()
+        dev = x2.device
+        ptr = _capi.ptr
+        fb = None if bias is None else bias.detach()
+        with torch.cuda.device(dev):
+            st = _capi.stream_of(dev)
+            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)   # noqa: E731
+            dx = new(B, T, H) if need_x else None
+            da = new(B, H) if need_a else None
+            dlg = new(B, C) if need_lg else None
+            G, dc0 = (new(B, 2 * H), new(B)) if (need_w or need_b) else (None, None)
+            _capi.check(lib.ggcn_scores_head_backward(
+                ptr(x2), x2.stride(0), ptr(a), a.stride(0), ptr(lg), lg.stride(0), ptr(w), w.stride(0), ptr(fb), ptr(d), d.stride(0),
+                ptr(scores), T, ptr(part), ptr(g_scores), T, ptr(g_kl), B, T, H, C,
+                ptr(dx), H, ptr(da), H, ptr(dlg), C, ptr(G), 2 * H, ptr(dc0), st), "ggcn_scores_head_backward")
+            dw = db = None
+            if need_w or need_b:
+                dw = new(C, 2 * H)
+                db = new(C) if bias is not None else None
+                ws = torch.empty(lib.ggcn_scores_head_dweight_workspace_bytes(B, H, C), dtype=torch.uint8, device=dev)
+                _capi.check(lib.ggcn_scores_head_dweight(ptr(lg), lg.stride(0), ptr(G), 2 * H, ptr(dc0), B, H, C, ptr(dw), 2 * H,
+                                                         ptr(db), ptr(ws), st), "ggcn_scores_head_dweight")
+        return dx, da, dlg, dw if need_w else None, db if need_b else None, None
+
+
+def scores_and_kl(x, aspect, logits, fc_linear, dist):
+    """``models/bert_amir5.py:645-648``: ``(scores [B,T], kl scalar)`` from the block's gated output ``x [B,T,H]``.
+    bfloat16 operands (``aspect`` and ``logits`` under bf16 autocast) are taken as float32 here.
+
+    Differentiable: with grad enabled and ``x``, ``aspect``, ``logits``, ``fc_linear.weight`` or ``fc_linear.bias`` requiring
+    a gradient the call goes through ``_ScoresAndKl`` -- the same two forward launches (the same bits as under ``no_grad``),
+    and a backward of one launch (``ggcn_scores_head_backward``: ``x`` read once, ``dX`` written once, nothing of size
+    ``[B,T,2H]`` or ``[B,T,C]`` kept) plus the fixed-order weight product.  ``dist`` gets no gradient.  Forward + backward
+    of the head alone against the literal PyTorch ops (``tools/head_backward_timing.py``, MI355X, taken with this change on top of
+    ``af09ca0``; ``profiles/head_backward_timing.txt``): 587 against 1435 us per step at 4096 x 32 x 768 (C = 34), 145 against
+    296 us at 256 x 31 x 256; peak memory on top of the inputs 429 against 1556 MiB and 9 against 33 MiB."""
+    x, aspect, logits = (t.float() if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 else t for t in (x, aspect, logits))
+    for name, t in (("x", x), ("aspect", aspect), ("logits", logits)):
+        if not (t.is_cuda and t.dtype == torch.float32):
+            raise RuntimeError("%s must be a float32 GPU tensor (no CPU path exists)" % name)
+    B, T, H = x.shape
+    C = logits.shape[1]
+    if fc_linear.in_features != 2 * H or fc_linear.out_features != C:
+        raise RuntimeError("fc must be Linear(%d, %d)" % (2 * H, C))
+    w, fb = fc_linear.weight, fc_linear.bias
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, aspect, logits, w, fb)):
+        return _ScoresAndKl.apply(x, aspect, logits, w, fb, dist)
+    scores, kl, _ = _head_forward(x, aspect, logits, w.detach(), None if fb is None else fb.detach(), dist)
     return scores, kl
 
 

@@ -606,6 +606,35 @@ int ggcn_scores_head(const float *X, int64_t ldx, const float *aspect, int64_t l
                      const float *dist, int64_t ldd, int B, int T, int H, int C,
                      float *scores, int64_t ld_scores, float *kl_part, ggcn_stream_t stream);
 
+/* ---- backward of the scores / kl head in one launch (training through models/bert_amir5.py:645-648) ------------------
+ * Inputs as ggcn_scores_head's, plus what its forward left: scores [B, ld_scores] and kl_part [B]; g_scores [B, ld_gs] is the
+ * gradient of scores, g_kl ONE DEVICE float, the gradient of kl (read on the device: no host read-back).  Either may be
+ * NULL (that term is zero); dist, scores and kl_part are read only with g_kl.  With v = Wx^T.logits_b, u = Wa.a_b + fc_bias:
+ *     ds[b,t] = g_scores[b,t] + (g_kl / B) p_t (q_t - kl_part[b])      p = softmax_t(scores_b), q = softmax_t(dist_b)
+ *     dX[b,t,:] = ds[b,t] v          [B*T, lddx]; NULL: not stored (x needs no gradient)
+ *     dc0[b]    = sum_t g_scores[b,t]           (= sum_t ds[b,t]: the kl term's share is identically zero and is left out)
+ *     d_logits[b] = Wx.dv_b + dc0[b] u          [B, lddl], dv_b = sum_t ds[b,t] x[b,t,:]
+ *     d_aspect[b] = dc0[b] (Wa^T.logits_b)      [B, ldda]
+ *     G[b] = [dv_b | dc0[b] a_b]                [B, ldg], ldg >= 2H: ggcn_scores_head_dweight's operand
+ * d_aspect, d_logits and the pair (G, dc0) may be NULL.  One workgroup per sentence; X is read once and dX written once, in
+ * 16-byte accesses when H % 4 == 0 and X / dX rows are 16-byte aligned, element by element otherwise.  Exact fp32 FMA chains,
+ * every sum in a fixed order, no atomics: two calls on the same inputs give the same bits.  No synchronisation.
+ * GGCN_EUNSUPPORTED when 6 H + C + T floats exceed 64 KiB of LDS.
+ *
+ * ggcn_scores_head_dweight: dW [C, lddw] = logits^T . G (the gradient of fc.weight [C, 2H]) and d_bias [C] = logits^T . dc0
+ * (NULL: fc has no bias), summed over the sentences in a fixed order (slices of 128 sentences, then the slices ascending; two
+ * launches).  workspace: ggcn_scores_head_dweight_workspace_bytes(B, H, C) bytes. */
+int ggcn_scores_head_backward(const float *X, int64_t ldx, const float *aspect, int64_t lda,
+                              const float *logits, int64_t ldl, const float *fc_weight, int64_t ldw, const float *fc_bias,
+                              const float *dist, int64_t ldd, const float *scores, int64_t ld_scores, const float *kl_part,
+                              const float *g_scores, int64_t ld_gs, const float *g_kl, int B, int T, int H, int C,
+                              float *dX, int64_t lddx, float *d_aspect, int64_t ldda, float *d_logits, int64_t lddl,
+                              float *G, int64_t ldg, float *dc0, ggcn_stream_t stream);
+size_t ggcn_scores_head_dweight_workspace_bytes(int B, int H, int C);
+int ggcn_scores_head_dweight(const float *logits, int64_t ldl, const float *G, int64_t ldg, const float *dc0,
+                             int B, int H, int C, float *dW, int64_t lddw, float *d_bias, void *workspace,
+                             ggcn_stream_t stream);
+
 /* ---- range check for GGCN_PREC_F16MX8 (on demand, not on the forward path) ----------------
  * out[0] = max |x| over the finite entries of X [M,K] (fp32, or IEEE half when is_half != 0; ld in
  * elements), out[1] = 1.0f when some entry is NaN or infinite.  f16mx8 needs |x|, |w| < 65504 and keeps
