@@ -53,6 +53,10 @@ PROTOTYPES = {
     "ggcn_overlap_reduce": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "ggcn_transpose": (c_i32, [c_vp, c_i32, c_i32, c_i64, c_vp, c_vp]),
     "ggcn_gate_mlp": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ggcn_gate_mlp_save": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp]),
+    "ggcn_gate_mlp_backward": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, c_i64, c_vp, c_i64, c_vp]),
     "ggcn_scores_head": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32,
                                  c_i32, c_i32, c_vp, c_i64, c_vp, c_vp]),
     "ggcn_scores_head_backward": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,

@@ -7,8 +7,9 @@ Sub-module names, shapes and construction order follow the reference, so a refer
 way.  ``forward(inputs) -> (logits, gate_reg, kl_reg, scores)`` like every live model of
 ``train.py:109``.  The sub-word pooling (``:600``), the gate MLPs (``:562-571``), the block (``:621-640``) and the
 ``scores`` / ``kl`` head (``:645-648``) run on the HIP path in inference; under autograd the gate MLPs and the
-head keep the reference's PyTorch ops (they are trained; ``opt.ggcn_head_backward`` puts the head on its HIP forward and
-one-launch backward), and with dropout active the gates are dropped per
+head keep the reference's PyTorch ops by default (they are trained; ``opt.ggcn_head_backward`` puts the head, and
+``opt.ggcn_gate_backward`` the gate MLPs, on their HIP forward and one-launch backward), and with dropout active the gates
+are dropped per
 token like the reference's (``:621-625``).  BERT, the BiLSTM and ``dense`` stay PyTorch-ROCm.
 """
 import os
@@ -83,6 +84,17 @@ class GatedGCNEventDetector(nn.Module):
         # in the last bits (both inside the gradient gate).
         self.head_backward = (bool(getattr(opt, "ggcn_head_backward", False))
                               or os.environ.get("GGCN_HEAD_BACKWARD", "0") == "1")
+        # training: the gate MLPs (:562-571) as the differentiable ``gate_mlps`` (the saving forward launch, one backward launch
+        # + the fixed-order weight products) instead of the two nn.Sequential.  Off by default, for the same reason.
+        self.gate_backward = (bool(getattr(opt, "ggcn_gate_backward", False))
+                              or os.environ.get("GGCN_GATE_BACKWARD", "0") == "1")
+
+    def _training_gates(self, aspect):
+        """``gate1(aspect), gate2(aspect)`` of the training branches: the two nn.Sequential (under bf16 autocast they give bf16)
+        or, with ``gate_backward``, the differentiable ``gate_mlps`` (float32 ``[B,H]``)."""
+        if self.gate_backward:
+            return gate_mlps(aspect, self.gate1, self.gate2)
+        return self.gate1(aspect), self.gate2(aspect)
 
     F16_RANGE_MARGIN = 32752.0   # half of fp16's largest finite value
     F16MX8_WINDOW = 448.0        # include/ggcn.h GGCN_RANGE_WINDOW: beyond it an activation's fp8 correction saturates
@@ -216,7 +228,7 @@ class GatedGCNEventDetector(nn.Module):
             p = float(self.dropout.p)
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())          # CPU generator: follows torch.manual_seed, no device sync
             # (under bf16 autocast the gate MLPs give bf16: the layers take float32 gates, the cast is differentiable)
-            g1, g2 = self.gate1(aspect).float().contiguous(), self.gate2(aspect).float().contiguous()
+            g1, g2 = (g.float().contiguous() for g in self._training_gates(aspect))
             gcn1, x1, y1 = self.gc1.forward_gated(x, csr, pool_gate_a=g1, pool_gate_b=g2, want_pool_a=True, want_pool_b=True,
                                                   dropout=(p, seed, (0, 1, 2)))          # :626-636
             xy = (x1 * y1).sum(1).mean()                                               # :638
@@ -227,8 +239,9 @@ class GatedGCNEventDetector(nn.Module):
         elif dropping:
             # ---- a layer off the one-launch path (weighted adjacency without ``weighted_dropout``, > 256 nodes, ...): gating, dropout and the pools as the reference's own
             # ops around the two HIP layers (three [B,T,H] temporaries) ----
-            gate1 = self.dropout(self.gate1(aspect)[:, None, :].expand(-1, T, -1))     # :621-624 (repeat, then dropout)
-            gate2 = self.dropout(self.gate2(aspect)[:, None, :].expand(-1, T, -1))
+            g1, g2 = self._training_gates(aspect)
+            gate1 = self.dropout(g1[:, None, :].expand(-1, T, -1))                     # :621-624 (repeat, then dropout)
+            gate2 = self.dropout(g2[:, None, :].expand(-1, T, -1))
             gcn1 = self.gc1(x, adj)                                                    # :626
             x1 = torch.max(gcn1 * gate1, 1)[0]                                         # :627-635
             y1 = torch.max(gcn1 * gate2, 1)[0]                                         # :631-636
@@ -238,8 +251,7 @@ class GatedGCNEventDetector(nn.Module):
             if pooled is not None and not v54:
                 self.dropout(pooled)                                                   # :641 (unused; keeps the RNG stream)
         else:
-            gate1 = self.gate1(aspect)                                                 # dropout is the identity here
-            gate2 = self.gate2(aspect)
+            gate1, gate2 = self._training_gates(aspect)                                # dropout is the identity here
             # (under bf16 autocast the gate MLPs give bf16: the block takes float32 gates, the cast is differentiable)
             r = gated_gcn_block(x, adj, gate1.float().contiguous(), gate2.float().contiguous(), self.gc1, self.gc2)   # :626-640
             xy, xg, out = r["xy"], r["x"], r["out"]

@@ -591,6 +591,23 @@ int ggcn_gate_mlp(const float *aspect, int64_t lda, int B, int H, const float *w
     return gate_mlp(aspect, lda, B, H, w1t_a, b1_a, w2t_a, b2_a, gate_a, w1t_b, b1_b, w2t_b, b2_b, gate_b, as_stream(stream));
 }
 
+int ggcn_gate_mlp_save(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a,
+                       const float *w2t_a, const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b,
+                       const float *w2t_b, const float *b2_b, float *gate_b, float *hid_a, float *hid_b, ggcn_stream_t stream)
+{
+    return gate_mlp_save(aspect, lda, B, H, w1t_a, b1_a, w2t_a, b2_a, gate_a, w1t_b, b1_b, w2t_b, b2_b, gate_b, hid_a, hid_b,
+                         as_stream(stream));
+}
+
+int ggcn_gate_mlp_backward(const float *aspect, int64_t lda, int B, int H, const float *w1_a, const float *w2_a, const float *hid_a,
+                           const float *gate_a, const float *d_gate_a, const float *w1_b, const float *w2_b, const float *hid_b,
+                           const float *gate_b, const float *d_gate_b, float *d_aspect, int64_t ldda, float *Z, int64_t ldz,
+                           ggcn_stream_t stream)
+{
+    return gate_mlp_backward(aspect, lda, B, H, w1_a, w2_a, hid_a, gate_a, d_gate_a, w1_b, w2_b, hid_b, gate_b, d_gate_b, d_aspect, ldda,
+                             Z, ldz, as_stream(stream));
+}
+
 int ggcn_scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
                      const float *fc_weight, int64_t ldw, const float *fc_bias, const float *dist, int64_t ldd, int B,
                      int T, int H, int C, float *scores, int64_t ld_scores, float *kl_part, ggcn_stream_t stream)

@@ -192,6 +192,12 @@ int transpose_f32(const float *W, int rows, int cols, int64_t ldw, float *Wt, hi
 int gate_mlp(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a, const float *w2t_a,
              const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b, const float *w2t_b,
              const float *b2_b, float *gate_b, hipStream_t st);
+int gate_mlp_save(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a, const float *w2t_a,
+                  const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b, const float *w2t_b,
+                  const float *b2_b, float *gate_b, float *hid_a, float *hid_b, hipStream_t st);
+int gate_mlp_backward(const float *aspect, int64_t lda, int B, int H, const float *w1_a, const float *w2_a, const float *hid_a,
+                      const float *gate_a, const float *d_gate_a, const float *w1_b, const float *w2_b, const float *hid_b,
+                      const float *gate_b, const float *d_gate_b, float *d_aspect, int64_t ldda, float *Z, int64_t ldz, hipStream_t st);
 int scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
                 const float *fcw, int64_t ldw, const float *fcb, const float *dist, int64_t ldd, int B, int T, int H,
                 int C, float *scores, int64_t lds_, float *kl_part, hipStream_t st);

@@ -12,7 +12,9 @@
 // -- one H-vector and one scalar per sentence, then one dot product per token: x is read once (HBM-bound).
 // Both kernels use plain fp32 FMA chains (exact fp32, no matrix cores: 0.1-0.3 GFLOP at the reference's
 // batch of 256 sentences).  The scores / kl head also has its backward here, for training through it: one launch per call
-// (scores_head_backward_kernel) and a fixed-order weight product (head_dweight_*_kernel).
+// (scores_head_backward_kernel) and a fixed-order weight product (head_dweight_*_kernel).  So have the gate MLPs: the forward
+// in a form that keeps the hidden activations (gate_mlp_kernel<true>) and one backward launch (gate_mlp_backward_kernel) that
+// leaves the operands of the library's own weight products.
 #include "common.h"
 
 namespace ggcn {
@@ -37,11 +39,14 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict_
 struct GateParams {
     const float *w1t, *b1, *w2t, *b2;   // transposed weights [in=H][out=H], biases [H]
     float *out;                         // [B,H]
+    float *hid;                         // [B,H]: the hidden sigmoid, kept for the backward (SAVE form only)
 };
 
 constexpr int kGateRows = 8;   // sentences per workgroup
 
-// grid (ceil(B / 8), 2 gates); dynamic LDS: 2 * 8 * H floats
+// grid (ceil(B / 8), 2 gates); dynamic LDS: 2 * 8 * H floats.  SAVE (ggcn_gate_mlp_save, the forward under autograd): the
+// hidden activations h also go to memory; the gates are the bits of the plain form.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void gate_mlp_kernel(const float *__restrict__ aspect, int64_t lda, int B, int H,
                                                        GateParams ga, GateParams gb)
 {
@@ -70,7 +75,11 @@ __global__ __launch_bounds__(256) void gate_mlp_kernel(const float *__restrict__
             const float bj = bias ? bias[j] : 0.0f;
             if (layer == 0) {
 #pragma unroll
-                for (int r = 0; r < kGateRows; ++r) h[r * H + j] = sigmoidf(acc[r] + bj);
+                for (int r = 0; r < kGateRows; ++r) {
+                    const float hv = sigmoidf(acc[r] + bj);
+                    h[r * H + j] = hv;
+                    if (SAVE && r < nr) gp.hid[(int64_t)(r0 + r) * H + j] = hv;
+                }
             } else {
 #pragma unroll
                 for (int r = 0; r < kGateRows; ++r)
@@ -78,6 +87,157 @@ __global__ __launch_bounds__(256) void gate_mlp_kernel(const float *__restrict__
             }
         }
         __syncthreads();
+    }
+}
+
+// ---- backward of the gate MLPs (training through bert_amir5.py:562-571) ----------------------------------------------------
+// Per gate, with s = sigmoid(a), h = sigmoid(s.W1^T + b1), g = sigmoid(h.W2^T + b2) and the incoming dG [B,H]:
+//     dz2 = dG * g(1-g)      dh = dz2.W2      dz1 = dh * h(1-h)      ds = dz1.W1      da = (ds_A + ds_B) * s(1-s)
+// h and g are the forward's stored float32 values (ggcn_gate_mlp_save); s is recomputed.  W1, W2 are read in nn.Linear's own
+// [out][in] layout: the products run over the rows j of W, so a thread that owns column k reads one coalesced row piece per j.
+// One workgroup per 8 sentences, gate A and then gate B, like the forward; two 8 x H LDS buffers (dz2, then dz1), 8
+// accumulators per column and all of a thread's columns k = tid, tid + 256, ... in one walk over j (each LDS read serves
+// them all), exact fp32 FMA chains with j ascending.  After gate A a thread stores its ds element into d_aspect;
+// after gate B the same thread reads that element again, adds to it and applies s(1-s): no atomics, the same bits on every
+// call.  Z [B, ldz] receives what the weight products read: dz1_A | dz1_B | dz2_A | dz2_B | s, each group Hp = H rounded up
+// to 4 columns wide (the up to 3 columns behind a group's H are written as zeros); a gate without an incoming gradient
+// contributes nothing to d_aspect and its groups are zeros.
+struct GateGrad {
+    const float *w1, *w2;             // nn.Linear weights [out=H][in=H], contiguous
+    const float *hid, *gate, *dg;     // [B,H] contiguous; dg NULL: no gradient reached this gate
+};
+
+// acc[c][r] += sum_j in[r][j] * W[j][k_c], j ascending, for the thread's NC columns k_c = tid + 256 c at once: one LDS
+// broadcast read of in[r][j] serves all of them (a column past H reads column 0 and is dropped by the caller).
+// VEC: H % 4 == 0, four j per step through one 16-byte LDS read per row; the order of every sum is the scalar loop's.
+template <bool VEC, int NC>
+__device__ __forceinline__ void gate_rows_times_columns(const float *in, const float *__restrict__ W, int H, int tid,
+                                                        float (&acc)[NC][kGateRows])
+{
+    int kc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        kc[c] = tid + 256 * c < H ? tid + 256 * c : 0;
+#pragma unroll
+        for (int r = 0; r < kGateRows; ++r) acc[c][r] = 0.0f;
+    }
+    if (VEC) {
+        for (int j = 0; j < H; j += 4) {
+            float w[NC][4];
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) w[c][q] = W[(int64_t)(j + q) * H + kc[c]];
+#pragma unroll
+            for (int r = 0; r < kGateRows; ++r) {
+                const float4 v = *reinterpret_cast<const float4 *>(in + r * H + j);
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    acc[c][r] = fmaf(v.x, w[c][0], acc[c][r]); acc[c][r] = fmaf(v.y, w[c][1], acc[c][r]);
+                    acc[c][r] = fmaf(v.z, w[c][2], acc[c][r]); acc[c][r] = fmaf(v.w, w[c][3], acc[c][r]);
+                }
+            }
+        }
+    } else {
+#pragma unroll 2
+        for (int j = 0; j < H; ++j) {
+            float w[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) w[c] = W[(int64_t)j * H + kc[c]];
+#pragma unroll
+            for (int r = 0; r < kGateRows; ++r) {
+                const float v = in[r * H + j];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) acc[c][r] = fmaf(v, w[c], acc[c][r]);
+            }
+        }
+    }
+}
+
+// grid ceil(B / 8); dynamic LDS: 2 * 8 * H floats; NC = ceil(H / 256) columns per thread (H <= 1024: at most 4)
+template <bool VEC, int NC>
+__global__ __launch_bounds__(256) void gate_mlp_backward_kernel(const float *__restrict__ aspect, int64_t lda, int B, int H, GateGrad ga,
+                                                                GateGrad gb, float *d_aspect, int64_t ldda, float *__restrict__ Z,
+                                                                int64_t ldz)
+{
+    extern __shared__ __attribute__((aligned(16))) float gate_bwd_lds[];
+    float *dz2 = gate_bwd_lds, *dz1 = gate_bwd_lds + kGateRows * H;
+    const int tid = threadIdx.x, Hp = (H + 3) & ~3;
+    const int r0 = blockIdx.x * kGateRows;
+    const int nr = B - r0 < kGateRows ? B - r0 : kGateRows;
+    if (Z) {
+        for (int i = tid; i < nr * H; i += 256) {                  // the s group: the other operand of dW1 = dz1^T.s
+            const int r = i / H, k = i - r * H;
+            Z[(int64_t)(r0 + r) * ldz + 4 * Hp + k] = sigmoidf(aspect[(int64_t)(r0 + r) * lda + k]);
+        }
+        const int pad = Hp - H;                                    // 0..3 columns behind each of the five groups
+        for (int i = tid; i < nr * 5 * pad; i += 256) {
+            const int r = i / (5 * pad), q = i - r * 5 * pad, g = q / pad;
+            Z[(int64_t)(r0 + r) * ldz + g * Hp + H + (q - g * pad)] = 0.0f;
+        }
+    }
+    const bool both = ga.dg && gb.dg;
+    for (int gi = 0; gi < 2; ++gi) {
+        const GateGrad gp = gi == 0 ? ga : gb;
+        float *z1 = Z ? Z + gi * Hp : nullptr, *z2 = Z ? Z + (2 + gi) * Hp : nullptr;
+        if (!gp.dg) {                                              // (kernel-uniform)
+            if (Z)
+                for (int i = tid; i < nr * H; i += 256) {
+                    const int r = i / H, k = i - r * H;
+                    z1[(int64_t)(r0 + r) * ldz + k] = 0.0f;
+                    z2[(int64_t)(r0 + r) * ldz + k] = 0.0f;
+                }
+            continue;
+        }
+        for (int i = tid; i < kGateRows * H; i += 256) {           // dz2 = dG * g(1-g)
+            const int r = i / H, k = i - r * H;
+            float v = 0.0f;
+            if (r < nr) {
+                const int64_t at = (int64_t)(r0 + r) * H + k;
+                const float g = gp.gate[at];
+                v = gp.dg[at] * (g * (1.0f - g));
+                if (z2) z2[(int64_t)(r0 + r) * ldz + k] = v;
+            }
+            dz2[i] = v;
+        }
+        __syncthreads();
+        float acc[NC][kGateRows];
+        gate_rows_times_columns<VEC, NC>(dz2, gp.w2, H, tid, acc);       // dz1 = (dz2.W2) * h(1-h)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int k = tid + 256 * c;
+            if (k >= H) continue;
+#pragma unroll
+            for (int r = 0; r < kGateRows; ++r) {
+                float v = 0.0f;
+                if (r < nr) {
+                    const float h = gp.hid[(int64_t)(r0 + r) * H + k];
+                    v = acc[c][r] * (h * (1.0f - h));
+                    if (z1) z1[(int64_t)(r0 + r) * ldz + k] = v;
+                }
+                dz1[r * H + k] = v;
+            }
+        }
+        __syncthreads();   // (also: nobody still reads dz2 when the next gate overwrites it, nor dz1 one barrier later)
+        if (!d_aspect) continue;
+        gate_rows_times_columns<VEC, NC>(dz1, gp.w1, H, tid, acc);       // ds = dz1.W1; d a = (ds_A + ds_B) * s(1-s)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int k = tid + 256 * c;
+            if (k >= H) continue;
+#pragma unroll
+            for (int r = 0; r < kGateRows; ++r) {
+                if (r >= nr) continue;
+                float *p = d_aspect + (int64_t)(r0 + r) * ldda + k;
+                if (both && gi == 0) {
+                    *p = acc[c][r];                                // gate A's share, picked up again by this thread after gate B
+                } else {
+                    const float ds = both ? *p + acc[c][r] : acc[c][r];
+                    const float s = sigmoidf(aspect[(int64_t)(r0 + r) * lda + k]);
+                    *p = ds * (s * (1.0f - s));
+                }
+            }
+        }
     }
 }
 
@@ -433,20 +593,67 @@ int transpose_f32(const float *W, int rows, int cols, int64_t ldw, float *Wt, hi
     return check_launch("ggcn_transpose");
 }
 
+// ggcn_gate_mlp (save = false) and ggcn_gate_mlp_save: the same checks under the entry's own name, the same launch geometry
+static int gate_mlp_launch(const char *who, bool save, const float *aspect, int64_t lda, int B, int H, const float *w1t_a,
+                           const float *b1_a, const float *w2t_a, const float *b2_a, float *gate_a, const float *w1t_b,
+                           const float *b1_b, const float *w2t_b, const float *b2_b, float *gate_b, float *hid_a, float *hid_b,
+                           hipStream_t st)
+{
+    if (!aspect || !w1t_a || !w2t_a || !gate_a || (save && !hid_a)) return fail(GGCN_EINVAL, "%s: null pointer", who);
+    if ((gate_b != nullptr) != (w1t_b != nullptr && w2t_b != nullptr))
+        return fail(GGCN_EINVAL, "%s: the second gate needs both of its weights and its output (or none)", who);
+    if (save && (gate_b != nullptr) != (hid_b != nullptr))
+        return fail(GGCN_EINVAL, "%s: hid_b goes with the second gate", who);
+    if (B <= 0 || H <= 0 || lda < H) return fail(GGCN_EINVAL, "%s: B=%d H=%d lda=%lld", who, B, H, (long long)lda);
+    const size_t lds = (size_t)2 * kGateRows * H * sizeof(float);
+    if (lds > 64 * 1024) return fail(GGCN_EUNSUPPORTED, "%s: H=%d needs more than 64 KiB of LDS", who, H);
+    GateParams ga{w1t_a, b1_a, w2t_a, b2_a, gate_a, hid_a}, gb{w1t_b, b1_b, w2t_b, b2_b, gate_b, hid_b};
+    hipLaunchKernelGGL(save ? gate_mlp_kernel<true> : gate_mlp_kernel<false>,
+                       dim3((unsigned)((B + kGateRows - 1) / kGateRows), gate_b ? 2u : 1u), dim3(256), lds, st, aspect, lda, B, H, ga, gb);
+    return check_launch(who);
+}
+
 int gate_mlp(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a, const float *w2t_a,
              const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b, const float *w2t_b,
              const float *b2_b, float *gate_b, hipStream_t st)
 {
-    if (!aspect || !w1t_a || !w2t_a || !gate_a) return fail(GGCN_EINVAL, "ggcn_gate_mlp: null pointer");
-    if ((gate_b != nullptr) != (w1t_b != nullptr && w2t_b != nullptr))
-        return fail(GGCN_EINVAL, "ggcn_gate_mlp: the second gate needs both of its weights and its output (or none)");
-    if (B <= 0 || H <= 0 || lda < H) return fail(GGCN_EINVAL, "ggcn_gate_mlp: B=%d H=%d lda=%lld", B, H, (long long)lda);
+    return gate_mlp_launch("ggcn_gate_mlp", false, aspect, lda, B, H, w1t_a, b1_a, w2t_a, b2_a, gate_a, w1t_b, b1_b, w2t_b, b2_b, gate_b,
+                           nullptr, nullptr, st);
+}
+
+int gate_mlp_save(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a, const float *w2t_a,
+                  const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b, const float *w2t_b,
+                  const float *b2_b, float *gate_b, float *hid_a, float *hid_b, hipStream_t st)
+{
+    return gate_mlp_launch("ggcn_gate_mlp_save", true, aspect, lda, B, H, w1t_a, b1_a, w2t_a, b2_a, gate_a, w1t_b, b1_b, w2t_b, b2_b,
+                           gate_b, hid_a, hid_b, st);
+}
+
+int gate_mlp_backward(const float *aspect, int64_t lda, int B, int H, const float *w1_a, const float *w2_a, const float *hid_a,
+                      const float *gate_a, const float *d_gate_a, const float *w1_b, const float *w2_b, const float *hid_b,
+                      const float *gate_b, const float *d_gate_b, float *d_aspect, int64_t ldda, float *Z, int64_t ldz, hipStream_t st)
+{
+    if (!aspect) return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: null pointer");
+    if (!d_gate_a && !d_gate_b) return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: no incoming gradient (both d_gate are NULL)");
+    if (!d_aspect && !Z) return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: nothing to compute (d_aspect and Z are NULL)");
+    if ((d_gate_a && (!w2_a || !hid_a || !gate_a || (d_aspect && !w1_a))) || (d_gate_b && (!w2_b || !hid_b || !gate_b || (d_aspect && !w1_b))))
+        return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: a gate with a gradient needs its weights, hid and gate");
+    if (B <= 0 || H <= 0) return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: B=%d H=%d", B, H);
+    const int64_t Hp = ((int64_t)H + 3) & ~(int64_t)3;
+    if (lda < H || (d_aspect && ldda < H) || (Z && ldz < 5 * Hp))
+        return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: leading dimension too small");
     const size_t lds = (size_t)2 * kGateRows * H * sizeof(float);
-    if (lds > 64 * 1024) return fail(GGCN_EUNSUPPORTED, "ggcn_gate_mlp: H=%d needs more than 64 KiB of LDS", H);
-    GateParams ga{w1t_a, b1_a, w2t_a, b2_a, gate_a}, gb{w1t_b, b1_b, w2t_b, b2_b, gate_b};
-    hipLaunchKernelGGL(gate_mlp_kernel, dim3((unsigned)((B + kGateRows - 1) / kGateRows), gate_b ? 2u : 1u), dim3(256), lds, st,
-                       aspect, lda, B, H, ga, gb);
-    return check_launch("ggcn_gate_mlp");
+    if (lds > 64 * 1024) return fail(GGCN_EUNSUPPORTED, "ggcn_gate_mlp_backward: H=%d needs more than 64 KiB of LDS", H);
+    GateGrad ga{w1_a, w2_a, hid_a, gate_a, d_gate_a}, gb{w1_b, w2_b, hid_b, gate_b, d_gate_b};
+    const bool vec = (H & 3) == 0;
+    const int nc = (H + 255) / 256;   // 1..4 under the LDS bound
+    auto kernel = nc == 1 ? (vec ? gate_mlp_backward_kernel<true, 1> : gate_mlp_backward_kernel<false, 1>)
+                : nc == 2 ? (vec ? gate_mlp_backward_kernel<true, 2> : gate_mlp_backward_kernel<false, 2>)
+                : nc == 3 ? (vec ? gate_mlp_backward_kernel<true, 3> : gate_mlp_backward_kernel<false, 3>)
+                          : (vec ? gate_mlp_backward_kernel<true, 4> : gate_mlp_backward_kernel<false, 4>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((B + kGateRows - 1) / kGateRows)), dim3(256), lds, st, aspect, lda, B, H, ga, gb, d_aspect,
+                       ldda, Z, ldz);
+    return check_launch("ggcn_gate_mlp_backward");
 }
 
 int scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,

@@ -5,11 +5,13 @@
 * ``scores_and_kl`` -- ``models/bert_amir5.py:645-648``: the ``fc`` / ``scores`` / ``kl`` head without its
   ``[B,T,2H]`` concat and ``[B,T,C]`` product.
 
-``gate_mlps`` is inference only (``torch.no_grad`` or no parameter needing a gradient): under autograd the classifier
-keeps the reference's PyTorch ops for the ``[B,H]`` gate MLPs.  ``scores_and_kl`` is differentiable: when a gradient is wanted
-it runs as ``_ScoresAndKl``, whose backward is one launch (``ggcn_scores_head_backward``) plus a fixed-order weight product
-(``ggcn_scores_head_dweight``).  The classifier takes it in training with ``opt.ggcn_head_backward`` / ``GGCN_HEAD_BACKWARD=1``
-(off by default: the fused sums differ from the PyTorch ops' in the last bits).
+Both are differentiable.  ``scores_and_kl``: when a gradient is wanted it runs as ``_ScoresAndKl``, whose backward is one launch
+(``ggcn_scores_head_backward``) plus a fixed-order weight product (``ggcn_scores_head_dweight``).  ``gate_mlps``: when ``aspect``
+or a gate parameter needs a gradient it runs as ``_GateMlps`` -- the forward launch in its saving form (``ggcn_gate_mlp_save``),
+a backward of one launch (``ggcn_gate_mlp_backward``) plus the library's fixed-order ``ggcn_dweight`` / ``ggcn_colsum`` for the
+parameters that train.  Without a gradient to compute both take the inference path they always took, bit for bit.  The
+classifier takes them in training with ``opt.ggcn_head_backward`` / ``GGCN_HEAD_BACKWARD=1`` and ``opt.ggcn_gate_backward`` /
+``GGCN_GATE_BACKWARD=1`` (both off by default: the fused sums differ from the PyTorch ops' in the last bits).
 """
 import torch
 
@@ -45,9 +47,111 @@ def _gate_linears(seq):
     return mods[1], mods[3]
 
 
+class _GateMlps(torch.autograd.Function):
+    """``gate_mlps`` under autograd: the forward is ``ggcn_gate_mlp_save`` (the gates are the bits of a ``no_grad`` call; the
+    hidden activations are kept), the backward one ``ggcn_gate_mlp_backward`` launch and, for the parameters that train, the
+    library's fixed-order products on what that launch left in ``Z``: ``ggcn_dweight`` (fp32) for ``dW1`` of both gates at
+    once and for each ``dW2``, one ``ggcn_colsum`` for the four bias gradients."""
+
+    @staticmethod
+    def forward(ctx, aspect, w1a, b1a, w2a, b2a, w1b, b1b, w2b, b2b, linears):
+        ctx.set_materialize_grads(False)     # a loss on one gate alone hands the launch a NULL, not zeros
+        lib = _capi.load_library()
+        a = aspect.detach()
+        if a.stride(1) != 1:
+            a = a.contiguous()
+        B, H = a.shape
+        dev = a.device
+        ptr = _capi.ptr
+        with torch.cuda.device(dev):
+            st = _capi.stream_of(dev)
+            g1, g2, hid_a, hid_b = (torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(4))
+            wt = [_transposed(lin, lib, st) for lin in linears]
+            bias = [None if b is None else b.detach() for b in (b1a, b2a, b1b, b2b)]
+            _capi.check(lib.ggcn_gate_mlp_save(ptr(a), a.stride(0), B, H, ptr(wt[0]), ptr(bias[0]), ptr(wt[1]), ptr(bias[1]), ptr(g1),
+                                               ptr(wt[2]), ptr(bias[2]), ptr(wt[3]), ptr(bias[3]), ptr(g2), ptr(hid_a), ptr(hid_b), st),
+                        "ggcn_gate_mlp_save")
+        weights = [w.detach() if w.is_contiguous() else w.detach().contiguous() for w in (w1a, w2a, w1b, w2b)]
+        ctx.save_for_backward(a, *weights, hid_a, hid_b, g1, g2)
+        ctx.has_bias = tuple(b is not None for b in (b1a, b2a, b1b, b2b))
+        return g1, g2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dg1, dg2):
+        a, w1a, w2a, w1b, w2b, hid_a, hid_b, g1, g2 = ctx.saved_tensors
+        none = (None,) * 10
+        if dg1 is None and dg2 is None:
+            return none
+        B, H = a.shape
+        Hp = (H + 3) & ~3
+        need_a = ctx.needs_input_grad[0]
+        # (w1, b1, w2, b2) of gate A, then of gate B; a gate that no gradient reached gets None (zero) for its parameters
+        live = (dg1 is not None,) * 4 + (dg2 is not None,) * 4
+        need = [n and l for n, l in zip(ctx.needs_input_grad[1:9], live)]
+        need = [n and (i % 2 == 0 or ctx.has_bias[i // 2]) for i, n in enumerate(need)]
+        if not need_a and not any(need):
+            return none
+        dg1, dg2 = (None if g is None else g.float().contiguous() for g in (dg1, dg2))
+        lib = _capi.load_library()
+        dev = a.device
+        ptr = _capi.ptr
+        fp32 = _capi.PREC["fp32"]
+        with torch.cuda.device(dev):
+            st = _capi.stream_of(dev)
+            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)   # noqa: E731
+            da = new(B, H) if need_a else None
+            Z = new(B, 5 * Hp) if any(need) else None
+            ldz = 5 * Hp
+            _capi.check(lib.ggcn_gate_mlp_backward(ptr(a), a.stride(0), B, H, ptr(w1a), ptr(w2a), ptr(hid_a), ptr(g1), ptr(dg1),
+                                                   ptr(w1b), ptr(w2b), ptr(hid_b), ptr(g2), ptr(dg2), ptr(da), H, ptr(Z), ldz, st),
+                        "ggcn_gate_mlp_backward")
+
+            def product(x_col, K, other, ld_other):
+                """``Z[:, x_col : x_col + K]^T . other`` -> ``[K, H]``, rows = the Linear's outputs: nn.Linear's layout."""
+                dw = new(K, H)
+                ws = torch.empty(max(16, lib.ggcn_dweight_workspace_bytes(B, K, H, fp32)), dtype=torch.uint8, device=dev)
+                _capi.check(lib.ggcn_dweight(ptr(Z[:, x_col:]), ldz, ptr(other), ld_other, B, K, H, ptr(dw), H, fp32, ptr(ws), st),
+                            "ggcn_dweight")
+                return dw
+
+            grads = [None] * 8
+            s = Z[:, 4 * Hp:] if Z is not None else None
+            if need[0] and need[4] and Hp == H:          # [dz1_A | dz1_B]^T . s: dW1_A over dW1_B in one product
+                dw1 = product(0, 2 * H, s, ldz)
+                grads[0], grads[4] = dw1[:H], dw1[H:]
+            else:
+                for g in (0, 1):
+                    if need[4 * g]:
+                        grads[4 * g] = product(g * Hp, H, s, ldz)
+            for g, hid in ((0, hid_a), (1, hid_b)):      # dz2^T . hid
+                if need[4 * g + 2]:
+                    grads[4 * g + 2] = product((2 + g) * Hp, H, hid, H)
+            if need[1] or need[3] or need[5] or need[7]:
+                db = new(4 * Hp)
+                ws = torch.empty(lib.ggcn_colsum_workspace_bytes(4 * Hp), dtype=torch.uint8, device=dev)
+                _capi.check(lib.ggcn_colsum(ptr(Z), ldz, B, 4 * Hp, ptr(db), ptr(ws), st), "ggcn_colsum")
+                for i, group in ((1, 0), (3, 2), (5, 1), (7, 3)):    # Z's groups: dz1_A | dz1_B | dz2_A | dz2_B
+                    if need[i]:
+                        grads[i] = db[group * Hp:group * Hp + H]
+        return (da, *grads, None)
+
+
 def gate_mlps(aspect, gate1_seq, gate2_seq):
     """``gate1(aspect), gate2(aspect)`` -> two contiguous ``[B,H]`` float32 tensors, one launch.  A bfloat16 ``aspect``
-    (the BiLSTM under bf16 autocast) is taken as float32 here: [B,H], negligible next to the block."""
+    (the BiLSTM under bf16 autocast) is taken as float32 here: [B,H], negligible next to the block.
+
+    Differentiable: with grad enabled and ``aspect`` or any of the eight parameters requiring a gradient the call goes through
+    ``_GateMlps`` -- the forward launch in its saving form (``ggcn_gate_mlp_save``: the same gate bits as under ``no_grad``,
+    the hidden activations kept), and a backward of one launch (``ggcn_gate_mlp_backward``) plus, for the parameters that
+    train, three ``ggcn_dweight`` and one ``ggcn_colsum`` on its ``Z`` output: five calls against about twenty PyTorch
+    launches.  The same ``Sequential`` may be passed for both gates (autograd adds the two gradients); a gate that no gradient
+    reaches gets ``None`` for its parameters.  The classifier takes it in training with ``opt.ggcn_gate_backward`` /
+    ``GGCN_GATE_BACKWARD=1``.  Forward + backward of both gate MLPs alone against the two ``nn.Sequential``
+    (``tools/gate_backward_timing.py``, MI355X; ``profiles/gate_backward_timing.txt``; the weights updated every step, so four
+    ``ggcn_transpose`` per step are included): 360 against 861 us per step at 256 x 256 (23 against 38 device kernels), but 3183
+    against 775 us at 4096 x 768 -- a negative result there: 2290 us of it is the exact-fp32 forward launch (the inference
+    kernel, unchanged), 503 us the backward launch, and rocBLAS does the same products on the matrix cores."""
     if isinstance(aspect, torch.Tensor) and aspect.dtype == torch.bfloat16:
         aspect = aspect.float()
     if not (aspect.is_cuda and aspect.dtype == torch.float32 and aspect.dim() == 2):
@@ -59,6 +163,10 @@ def gate_mlps(aspect, gate1_seq, gate2_seq):
     for lin in (la1, la2, lb1, lb2):
         if lin.in_features != H or lin.out_features != H:
             raise RuntimeError("gate linears must be %d -> %d" % (H, H))
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in
+                                       (aspect,) + tuple(p for lin in (la1, la2, lb1, lb2) for p in (lin.weight, lin.bias))):
+        return _GateMlps.apply(aspect, la1.weight, la1.bias, la2.weight, la2.bias, lb1.weight, lb1.bias, lb2.weight, lb2.bias,
+                               (la1, la2, lb1, lb2))
     a = aspect if aspect.stride(1) == 1 else aspect.contiguous()
     dev = aspect.device
     with torch.cuda.device(dev):

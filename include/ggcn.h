@@ -592,6 +592,35 @@ int ggcn_gate_mlp(const float *aspect, int64_t lda, int B, int H,
                   const float *w1t_b, const float *b1_b, const float *w2t_b, const float *b2_b, float *gate_b,
                   ggcn_stream_t stream);
 
+/* ---- the gate MLPs under autograd: saving forward, backward in one launch (training through models/bert_amir5.py:562-571) ----
+ * ggcn_gate_mlp_save: ggcn_gate_mlp's launch and arguments, plus hid_a, hid_b [B,H] contiguous, which receive the hidden
+ * activations h = Sigmoid(Linear1(Sigmoid(aspect))).  The gates are the bits ggcn_gate_mlp writes.  The refusals are
+ * ggcn_gate_mlp's, plus a NULL hid_a (hid_b goes with the second gate: both NULL or neither).
+ *
+ * ggcn_gate_mlp_backward: per gate, with s = Sigmoid(aspect), the saved hid = h and gate = g, and d_gate = dG [B,H]:
+ *     dz2 = dG * g(1-g)     dh = dz2.W2     dz1 = dh * h(1-h)     ds = dz1.W1
+ *     d_aspect = (ds_A + ds_B) * s(1-s)     [B, ldda]; gate A first, then gate B; NULL: the W1 pass is skipped
+ * w1_*, w2_* are the nn.Linear weights AS THEY LIE, [out][in] = [H,H] contiguous (no transposed copy); hid_*, gate_*, d_gate_*
+ * are [B,H] contiguous.  g(1-g) and h(1-h) are taken from the stored float32 values.  A NULL d_gate_* means that gate
+ * contributes nothing to d_aspect (its other pointers are not read); both NULL is refused.  w1_* is read only with d_aspect.
+ * Z [B, ldz] (NULL: no weight or bias trains) receives what the weight products read, five column groups that each start at a
+ * multiple of Hp = (H + 3) & ~3:   dz1_A | dz1_B | dz2_A | dz2_B | s   (ldz >= 5 Hp; the Hp - H columns behind each group are
+ * written as zeros, the groups of a gate with a NULL d_gate as zeros).  From it, with the library's fixed-order products:
+ *     dW1_A over dW1_B [2H,H] = ggcn_dweight(X = Z, K = 2 Hp, dH = Z + 4 Hp, F = H)    (Hp == H; else one call per gate, K = H)
+ *     dW2_g [H,H]  = ggcn_dweight(X = Z + (2 + g) Hp, K = H, dH = hid_g, F = H)         both already in nn.Linear layout
+ *     db1_A | db1_B | db2_A | db2_B = ggcn_colsum(Z, ldz, B, 4 Hp), each at its group's offset
+ * One workgroup of 256 threads per 8 sentences, two 8 x H LDS buffers; exact fp32 FMA chains in a fixed order, no atomics: two
+ * calls on the same inputs give the same bits.  No synchronisation.  GGCN_EUNSUPPORTED when 16 H floats exceed 64 KiB of
+ * LDS (H > 1024), as ggcn_gate_mlp. */
+int ggcn_gate_mlp_save(const float *aspect, int64_t lda, int B, int H,
+                       const float *w1t_a, const float *b1_a, const float *w2t_a, const float *b2_a, float *gate_a,
+                       const float *w1t_b, const float *b1_b, const float *w2t_b, const float *b2_b, float *gate_b,
+                       float *hid_a, float *hid_b, ggcn_stream_t stream);
+int ggcn_gate_mlp_backward(const float *aspect, int64_t lda, int B, int H,
+                           const float *w1_a, const float *w2_a, const float *hid_a, const float *gate_a, const float *d_gate_a,
+                           const float *w1_b, const float *w2_b, const float *hid_b, const float *gate_b, const float *d_gate_b,
+                           float *d_aspect, int64_t ldda, float *Z, int64_t ldz, ggcn_stream_t stream);
+
 /* ---- scores / kl head in one launch ----------------------------------------
  * Replaces models/bert_amir5.py:645-648:
  *     output_w = fc(cat[x, aspect repeated over t])       [B,T,C], fc.weight [C, 2H], fc.bias [C]
