@@ -57,9 +57,10 @@ def poisoned(nbytes, dev):
     return torch.full((max(256, int(nbytes)),), 0xFF, dtype=torch.uint8, device=dev)
 
 
-def poisoned_rows(dev, rows, ld, guard):
-    """``rows`` x ``ld`` floats of NaN between two guard bands of ``guard`` NaN: ``(whole buffer, the view handed to the library)``."""
-    buf = torch.full((rows * ld + 2 * guard,), NAN, dtype=torch.float32, device=dev)
+def poisoned_rows(dev, rows, ld, guard, dtype=torch.float32):
+    """``rows`` x ``ld`` floats (or ``dtype``) of NaN between two guard bands of ``guard`` NaN: ``(whole buffer, the view handed to
+    the library)``."""
+    buf = torch.full((rows * ld + 2 * guard,), NAN, dtype=dtype, device=dev)
     return buf, buf[guard:guard + rows * ld].view(rows, ld)
 
 

@@ -128,6 +128,10 @@ def test_hostile_leaves_t_in_place_and_only_fill_elsewhere():
     assert ws.dtype == torch.uint8 and ws.numel() == 256 and bool((ws == 0xFF).all()) and gates.poisoned(1000, "cpu").numel() == 1000
     whole, view = gates.poisoned_rows("cpu", 3, 5, 8)
     assert whole.numel() == 31 and view.shape == (3, 5) and view.data_ptr() == whole[8:].data_ptr() and bool(torch.isnan(whole).all())
+    assert whole.dtype == torch.float32
+    whole, view = gates.poisoned_rows("cpu", 3, 5, 8, dtype=torch.float16)           # the half outputs of ggcn_aggregate_h
+    assert whole.dtype == view.dtype == torch.float16 and whole.numel() == 31 and view.data_ptr() == whole[8:].data_ptr()
+    assert bool(torch.isnan(whole).all())
 
 
 def test_statement64_without_keep_factors_is_the_same_statement_bit_for_bit():
