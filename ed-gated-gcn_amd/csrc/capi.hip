@@ -1,9 +1,12 @@
 // extern "C" surface of libggcn_hip.so -- see include/ggcn.h for the contract.
 // Argument checking lives here and in the per-kernel launchers; nothing in this
 // library allocates, frees, copies to the host or synchronises.
-#include "common.h"
+// The one-launch entries (ggcn_layer_fused*, ggcn_block_fused*, ggcn_lab_block_fused8, ggcn_debug_block_fused_stamped) check here
+// only what is their own -- the graph sizes they take, the operands only they have, what must be looked at before it narrows into a
+// field -- and write their arguments into a FusedArgs (fused_args.h) by name.  Everything else is checked once, on that description:
+// launch_fused / fused_part_checks for a layer, launch_block for the three blocks, block_fused8 for the eight-wavefront kernel.
+#include "fused_args.h"
 #include <cstdlib>
-#include "dropout_hash.h"
 
 #include <cstring>
 
@@ -37,12 +40,31 @@ int drop_entry_checks(const char *who, float p, int sel_store, int sel_a, int se
     return GGCN_OK;
 }
 
-// what the bf16 one-launch entries check alike before anything else: X's alignment, then the dropout arguments
-int bf16_entry_checks(const char *who, const void *X, float p, int sel_store, int sel_a, int sel_b)
+// the same for the one-launch entries, which hand the kernels' DropSpec on (p = 0: thr = 0, nothing is dropped)
+int entry_drop_spec(const char *who, float p, uint64_t seed, int sel_store, int sel_a, int sel_b, DropSpec &d)
 {
-    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
-    return drop_entry_checks(who, p, sel_store, sel_a, sel_b);
+    if (int rc = drop_entry_checks(who, p, sel_store, sel_a, sel_b)) return rc;
+    d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);
+    return GGCN_OK;
 }
+
+// what the one-launch layer entries check before their arguments narrow into a LayerPart (its ldo is an int)
+int layer_entry_checks(const char *who, const float *out, int64_t ldo, const float *overlap_in, const float *overlap_out)
+{
+    if ((overlap_in == nullptr) != (overlap_out == nullptr)) return fail(GGCN_EINVAL, "%s: overlap_in and overlap_out go together", who);
+    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: ldo too large", who);
+    return GGCN_OK;
+}
+
+// the same for the three blocks' two outputs
+int block_entry_checks(const char *who, const float *gcn1, int64_t ld1, const float *x_out, int64_t ld2)
+{
+    if ((gcn1 && ld1 > (int64_t)INT32_MAX) || (x_out && ld2 > (int64_t)INT32_MAX))
+        return fail(GGCN_EUNSUPPORTED, "%s: leading dimension too large", who);
+    return GGCN_OK;
+}
+
+const char *bytes(const void *p) { return static_cast<const char *>(p); }
 
 // the preamble of the four ggcn_linear* entries (`null_operand`: one of the pointers that entry needs is NULL)
 int linear_entry_checks(const char *who, bool null_operand, int64_t M, int K, int F, int64_t ldx, int64_t ldy)
@@ -123,8 +145,16 @@ int ggcn_layer_fused(const float *X, int64_t ldx, const void *wpack, const uint3
                      float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in,
                      float *overlap_out, int precision, ggcn_stream_t stream)
 {
-    return layer_fused(X, ldx, wpack, rowmask, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out,
-                       ldo, pool_a, pool_b, overlap_partial, overlap_in, overlap_out, precision, as_stream(stream));
+    const char *who = "ggcn_layer_fused";
+    if (int rc = layer_entry_checks(who, out, ldo, overlap_in, overlap_out)) return rc;
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.rowmask = rowmask; a.graph_ops = bytes(graph_ops);
+    a.ov_in = overlap_in; a.ov_out = overlap_out;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b; l.ov_partial = overlap_partial;
+    return launch_fused(who, a, precision, as_stream(stream));
 }
 
 int ggcn_layer_fused_prebias(const float *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const float *bias,
@@ -133,8 +163,17 @@ int ggcn_layer_fused_prebias(const float *X, int64_t ldx, const void *wpack, con
                              float *pool_a, float *pool_b, int precision, ggcn_stream_t stream)
 {
     if (!bias_pre) return fail(GGCN_EINVAL, "ggcn_layer_fused_prebias: null bias_pre (ggcn_layer_fused is the plain form)");
-    return layer_fused(X, ldx, wpack, rowmask, nullptr, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out,
-                       ldo, pool_a, pool_b, nullptr, nullptr, nullptr, precision, as_stream(stream), nullptr, bias_pre);
+    const char *who = "ggcn_layer_fused";   // (what this entry's shared refusals have always been reported as)
+    if (int rc = layer_entry_checks(who, out, ldo, nullptr, nullptr)) return rc;
+    if (T <= 32)
+        return fail(GGCN_EUNSUPPORTED, "ggcn_layer_fused_prebias: graphs of <= 32 nodes fold both layers in ggcn_block_fused (its eval form); bias_pre is for 33..256 nodes");
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.rowmask = rowmask;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.pre = bias_pre; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b;
+    return launch_fused(who, a, precision, as_stream(stream));
 }
 
 int ggcn_graph_operands_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane,
@@ -149,8 +188,22 @@ int ggcn_layer_fused_weighted(const float *X, int64_t ldx, const void *wpack, co
                               float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out, int precision,
                               ggcn_stream_t stream)
 {
-    return layer_fused_weighted(X, ldx, wpack, graph_opsw, bias, zero_mid, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo,
-                                pool_a, pool_b, overlap_partial, overlap_in, overlap_out, precision, as_stream(stream));
+    // gcn.py:30-45 with a real-valued adjacency for graphs of <= 32 nodes in ONE launch: the W12 column tiles' form of the block
+    // (MID epilogue: one split of `hidden`, 6 MFMAs with the hi / lo operand) on ggcn_graph_operands_weighted blocks; zero_mid is the
+    // all-zero `mid` row that form reads ([F] floats)
+    const char *who = "ggcn_layer_fused_weighted";
+    if (!graph_opsw || !zero_mid) return fail(GGCN_EINVAL, "%s: the weighted operand blocks and the zero row are required", who);
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (use ggcn_linear + ggcn_aggregate)", who, T);
+    if (precision == GGCN_PREC_F16MX6) return fail(GGCN_EUNSUPPORTED, "%s: bf16x3 or f16mx8", who);
+    if (int rc = layer_entry_checks(who, out, ldo, overlap_in, overlap_out)) return rc;
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_opsw); a.graph_ops2 = a.graph_ops;
+    a.ov_in = overlap_in; a.ov_out = overlap_out;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.mid = zero_mid; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b; l.ov_partial = overlap_partial;
+    return launch_fused(who, a, precision, as_stream(stream));
 }
 
 size_t ggcn_graph_operands_weighted_wide_bytes(int B, int T) { return graph_operands_weighted_wide_bytes(B, T); }
@@ -166,8 +219,16 @@ int ggcn_layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpac
                                    const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b, int precision,
                                    ggcn_stream_t stream)
 {
-    return layer_fused_weighted_wide(X, ldx, wpack, graph_opsww, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo,
-                                     pool_a, pool_b, precision, as_stream(stream));
+    const char *who = "ggcn_layer_fused_weighted_wide";
+    FusedArgs a = {};
+    // (LayerPart's ldo is an int)
+    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: T*ldo does not fit 32-bit offsets", who);
+    a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_opsww);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b;
+    return launch_fused_weighted_wide(who, a, precision, as_stream(stream));
 }
 
 int ggcn_layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias,
@@ -176,10 +237,23 @@ int ggcn_layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpac
                                    float *pool_b, int precision, float p, uint64_t seed, int sel_store, int sel_a, int sel_b,
                                    ggcn_stream_t stream)
 {
-    if (int rc = drop_entry_checks("ggcn_layer_fused_weighted_drop", p, sel_store, sel_a, sel_b)) return rc;
-    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);   // p = 0: thr = 0, nothing is dropped
-    return layer_fused_weighted_drop(X, ldx, wpack, graph_opsw, bias, zero_mid, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo,
-                                     pool_a, pool_b, precision, as_stream(stream), &d);
+    // ggcn_layer_fused_weighted under the gates' training-mode dropout: layer_fused_weighted_drop_kernel on the same blocks; thr = 0
+    // (p = 0) launches layer_fused_kernel's MID form -- ggcn_layer_fused_weighted's launch, bit for bit
+    const char *who = "ggcn_layer_fused_weighted_drop";
+    FusedArgs a = {};
+    if (int rc = entry_drop_spec(who, p, seed, sel_store, sel_a, sel_b, a.drop)) return rc;
+    if (!graph_opsw || !zero_mid) return fail(GGCN_EINVAL, "%s: the weighted operand blocks and the zero row are required", who);
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (33..128 nodes: ggcn_layer_fused_weighted_wide_drop)", who, T);
+    if (precision == GGCN_PREC_F16MX6) return fail(GGCN_EUNSUPPORTED, "%s: bf16x3 or f16mx8", who);
+    if ((int64_t)B * T * F >= ((int64_t)1 << 32))   // (whatever p is)
+        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)B * T * F);
+    if (int rc = layer_entry_checks(who, out, ldo, nullptr, nullptr)) return rc;
+    a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_opsw); a.graph_ops2 = a.graph_ops;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.mid = zero_mid; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b;
+    return launch_fused(who, a, precision, as_stream(stream));
 }
 
 int ggcn_layer_fused_weighted_wide_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsww, const float *bias,
@@ -187,10 +261,19 @@ int ggcn_layer_fused_weighted_wide_drop(const float *X, int64_t ldx, const void 
                                         const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b, int precision,
                                         float p, uint64_t seed, int sel_store, int sel_a, int sel_b, ggcn_stream_t stream)
 {
-    if (int rc = drop_entry_checks("ggcn_layer_fused_weighted_wide_drop", p, sel_store, sel_a, sel_b)) return rc;
-    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);   // p = 0: thr = 0, nothing is dropped
-    return layer_fused_weighted_wide(X, ldx, wpack, graph_opsww, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo,
-                                     pool_a, pool_b, precision, as_stream(stream), &d);
+    const char *who = "ggcn_layer_fused_weighted_wide_drop";
+    FusedArgs a = {};
+    if (int rc = entry_drop_spec(who, p, seed, sel_store, sel_a, sel_b, a.drop)) return rc;
+    if ((int64_t)B * T * F >= ((int64_t)1 << 32))   // (whatever p is)
+        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)B * T * F);
+    // (LayerPart's ldo is an int)
+    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: T*ldo does not fit 32-bit offsets", who);
+    a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_opsww);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b;
+    return launch_fused_weighted_wide(who, a, precision, as_stream(stream));
 }
 
 int ggcn_gate_pool_backward_weighted_drop(const float *out, int64_t ldo, const float *store_gate, const float *gate_a,
@@ -211,8 +294,19 @@ int ggcn_block_fused(const float *X, int64_t ldx, const void *wpack1, const void
                      float *x1, float *y1, float *pool_out, float *overlap_partial, int precision,
                      ggcn_stream_t stream)
 {
-    return block_fused(X, ldx, wpack1, wpack12, graph_ops, graph_ops2, bias1, bias_mid, bias2, B, T, K, F, gate1, gate2, gcn1, ld1,
-                       x_out, ld2, x1, y1, pool_out, overlap_partial, precision, as_stream(stream));
+    const char *who = "ggcn_block_fused";
+    if (int rc = block_entry_checks(who, gcn1, ld1, x_out, ld2)) return rc;
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_ops); a.graph_ops2 = bytes(graph_ops2);
+    // bert_amir5.py:626-636: gcn1 (ungated; optional here), x1 = max_t gcn1*gate1, y1 = max_t gcn1*gate2 in part[0];
+    // bert_amir5.py:639-640: x = gate2 * gc2(gcn1), out = max_t x in part[1] (the other block entries describe theirs alike)
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 2;
+    LayerPart &l1 = a.part[0], &l2 = a.part[1];
+    l1.wpack = bytes(wpack1); l1.bias = bias1; l1.pool_gate_a = gate1; l1.pool_gate_b = gate2;
+    l1.out = gcn1; l1.ldo = (int)ld1; l1.pool_a = x1; l1.pool_b = y1; l1.ov_partial = overlap_partial;
+    l2.wpack = bytes(wpack12); l2.bias = bias2; l2.mid = bias_mid; l2.store_gate = gate2; l2.pool_gate_a = gate2;
+    l2.out = x_out; l2.ldo = (int)ld2; l2.pool_a = pool_out;
+    return launch_block(who, a, kBlockBinary, precision, as_stream(stream));
 }
 
 int ggcn_graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane,
@@ -227,8 +321,20 @@ int ggcn_block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, c
                               int64_t ld1, float *x_out, int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial,
                               int precision, ggcn_stream_t stream)
 {
-    return block_fused_weighted(X, ldx, wpack1, wpack12, graph_opsw, graph_ops2w, bias1, bias_mid, bias2, zero_mid, B, T, K, F, gate1,
-                                gate2, gcn1, ld1, x_out, ld2, x1, y1, pool_out, overlap_partial, precision, as_stream(stream));
+    // ggcn_block_fused on a REAL-valued adjacency: layer 1's tiles apply M = D.A_w (ggcn_graph_operands_weighted blocks) with the zero
+    // `mid` row, layer 2's tiles M2 = (D.A_w)^2 (ggcn_graph_operands2_weighted blocks) with bias_mid, both through the MID epilogue
+    // (block_fused_weighted_kernel, fused_weighted_drop.hip).  Never the eight-wavefront kernel: fused_block8.hip reads the 0/1 format.
+    const char *who = "ggcn_block_fused_weighted";
+    if (int rc = block_entry_checks(who, gcn1, ld1, x_out, ld2)) return rc;
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_opsw); a.graph_ops2 = bytes(graph_ops2w);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 2;
+    LayerPart &l1 = a.part[0], &l2 = a.part[1];
+    l1.wpack = bytes(wpack1); l1.bias = bias1; l1.mid = zero_mid; l1.pool_gate_a = gate1; l1.pool_gate_b = gate2;
+    l1.out = gcn1; l1.ldo = (int)ld1; l1.pool_a = x1; l1.pool_b = y1; l1.ov_partial = overlap_partial;
+    l2.wpack = bytes(wpack12); l2.bias = bias2; l2.mid = bias_mid; l2.store_gate = gate2; l2.pool_gate_a = gate2;
+    l2.out = x_out; l2.ldo = (int)ld2; l2.pool_a = pool_out;
+    return launch_block(who, a, kBlockWeighted, precision, as_stream(stream));
 }
 
 int ggcn_overlap_reduce(const float *partials, int B, int F, float *xy, ggcn_stream_t stream)
@@ -304,10 +410,21 @@ int ggcn_layer_fused_bf16(const void *X, int64_t ldx, const void *wpack, const v
                           float *overlap_out, ggcn_stream_t stream)
 {
     const char *who = "ggcn_layer_fused_bf16";
-    if (int rc = bf16_entry_checks(who, X, 0.0f, 0, 0, 0)) return rc;
+    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
     if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (use ggcn_layer_fused_bf16_wide up to %d nodes, ggcn_linear_bf16 + ggcn_aggregate beyond)", who, T, GGCN_MASK_MAX_T);
-    return layer_fused_bf16(who, X, ldx, wpack, nullptr, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo, pool_a,
-                            pool_b, overlap_partial, overlap_in, overlap_out, as_stream(stream));
+    FusedArgs a = {};
+    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);   // (launch_fused sees the weight image in a.X)
+    if (int rc = layer_entry_checks(who, out, ldo, overlap_in, overlap_out)) return rc;
+    // a.X stays the fallback READ address for an absent gate / bias (the epilogues load unconditionally and discard the
+    // value): it must be valid memory, and the weight image always is (>= 4 KiB; its NULL case is refused before the launch)
+    a.X = static_cast<const float *>(wpack);
+    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx; a.graph_ops = bytes(graph_ops);
+    a.ov_in = overlap_in; a.ov_out = overlap_out;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b; l.ov_partial = overlap_partial;
+    return launch_fused(who, a, GGCN_PREC_BF16X3, as_stream(stream));
 }
 
 int ggcn_layer_fused_bf16_drop(const void *X, int64_t ldx, const void *wpack, const void *graph_ops, const float *bias, int B, int T,
@@ -316,11 +433,20 @@ int ggcn_layer_fused_bf16_drop(const void *X, int64_t ldx, const void *wpack, co
                                float *overlap_out, float p, uint64_t seed, int sel_store, int sel_a, int sel_b, ggcn_stream_t stream)
 {
     const char *who = "ggcn_layer_fused_bf16_drop";
-    if (int rc = bf16_entry_checks(who, X, p, sel_store, sel_a, sel_b)) return rc;
+    FusedArgs a = {};
+    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
+    if (int rc = entry_drop_spec(who, p, seed, sel_store, sel_a, sel_b, a.drop)) return rc;
     if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (use ggcn_layer_fused_bf16_wide up to %d nodes)", who, T, GGCN_MASK_MAX_T);
-    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);
-    return layer_fused_bf16(who, X, ldx, wpack, nullptr, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out, ldo, pool_a,
-                            pool_b, overlap_partial, overlap_in, overlap_out, as_stream(stream), &d);
+    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);   // (launch_fused sees the weight image in a.X)
+    if (int rc = layer_entry_checks(who, out, ldo, overlap_in, overlap_out)) return rc;
+    a.X = static_cast<const float *>(wpack);   // (the fallback read address: ggcn_layer_fused_bf16)
+    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx; a.graph_ops = bytes(graph_ops);
+    a.ov_in = overlap_in; a.ov_out = overlap_out;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b; l.ov_partial = overlap_partial;
+    return launch_fused(who, a, GGCN_PREC_BF16X3, as_stream(stream));
 }
 
 int ggcn_layer_fused_bf16_wide(const void *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *edge_lists,
@@ -330,12 +456,21 @@ int ggcn_layer_fused_bf16_wide(const void *X, int64_t ldx, const void *wpack, co
                                ggcn_stream_t stream)
 {
     const char *who = "ggcn_layer_fused_bf16_wide";
-    if (int rc = bf16_entry_checks(who, X, p, sel_store, sel_a, sel_b)) return rc;
+    FusedArgs a = {};
+    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
+    if (int rc = entry_drop_spec(who, p, seed, sel_store, sel_a, sel_b, a.drop)) return rc;
     if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32 (use ggcn_layer_fused_bf16 / ggcn_layer_fused_bf16_drop)", who, T);
     if (T > GGCN_MASK_MAX_T) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > %d (use ggcn_linear_bf16 + ggcn_aggregate)", who, T, GGCN_MASK_MAX_T);
-    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);   // p = 0: thr = 0, nothing is dropped
-    return layer_fused_bf16(who, X, ldx, wpack, rowmask, T > 128 ? edge_lists : nullptr, bias, B, T, K, F, store_gate, pool_gate_a,
-                            pool_gate_b, out, ldo, pool_a, pool_b, overlap_partial, overlap_in, overlap_out, as_stream(stream), &d);
+    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);   // (launch_fused sees the weight image in a.X)
+    if (int rc = layer_entry_checks(who, out, ldo, overlap_in, overlap_out)) return rc;
+    a.X = static_cast<const float *>(wpack);   // (the fallback read address: ggcn_layer_fused_bf16)
+    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx; a.rowmask = rowmask; a.graph_ops = T > 128 ? bytes(edge_lists) : nullptr;
+    a.ov_in = overlap_in; a.ov_out = overlap_out;
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b; l.ov_partial = overlap_partial;
+    return launch_fused(who, a, GGCN_PREC_BF16X3, as_stream(stream));
 }
 
 int ggcn_block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
@@ -343,9 +478,22 @@ int ggcn_block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const 
                           int F, const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
                           float *x1, float *y1, float *pool_out, float *overlap_partial, ggcn_stream_t stream)
 {
-    if (int rc = bf16_entry_checks("ggcn_block_fused_bf16", X, 0.0f, 0, 0, 0)) return rc;
-    return block_fused_bf16(X, ldx, wpack1, wpack12, graph_ops, graph_ops2, bias1, bias_mid, bias2, B, T, K, F, gate1, gate2, gcn1, ld1,
-                            x_out, ld2, x1, y1, pool_out, overlap_partial, as_stream(stream));
+    // ggcn_block_fused on bf16 features: the bf16 pair main loop on the bf16x3 images of W1 and W12, bf16 planes of (D.A)^2
+    // (ggcn_graph_operands2 plane 0)
+    const char *who = "ggcn_block_fused_bf16";
+    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "%s: X not 2-byte aligned", who);
+    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);   // (launch_fused sees the weight image in a.X)
+    if (int rc = block_entry_checks(who, gcn1, ld1, x_out, ld2)) return rc;
+    FusedArgs a = {};
+    a.X = static_cast<const float *>(wpack12);   // (the fallback read address: ggcn_layer_fused_bf16)
+    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx; a.graph_ops = bytes(graph_ops); a.graph_ops2 = bytes(graph_ops2);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 2;
+    LayerPart &l1 = a.part[0], &l2 = a.part[1];
+    l1.wpack = bytes(wpack1); l1.bias = bias1; l1.pool_gate_a = gate1; l1.pool_gate_b = gate2;
+    l1.out = gcn1; l1.ldo = (int)ld1; l1.pool_a = x1; l1.pool_b = y1; l1.ov_partial = overlap_partial;
+    l2.wpack = bytes(wpack12); l2.bias = bias2; l2.mid = bias_mid; l2.store_gate = gate2; l2.pool_gate_a = gate2;
+    l2.out = x_out; l2.ldo = (int)ld2; l2.pool_a = pool_out;
+    return launch_block(who, a, kBlockBf16, GGCN_PREC_BF16X3, as_stream(stream));
 }
 
 int ggcn_aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T,
@@ -436,8 +584,17 @@ int ggcn_lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const
 {
     const int flags = (getenv("GGCN_LAB_BLOCK8_ROWMAJOR") ? kBlock8RowMajor : 0) | (getenv("GGCN_LAB_BLOCK8_NODMA") ? kBlock8NoDma : 0) |
                       (getenv("GGCN_LAB_BLOCK8_SAMESLOTS") ? kBlock8SameSlots : 0);   // (the experiment's switches, read per call)
-    return lab_block_fused8(X, ldx, wpack1, wpack12, graph_ops, graph_ops2, bias1, bias_mid, bias2, B, T, K, F, gate1, gate2, x_out, ld2,
-                            x1, y1, pool_out, overlap_partial, as_stream(stream), reinterpret_cast<unsigned long long *>(stamps), flags);
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_ops); a.graph_ops2 = bytes(graph_ops2);
+    a.stamps = reinterpret_cast<unsigned long long *>(stamps);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 2;
+    LayerPart &l1 = a.part[0], &l2 = a.part[1];
+    l1.wpack = bytes(wpack1); l1.bias = bias1; l1.pool_gate_a = gate1; l1.pool_gate_b = gate2;
+    l1.pool_a = x1; l1.pool_b = y1; l1.ov_partial = overlap_partial;
+    l2.wpack = bytes(wpack12); l2.bias = bias2; l2.mid = bias_mid; l2.store_gate = gate2; l2.pool_gate_a = gate2;
+    // (a leading dimension that does not fit LayerPart's int stays one that block_fused8 refuses: too small below 0, no row stores beyond)
+    l2.out = x_out; l2.ldo = (int)(ld2 < 0 ? -1 : ld2 > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : ld2); l2.pool_a = pool_out;
+    return block_fused8("ggcn_lab_block_fused8", a, flags, as_stream(stream));
 }
 
 int ggcn_rowmask_transpose(const uint32_t *rowmask, int B, int T, uint32_t *rowmask_t, ggcn_stream_t stream)
@@ -483,10 +640,16 @@ int ggcn_layer_fused_drop(const float *X, int64_t ldx, const void *wpack, const 
                           float *pool_a, float *pool_b, int precision, float p, uint64_t seed, int sel_store,
                           int sel_a, int sel_b, ggcn_stream_t stream)
 {
-    if (int rc = drop_entry_checks("ggcn_layer_fused_drop", p, sel_store, sel_a, sel_b)) return rc;
-    const DropSpec d = make_drop_spec(p, seed, sel_store, sel_a, sel_b);
-    return layer_fused(X, ldx, wpack, rowmask, graph_ops, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b, out,
-                       ldo, pool_a, pool_b, nullptr, nullptr, nullptr, precision, as_stream(stream), &d);
+    const char *who = "ggcn_layer_fused";   // (what this entry's shared refusals have always been reported as)
+    FusedArgs a = {};
+    if (int rc = entry_drop_spec("ggcn_layer_fused_drop", p, seed, sel_store, sel_a, sel_b, a.drop)) return rc;
+    if (int rc = layer_entry_checks(who, out, ldo, nullptr, nullptr)) return rc;
+    a.X = X; a.ldx = ldx; a.rowmask = rowmask; a.graph_ops = bytes(graph_ops);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
+    LayerPart &l = a.part[0];
+    l.wpack = bytes(wpack); l.bias = bias; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
+    l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b;
+    return launch_fused(who, a, precision, as_stream(stream));
 }
 
 int ggcn_dropout_mask(int64_t rows, int F, float p, uint64_t seed, int stream_id, float *mask, ggcn_stream_t stream)
@@ -558,9 +721,18 @@ int ggcn_debug_block_fused_stamped(const float *X, int64_t ldx, const void *wpac
                                    int precision, uint64_t *stamps, ggcn_stream_t stream)
 {
     if (!stamps) return fail(GGCN_EINVAL, "ggcn_debug_block_fused_stamped: null stamp buffer");
-    return block_fused(X, ldx, wpack1, wpack12, graph_ops, graph_ops2, bias1, bias_mid, bias2, B, T, K, F, gate1, gate2, gcn1, ld1,
-                       x_out, ld2, x1, y1, pool_out, overlap_partial, precision, as_stream(stream),
-                       reinterpret_cast<unsigned long long *>(stamps));
+    const char *who = "ggcn_block_fused";   // (what this entry's shared refusals have always been reported as)
+    if (int rc = block_entry_checks(who, gcn1, ld1, x_out, ld2)) return rc;
+    FusedArgs a = {};
+    a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_ops); a.graph_ops2 = bytes(graph_ops2);
+    a.stamps = reinterpret_cast<unsigned long long *>(stamps);
+    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 2;
+    LayerPart &l1 = a.part[0], &l2 = a.part[1];
+    l1.wpack = bytes(wpack1); l1.bias = bias1; l1.pool_gate_a = gate1; l1.pool_gate_b = gate2;
+    l1.out = gcn1; l1.ldo = (int)ld1; l1.pool_a = x1; l1.pool_b = y1; l1.ov_partial = overlap_partial;
+    l2.wpack = bytes(wpack12); l2.bias = bias2; l2.mid = bias_mid; l2.store_gate = gate2; l2.pool_gate_a = gate2;
+    l2.out = x_out; l2.ldo = (int)ld2; l2.pool_a = pool_out;
+    return launch_block(who, a, kBlockBinary, precision, as_stream(stream));
 }
 
 int ggcn_range_flag(uint32_t *flag, int clear, ggcn_stream_t stream)

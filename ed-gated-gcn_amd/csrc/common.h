@@ -87,46 +87,12 @@ int graph_edge_lists(const uint32_t *rowmask, int B, int T, void *lists, hipStre
 int graph_operands2(const uint32_t *rowmask, int B, int T, int plane, void *ops2, hipStream_t st);
 int graph_operands_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane, void *ops,
                             int *flag, hipStream_t st);
-int layer_fused_weighted(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias, const float *zero_mid,
-                         int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
-                         float *out, int64_t ldo, float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in,
-                         float *overlap_out, int precision, hipStream_t st);
 size_t graph_operands_weighted_wide_bytes(int B, int T);   // fused_wide.hip
 int graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops, int *flag,
                                  hipStream_t st);
-int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, const void *ops, const float *bias, int B, int T, int K, int F,
-                              const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-                              float *pool_a, float *pool_b, int precision, hipStream_t st, const struct DropSpec *drop = nullptr);
-int layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias, const float *zero_mid,
-                              int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
-                              float *out, int64_t ldo, float *pool_a, float *pool_b, int precision, hipStream_t st, const struct DropSpec *drop);
-int layer_fused(const float *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops, const float *bias,
-                int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a,
-                const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b,
-                float *overlap_partial, const float *overlap_in, float *overlap_out, int precision, hipStream_t st,
-                const struct DropSpec *drop = nullptr, const float *bias_pre = nullptr);
-int layer_fused_bf16(const char *who, const void *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops,
-                     const float *bias, int B, int T, int K, int F,
-                     const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-                     float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out,
-                     hipStream_t st, const struct DropSpec *drop = nullptr);
-int block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,
-                     const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
-                     const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
-                     float *x1, float *y1, float *pool_out, float *overlap_partial, hipStream_t st);
 int graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane, void *ops2,
                              int *flag, hipStream_t st);   // fused_weighted_drop.hip
-int block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_opsw,
-                         const void *graph_ops2w, const float *bias1, const float *bias_mid, const float *bias2, const float *zero_mid,
-                         int B, int T, int K, int F, const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out,
-                         int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial, int precision, hipStream_t st);
 int dropout_mask(int64_t rows, int F, float p, uint64_t seed, int sel, float *out, hipStream_t st);
-
-int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,
-                const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
-                const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
-                float *x1, float *y1, float *pool_out, float *overlap_partial, int precision, hipStream_t st,
-                unsigned long long *stamps = nullptr);
 int mfma_calibrate(int n_wg, int stages, unsigned long long *stamps, float *sink, hipStream_t st);   // calib.hip (diagnostics)
 int overlap_reduce(const float *partials, int B, int F, float *xy, hipStream_t st);
 
@@ -177,15 +143,6 @@ int range_flag_wide(unsigned int *dst, int clear, hipStream_t st);     // fused_
 int range_flag_wide8(unsigned int *dst, int clear, hipStream_t st);    // fused_wide8.hip
 int range_flag_block8(unsigned int *dst, int clear, hipStream_t st);   // fused_block8.hip
 int range_flag_weighted_drop(unsigned int *dst, int clear, hipStream_t st);   // fused_weighted_drop.hip
-int lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,
-                     const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F, const float *gate1,
-                     const float *gate2, float *x_out, int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial,
-                     hipStream_t st, unsigned long long *stamps = nullptr, int flags = 0);
-constexpr int kBlock8RowMajor = 1, kBlock8NoDma = 2, kBlock8SameSlots = 4, kBlock8Product = 8;
-bool block8_shape(int B, int T, int K, int F);
-bool block8_takes(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, int B, int T, int K, int F, const float *gate1,
-                  const float *gate2, const float *bias1, const float *bias_mid, const float *bias2, const void *graph_ops,
-                  const void *graph_ops2, const float *x_out, int64_t ld2);
 int range_flag_fused6(unsigned int *dst, int clear, hipStream_t st);   // fused6.hip (GGCN_WITH_F16MX6)
 
 int transpose_f32(const float *W, int rows, int cols, int64_t ldw, float *Wt, hipStream_t st);

@@ -151,61 +151,61 @@ bool block8_shape(int B, int T, int K, int F)
     const int64_t total = (int64_t)((B + 3) / 4) * (F / BN), cus = device_cu_count();
     return total >= 6 * cus || (total >= 3 * cus && total % cus == 0);
 }
-bool block8_takes(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, int B, int T, int K, int F, const float *gate1,
-                  const float *gate2, const float *bias1, const float *bias_mid, const float *bias2, const void *graph_ops,
-                  const void *graph_ops2, const float *x_out, int64_t ld2)
+// the fast shape of X (buffer loads: a tile's rows at 32-bit byte offsets from its first row) and, for the LDS-DMA staging of the
+// epilogue's operands (the form that was measured), every gate / bias row and operand block this launch reads 16-byte aligned
+static bool block8_fast_x(const FusedArgs &a)
 {
-    if (!block8_shape(B, T, K, F)) return false;
+    return (a.K % BK == 0) && (a.ldx % 4 == 0) && aligned16(a.X) && (int64_t)a.ldx * 4 * 257 < ((int64_t)1 << 31);
+}
+static bool block8_dma_aligned(const FusedArgs &a)
+{
+    const LayerPart &l1 = a.part[0], &l2 = a.part[1];
+    return aligned16(l1.pool_gate_a) && aligned16(l2.store_gate) && aligned16(l1.bias) && aligned16(l2.bias) && aligned16(l2.mid) &&
+           aligned16(a.graph_ops) && aligned16(a.graph_ops2);
+}
+// a: the block as launch_block (fused_layer.hip) holds it, layer 1 in part[0] and layer 2 in part[1]
+bool block8_takes(const FusedArgs &a)
+{
+    const LayerPart &l1 = a.part[0], &l2 = a.part[1];
+    if (!block8_shape(a.B, a.T, a.K, a.F)) return false;
     // what launch_fused would refuse goes there, so that both forms answer a bad call with the same code and message
-    if (ldx < K || !aligned16(wpack1) || !aligned16(wpack12) || (x_out && ld2 < F)) return false;
-    if (!((ldx % 4 == 0) && aligned16(X) && (int64_t)ldx * 4 * 257 < ((int64_t)1 << 31))) return false;
-    if (!graph_ops || !graph_ops2 || !gate1 || !gate2 || !bias_mid) return false;
-    if (!(aligned16(gate1) && aligned16(gate2) && aligned16(bias1) && aligned16(bias2) && aligned16(bias_mid) && aligned16(graph_ops) &&
-          aligned16(graph_ops2)))
-        return false;   // (the LDS-DMA staging of the epilogue's operands: the form that was measured)
-    if (x_out && !((ld2 % 4 == 0) && aligned16(x_out) && (int64_t)T * ld2 * 4 < ((int64_t)1 << 31))) return false;
+    if (!a.X || !l1.wpack || !l2.wpack || a.ldx < a.K || !aligned16(l1.wpack) || !aligned16(l2.wpack) || (l2.out && l2.ldo < a.F)) return false;
+    if (!block8_fast_x(a)) return false;
+    if (!a.graph_ops || !a.graph_ops2 || !l1.pool_gate_a || !l2.store_gate || !l2.mid) return false;
+    if (!block8_dma_aligned(a)) return false;
+    if (l2.out && !vector_row_stores(a, l2)) return false;
     return true;
 }
 
-int lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops, const void *graph_ops2,
-                     const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F, const float *gate1,
-                     const float *gate2, float *x_out, int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial,
-                     hipStream_t st, unsigned long long *stamps, int flags)
+// who: the entry (ggcn_block_fused through launch_block, or ggcn_lab_block_fused8); a: the block, layer 1 in part[0] and layer 2 in part[1].
+// flags (fused_args.h kBlock8*): ROWMAJOR = a row block's three column slices on one XCD (the product's map: ggcn_block_fused takes
+// this kernel for large batches), else column slices pinned to XCDs; NODMA / SAMESLOTS: lab switches of ggcn_lab_block_fused8
+int block_fused8(const char *who, FusedArgs &a, int flags, hipStream_t st)
 {
-    // flags (common.h kBlock8*): ROWMAJOR = a row block's three column slices on one XCD (the product's map: ggcn_block_fused takes
-    // this kernel for large batches), else column slices pinned to XCDs; NODMA / SAMESLOTS: lab switches of ggcn_lab_block_fused8
-    const char *who = (flags & kBlock8Product) ? "ggcn_block_fused" : "ggcn_lab_block_fused8";
-    if (!X || !wpack1 || !wpack12 || !graph_ops || !graph_ops2 || !gate1 || !gate2 || !x1 || !y1 || !bias_mid)
+    LayerPart &l1 = a.part[0], &l2 = a.part[1];
+    if (!a.X || !l1.wpack || !l2.wpack || !a.graph_ops || !a.graph_ops2 || !l1.pool_gate_a || !l2.store_gate || !l1.pool_a || !l1.pool_b || !l2.mid)
         return fail(GGCN_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || T <= 0 || T > 32 || K <= 0 || F <= 0) return fail(GGCN_EUNSUPPORTED, "%s: B=%d T=%d K=%d F=%d (graphs of <= 32 nodes)", who, B, T, K, F);
-    // launch_fused's checks (fused_layer.hip), with its messages
-    if (ldx < K) return fail(GGCN_EINVAL, "%s: ldx < K", who);
-    if (!aligned16(wpack1) || !aligned16(wpack12)) return fail(GGCN_EINVAL, "%s: wpack must be 16-byte aligned", who);
-    if (x_out && ld2 < F) return fail(GGCN_EINVAL, "%s: leading dimension of the output too small", who);
-    const bool avec = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(X) && (int64_t)ldx * 4 * 257 < ((int64_t)1 << 31);
-    if (!avec || K % BK != 0) return fail(GGCN_EUNSUPPORTED, "%s: fast shapes only (K %% 32 == 0, 16-byte aligned rows)", who);
-    if (!x_out && !pool_out) return fail(GGCN_EINVAL, "%s: neither x nor its pool requested", who);
-    FusedArgs a = {};
-    a.X = X; a.ldx = ldx; a.graph_ops = static_cast<const char *>(graph_ops); a.graph_ops2 = static_cast<const char *>(graph_ops2);
+    if (a.B <= 0 || a.T <= 0 || a.T > 32 || a.K <= 0 || a.F <= 0)
+        return fail(GGCN_EUNSUPPORTED, "%s: B=%d T=%d K=%d F=%d (graphs of <= 32 nodes)", who, a.B, a.T, a.K, a.F);
+    if (!l2.out && !l2.pool_a) return fail(GGCN_EINVAL, "%s: neither x nor its pool requested", who);
+    // x leaves as 16-byte row stores or not at all (a leading dimension below F is fused_part_checks' to name)
+    if (l2.out && l2.ldo >= a.F && !vector_row_stores(a, l2)) return fail(GGCN_EUNSUPPORTED, "%s: x needs F %% 4 == 0 and 16-byte aligned rows", who);
+    l1.out = nullptr; l1.ldo = 0;   // (this kernel stores no gcn1)
+    bool vst;
+    if (int rc = fused_part_checks(who, a, vst)) return rc;
+    if (!block8_fast_x(a)) return fail(GGCN_EUNSUPPORTED, "%s: fast shapes only (K %% 32 == 0, 16-byte aligned rows)", who);
     const bool rowmajor = (flags & kBlock8RowMajor) != 0;
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = rowmajor ? 3 : 2;
-    a.part[0] = LayerPart{static_cast<const char *>(wpack1), bias1, nullptr, nullptr, nullptr, gate1, gate2, nullptr, x1, y1, overlap_partial, 0};
-    a.part[1] = LayerPart{static_cast<const char *>(wpack12), bias2, bias_mid, nullptr, gate2, gate2, nullptr, x_out, pool_out, nullptr, nullptr, (int)ld2};
-    a.stamps = stamps;
-    a.k_steps = round_up(K, BK) / KSTEP;
+    a.n_parts = rowmajor ? 3 : 2;
+    a.k_steps = round_up(a.K, BK) / KSTEP;
     // (bit 30 of k_steps: every gate / bias row this launch reads starts 16-byte aligned -- the LDS-DMA staging may be used)
-    const bool al = (F % 4 == 0) && aligned16(gate1) && aligned16(gate2) && aligned16(bias1) && aligned16(bias2) && aligned16(bias_mid) &&
-                    aligned16(graph_ops) && aligned16(graph_ops2) && !(flags & kBlock8NoDma);
-    if (al) a.k_steps |= 0x40000000;
+    if ((a.F % 4 == 0) && block8_dma_aligned(a) && !(flags & kBlock8NoDma)) a.k_steps |= 0x40000000;
     if (flags & kBlock8SameSlots) a.k_steps |= 0x20000000;
-    a.n_wg = (F + BN - 1) / BN;
-    a.g_tiles = (B + 3) / 4;
-    const bool vst = x_out && (F % 4 == 0) && (ld2 % 4 == 0) && aligned16(x_out) && (int64_t)T * ld2 * 4 < ((int64_t)1 << 31);
-    if (x_out && !vst) return fail(GGCN_EUNSUPPORTED, "%s: x needs F %% 4 == 0 and 16-byte aligned rows", who);
-    const bool fullt = (T == 32) && (B % 4 == 0);
-    const int64_t total = (int64_t)a.g_tiles * a.n_wg;
-    const int64_t grid = rowmajor ? grid_for(a.g_tiles, a.n_wg) : 8 * ((total + 7) / 8);
+    a.n_wg = (a.F + BN - 1) / BN;
+    const bool fullt = (a.T == 32) && (a.B % 4 == 0);
+    const int64_t g_tiles = ((int64_t)a.B + 3) / 4, total = g_tiles * a.n_wg;   // (in 64 bits: B + 3 may not fit an int)
+    const int64_t grid = rowmajor ? grid_for(g_tiles, a.n_wg) : 8 * ((total + 7) / 8);
     if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
+    a.g_tiles = (int)g_tiles;
 #define GGCN_L8(FT, VS)                                                                                                           \
     do {                                                                                                                          \
         auto kern = block_fused8_kernel<FT, VS>;                                                                                  \

@@ -1,48 +1,12 @@
 // Shared by the one-launch layer kernels (fused_layer.hip: graphs of <= 32 nodes and the two-layer block; fused_wide.hip:
-// 33..128 nodes; fused_wide8.hip: 129..256 nodes; fused6.hip: the optional f16mx6 form): argument blocks, the split of an
+// 33..128 nodes; fused_wide8.hip: 129..256 nodes; fused6.hip: the optional f16mx6 form): the argument blocks (fused_args.h), the split of an
 // accumulator tile into MFMA operand planes, the operands staged in LDS for the 32-node epilogue, and that epilogue.
 #pragma once
 #include "f16mx8_core.h"
-#include "dropout_hash.h"
+#include "fused_args.h"
 #include "lab_hooks.h"
 
 namespace ggcn {
-
-// what one group of column tiles ("part") computes: part 0 = the layer itself (or layer 1 of the block),
-// part 1 = layer 2 of the block through W12
-struct LayerPart {
-    const char *wpack;          // ggcn_weight_pack image of this part's [K, F] matrix
-    const float *bias;          // added after the (last) normalised aggregation, or NULL
-    const float *mid;           // NULL: one aggregation.  Else: y = D.A.(D.A.h + mid) + bias
-    const float *pre;           // NULL, or [F] added to `hidden` BEFORE the aggregation (graphs of 33..256 nodes): y = D.A.(h + 1.pre^T) + bias
-    const float *store_gate;    // [B,F] or NULL (ones)
-    const float *pool_gate_a;   // [B,F] or NULL (ones)
-    const float *pool_gate_b;
-    float *out;                 // [N, ldo] or NULL
-    float *pool_a, *pool_b;     // [B,F] or NULL
-    float *ov_partial;          // [B, ceil(F/64)] or NULL: sum_f pool_a*pool_b per graph and 64 columns
-    int ldo;
-};
-
-struct FusedArgs {
-    const float *X;
-    int64_t ldx;
-    const uint32_t *rowmask;    // graphs of 33..256 nodes (layer_fused_wide_kernel)
-    const char *graph_ops;      // graphs of <= 32 nodes: ggcn_graph_operands blocks (layer_fused_kernel); 129..256: optional edge-list blocks;
-                                // layer_fused_wide_kernel<.., WEIGHTED>: ggcn_graph_operands_weighted_wide blocks (rowmask NULL)
-    const char *graph_ops2;     // the block's W12 tiles: ggcn_graph_operands2 blocks ((D.A)^2 in the launch's plane type)
-    const float *ov_in;         // partials an EARLIER launch wrote: block 0 reduces them to *ov_out first
-    float *ov_out;
-    int B, T, K, F;
-    int g_tiles, n_wg, n_parts, k_steps;
-    LayerPart part[2];
-    DropSpec drop;              // training-mode keep masks of the gates (thr = 0: none); one part only
-    unsigned long long *stamps; // diagnostics only (ggcn_debug_block_fused_stamped): [workgroup][2] = d(s_memtime), d(s_memrealtime) around the main loop
-    const __bf16 *Xb;           // bf16 features (ggcn_layer_fused_bf16[_drop]: graphs of <= 32 nodes, ggcn_layer_fused_bf16_wide: 33..256;
-                                // one layer, bf16x3 image); X then only names readable memory (the weight image) for the
-                                // discarded fallback reads of an absent gate / bias
-};
-
 
 // per-file launchers behind launch_fused (fused_layer.hip); shapes and flags are validated there
 int launch_fused_wide(const char *who, const FusedArgs &a, int precision, int sb, bool fast, bool vst, int64_t grid, hipStream_t st);

@@ -384,30 +384,15 @@ __global__ __launch_bounds__(256) void rowmask_kernel(const int32_t *__restrict_
         if (w < W) rowmask[i * W + w] = m[w];
 }
 
-// shared argument checks + launch of layer_fused_kernel for 1 or 2 parts
-// (weighted_block: ggcn_block_fused_weighted -- both parts on hi / lo operand blocks, kernels of their own in fused_weighted_drop.hip)
-int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, bool weighted_block = false)
+}  // namespace
+
+int fused_part_checks(const char *who, const FusedArgs &a, bool &vst)
 {
-    if (precision != GGCN_PREC_BF16X3 && precision != GGCN_PREC_F16MX8 && precision != GGCN_PREC_F16MX6)
-        return fail(GGCN_EUNSUPPORTED, "%s: precision %d (use bf16x3 or f16mx8)", who, precision);
-#ifndef GGCN_WITH_F16MX6
-    if (precision == GGCN_PREC_F16MX6)
-        return fail(GGCN_EUNSUPPORTED, "%s: f16mx6 is an experiment this library was built without (make F16MX6=1); use f16mx8", who);
-#endif
-    if (!a.X && !a.Xb) return fail(GGCN_EINVAL, "%s: null input pointer", who);   // (bf16: a.X is the weight image, see layer_fused_bf16)
-    if (a.T > 32 ? !a.rowmask : !a.graph_ops)
-        return fail(GGCN_EINVAL, "%s: graphs of %d nodes need %s", who, a.T,
-                    a.T > 32 ? "the row masks" : "the per-graph operand blocks of ggcn_graph_operands");
-    if (a.T <= 32 && !aligned16(a.graph_ops)) return fail(GGCN_EINVAL, "%s: graph_ops must be 16-byte aligned", who);
-    if (a.T > 128 && a.graph_ops && !aligned16(a.graph_ops)) return fail(GGCN_EINVAL, "%s: the edge-list blocks must be 16-byte aligned", who);
     if (a.B <= 0 || a.T <= 0 || a.K <= 0 || a.F <= 0)
         return fail(GGCN_EINVAL, "%s: B=%d T=%d K=%d F=%d must be positive", who, a.B, a.T, a.K, a.F);
-    if (a.T > GGCN_MASK_MAX_T)
-        return fail(GGCN_EUNSUPPORTED, "%s: T=%d > %d; use ggcn_linear + ggcn_aggregate", who, a.T, GGCN_MASK_MAX_T);
-    if (a.T > 32 && a.n_parts != 1)
-        return fail(GGCN_EUNSUPPORTED, "%s: the two-layer form takes graphs of <= 32 nodes (T=%d): one ggcn_layer_fused per layer", who, a.T);
     if (a.ldx < a.K) return fail(GGCN_EINVAL, "%s: ldx < K", who);
-    bool vst = true, any_out = false;
+    bool any_out = false;
+    vst = true;
     for (int p = 0; p < a.n_parts; ++p) {
         const LayerPart &lp = a.part[p];
         if (!lp.wpack) return fail(GGCN_EINVAL, "%s: null weight image", who);
@@ -418,50 +403,84 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, b
             if ((int64_t)a.T * lp.ldo >= (int64_t)INT32_MAX)
                 return fail(GGCN_EUNSUPPORTED, "%s: T*ldo does not fit 32-bit offsets", who);
             any_out = true;
-            // (the 16-byte row stores address a graph's rows with 32-bit byte offsets from its first row)
-            vst = vst && (a.F % 4 == 0) && (lp.ldo % 4 == 0) && aligned16(lp.out) && (int64_t)a.T * lp.ldo * 4 < ((int64_t)1 << 31);
+            vst = vst && vector_row_stores(a, lp);
         }
     }
     vst = vst && any_out;
+    return GGCN_OK;
+}
+
+// the argument checks every one-launch layer and block shares + the launch of layer_fused_kernel (or of the per-file launchers of
+// fused_common.h) for 1 or 2 parts
+int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, bool weighted_block)
+{
+    if (precision != GGCN_PREC_BF16X3 && precision != GGCN_PREC_F16MX8 && precision != GGCN_PREC_F16MX6)
+        return fail(GGCN_EUNSUPPORTED, "%s: precision %d (use bf16x3 or f16mx8)", who, precision);
+#ifndef GGCN_WITH_F16MX6
+    if (precision == GGCN_PREC_F16MX6)
+        return fail(GGCN_EUNSUPPORTED, "%s: f16mx6 is an experiment this library was built without (make F16MX6=1); use f16mx8", who);
+#endif
+    if (!a.X && !a.Xb) return fail(GGCN_EINVAL, "%s: null input pointer", who);   // (bf16: a.X is the weight image, see ggcn_layer_fused_bf16)
+    if (a.T > 32 ? !a.rowmask : !a.graph_ops)
+        return fail(GGCN_EINVAL, "%s: graphs of %d nodes need %s", who, a.T,
+                    a.T > 32 ? "the row masks" : "the per-graph operand blocks of ggcn_graph_operands");
+    if (a.T <= 32 && !aligned16(a.graph_ops)) return fail(GGCN_EINVAL, "%s: graph_ops must be 16-byte aligned", who);
+    if (a.T > 128 && a.graph_ops && !aligned16(a.graph_ops)) return fail(GGCN_EINVAL, "%s: the edge-list blocks must be 16-byte aligned", who);
+    if (a.T > GGCN_MASK_MAX_T)
+        return fail(GGCN_EUNSUPPORTED, "%s: T=%d > %d; use ggcn_linear + ggcn_aggregate", who, a.T, GGCN_MASK_MAX_T);
+    if (a.T > 32 && a.n_parts != 1)
+        return fail(GGCN_EUNSUPPORTED, "%s: the two-layer form takes graphs of <= 32 nodes (T=%d): one ggcn_layer_fused per layer", who, a.T);
+    bool vst;
+    if (int rc = fused_part_checks(who, a, vst)) return rc;
+    bool any_out = false, folded = a.n_parts != 1;   // folded: the two-layer block (W1 + W12 tiles, or the W12 tiles alone)
+    for (int p = 0; p < a.n_parts; ++p) {
+        any_out = any_out || a.part[p].out;
+        folded = folded || a.part[p].mid;
+    }
     if (a.Xb) {   // bf16 features on the bf16x3 image (bf16 pair form, two MFMAs per product); the entry points fix the range of T
         if (precision != GGCN_PREC_BF16X3)
             return fail(GGCN_EUNSUPPORTED, "%s: bf16 features take the bf16x3 weight image (precision %d)", who, precision);
-        // one layer, or the two-layer block of graphs of <= 32 nodes (ggcn_block_fused_bf16: W1 + W12 tiles, or the W12 tiles alone)
-        bool folded = a.n_parts != 1;
-        for (int p = 0; p < a.n_parts; ++p) folded = folded || a.part[p].mid;
         if (a.stamps || a.part[0].pre || a.part[a.n_parts - 1].pre)
             return fail(GGCN_EUNSUPPORTED, "%s: bf16 features take no bias_pre and no stamps", who);
         if (folded && (a.T > 32 || !a.graph_ops2 || !aligned16(a.graph_ops2)))
             return fail(GGCN_EUNSUPPORTED, "%s: the two-layer form takes graphs of <= 32 nodes and their ggcn_graph_operands2 blocks (T=%d)", who, a.T);
         if (folded && a.drop.thr != 0)
             return fail(GGCN_EUNSUPPORTED, "%s: gate dropout is built into the one-launch LAYER, not the two-layer block", who);
-        if ((int64_t)a.B * a.T * a.F >= ((int64_t)1 << 32) && a.drop.thr != 0)
-            return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)a.B * a.T * a.F);
-        const bool avecb = (a.K % 8 == 0) && (a.ldx % 8 == 0) && aligned16(a.Xb);
-        const bool kfullb = (a.K % BK == 0);
-        a.k_steps = round_up(a.K, BK) / KSTEP;
-        a.n_wg = (a.F + BN - 1) / BN;
-        if (a.T > 32) {   // 64-, 128- or 256-row graph slots, as for float32 features below
-            const int sb = a.T <= 64 ? 2 : a.T <= 128 ? 4 : 8;
-            const int gpt = sb == 2 ? 2 : 1;
-            const int64_t gt = ((int64_t)a.B + gpt - 1) / gpt;
-            const int64_t gridw = grid_for(gt, a.n_wg);
-            if (gridw > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
-            a.g_tiles = (int)gt;
-            // (a launch without `out` stores no rows: the vector-store form is as good as any, and it is the fast shape's only form)
-            const bool vstw = vst || !any_out;
-            if (sb == 8) return launch_fused_wide8(who, a, precision, avecb && kfullb, vstw, gridw, st);
-            return launch_fused_wide(who, a, precision, sb, avecb && kfullb, vstw, gridw, st);
-        }
-        const int64_t g_tiles = ((int64_t)a.B + 4 * WM - 1) / (4 * WM);
-        // the block: W1 tiles on four XCDs, W12 tiles on the other four (layer_fused_kernel), as for float32 features below
-        const int64_t grid = a.n_parts == 1 ? grid_for(g_tiles, a.n_wg) : (g_tiles + 3) / 4 * a.n_wg * 8;
-        if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
-        a.g_tiles = (int)g_tiles;
-        const bool fullt = (a.T == 32) && (a.B % (4 * WM) == 0);
+    } else if (a.drop.thr != 0 && (a.n_parts != 1 || precision == GGCN_PREC_F16MX6))
+        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout is built into the one-launch LAYER (bf16x3 / f16mx8), not the two-layer block", who);
+    if ((int64_t)a.B * a.T * a.F >= ((int64_t)1 << 32) && a.drop.thr != 0)
+        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)a.B * a.T * a.F);
+    if (!a.Xb && a.T > 32 && precision == GGCN_PREC_F16MX6)
+        return fail(GGCN_EUNSUPPORTED, "%s: f16mx6 takes graphs of <= 32 nodes (T=%d); use f16mx8", who, a.T);
+    // (float32: the fast shapes address a tile's 128 rows with 32-bit byte offsets from its first row: buffer loads)
+    const bool avec = a.Xb ? (a.K % 8 == 0) && (a.ldx % 8 == 0) && aligned16(a.Xb)
+                           : (a.K % 4 == 0) && (a.ldx % 4 == 0) && aligned16(a.X) && (int64_t)a.ldx * 4 * 257 < ((int64_t)1 << 31);
+    const bool kfull = (a.K % BK == 0);
+    a.k_steps = round_up(a.K, BK) / KSTEP;
+    a.n_wg = (a.F + BN - 1) / BN;
+    if (a.T > 32) {   // 64-, 128- or 256-row graph slots: layer_fused_wide_kernel
+        const int sb = a.T <= 64 ? 2 : a.T <= 128 ? 4 : 8;
+        const int gpt = sb == 2 ? 2 : 1;   // graphs per workgroup
+        const int64_t gt = ((int64_t)a.B + gpt - 1) / gpt;
+        const int64_t gridw = grid_for(gt, a.n_wg);
+        if (gridw > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
+        a.g_tiles = (int)gt;
+        const bool fast = avec && kfull;
+        // (bf16 features: a launch without `out` stores no rows: the vector-store form is as good as any, and it is the fast shape's only form)
+        const bool vstw = vst || (a.Xb && !any_out);
+        if (sb == 8 && (a.Xb || !GGCN_LAB_WIDE_SB8)) return launch_fused_wide8(who, a, precision, fast, vstw, gridw, st);   // 129..256 nodes: eight wavefronts per graph
+        return launch_fused_wide(who, a, precision, sb, fast, vstw, gridw, st);
+    }
+    const int64_t g_tiles = ((int64_t)a.B + 4 * WM - 1) / (4 * WM);
+    // the block: W1 tiles on four XCDs, W12 tiles on the other four (layer_fused_kernel)
+    const int64_t grid = a.n_parts == 1 ? grid_for(g_tiles, a.n_wg) : (g_tiles + 3) / 4 * a.n_wg * 8;
+    if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
+    a.g_tiles = (int)g_tiles;
+    const bool fullt = (a.T == 32) && (a.B % (4 * WM) == 0);
+    if (a.Xb) {
         // the block's eval form without `x` stores no rows: the vector-store instantiations (the fast shape's only ones) serve it
         // with the same arithmetic.  A plain layer keeps the instantiation it always had.
-        const bool vstb = vst || (folded && !any_out);
+        const bool avecb = avec, kfullb = kfull, vstb = vst || (folded && !any_out);
 #define GGCN_LAUNCH_B(AV, KF, FT, VS) \
     hipLaunchKernelGGL((layer_fused_kernel<0, AV, KF, FT, VS, false, __bf16>), dim3((unsigned)grid), dim3(kThreads), 0, st, a)
         if (avecb && kfullb && fullt && vstb) GGCN_LAUNCH_B(true, true, true, true);
@@ -473,33 +492,6 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, b
 #undef GGCN_LAUNCH_B
         return check_launch(who);
     }
-    // (the fast shapes address a tile's 128 rows with 32-bit byte offsets from its first row: buffer loads)
-    const bool avec = (a.K % 4 == 0) && (a.ldx % 4 == 0) && aligned16(a.X) && (int64_t)a.ldx * 4 * 257 < ((int64_t)1 << 31);
-    const bool kfull = (a.K % BK == 0);
-    a.k_steps = round_up(a.K, BK) / KSTEP;
-    a.n_wg = (a.F + BN - 1) / BN;
-    if (a.drop.thr != 0 && (a.n_parts != 1 || precision == GGCN_PREC_F16MX6))
-        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout is built into the one-launch LAYER (bf16x3 / f16mx8), not the two-layer block", who);
-    if ((int64_t)a.B * a.T * a.F >= ((int64_t)1 << 32) && a.drop.thr != 0)
-        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)a.B * a.T * a.F);
-    if (a.T > 32 && precision == GGCN_PREC_F16MX6)
-        return fail(GGCN_EUNSUPPORTED, "%s: f16mx6 takes graphs of <= 32 nodes (T=%d); use f16mx8", who, a.T);
-    if (a.T > 32) {   // 64-, 128- or 256-row graph slots: layer_fused_wide_kernel
-        const int sb = a.T <= 64 ? 2 : a.T <= 128 ? 4 : 8;
-        const int gpt = sb == 2 ? 2 : 1;   // graphs per workgroup
-        const int64_t gt = ((int64_t)a.B + gpt - 1) / gpt;
-        const int64_t gridw = grid_for(gt, a.n_wg);
-        if (gridw > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
-        a.g_tiles = (int)gt;
-        const bool fast = avec && kfull;
-        if (sb == 8 && !GGCN_LAB_WIDE_SB8) return launch_fused_wide8(who, a, precision, fast, vst, gridw, st);   // 129..256 nodes: eight wavefronts per graph
-        return launch_fused_wide(who, a, precision, sb, fast, vst, gridw, st);
-    }
-    const int64_t g_tiles = ((int64_t)a.B + 4 * WM - 1) / (4 * WM);
-    const int64_t grid = a.n_parts == 1 ? grid_for(g_tiles, a.n_wg) : (g_tiles + 3) / 4 * a.n_wg * 8;
-    if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
-    a.g_tiles = (int)g_tiles;
-    const bool fullt = (a.T == 32) && (a.B % (4 * WM) == 0);
     if (precision == GGCN_PREC_F16MX6) {
         if (!(avec && kfull) || (int64_t)128 * a.ldx * 4 >= ((int64_t)1 << 31))
             return fail(GGCN_EUNSUPPORTED, "%s: f16mx6 needs K %% 32 == 0 and 16-byte aligned rows of X (K=%d ldx=%lld); use f16mx8",
@@ -532,8 +524,6 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, b
 #undef GGCN_LAUNCH
     return check_launch(who);
 }
-
-}  // namespace
 
 GGCN_TRACE_READER
 
@@ -607,231 +597,54 @@ int graph_operands_weighted(const int32_t *rowptr, const int32_t *colidx, const 
     return check_launch(who);
 }
 
-// gcn.py:30-45 with a real-valued adjacency for graphs of <= 32 nodes in ONE launch: the W12 column tiles' form of the block
-// (MID epilogue: one split of `hidden`, 6 MFMAs with the hi / lo operand) on ggcn_graph_operands_weighted blocks; zero_mid is the
-// all-zero `mid` row that form reads ([F] floats)
-int layer_fused_weighted(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias, const float *zero_mid,
-                         int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
-                         float *out, int64_t ldo, float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in,
-                         float *overlap_out, int precision, hipStream_t st)
+// The three two-layer blocks.  The entry described layer 1 in part[0] and layer 2 (through W12) in part[1]; every refusal comes before
+// the launch and names the entry.
+int launch_block(const char *who, FusedArgs &a, BlockKind kind, int precision, hipStream_t st)
 {
-    const char *who = "ggcn_layer_fused_weighted";
-    if ((overlap_in == nullptr) != (overlap_out == nullptr)) return fail(GGCN_EINVAL, "%s: overlap_in and overlap_out go together", who);
-    if (!graph_opsw || !zero_mid) return fail(GGCN_EINVAL, "%s: the weighted operand blocks and the zero row are required", who);
-    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (use ggcn_linear + ggcn_aggregate)", who, T);
-    if (precision == GGCN_PREC_F16MX6) return fail(GGCN_EUNSUPPORTED, "%s: bf16x3 or f16mx8", who);
-    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: ldo too large", who);
-    FusedArgs a = {};
-    a.X = X; a.ldx = ldx; a.graph_ops = static_cast<const char *>(graph_opsw); a.graph_ops2 = a.graph_ops;
-    a.ov_in = overlap_in; a.ov_out = overlap_out;
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
-    a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, zero_mid, nullptr, store_gate, pool_gate_a, pool_gate_b,
-                          out, pool_a, pool_b, overlap_partial, (int)ldo};
-    return launch_fused(who, a, precision, st);
-}
-
-// ggcn_layer_fused_weighted under the gates' training-mode dropout: layer_fused_weighted_drop_kernel on the same blocks; thr = 0
-// (p = 0) launches layer_fused_kernel's MID form -- ggcn_layer_fused_weighted's launch, bit for bit
-int layer_fused_weighted_drop(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias, const float *zero_mid,
-                              int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a, const float *pool_gate_b,
-                              float *out, int64_t ldo, float *pool_a, float *pool_b, int precision, hipStream_t st, const DropSpec *drop)
-{
-    const char *who = "ggcn_layer_fused_weighted_drop";
-    if (!graph_opsw || !zero_mid) return fail(GGCN_EINVAL, "%s: the weighted operand blocks and the zero row are required", who);
-    if (!drop) return fail(GGCN_EINVAL, "%s: no keep streams", who);
-    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (33..128 nodes: ggcn_layer_fused_weighted_wide_drop)", who, T);
-    if (precision == GGCN_PREC_F16MX6) return fail(GGCN_EUNSUPPORTED, "%s: bf16x3 or f16mx8", who);
-    if ((int64_t)B * T * F >= ((int64_t)1 << 32))
-        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)B * T * F);
-    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: ldo too large", who);
-    FusedArgs a = {};
-    a.X = X; a.ldx = ldx; a.graph_ops = static_cast<const char *>(graph_opsw); a.graph_ops2 = a.graph_ops;
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
-    a.drop = *drop;
-    a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, zero_mid, nullptr, store_gate, pool_gate_a, pool_gate_b,
-                          out, pool_a, pool_b, nullptr, (int)ldo};
-    return launch_fused(who, a, precision, st);
-}
-
-int layer_fused(const float *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops,
-                const float *bias, int B, int T, int K, int F, const float *store_gate, const float *pool_gate_a,
-                const float *pool_gate_b, float *out, int64_t ldo, float *pool_a, float *pool_b,
-                float *overlap_partial, const float *overlap_in, float *overlap_out, int precision, hipStream_t st,
-                const DropSpec *drop, const float *bias_pre)
-{
-    if ((overlap_in == nullptr) != (overlap_out == nullptr))
-        return fail(GGCN_EINVAL, "ggcn_layer_fused: overlap_in and overlap_out go together");
-    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "ggcn_layer_fused: ldo too large");
-    FusedArgs a = {};
-    a.X = X; a.ldx = ldx; a.rowmask = rowmask; a.graph_ops = static_cast<const char *>(graph_ops);
-    a.ov_in = overlap_in; a.ov_out = overlap_out;
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
-    if (drop) a.drop = *drop;
-    a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, nullptr, bias_pre, store_gate, pool_gate_a, pool_gate_b,
-                          out, pool_a, pool_b, overlap_partial, (int)ldo};
-    if (bias_pre && T <= 32)
-        return fail(GGCN_EUNSUPPORTED, "ggcn_layer_fused_prebias: graphs of <= 32 nodes fold both layers in ggcn_block_fused (its eval form); bias_pre is for 33..256 nodes");
-    if (bias_pre && drop)
-        return fail(GGCN_EUNSUPPORTED, "ggcn_layer_fused_prebias: an inference form (no gate dropout)");
-    return launch_fused("ggcn_layer_fused", a, precision, st);
-}
-
-// bf16 features.  who: the entry point, which has checked the graph size it takes (ggcn_layer_fused_bf16[_drop]: <= 32 nodes on
-// graph_ops; ggcn_layer_fused_bf16_wide: 33..256 on the row masks, graph_ops = optional edge-list blocks); drop: NULL or the gates' keep streams
-int layer_fused_bf16(const char *who, const void *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops,
-                     const float *bias, int B, int T, int K, int F,
-                     const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-                     float *pool_a, float *pool_b, float *overlap_partial, const float *overlap_in, float *overlap_out,
-                     hipStream_t st, const DropSpec *drop)
-{
-    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
-    if ((overlap_in == nullptr) != (overlap_out == nullptr)) return fail(GGCN_EINVAL, "%s: overlap_in and overlap_out go together", who);
-    if (out && ldo > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: ldo too large", who);
-    FusedArgs a = {};
-    // a.X stays the fallback READ address for an absent gate / bias (the epilogues load unconditionally and discard the
-    // value): it must be valid memory, and the weight image always is (>= 4 KiB; its NULL case is refused before the launch)
-    a.X = static_cast<const float *>(wpack);
-    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx; a.rowmask = rowmask; a.graph_ops = static_cast<const char *>(graph_ops);
-    a.ov_in = overlap_in; a.ov_out = overlap_out;
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
-    if (drop) a.drop = *drop;
-    a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, nullptr, nullptr, store_gate, pool_gate_a, pool_gate_b,
-                          out, pool_a, pool_b, overlap_partial, (int)ldo};
-    return launch_fused(who, a, GGCN_PREC_BF16X3, st);
-}
-
-int block_fused(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
-                const void *graph_ops2, const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
-                const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
-                float *x1, float *y1, float *pool_out, float *overlap_partial, int precision, hipStream_t st,
-                unsigned long long *stamps)
-{
-    if (!gate2) return fail(GGCN_EINVAL, "ggcn_block_fused: gate2 is required");
+    const LayerPart &first = a.part[0], &second = a.part[1];
+    if (kind == kBlockWeighted && a.T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (one weighted layer launch per layer)", who, a.T);
+    if (kind == kBlockWeighted && precision == GGCN_PREC_F16MX6) return fail(GGCN_EUNSUPPORTED, "%s: bf16x3 or f16mx8", who);
+    if (kind == kBlockBf16 && a.T > 32)
+        return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (one ggcn_layer_fused_bf16_wide per layer up to %d nodes)", who, a.T, GGCN_MASK_MAX_T);
+    if (!second.store_gate) return fail(GGCN_EINVAL, "%s: gate2 is required", who);
     // train.py:227 keeps the logits only, and those need `out` alone (bert_amir5.py:640,643): with x1 = y1 = gcn1 =
     // overlap_partial = NULL the W1 column tiles are not launched at all (half of the matrix work) -- the EVAL form
-    const bool layer1 = x1 || y1 || gcn1 || overlap_partial;
-    if (layer1 && (!x1 || !y1 || !gate1))
-        return fail(GGCN_EINVAL, "ggcn_block_fused: layer 1's outputs go together (gate1, x1 and y1; all NULL with gcn1 and overlap_partial = the eval form)");
-    if (!x_out && !pool_out) return fail(GGCN_EINVAL, "ggcn_block_fused: neither x nor its pool requested");
-    if ((gcn1 && ld1 > (int64_t)INT32_MAX) || (x_out && ld2 > (int64_t)INT32_MAX))
-        return fail(GGCN_EUNSUPPORTED, "ggcn_block_fused: leading dimension too large");
-    FusedArgs a = {};
-    if (!graph_ops2 || !aligned16(graph_ops2))
-        return fail(GGCN_EINVAL, "ggcn_block_fused: graph_ops2 (ggcn_graph_operands2 blocks, 16-byte aligned) is required");
-    // large batches, every output, f16mx8: the eight-wavefront workgroup that stages a row block's X planes once for a W1 and a W12
-    // column slice (fused_block8.hip: bit-identical results, 2 % less time in steady state from 2048 graphs up).
-    // GGCN_BLOCK_FORM=4 (read per call) keeps the four-wavefront kernel: A/B timing, tests.
-    if (layer1 && !gcn1 && !stamps && precision == GGCN_PREC_F16MX8 && X && wpack1 && wpack12 && bias_mid &&
-        block8_takes(X, ldx, wpack1, wpack12, B, T, K, F, gate1, gate2, bias1, bias_mid, bias2, graph_ops, graph_ops2, x_out, ld2)) {
-        const char *form = getenv("GGCN_BLOCK_FORM");
-        if (!(form && form[0] == '4'))
-            return lab_block_fused8(X, ldx, wpack1, wpack12, graph_ops, graph_ops2, bias1, bias_mid, bias2, B, T, K, F, gate1, gate2, x_out,
-                                    ld2, x1, y1, pool_out, overlap_partial, st, nullptr, kBlock8RowMajor | kBlock8Product);
-    }
-    a.X = X; a.ldx = ldx; a.graph_ops = static_cast<const char *>(graph_ops); a.graph_ops2 = static_cast<const char *>(graph_ops2);
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = layer1 ? 2 : 1;
-    a.stamps = stamps;
-    // bert_amir5.py:639-640: x = gate2 * gc2(gcn1), out = max_t x.  A NULL mid bias (gc1 without bias) still
-    // needs the second aggregation: a vector of zeros cannot be conjured here, so the caller passes one.
-    if (!bias_mid) return fail(GGCN_EINVAL, "ggcn_block_fused: bias_mid (W2^T.b1, zeros when gc1 has no bias) is required");
-    const LayerPart second = LayerPart{static_cast<const char *>(wpack12), bias2, bias_mid, nullptr, gate2, gate2, nullptr,
-                                       x_out, pool_out, nullptr, nullptr, (int)ld2};
-    if (layer1) {
-        // bert_amir5.py:626-636: gcn1 (ungated; optional here), x1 = max_t gcn1*gate1, y1 = max_t gcn1*gate2
-        a.part[0] = LayerPart{static_cast<const char *>(wpack1), bias1, nullptr, nullptr, nullptr, gate1, gate2,
-                              gcn1, x1, y1, overlap_partial, (int)ld1};
-        a.part[1] = second;
-    } else {
-        if (stamps) return fail(GGCN_EUNSUPPORTED, "ggcn_debug_block_fused_stamped: the eval form is not stamped");
-        if (!a.graph_ops) a.graph_ops = a.graph_ops2;   // (the W12 tiles read graph_ops2 only; launch_fused insists on a block pointer)
-        a.part[0] = second;   // every XCD runs W12 tiles (tile_of_block: the column tiles of a row block share an XCD)
-    }
-    return launch_fused("ggcn_block_fused", a, precision, st);
-}
-
-// ggcn_block_fused on a REAL-valued adjacency: layer 1's tiles apply M = D.A_w (ggcn_graph_operands_weighted blocks) with the zero
-// `mid` row, layer 2's tiles M2 = (D.A_w)^2 (ggcn_graph_operands2_weighted blocks) with bias_mid, both through the MID epilogue
-// (block_fused_weighted_kernel, fused_weighted_drop.hip).  Never the eight-wavefront kernel: fused_block8.hip reads the 0/1 format.
-// Every refusal comes before the launch and names this entry.
-int block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_opsw,
-                         const void *graph_ops2w, const float *bias1, const float *bias_mid, const float *bias2, const float *zero_mid,
-                         int B, int T, int K, int F, const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out,
-                         int64_t ld2, float *x1, float *y1, float *pool_out, float *overlap_partial, int precision, hipStream_t st)
-{
-    const char *who = "ggcn_block_fused_weighted";
-    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
-    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (one weighted layer launch per layer)", who, T);
-    if (precision == GGCN_PREC_F16MX6) return fail(GGCN_EUNSUPPORTED, "%s: bf16x3 or f16mx8", who);
-    if (!gate2) return fail(GGCN_EINVAL, "%s: gate2 is required", who);
-    const bool layer1 = x1 || y1 || gcn1 || overlap_partial;   // none of them: the eval form (only the W12 tiles are launched)
-    if (layer1 && (!x1 || !y1 || !gate1))
+    const bool layer1 = first.pool_a || first.pool_b || first.out || first.ov_partial;
+    if (layer1 && (!first.pool_a || !first.pool_b || !first.pool_gate_a))
         return fail(GGCN_EINVAL, "%s: layer 1's outputs go together (gate1, x1 and y1; all NULL with gcn1 and overlap_partial = the eval form)", who);
-    if (!x_out && !pool_out) return fail(GGCN_EINVAL, "%s: neither x nor its pool requested", who);
-    if ((gcn1 && ld1 > (int64_t)INT32_MAX) || (x_out && ld2 > (int64_t)INT32_MAX))
-        return fail(GGCN_EUNSUPPORTED, "%s: leading dimension too large", who);
-    if (!wpack12 || (layer1 && !wpack1)) return fail(GGCN_EINVAL, "%s: null weight image", who);
-    if (!graph_ops2w || !aligned16(graph_ops2w))
+    if (!second.out && !second.pool_a) return fail(GGCN_EINVAL, "%s: neither x nor its pool requested", who);
+    if (kind != kBlockBinary && (!second.wpack || (layer1 && !first.wpack))) return fail(GGCN_EINVAL, "%s: null weight image", who);
+    const bool ops2_ok = a.graph_ops2 && aligned16(a.graph_ops2);
+    if (kind == kBlockBinary && !ops2_ok)
+        return fail(GGCN_EINVAL, "%s: graph_ops2 (ggcn_graph_operands2 blocks, 16-byte aligned) is required", who);
+    if (kind == kBlockWeighted && !ops2_ok)
         return fail(GGCN_EINVAL, "%s: graph_ops2w (ggcn_graph_operands2_weighted blocks, 16-byte aligned) is required", who);
-    if (layer1 && (!graph_opsw || !aligned16(graph_opsw)))
+    if (kind == kBlockBf16 && !a.graph_ops2) return fail(GGCN_EINVAL, "%s: graph_ops2 (the ggcn_graph_operands2 blocks of plane 0) is required", who);
+    if (kind == kBlockBf16 && !ops2_ok) return fail(GGCN_EINVAL, "%s: graph_ops2 must be 16-byte aligned", who);
+    if (kind == kBlockWeighted && layer1 && (!a.graph_ops || !aligned16(a.graph_ops)))
         return fail(GGCN_EINVAL, "%s: layer 1 needs graph_opsw (ggcn_graph_operands_weighted blocks, 16-byte aligned)", who);
-    if (!bias_mid) return fail(GGCN_EINVAL, "%s: bias_mid (W2^T.b1, zeros when gc1 has no bias) is required", who);
-    if (layer1 && (!zero_mid || !aligned16(zero_mid))) return fail(GGCN_EINVAL, "%s: zero_mid ([F] zeros, 16-byte aligned) is required", who);
-    FusedArgs a = {};
-    a.X = X; a.ldx = ldx; a.graph_ops2 = static_cast<const char *>(graph_ops2w);
-    a.graph_ops = layer1 ? static_cast<const char *>(graph_opsw) : a.graph_ops2;   // (the eval form reads graph_ops2 only; launch_fused insists on a block pointer)
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = layer1 ? 2 : 1;
-    const LayerPart second = LayerPart{static_cast<const char *>(wpack12), bias2, bias_mid, nullptr, gate2, gate2, nullptr,
-                                       x_out, pool_out, nullptr, nullptr, (int)ld2};
-    if (layer1) {
-        a.part[0] = LayerPart{static_cast<const char *>(wpack1), bias1, zero_mid, nullptr, nullptr, gate1, gate2,
-                              gcn1, x1, y1, overlap_partial, (int)ld1};
-        a.part[1] = second;
-    } else {
-        a.part[0] = second;
+    if (kind == kBlockBf16 && layer1 && !a.graph_ops) return fail(GGCN_EINVAL, "%s: layer 1 needs the per-graph operand blocks of ggcn_graph_operands", who);
+    // large batches, every output, f16mx8: the eight-wavefront workgroup that stages a row block's X planes once for a W1 and a W12
+    // column slice (fused_block8.hip: bit-identical results, 2 % less time in steady state from 2048 graphs up; it reads the 0/1 format).
+    // GGCN_BLOCK_FORM=4 (read per call) keeps the four-wavefront kernel: A/B timing, tests.
+    if (kind == kBlockBinary && layer1 && !first.out && !a.stamps && precision == GGCN_PREC_F16MX8 && block8_takes(a)) {
+        const char *form = getenv("GGCN_BLOCK_FORM");
+        if (!(form && form[0] == '4')) return block_fused8(who, a, kBlock8RowMajor, st);
     }
-    return launch_fused(who, a, precision, st, true);
-}
-
-// ggcn_block_fused on bf16 features: the bf16 pair main loop on the bf16x3 images of W1 and W12, bf16 planes of (D.A)^2
-// (ggcn_graph_operands2 plane 0).  Every refusal comes before the launch and names its argument.
-int block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
-                     const void *graph_ops2, const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
-                     const float *gate1, const float *gate2, float *gcn1, int64_t ld1, float *x_out, int64_t ld2,
-                     float *x1, float *y1, float *pool_out, float *overlap_partial, hipStream_t st)
-{
-    const char *who = "ggcn_block_fused_bf16";
-    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
-    if (T > 32)
-        return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (one ggcn_layer_fused_bf16_wide per layer up to %d nodes)", who, T, GGCN_MASK_MAX_T);
-    if (!gate2) return fail(GGCN_EINVAL, "%s: gate2 is required", who);
-    const bool layer1 = x1 || y1 || gcn1 || overlap_partial;   // none of them: the eval form (only the W12 tiles are launched)
-    if (layer1 && (!x1 || !y1 || !gate1))
-        return fail(GGCN_EINVAL, "%s: layer 1's outputs go together (gate1, x1 and y1; all NULL with gcn1 and overlap_partial = the eval form)", who);
-    if (!x_out && !pool_out) return fail(GGCN_EINVAL, "%s: neither x nor its pool requested", who);
-    if ((gcn1 && ld1 > (int64_t)INT32_MAX) || (x_out && ld2 > (int64_t)INT32_MAX))
-        return fail(GGCN_EUNSUPPORTED, "%s: leading dimension too large", who);
-    if (!wpack12 || (layer1 && !wpack1)) return fail(GGCN_EINVAL, "%s: null weight image", who);
-    if (!graph_ops2) return fail(GGCN_EINVAL, "%s: graph_ops2 (the ggcn_graph_operands2 blocks of plane 0) is required", who);
-    if (!aligned16(graph_ops2)) return fail(GGCN_EINVAL, "%s: graph_ops2 must be 16-byte aligned", who);
-    if (layer1 && !graph_ops) return fail(GGCN_EINVAL, "%s: layer 1 needs the per-graph operand blocks of ggcn_graph_operands", who);
-    if (!bias_mid) return fail(GGCN_EINVAL, "%s: bias_mid (W2^T.b1, zeros when gc1 has no bias) is required", who);
-    FusedArgs a = {};
-    // (the fallback read address of absent gates and biases: layer_fused_bf16)
-    a.X = static_cast<const float *>(wpack12);
-    a.Xb = static_cast<const __bf16 *>(X); a.ldx = ldx;
-    a.graph_ops = static_cast<const char *>(graph_ops); a.graph_ops2 = static_cast<const char *>(graph_ops2);
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = layer1 ? 2 : 1;
-    const LayerPart second = LayerPart{static_cast<const char *>(wpack12), bias2, bias_mid, nullptr, gate2, gate2, nullptr,
-                                       x_out, pool_out, nullptr, nullptr, (int)ld2};
-    if (layer1) {
-        a.part[0] = LayerPart{static_cast<const char *>(wpack1), bias1, nullptr, nullptr, nullptr, gate1, gate2,
-                              gcn1, x1, y1, overlap_partial, (int)ld1};
-        a.part[1] = second;
-    } else {
-        if (!a.graph_ops) a.graph_ops = a.graph_ops2;   // (the W12 tiles read graph_ops2 only; launch_fused insists on a block pointer)
-        a.part[0] = second;
+    // A NULL mid bias (gc1 without bias) still needs the second aggregation: a vector of zeros cannot be conjured here, so the
+    // caller passes one.
+    if (!second.mid) return fail(GGCN_EINVAL, "%s: bias_mid (W2^T.b1, zeros when gc1 has no bias) is required", who);
+    if (kind == kBlockWeighted && layer1 && (!first.mid || !aligned16(first.mid)))
+        return fail(GGCN_EINVAL, "%s: zero_mid ([F] zeros, 16-byte aligned) is required", who);
+    if (!layer1) {
+        if (a.stamps) return fail(GGCN_EUNSUPPORTED, "ggcn_debug_block_fused_stamped: the eval form is not stamped");
+        // (the W12 tiles read graph_ops2 only; launch_fused insists on a block pointer)
+        if (kind == kBlockWeighted || !a.graph_ops) a.graph_ops = a.graph_ops2;
+        a.part[0] = second;   // every XCD runs W12 tiles (tile_of_block: the column tiles of a row block share an XCD)
+        a.part[1] = LayerPart{};
+        a.n_parts = 1;
     }
-    return launch_fused(who, a, GGCN_PREC_BF16X3, st);
+    return launch_fused(who, a, precision, st, kind == kBlockWeighted);
 }
 
 int overlap_reduce(const float *partials, int B, int F, float *xy, hipStream_t st)

@@ -470,44 +470,24 @@ int graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, c
 }
 
 // gcn.py:30-45 with a real-valued adjacency for graphs of 33..128 nodes in ONE launch: layer_fused_wide_kernel<.., WEIGHTED> on
-// ggcn_graph_operands_weighted_wide blocks.  The argument checks are launch_fused's (fused_layer.hip) for one part.
-// drop: NULL, or the gates' keep streams (ggcn_layer_fused_weighted_wide_drop; thr = 0: the launch without dropout)
-int layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, const void *ops, const float *bias, int B, int T, int K, int F,
-                              const float *store_gate, const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-                              float *pool_a, float *pool_b, int precision, hipStream_t st, const DropSpec *drop)
+// ggcn_graph_operands_weighted_wide blocks (a.graph_ops; no row masks).  The shape and the part are checked by fused_part_checks
+// (fused_layer.hip), as launch_fused's are.  a.drop: the gates' keep streams (thr = 0: the launch without dropout)
+int launch_fused_weighted_wide(const char *who, FusedArgs &a, int precision, hipStream_t st)
 {
-    const char *who = drop ? "ggcn_layer_fused_weighted_wide_drop" : "ggcn_layer_fused_weighted_wide";
     if (precision != GGCN_PREC_BF16X3 && precision != GGCN_PREC_F16MX8)
         return fail(GGCN_EUNSUPPORTED, "%s: precision %d (bf16x3 or f16mx8)", who, precision);
-    if (!X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
-    if (!ops) return fail(GGCN_EINVAL, "%s: the weighted operand blocks are required", who);
-    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: the operand blocks must be 16-byte aligned", who);
-    if (B <= 0 || T <= 0 || K <= 0 || F <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d K=%d F=%d must be positive", who, B, T, K, F);
-    if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32 (ggcn_layer_fused_weighted)", who, T);
-    if (T > 128) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 128 (use ggcn_linear + ggcn_aggregate)", who, T);
-    if (ldx < K) return fail(GGCN_EINVAL, "%s: ldx < K", who);
-    if (!wpack) return fail(GGCN_EINVAL, "%s: null weight image", who);
-    if (!aligned16(wpack)) return fail(GGCN_EINVAL, "%s: wpack must be 16-byte aligned", who);
-    if (!out && !pool_a && !pool_b) return fail(GGCN_EINVAL, "%s: no output requested", who);
-    if (drop && (int64_t)B * T * F >= ((int64_t)1 << 32))
-        return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)B * T * F);
-    bool vst = false;
-    if (out) {
-        if (ldo < F) return fail(GGCN_EINVAL, "%s: leading dimension of the output too small", who);
-        if (ldo > (int64_t)INT32_MAX || (int64_t)T * ldo >= (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: T*ldo does not fit 32-bit offsets", who);
-        vst = (F % 4 == 0) && (ldo % 4 == 0) && aligned16(out) && (int64_t)T * ldo * 4 < ((int64_t)1 << 31);
-    }
-    FusedArgs a = {};
-    a.X = X; a.ldx = ldx; a.graph_ops = static_cast<const char *>(ops);
-    a.B = B; a.T = T; a.K = K; a.F = F; a.n_parts = 1;
-    if (drop) a.drop = *drop;
-    a.part[0] = LayerPart{static_cast<const char *>(wpack), bias, nullptr, nullptr, store_gate, pool_gate_a, pool_gate_b,
-                          out, pool_a, pool_b, nullptr, (int)ldo};
-    const bool fast = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(X) && (int64_t)ldx * 4 * 257 < ((int64_t)1 << 31) && (K % BK == 0);
-    a.k_steps = round_up(K, BK) / KSTEP;
-    a.n_wg = (F + BN - 1) / BN;
-    const int sb = T <= 64 ? 2 : 4;
-    const int64_t gt = sb == 2 ? ((int64_t)B + 1) / 2 : B;   // two graphs per workgroup in the 64-row slot
+    if (!a.X) return fail(GGCN_EINVAL, "%s: null input pointer", who);
+    if (!a.graph_ops) return fail(GGCN_EINVAL, "%s: the weighted operand blocks are required", who);
+    if (!aligned16(a.graph_ops)) return fail(GGCN_EINVAL, "%s: the operand blocks must be 16-byte aligned", who);
+    bool vst;
+    if (int rc = fused_part_checks(who, a, vst)) return rc;
+    if (a.T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32 (ggcn_layer_fused_weighted)", who, a.T);
+    if (a.T > 128) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 128 (use ggcn_linear + ggcn_aggregate)", who, a.T);
+    const bool fast = (a.K % 4 == 0) && (a.ldx % 4 == 0) && aligned16(a.X) && (int64_t)a.ldx * 4 * 257 < ((int64_t)1 << 31) && (a.K % BK == 0);
+    a.k_steps = round_up(a.K, BK) / KSTEP;
+    a.n_wg = (a.F + BN - 1) / BN;
+    const int sb = a.T <= 64 ? 2 : 4;
+    const int64_t gt = sb == 2 ? ((int64_t)a.B + 1) / 2 : a.B;   // two graphs per workgroup in the 64-row slot
     const int64_t gridw = grid_for(gt, a.n_wg);
     if (gridw > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
     a.g_tiles = (int)gt;

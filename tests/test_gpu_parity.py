@@ -1784,6 +1784,48 @@ def test_large_batches_take_the_eight_wavefront_block_and_nothing_changes(pkg, d
         np.testing.assert_allclose(r8[k][sl].cpu().numpy(), ref[k].numpy(), rtol=0, atol=TOL["f16mx8"] * max(1.0, float(ref[k].abs().max())))
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,F,with_gcn1", [(4, 256, False), (4, 512, False), (20, 256, False), (20, 512, True)])
+def test_stamped_block_writes_the_blocks_outputs_bit_for_bit(pkg, dev, B, F, with_gcn1):
+    """ggcn_debug_block_fused_stamped (what bench.py reads the clock inside the main loop with) is ggcn_block_fused through a
+    diagnostic instantiation of the same kernel: x1, y1, x, out, the regulariser's partials and gcn1 are the same bits.  The smallest
+    shapes that form takes (f16mx8, T = 32, K = 32, B % 4 == 0) that still cross a tile edge: one and two groups of sixteen graphs
+    (the second ragged), one and two 256-column tiles.  The stamps go to 2 * ceil(B/16) * ceil(F/256) * 8 words (include/ggcn.h)
+    and to none of the 16 guard words behind them."""
+    from ed_gated_gcn_amd import _capi, synth
+    from ed_gated_gcn_amd.gated_block import _block_operands
+    lib, T, K = pkg.load_library(), 32, 32
+    rng = np.random.default_rng(1000 * B + F)
+    adj = synth.dependency_batch(B, T, 4.0, seed=7, lengths=rng.integers(1, T + 1, size=B))
+    rp, ci, _ = synth.csr_from_dense_host(adj)
+    csr = pkg.BatchedCSR.from_arrays(rp, ci, B, T, dev)
+    x = torch.from_numpy(rng.standard_normal((B * T, K)).astype(np.float32)).to(dev)
+    g1, g2 = (torch.from_numpy(rng.random((B, F), dtype=np.float32)).to(dev) for _ in range(2))
+    (w1, b1), (w2, b2) = synth.layer_params(K, F, seed=1), synth.layer_params(F, F, seed=2)
+    l1, l2 = _layer(pkg, dev, w1, b1, "f16mx8"), _layer(pkg, dev, w2, b2, "f16mx8")
+    st, P = _capi.stream_of(dev), _capi.ptr
+    pack1, pack12, mid = _block_operands(l1, l2, lib, st, precision="f16mx8")
+    bb1, bb2 = l1.bias.detach(), l2.bias.detach()
+    n_words = 2 * ((B + 15) // 16) * ((F + 255) // 256) * 8
+    stamps = torch.zeros(n_words + 16, dtype=torch.int64, device=dev)
+
+    def run(entry, *tail):
+        e = lambda *s: torch.full(s, float("nan"), device=dev)   # noqa: E731
+        r = dict(gcn1=e(B * T, F) if with_gcn1 else None, xo=e(B * T, F), x1=e(B, F), y1=e(B, F), out=e(B, F), part=e(B, (F + 63) // 64))
+        _capi.check(getattr(lib, entry)(P(x), K, P(pack1), P(pack12), P(csr.graph_ops), P(csr.graph_ops2(1)), P(bb1), P(mid), P(bb2), B, T, K, F,
+                                        P(g1), P(g2), P(r["gcn1"]) if with_gcn1 else None, F, P(r["xo"]), F, P(r["x1"]), P(r["y1"]),
+                                        P(r["out"]), P(r["part"]), _capi.PREC["f16mx8"], *tail, st), entry)
+        torch.cuda.synchronize()
+        return r
+    ref = run("ggcn_block_fused")
+    got = run("ggcn_debug_block_fused_stamped", P(stamps))
+    for k, v in ref.items():
+        if v is not None:
+            assert not bool(torch.isnan(v).any()) and torch.equal(v, got[k]), k
+    assert bool((stamps[:n_words] != 0).any()), "the stamped instantiation wrote no stamp"
+    assert not bool(stamps[n_words:].any()), "a stamp behind 2 * ceil(B/16) * ceil(F/256) * 8 words"
+
+
 # ---------------------------------------------------------------- N > 1 product path on one device (SURVEY 8e)
 def _shard_worker(rank, world, port, ret):
     import traceback
