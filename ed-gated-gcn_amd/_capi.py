@@ -115,6 +115,10 @@ PROTOTYPES = {
     "ggcn_rowmask_transpose_wide": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "ggcn_gate_pool_backward_wide": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                              c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ggcn_graph_operands_weighted_wide_t_bytes": (c_sz, [c_i32, c_i32]),
+    "ggcn_graph_operands_weighted_wide_t": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ggcn_gate_pool_backward_weighted_wide": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                                      c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ggcn_linear_scaled": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp]),
     "ggcn_layer_fused_drop": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                       c_vp, c_i64, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_uint64, c_i32, c_i32, c_i32, c_vp]),

@@ -12,7 +12,8 @@ head keep the reference's PyTorch ops by default (they are trained; ``opt.ggcn_h
 are dropped per
 token like the reference's (``:621-625``); ``opt.ggcn_wide_backward`` reaches ``gc1`` and ``gc2`` through their constructor and
 puts their backward on graphs of 33..128 nodes into one launch each where no gate dropout is active
-(``dispatch.takes_wide_backward``).  BERT, the BiLSTM and ``dense`` stay PyTorch-ROCm.
+(``dispatch.takes_wide_backward``); ``opt.ggcn_weighted_wide_backward`` reaches them the same way and does the same on a
+real-valued adjacency of 33..128 nodes (``dispatch.takes_weighted_wide_backward``).  BERT, the BiLSTM and ``dense`` stay PyTorch-ROCm.
 """
 import os
 

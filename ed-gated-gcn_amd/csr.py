@@ -61,7 +61,7 @@ class BatchedCSR:
     kernel: all the fused layer needs); the CSR arrays are materialised on first access."""
 
     __slots__ = ("_rowptr", "_colidx", "_vals", "rowmask", "B", "T", "nnz", "is_binary",
-                 "_dense", "_dense_version", "_t", "_inv", "_graph_ops", "_graph_ops2", "_graph_ops_t", "_edge_lists", "_graph_ops_w", "_graph_ops_ww", "_graph_ops_wt", "_graph_ops2_w", "_rowmask_t_wide",
+                 "_dense", "_dense_version", "_t", "_inv", "_graph_ops", "_graph_ops2", "_graph_ops_t", "_edge_lists", "_graph_ops_w", "_graph_ops_ww", "_graph_ops_wt", "_graph_ops2_w", "_rowmask_t_wide", "_graph_ops_wwt",
                  "__weakref__")
 
     def __init__(self, rowptr, colidx, vals, B, T, nnz=None, rowmask=None):
@@ -81,6 +81,7 @@ class BatchedCSR:
         self._graph_ops_wt = None  # cached ggcn_graph_operands_weighted_t blocks (A_w^T of <= 32 nodes: the weighted backward); False: refused
         self._graph_ops2_w = None  # cached ggcn_graph_operands2_weighted blocks per plane type ((D.A_w)^2: the weighted one-launch block)
         self._rowmask_t_wide = None  # cached ggcn_rowmask_transpose_wide masks (0/1 graphs of 33..128 nodes: the wide backward)
+        self._graph_ops_wwt = None  # cached ggcn_graph_operands_weighted_wide_t blocks (A_w^T of 33..128 nodes: the weighted wide backward); False: refused
 
     def _build(self, entry, sizer, source, extra=(), by_length=False, flagged=False):
         """What every cached operand builder does once its precondition holds: ask ``sizer`` for the bytes of B graphs (``by_length``:
@@ -209,6 +210,21 @@ class BatchedCSR:
                               (self.rowptr, self.colidx, self.vals), flagged=True)
             self._graph_ops_wt = False if ops is None else ops
         return None if self._graph_ops_wt is False else self._graph_ops_wt
+
+    def graph_ops_weighted_wide_t(self):
+        """uint8 [``ggcn_graph_operands_weighted_wide_t_bytes(B, T)``] or None: A_w^T of a REAL-valued adjacency of graphs of
+        33..128 nodes as ceil(T/32)^2 blocks of three bf16 planes and one summary word per graph, the A operand of the backward's
+        ``dH = A_w^T . D . dY`` on the matrix cores (``ggcn_gate_pool_backward_weighted_wide``), built from the CSR arrays on first
+        use -- no transposed CSR.  None for graphs of other sizes, arrays that are not on the GPU, or an entry that is not finite
+        (one read-back of the builder's flag per adjacency): that adjacency keeps ``ggcn_gate_pool_backward`` +
+        ``ggcn_aggregate_t``."""
+        if self._graph_ops_wwt is None:
+            if not 32 < self.T <= 128 or not self.rowptr.is_cuda:
+                return None
+            ops = self._build("ggcn_graph_operands_weighted_wide_t", "ggcn_graph_operands_weighted_wide_t_bytes",
+                              (self.rowptr, self.colidx, self.vals), by_length=True, flagged=True)
+            self._graph_ops_wwt = False if ops is None else ops
+        return None if self._graph_ops_wwt is False else self._graph_ops_wwt
 
     @property
     def device(self):

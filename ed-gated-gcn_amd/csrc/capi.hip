@@ -642,6 +642,23 @@ int ggcn_gate_pool_backward_wide(const float *out, int64_t ldo, const float *sto
                                    d_ga, d_gb, d_bsum, as_stream(stream));
 }
 
+size_t ggcn_graph_operands_weighted_wide_t_bytes(int B, int T) { return graph_operands_weighted_wide_t_bytes(B, T); }
+
+int ggcn_graph_operands_weighted_wide_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *graph_ops_wwt,
+                                        int32_t *flag, ggcn_stream_t stream)
+{
+    return graph_operands_weighted_wide_t(rowptr, colidx, vals, B, T, graph_ops_wwt, flag, as_stream(stream));
+}
+
+int ggcn_gate_pool_backward_weighted_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
+                                          const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wwt,
+                                          const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
+                                          float *d_ga, float *d_gb, float *d_bsum, ggcn_stream_t stream)
+{
+    return gate_pool_backward_weighted_wide(out, ldo, store_gate, gate_a, gate_b, d_out, ldd, d_pa, d_pb, graph_ops_wwt, inv, B, T, F, dH,
+                                            ldh, dY, ldy, d_sg, d_ga, d_gb, d_bsum, as_stream(stream));
+}
+
 int ggcn_linear_scaled(const float *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F,
                        const float *amax, ggcn_stream_t stream)
 {

@@ -122,6 +122,13 @@ int gate_pool_backward_wide(const float *out, int64_t ldo, const float *store_ga
                             const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const uint32_t *rowmask_t,
                             const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *d_sg, float *d_ga, float *d_gb,
                             float *d_bsum, hipStream_t st);
+size_t graph_operands_weighted_wide_t_bytes(int B, int T);   // gate_pool_backward_weighted_wide.hip
+int graph_operands_weighted_wide_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops, int *flag,
+                                   hipStream_t st);
+int gate_pool_backward_weighted_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
+                                     const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wwt,
+                                     const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
+                                     float *d_ga, float *d_gb, float *d_bsum, hipStream_t st);
 size_t colsum_workspace_bytes(int F);
 int colsum(const float *X, int64_t ld, int64_t M, int F, float *out, void *workspace, hipStream_t st);
 

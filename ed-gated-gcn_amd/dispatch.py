@@ -26,6 +26,7 @@ DROPOUT_LAUNCHES = DROPOUT_PATHS + ("weighted_drop", "weighted_wide_drop")
 OVERLAP_LAUNCHES = OVERLAP_PATHS
 BACKWARD_LAUNCHES = BACKWARD_PASSES + ("weighted", "weighted_drop")
 WIDE_BACKWARD_LAUNCHES = ("wide",)                                      # the opt-in one-launch backward of 0/1 graphs of 33..128 nodes
+WEIGHTED_WIDE_BACKWARD_LAUNCHES = ("weighted_wide",)                     # the opt-in one-launch backward of real-valued graphs of 33..128 nodes
 DX_FORMS = ("bf16", "scaled", "bf16x3", "fp32")                         # the dW forms are these without "scaled"
 BLOCK_PATHS = ("block", "bf16_block", "folded_eval", "bf16_folded_eval", "two_fused", "layers_eval", "layers")
 BLOCK_LAUNCHES = BLOCK_PATHS + ("weighted_block",)                    # the pinned names plus the opt-in block on a real-valued adjacency
@@ -264,10 +265,38 @@ def takes_wide_backward(layer, csr, B, F, dropout, operands):
     return csr.rowmask_t_wide is not None
 
 
+def takes_weighted_wide_backward(layer, csr, F, dropout, operands):
+    """True when the backward of a layer on a REAL-valued adjacency of graphs of 33..128 nodes runs its gate / pool pass AND
+    ``dH = A_w^T . D . dY`` as ONE launch on the matrix cores (``ggcn_gate_pool_backward_weighted_wide``) where ``backward_plan``
+    says "two_pass": the option ``layer.weighted_wide_backward`` (``opt.ggcn_weighted_wide_backward`` /
+    ``GGCN_WEIGHTED_WIDE_BACKWARD=1``; OFF by default, and separate from ``weighted_backward``) -- looked at FIRST, so that a layer
+    without it asks the graph nothing -- no gate dropout (the launch has no form under it: "two_pass_drop" stays), a real-valued
+    adjacency, 32 < T <= 128, F % 4 == 0, every operand 16-byte aligned, ``GGCN_BACKWARD_TWO_PASS`` not set, and -- asked last,
+    so that a refused call builds nothing -- the graph's A_w^T operand (``BatchedCSR.graph_ops_weighted_wide_t``: None when an
+    entry is not finite).  It replaces ``ggcn_gate_pool_backward`` + ``BatchedCSR.transposed()`` + ``ggcn_aggregate_t``; unlike
+    "wide" it is taken with an adjacency gradient too: the launch stores dY for ``ggcn_adjacency_grad``.  The dX / dW forms stay
+    the plan's.  float32 and bfloat16 features alike (``out``, dY and dH are float32 in both).  It stays opt-in: dH differs in the
+    last bits.
+    Measured (``tools/weighted_wide_backward_timing.py``, one MI355X, one process, each form alone in steady state, H = 768,
+    f16mx8, us, option off -> on, the per-adjacency builders inside every call; sparse / dense softmax rows).  The replaced
+    stage: 512 x 100: 324 -> 210 / 1081 -> 236, 1024 x 64: 362 -> 203 / 921 -> 217, 512 x 128: 451 -> 237 / 1664 -> 272; with the dY
+    store 239 / 266, 248 / 262, 282 / 314.  The whole layer backward: 758 -> 654 / 1569 -> 688, 879 -> 736 / 1478 -> 757,
+    968 -> 753 / 2241 -> 799; with ``d adj`` 1116 -> 1034 / 1957 -> 1091 at 512 x 100.  The builders alone: transposed CSR 73-144,
+    the operand 34-38 (sparse), 53-71 (dense).  NEGATIVE: 64 x 100 on a sparse graph LOSES (stage 98 -> 129, backward 214 -> 241);
+    on dense rows it wins there too (222 -> 142).
+    The compiler's report: 214 VGPRs, no scratch, 19 KiB of LDS, two workgroups per CU."""
+    if not getattr(layer, "weighted_wide_backward", False):
+        return False
+    if not (dropout is None and not csr.is_binary and 32 < csr.T <= 128 and F % 4 == 0 and _aligned16(operands) and not _two_pass_forced()):
+        return False
+    return csr.graph_ops_weighted_wide_t() is not None
+
+
 def backward_launch(layer, csr, dtype, B, K, F, need_x, need_adj, dropout, operands):
-    """``backward_plan`` with its pass replaced by "weighted" / "weighted_drop" (``BACKWARD_LAUNCHES``) or "wide"
-    (``WIDE_BACKWARD_LAUNCHES``) where the predicates above hold: asked after the plan and only where it says "two_pass" /
-    "two_pass_drop", so the plan's answers stay as pinned; the wide launch only where no adjacency gradient is wanted."""
+    """``backward_plan`` with its pass replaced by "weighted" / "weighted_drop" (``BACKWARD_LAUNCHES``), "wide"
+    (``WIDE_BACKWARD_LAUNCHES``) or "weighted_wide" (``WEIGHTED_WIDE_BACKWARD_LAUNCHES``) where the predicates above hold: asked
+    after the plan and only where it says "two_pass" / "two_pass_drop", so the plan's answers stay as pinned; the wide launch only
+    where no adjacency gradient is wanted, the weighted wide one with it as well (it stores dY)."""
     passes, dx, dw = backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands)
     if passes == "two_pass" and takes_weighted_backward(layer, csr, F, dropout, operands):
         passes = "weighted"
@@ -275,6 +304,8 @@ def backward_launch(layer, csr, dtype, B, K, F, need_x, need_adj, dropout, opera
         passes = "weighted_drop"
     elif passes == "two_pass" and not need_adj and takes_wide_backward(layer, csr, B, F, dropout, operands):
         passes = "wide"
+    elif passes == "two_pass" and takes_weighted_wide_backward(layer, csr, F, dropout, operands):
+        passes = "weighted_wide"
     return passes, dx, dw
 
 

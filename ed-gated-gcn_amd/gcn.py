@@ -106,6 +106,10 @@ _BACKWARD_LAUNCHES = {
     "weighted_drop": ("ggcn_gate_pool_backward_weighted_drop", _weighted_t, "both", ("drop",)),
     "wide": ("ggcn_gate_pool_backward_wide", _wide_t, "dH", ()),
 }
+# dispatch.WEIGHTED_WIDE_BACKWARD_LAUNCHES, a table of its own: consulted where the name is not in the one above
+_WEIGHTED_WIDE_BACKWARD_LAUNCHES = {
+    "weighted_wide": ("ggcn_gate_pool_backward_weighted_wide", lambda c: (c.graph_ops_weighted_wide_t(), c.inv_denominators()), "both", ()),
+}
 
 
 class _GatedLayerFunction(torch.autograd.Function):
@@ -118,7 +122,9 @@ class _GatedLayerFunction(torch.autograd.Function):
         dH = A^T.(D.dY)        HIP, one wavefront per SOURCE node on the transposed CSR (0/1 graphs of <= 32 nodes: one launch with
                                the line above; real-valued ones with ``weighted_backward``:
                                ggcn_gate_pool_backward_weighted[_drop]; 0/1 graphs of 33..128 nodes with ``wide_backward``,
-                               without gate dropout: ggcn_gate_pool_backward_wide; dispatch.backward_launch names the launch)
+                               without gate dropout: ggcn_gate_pool_backward_wide; real-valued ones of 33..128 nodes with
+                               ``weighted_wide_backward``: ggcn_gate_pool_backward_weighted_wide; dispatch.backward_launch names
+                               the launch)
         dX = dH.W^T            HIP bf16x3 MFMA linear on the packed W^T (bfloat16 features: stored as bf16, RNE)
         dW = X^T.dH            HIP split-K: bf16x3 main loop on X^T and packed dH (dweight_bx3.hip; bfloat16 features:
                                X^T in bf16, ggcn_dweight_bf16), or the exact-fp32 MFMA form for precision 'fp32' (dweight_fp32.hip)
@@ -173,7 +179,7 @@ class _GatedLayerFunction(torch.autograd.Function):
             need_adj = ctx.adj_dtype is not None and need[11]
             operands = (out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum)
             launch, dx_form, dw_form = dispatch.backward_launch(layer, csr, text.dtype, B, K, F, need[0], need_adj, ctx.dropout, operands)
-            entry, graph, writes, tail = _BACKWARD_LAUNCHES[launch]
+            entry, graph, writes, tail = (_BACKWARD_LAUNCHES if launch in _BACKWARD_LAUNCHES else _WEIGHTED_WIDE_BACKWARD_LAUNCHES)[launch]
             dh_amax = torch.zeros(1, **f32) if dx_form == "scaled" else None
             dy = torch.empty(B * T, F, **f32) if (writes == "dY" or (writes == "both" and need_adj)) else None
             # "drop": the keep factors of the forward launch, drawn again from (seed, element)
@@ -294,6 +300,13 @@ class GraphConvolution(nn.Module):
         # passes stay.  Off by default: dH's sums differ in the last bits.
         self.wide_backward = (bool(getattr(opt, "ggcn_wide_backward", False))
                               or os.environ.get("GGCN_WIDE_BACKWARD", "0") == "1")
+        # a REAL-valued adjacency of graphs of 33..128 nodes under autograd (a soft or learned graph at LitBank's lengths) without
+        # gate dropout: gate / pool backward and dH = A_w^T.D.dY as ONE launch on the matrix cores
+        # (ggcn_gate_pool_backward_weighted_wide on BatchedCSR.graph_ops_weighted_wide_t; dispatch.takes_weighted_wide_backward)
+        # instead of ggcn_gate_pool_backward + a transposed CSR + ggcn_aggregate_t; dY is stored only for an adjacency gradient.
+        # Separate from weighted_backward, which stays what it is at 33 nodes.  Off by default: dH's sums differ in the last bits.
+        self.weighted_wide_backward = (bool(getattr(opt, "ggcn_weighted_wide_backward", False))
+                                       or os.environ.get("GGCN_WEIGHTED_WIDE_BACKWARD", "0") == "1")
         # dense adjacency handed to forward(): None = let the device detect edge weights (one 4-byte
         # read-back per conversion), True = promise 0/1 entries like the reference's (graph.py:66-74)
         # and stay sync-free, False = always keep the values

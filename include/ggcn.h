@@ -341,6 +341,40 @@ int ggcn_gate_pool_backward_wide(const float *out, int64_t ldo, const float *sto
                                  const uint32_t *rowmask_t, const float *inv, int B, int T, int F, float *dH, int64_t ldh,
                                  float *d_sg, float *d_ga, float *d_gb, float *d_bsum, ggcn_stream_t stream);
 
+/* ggcn_gate_pool_backward_weighted for a REAL-valued adjacency of graphs of 33..128 nodes, without gate dropout: gate / pool
+ * backward and dH = A_w^T . D . dY in ONE launch on the matrix cores -- no transposed CSR, no ggcn_aggregate_t.
+ * ggcn_graph_operands_weighted_wide_t: N = A_w^T (N[s][t] = A_w[t][s]) per graph as W x W blocks of 32 x 32, W = ceil(T/32), each
+ * THREE bf16 planes p0 + p1 + p2 (p0 = RNE bf16 of the entry, p1 of the rest, p2 of what is left: 2^-25 of the entry) of two
+ * k-steps of 64 lanes x 16 bytes in A-operand order (lane l = row l % 32 of the block, element j of k-step k = column
+ * 16 k + 8 (j >> 2) + 4 (l / 32) + (j & 3)): plane p, k-step k of block (s, t) at ((s W + t) * 6 + 2 p + k) * 1024 bytes of the
+ * graph's W^2 * 6144.  Rows and columns >= T are zero; nothing is folded in (1 / (rowsum + 1) stays with dY).  Behind the blocks
+ * of all B graphs: one uint32 per graph, bit 4 s + t set when block (s, t) has a non-zero entry.  Built from the batched CSR
+ * (entries of one (t, s) add up; ids outside the graph are not followed), once per adjacency tensor.  An entry of -0.0 counts as
+ * zero for the summary: a block that holds nothing else is skipped (its products would be zeros of either sign, or NaN against
+ * a D.dY that is not finite).  flag (optional, zeroed by the caller): bit 0 is raised when an entry, or the sum of the entries
+ * of one (t, s), is not finite OR its magnitude is not below 3.0e38 -- a finite value that close to FLT_MAX would round to an
+ * infinite bf16 plane; the caller then keeps the two calls.  ggcn_graph_operands_weighted_wide_t_bytes(B, T) =
+ * B * (W^2 * 6144 + 4), or 0 outside 32 < T <= 128.  Null rowptr / colidx / blocks, B or T < 1 -> GGCN_EINVAL; T <= 32
+ * (ggcn_graph_operands_weighted_t) or T > 128 -> GGCN_EUNSUPPORTED; the blocks must be 16-byte aligned.
+ * ggcn_gate_pool_backward_weighted_wide: arguments exactly as ggcn_gate_pool_backward_weighted, with graph_ops_wwt the blocks
+ * above (16-byte aligned) and inv = float[B*T] 1 / (rowsum(A_w) + 1) (ggcn_inv_denominators).  dY (optional): the unscaled dY
+ * for ggcn_adjacency_grad; NULL: no dY store, and dH is bit for bit the same.  One workgroup per graph; per 32 columns the
+ * winners of both pools are found over all W row blocks, then D.dY of every source block is split into three bf16 planes and
+ * multiplied by the non-empty blocks of N: the six plane products of weight >= 2^-16, smallest first (12 MFMAs per block), source
+ * blocks in ascending order.  No atomics, a fixed summation order: bit-identical from run to run; dH differs from the two calls'
+ * in the last bits.  No form under gate dropout.
+ * Needs 32 < T <= 128, F % 4 == 0, ldh % 4 == 0, 16-byte aligned dH / graph_ops_wwt, a graph's rows (in whole 32-row blocks) below
+ * 2 GiB (GGCN_EUNSUPPORTED); null out / dH / graph_ops_wwt / inv, B, T or F < 1, a leading dimension below F (ldy where dY is
+ * given) -> GGCN_EINVAL; every check comes before the launch. */
+size_t ggcn_graph_operands_weighted_wide_t_bytes(int B, int T);
+int ggcn_graph_operands_weighted_wide_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T,
+                                        void *graph_ops_wwt, int32_t *flag, ggcn_stream_t stream);
+int ggcn_gate_pool_backward_weighted_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a,
+                                          const float *gate_b, const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb,
+                                          const void *graph_ops_wwt, const float *inv, int B, int T, int F, float *dH, int64_t ldh,
+                                          float *dY, int64_t ldy, float *d_sg, float *d_ga, float *d_gb, float *d_bsum,
+                                          ggcn_stream_t stream);
+
 /* ---- fp16 features (BASELINE configs[3]: 512-token graphs, hidden 1024) ------------------
  * Same operations with X / hidden / out stored as IEEE half and fp32 accumulation; weights
  * (wpack), bias, gates and pooled outputs stay fp32.  The reference cannot run half inputs
