@@ -4,17 +4,13 @@
 //   dY[t] = d_out[t]*sg + [t = argmax_a] d_pa*ga + [t = argmax_b] d_pb*gb         models/bert_amir5.py:627-640 backwards
 //   dH    = A_w^T . D . dY,   D = diag(1 / (rowsum(A_w) + 1))                       models/gcn.py:35,41 backwards (train.py:120)
 //
-// The 0/1 form of this launch is gate_pool_backward_mma.hip; its structure is kept: ONE workgroup per graph (its rows are one
-// contiguous block of `out`, `d_out`, dH and dY), four wavefronts that walk the 64-column groups w, w + 4, ..., lane (c, h)
-// holding the 16 rows (r & 3) + 8 (r >> 2) + 4 h of column c -- the accumulator's register -> row map and the k order of the
-// operand blocks -- buffer-resource loads whose range check zeroes rows >= T, dH through LDS as 16-byte row stores.  The element
-// math before the MFMAs (y read back from `out`, both arg-maxima with ties to the smaller row, dY, d_sg, d_ga, d_gb, d_bsum in
-// two partial sums per column) is that kernel's, line for line.  What differs:
+// The tile is gate_pool_backward_tile.h, the loop gate_pool_backward_mma.hip's (the 0/1 form of this launch): one workgroup per
+// graph, four wavefronts that walk the 64-column groups w, w + 4, ..., two 32-column tiles per group, one pass each.  This
+// file's own:
 //   * A^T is no 0/1 operand: N = A_w^T arrives as THREE bf16 planes (n0 + n1 + n2 = N to 2^-24 of an entry) in
 //     ggcn_graph_operands_weighted_t blocks, built once per adjacency from the CSR (graph_operands_wt_kernel below: no transposed
-//     CSR).  D.dY is split into three planes y0 + y1 + y2 as before.  Of the nine plane products the six whose weight is
-//     >= 2^-16 of the leading one are kept -- n0.y0, n0.y1, n1.y0, n0.y2, n1.y1, n2.y0 -- and summed smallest first:
-//     12 MFMAs per 32-column tile where the 0/1 form needs 6.  The dropped products are 2^-24 of the leading one.
+//     CSR).  D.dY is split into three planes y0 + y1 + y2 as before, and the six plane products of GGCN_MMA_PLANES6 -- n0.y0, n0.y1,
+//     n1.y0, n0.y2, n1.y1, n2.y0 -- are summed: 12 MFMAs per 32-column tile where the 0/1 form needs 6.
 //   * 1 / (rowsum + 1) comes from `inv` (ggcn_inv_denominators: float[B*T]), not from a 0/1 operand block's table; nothing is
 //     folded into N, so the blocks depend on the adjacency's entries alone.
 //   * dY (optional): the UNSCALED dY, stored for ggcn_adjacency_grad, which reads it from memory.  NULL: nothing of size
@@ -30,39 +26,19 @@
 // Registers (`make resources`): with the three operand planes held in 24 VGPRs and dY stored through lane pointers the kernel
 // wants 208 VGPRs and spills 92 bytes per lane under __launch_bounds__(256, 3).  So the planes wait in LDS (6 KiB per workgroup,
 // read per tile right before the MFMAs) and dY leaves through a buffer resource (scalar row offsets, no address pairs):
-// 165 VGPRs, no scratch, 38 KiB of LDS -- three workgroups per CU, as the 0/1 form (150 VGPRs).
+// 153 VGPRs, no scratch, 38 KiB of LDS -- three workgroups per CU (at most 168 VGPRs), as the 0/1 form (149 VGPRs).
 // DROP: under that bound the keep factors spill 84 bytes per lane, so the DROP instantiation alone is bound to TWO workgroups per
-// CU: 219 VGPRs, no scratch.  The instantiation without dropout keeps the figures above.
-#include "bf16x3_core.h"
-#include "common.h"
+// CU: 189 VGPRs, no scratch.  The instantiation without dropout keeps the figures above.
 #include "dropout_hash.h"
+#include "gate_pool_backward_tile.h"
 
 namespace ggcn {
 namespace {
 
 using namespace bx3;
+using namespace gpb;
 
 constexpr int kOpsBytesWT = GGCN_GRAPH_OPSWT_BYTES;   // plane p, k-step s at (2 p + s) * 1024: 64 lanes x 16 bytes
-
-__device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// v -> three bf16 planes (p0 + p1 + p2 = v to 2^-25) as B-operand fragments of the two k-steps
-__device__ __forceinline__ void split3(const float (&v)[16], bf16x8 (&f)[3][2])
-{
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float x = v[8 * s + e];
-            const __bf16 p0 = (__bf16)x;
-            const float r1 = x - (float)p0;
-            const __bf16 p1 = (__bf16)r1;
-            const float r2 = r1 - (float)p1;
-            f[0][s][e] = p0;
-            f[1][s][e] = p1;
-            f[2][s][e] = (__bf16)r2;
-        }
-}
 
 template <bool DROP>
 __global__ __launch_bounds__(256, DROP ? 2 : 3) void gate_pool_backward_weighted_kernel(
@@ -97,94 +73,55 @@ __global__ __launch_bounds__(256, DROP ? 2 : 3) void gate_pool_backward_weighted
 #pragma unroll 1   // (one tile at a time, as in the 0/1 form)
     for (int j = 0; j < 2; ++j) {
         if (col0 + 32 * j >= F) break;   // wavefront-uniform: the group's last tile
-        const int col = col0 + 32 * j + c;
-        const bool cok = col < F;
-        const int colc = cok ? col : 0;      // (a lane past F works on column 0's data and stores nothing)
-        const int64_t gf = (int64_t)b * F + colc;
-        const float sg = store_gate ? store_gate[gf] : 1.0f;
-        const float inv_sg = store_gate ? (sg != 0.0f ? 1.0f / sg : 0.0f) : 1.0f;
-        const float ga = gate_a ? gate_a[gf] : 1.0f, gb = gate_b ? gate_b[gf] : 1.0f;
-        const float dpa = d_pa ? d_pa[gf] : 0.0f, dpb = d_pb ? d_pb[gf] : 0.0f;
-        // the graph's rows of `out` and `d_out` behind buffer resources that END with its last row: a lane's 16 rows are one lane
-        // offset (its column, its half's 4-row shift) + 16 SCALAR offsets, and rows past T read zeros by the hardware's range check
-        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(out + (int64_t)b * T * ldo), 0,
-                                                                              (int)((((int64_t)T - 1) * ldo + F) * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>((d_out ? d_out : out) + (int64_t)b * T * (d_out ? ldd : ldo)), 0,
-                                                                              d_out ? (int)((((int64_t)T - 1) * ldd + F) * 4) : 0, 0x00020000);
-        const int ovoff = (int)((4 * h * ldo + colc) * 4), dvoff = (int)((4 * h * ldd + colc) * 4);
+        const Column k = column_operands(b, col0 + 32 * j + c, F, store_gate, gate_a, gate_b, d_pa, d_pb);
         float ov[16], dv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rs = (r & 3) + 8 * (r >> 2);   // this lane's row is rs + 4 h
-            ov[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(orsrc, ovoff, (int)(rs * ldo * 4), 0));
-            dv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(drsrc, dvoff, (int)(rs * ldd * 4), 0));   // (no d_out: an empty resource, zeros)
-        }
-        // forward values and the pools' winners (bert_amir5.py:627-640): first maximum in ascending row order
-        float best_a = -INFINITY, best_b = -INFINITY, ya = 0.0f, yb = 0.0f, acc_sg = 0.0f;
-        int ia = 0, ib = 0;
+        GraphRows(out, ldo, d_out, ldd, b, T, F, h, k.colc).load(0, ov, dv);
+        Winners w;
         // DROP: the element of this lane's row 4 h (rows add rs * F), as the forward launch and ggcn_dropout_mask count it
-        const uint32_t e0 = DROP ? (uint32_t)(((int64_t)b * T + 4 * h) * F + colc) : 0u;
+        const uint32_t e0 = DROP ? (uint32_t)(((int64_t)b * T + 4 * h) * F + k.colc) : 0u;
+        if constexpr (DROP) {   // scan_rows under the keep factors
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = row_of(r, h);
-            const bool valid = row < T;
-            if constexpr (DROP) {
+            for (int r = 0; r < 16; ++r) {
+                const int row = row_of(r, h);
+                const bool valid = row < T;
                 const uint32_t hh = drop_hash(e0 + (uint32_t)(((r & 3) + 8 * (r >> 2)) * F), drop.seed_lo, drop.seed_hi);
                 const float ks = drop_keep(hh, drop.sel[0], drop.thr, drop.scale);
                 const float ka = drop_keep(hh, drop.sel[1], drop.thr, drop.scale);
                 const float kb = drop_keep(hh, drop.sel[2], drop.thr, drop.scale);
-                const float y = ks != 0.0f ? ov[r] * inv_sg / ks : 0.0f;   // (rows past T: 0)
-                const float va = y * ga * ka, vb = y * gb * kb;
-                if (valid && va > best_a) { best_a = va; ia = row; ya = y * ka; }
-                if (valid && vb > best_b) { best_b = vb; ib = row; yb = y * kb; }
-                acc_sg = fmaf(dv[r], y * ks, acc_sg);
-            } else {
-                const float y = ov[r] * inv_sg;          // (rows past T: 0)
-                const float va = y * ga, vb = y * gb;
-                if (valid && va > best_a) { best_a = va; ia = row; ya = y; }
-                if (valid && vb > best_b) { best_b = vb; ib = row; yb = y; }
-                acc_sg = fmaf(dv[r], y, acc_sg);
+                const float y = ks != 0.0f ? ov[r] * k.inv_sg / ks : 0.0f;   // (rows past T: 0)
+                const float va = y * k.ga * ka, vb = y * k.gb * kb;
+                if (valid && va > w.best_a) { w.best_a = va; w.ia = row; w.ya = y * ka; }
+                if (valid && vb > w.best_b) { w.best_b = vb; w.ib = row; w.yb = y * kb; }
+                w.acc_sg = fmaf(dv[r], y * ks, w.acc_sg);
             }
+        } else {
+            scan_rows(w, k, ov, dv, 0, h, T);
         }
-        {   // the two lane halves hold different rows of the same column: the smaller row wins a tie
-            const float oa = __shfl_xor(best_a, 32), oya = __shfl_xor(ya, 32);
-            const int oia = __shfl_xor(ia, 32);
-            const bool ta = oa > best_a || (oa == best_a && oia < ia);
-            best_a = ta ? oa : best_a; ia = ta ? oia : ia; ya = ta ? oya : ya;
-            const float ob = __shfl_xor(best_b, 32), oyb = __shfl_xor(yb, 32);
-            const int oib = __shfl_xor(ib, 32);
-            const bool tb = ob > best_b || (ob == best_b && oib < ib);
-            best_b = tb ? ob : best_b; ib = tb ? oib : ib; yb = tb ? oyb : yb;
-        }
-        // dY (stored unscaled where the adjacency gradient wants it) and D.dY in register order
+        exchange_halves(w);
+        // dY (stored unscaled where the adjacency gradient wants it, behind a resource like the loads') and D.dY in register order
         float gw[16], bsum = 0.0f;
-        const float pa_g = dpa * ga, pb_g = dpb * gb;
-        // (dY behind a resource that ends with the graph's last row, like the loads: one lane offset + 16 scalar offsets)
-        const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(dY ? dY + (int64_t)b * T * ldy : const_cast<float *>(out), 0,
-                                                                              dY ? (int)((((int64_t)T - 1) * ldy + F) * 4) : 0, 0x00020000);
-        const int yvoff = (int)((4 * h * ldy + colc) * 4);
+        const float pa_g = k.dpa * k.ga, pb_g = k.dpb * k.gb;
+        const __amdgpu_buffer_rsrc_t yrsrc = graph_rows(dY, ldy, b, T, F, out);
+        const int yvoff = lane_voff(h, ldy, k.colc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = row_of(r, h);
             float g;
             if constexpr (DROP) {   // the keep factors once more (see the head of the file)
                 const uint32_t hh = drop_hash(e0 + (uint32_t)(((r & 3) + 8 * (r >> 2)) * F), drop.seed_lo, drop.seed_hi);
-                g = dv[r] * sg * drop_keep(hh, drop.sel[0], drop.thr, drop.scale);
-                if (d_pa && row == ia && row < T) g = fmaf(dpa, ga * drop_keep(hh, drop.sel[1], drop.thr, drop.scale), g);
-                if (d_pb && row == ib && row < T) g = fmaf(dpb, gb * drop_keep(hh, drop.sel[2], drop.thr, drop.scale), g);
+                g = dv[r] * k.sg * drop_keep(hh, drop.sel[0], drop.thr, drop.scale);
+                if (wins_a(k, w, row, T)) g = fmaf(k.dpa, k.ga * drop_keep(hh, drop.sel[1], drop.thr, drop.scale), g);
+                if (wins_b(k, w, row, T)) g = fmaf(k.dpb, k.gb * drop_keep(hh, drop.sel[2], drop.thr, drop.scale), g);
             } else {
-                g = dv[r] * sg;
-                if (d_pa && row == ia && row < T) g += pa_g;
-                if (d_pb && row == ib && row < T) g += pb_g;
+                g = dy_row(k, w, dv[r], row, T, pa_g, pb_g);
             }
             bsum += g;
-            if (dY && cok && row < T)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g), yrsrc, yvoff, (int)(((r & 3) + 8 * (r >> 2)) * ldy * 4), 0);
+            if (dY && k.cok && row < T) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g), yrsrc, yvoff, row_soff(0, r, ldy), 0);
             gw[r] = g * rinv[r];                                   // gcn.py:35: the row's own 1 / (rowsum + 1)
         }
         bsum += __shfl_xor(bsum, 32);
-        acc_sg += __shfl_xor(acc_sg, 32);
-        // dH tile = N . (D.dY), N = n0 + n1 + n2, D.dY = y0 + y1 + y2: the six products of weight >= 2^-16, smallest first
+        w.acc_sg += __shfl_xor(w.acc_sg, 32);
+        // dH tile = N . (D.dY), N = n0 + n1 + n2, D.dY = y0 + y1 + y2
         bf16x8 pl[3][2];
         split3(gw, pl);
         bf16x8 nft[3][2];
@@ -199,36 +136,11 @@ __global__ __launch_bounds__(256, DROP ? 2 : 3) void gate_pool_backward_weighted
         f32x16 y;
 #pragma unroll
         for (int r = 0; r < 16; ++r) y[r] = 0.0f;
-#define GGCN_NY(P, Q)                                                                                       \
-        _Pragma("unroll") for (int s = 0; s < 2; ++s) y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(nft[P][s], pl[Q][s], y, 0, 0, 0)
-        GGCN_NY(2, 0); GGCN_NY(1, 1); GGCN_NY(0, 2);   // 2^-16
-        GGCN_NY(1, 0); GGCN_NY(0, 1);                  // 2^-8
-        GGCN_NY(0, 0);
-#undef GGCN_NY
-#pragma unroll
-        for (int r = 0; r < 16; ++r)   // staged for the 16-byte row stores below (rows with bit 2 set swap their 32-column halves)
-            stage[row_of(r, h) * 64 + ((32 * j + c) ^ (32 * h))] = y[r];
-        if (h == 0 && cok) {
-            if (d_bsum) d_bsum[gf] = bsum;
-            if (d_sg) d_sg[gf] = acc_sg;
-            if (d_ga) d_ga[gf] = dpa * ya;
-            if (d_gb) d_gb[gf] = dpb * yb;
-        }
+        GGCN_MMA_PLANES6(y, nft, pl);
+        stage64_put(stage, y, j, c, h);
+        store_column_grads(k, w, h, bsum, d_bsum, d_sg, d_ga, d_gb);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    {
-        const int colq = (lane & 15) * 4;
-        float *gbase = dH + (int64_t)b * T * ldh + col0 + colq;
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int row = 4 * it + (lane >> 4);
-            const float4 v4 = *reinterpret_cast<const float4 *>(&stage[row * 64 + (colq ^ (32 * ((row >> 2) & 1)))]);
-            if (row < T && col0 + colq < F) *reinterpret_cast<float4 *>(gbase + (int64_t)row * ldh) = v4;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (the next group's tiles overwrite the staging area)
-    __builtin_amdgcn_wave_barrier();
+    stage64_store(stage, dH, ldh, b, T, F, col0, lane);
     }   // column groups
 }
 
@@ -272,10 +184,8 @@ __global__ __launch_bounds__(256) void graph_operands_wt_kernel(const int32_t *_
             const int t = 16 * s + 8 * (j >> 2) + 4 * h + (j & 3);   // the column of N = the row of A_w
             const float x = dense[t * 33 + s_row];
             bad = bad || !(fabsf(x) < 3.0e38f);                      // (a sum of finite duplicates may overflow)
-            const __bf16 p0 = (__bf16)x;
-            const float r1 = x - (float)p0;
-            const __bf16 p1 = (__bf16)r1;
-            const __bf16 p2 = (__bf16)(r1 - (float)p1);
+            __bf16 p0, p1, p2;
+            planes_of(x, p0, p1, p2);
             pl[0].u[j] = __builtin_bit_cast(unsigned short, p0);
             pl[1].u[j] = __builtin_bit_cast(unsigned short, p1);
             pl[2].u[j] = __builtin_bit_cast(unsigned short, p2);
@@ -318,18 +228,14 @@ int gate_pool_backward_weighted(const float *out, int64_t ldo, const float *stor
     if (!dH) return fail(GGCN_EINVAL, "%s: dH is null", who);
     if (!inv) return fail(GGCN_EINVAL, "%s: inv is null", who);
     if (!graph_ops_wt) return fail(GGCN_EINVAL, "%s: graph_ops_wt is null", who);
-    if (B < 0 || T < 1 || F < 1) return fail(GGCN_EINVAL, "%s: B=%d T=%d F=%d (B >= 0, T and F positive)", who, B, T, F);
-    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32; use ggcn_gate_pool_backward + ggcn_aggregate_t", who, T);
-    if (ldo < F || ldh < F || (d_out && ldd < F) || (dY && ldy < F))
-        return fail(GGCN_EINVAL, "%s: leading dimension (ldo, ldd, ldh, ldy) smaller than F=%d", who, F);
-    int64_t ldmax = ldo > ldh ? ldo : ldh;
-    if (d_out && ldd > ldmax) ldmax = ldd;
-    if (dY && ldy > ldmax) ldmax = ldy;
-    if ((int64_t)T * ldmax * 4 >= ((int64_t)1 << 31)) return fail(GGCN_EUNSUPPORTED, "%s: a graph's rows exceed 2 GiB", who);
-    if (F % 4 != 0 || ldh % 4 != 0 || ldo % 4 != 0 || (d_out && ldd % 4 != 0) || (dY && ldy % 4 != 0) || !aligned16(dH) ||
-        (dY && !aligned16(dY)) || !aligned16(graph_ops_wt))
-        return fail(GGCN_EUNSUPPORTED, "%s: needs F %% 4 == 0, ldo, ldd, ldh, ldy %% 4 == 0 and 16-byte aligned dH / dY / graph_ops_wt; use "
-                                       "ggcn_gate_pool_backward + ggcn_aggregate_t", who);
+    const EntryRules rules = {who, true, 1, "", 32, " (ldo, ldd, ldh, ldy)", false,
+                              "F % 4 == 0, ldo, ldd, ldh, ldy % 4 == 0 and 16-byte aligned dH / dY / graph_ops_wt; use "
+                              "ggcn_gate_pool_backward + ggcn_aggregate_t"};
+    const int64_t ldd_in = d_out ? ldd : F, ldy_in = dY ? ldy : F;   // (an operand that is not there: its leading dimension is not read)
+    if (const int rc = backward_entry_checks(rules, B, T, F, {ldo, ldh, ldd_in, ldy_in}, {ldo, ldh, ldd_in, ldy_in},
+                                             F % 4 == 0 && ldh % 4 == 0 && ldo % 4 == 0 && ldd_in % 4 == 0 && ldy_in % 4 == 0 && aligned16(dH) &&
+                                                 (!dY || aligned16(dY)) && aligned16(graph_ops_wt)))
+        return rc;
     if (drop && (int64_t)B * T * F >= ((int64_t)1 << 32))
         return fail(GGCN_EUNSUPPORTED, "%s: gate dropout indexes elements with 32 bits (B*T*F = %lld)", who, (long long)B * T * F);
     if (B == 0) return GGCN_OK;

@@ -4,19 +4,14 @@
 //   dY[t] = d_out[t]*sg + [t = argmax_a] d_pa*ga + [t = argmax_b] d_pb*gb         models/bert_amir5.py:627-640 backwards
 //   dH    = A_w^T . D . dY,   D = diag(1 / (rowsum(A_w) + 1))                       models/gcn.py:35,41 backwards (train.py:120)
 //
-// The 0/1 form of this launch is gate_pool_backward_wide.hip; its structure is kept as a COPY (no shared header: that file's code
-// object stays what it was): ONE workgroup per graph (its rows are one contiguous block of `out`, `d_out`, dH and dY), four
-// wavefronts that walk the 32-column tiles w, w + 4, ..., lane (c, h) holding, of column c and of every 32-row block, the 16 rows
-// (r & 3) + 8 (r >> 2) + 4 h -- the accumulator's register -> row map and the k order of the operand blocks -- buffer-resource
-// loads whose range check zeroes rows >= T, dH through LDS as 16-byte row stores, winners = the first maximum in ascending row
-// order (strict > inside a lane, whose rows ascend with block and register; the smaller row wins between the two lane halves).
-// Pass 1 walks the NB = ceil(T/32) row blocks of `out` and `d_out` for the winners and d_sg; pass 2 reloads d_out per SOURCE block
-// t (L2-hot), forms dY and D.dY and splits the latter into three bf16 planes y0 + y1 + y2 (split3: residual 2^-25).  What differs:
+// The tile is gate_pool_backward_tile.h, the two-pass loop gate_pool_backward_wide.hip's (the 0/1 form of this launch): one
+// workgroup per graph, four wavefronts that walk the 32-column tiles w, w + 4, ...; pass 1 walks the NB = ceil(T/32) row blocks
+// of `out` and `d_out` for the winners and d_sg; pass 2 reloads d_out per SOURCE block t (L2-hot), forms dY and D.dY and splits
+// the latter into three bf16 planes y0 + y1 + y2.  This file's own:
 //   * A^T is no 0/1 operand: N = A_w^T arrives as THREE bf16 planes n0 + n1 + n2 per 32 x 32 block
 //     (ggcn_graph_operands_weighted_wide_t, built once per adjacency from the CSR: no transposed CSR), the three-plane scheme of
-//     gate_pool_backward_weighted.hip.  Of the nine plane products the six whose weight is >= 2^-16 of the leading one are kept
-//     -- n0.y0, n0.y1, n1.y0, n0.y2, n1.y1, n2.y0 -- and added smallest first into acc[s] for every DESTINATION block s whose
-//     (s, t) block is not empty: 12 MFMAs (v_mfma_f32_32x32x16_bf16) per block where the 0/1 form needs 6.
+//     gate_pool_backward_weighted.hip.  The six plane products of GGCN_MMA_PLANES6 are added into acc[s] for every DESTINATION block s
+//     whose (s, t) block is not empty: 12 MFMAs (v_mfma_f32_32x32x16_bf16) per block where the 0/1 form needs 6.
 //   * the A-operand fragments come straight from global memory / L2 in fragment order (6 x 1 KiB per block, one 16-byte load per
 //     lane and fragment): 96 KiB per graph at NB = 4 does not fit in LDS beside a second workgroup.  They are requested one
 //     non-empty block AHEAD of their MFMAs (two sets of 24 registers), so that a block's L2 latency lies under the block before
@@ -38,37 +33,15 @@
 // Registers (`make resources`): 214 VGPRs (four accumulators, two sets of six fragments, the loads of a block in flight), no
 // scratch, 18944 bytes of LDS: two workgroups per CU (__launch_bounds__(256, 2)).  graph_operands_wwt_kernel: 63 VGPRs, no
 // scratch, 65552 bytes of LDS (four strips of 32 x 128 floats), two workgroups per CU.
-#include "bf16x3_core.h"
-#include "common.h"
+#include "gate_pool_backward_tile.h"
 
 namespace ggcn {
 namespace {
 
 using namespace bx3;
+using namespace gpb;
 
-constexpr int kMaxT = 128, kMaxNB = kMaxT / 32;
-constexpr int kStageLd = 36;          // words per staged row: 16-byte aligned, and the two lane halves (4 rows apart) miss each other's banks
 constexpr int kBlockBytes = 6 * 1024; // one 32 x 32 block of A_w^T: plane p, k-step k at (2 p + k) * 1024, 64 lanes x 16 bytes
-
-__device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// v -> three bf16 planes (p0 + p1 + p2 = v to 2^-25) as B-operand fragments of the two k-steps
-__device__ __forceinline__ void split3(const float (&v)[16], bf16x8 (&f)[3][2])
-{
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float x = v[8 * s + e];
-            const __bf16 p0 = (__bf16)x;
-            const float r1 = x - (float)p0;
-            const __bf16 p1 = (__bf16)r1;
-            const float r2 = r1 - (float)p1;
-            f[0][s][e] = p0;
-            f[1][s][e] = p1;
-            f[2][s][e] = (__bf16)r2;
-        }
-}
 
 __global__ __launch_bounds__(256, 2) void gate_pool_backward_weighted_wide_kernel(
     const float *__restrict__ out, int64_t ldo, const float *__restrict__ store_gate, const float *__restrict__ gate_a,
@@ -114,16 +87,9 @@ __global__ __launch_bounds__(256, 2) void gate_pool_backward_weighted_wide_kerne
 
 #pragma unroll 1
     for (int col0 = wave * 32; col0 < F; col0 += 128) {   // wavefront-uniform walk over this wavefront's 32-column tiles
-        const int col = col0 + c;
-        const bool cok = col < F;
-        const int colc = cok ? col : 0;      // (a lane past F works on column 0's data and stores nothing)
-        const int64_t gf = (int64_t)b * F + colc;
-        const float sg = store_gate ? store_gate[gf] : 1.0f;
-        const float inv_sg = store_gate ? (sg != 0.0f ? 1.0f / sg : 0.0f) : 1.0f;
-        const float ga = gate_a ? gate_a[gf] : 1.0f, gb = gate_b ? gate_b[gf] : 1.0f;
-        const float dpa = d_pa ? d_pa[gf] : 0.0f, dpb = d_pb ? d_pb[gf] : 0.0f;
-        // the graph's rows of `out`, `d_out` and dY behind buffer resources that END with its last row: a lane's rows are one lane
-        // offset (its column, its half's 4-row shift) + SCALAR offsets, and rows past T read zeros by the hardware's range check
+        const Column k = column_operands(b, col0 + c, F, store_gate, gate_a, gate_b, d_pa, d_pb);
+        // (this kernel's own text, not GraphRows: through the struct the kernel keeps 12 more scalars in VGPR lanes)
+        const int colc = k.colc;
         const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(out + (int64_t)b * T * ldo), 0,
                                                                               (int)((((int64_t)T - 1) * ldo + F) * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>((d_out ? d_out : out) + (int64_t)b * T * (d_out ? ldd : ldo)), 0,
@@ -132,39 +98,19 @@ __global__ __launch_bounds__(256, 2) void gate_pool_backward_weighted_wide_kerne
                                                                               dY ? (int)((((int64_t)T - 1) * ldy + F) * 4) : 0, 0x00020000);
         const int ovoff = (int)((4 * h * ldo + colc) * 4), dvoff = (int)((4 * h * ldd + colc) * 4), yvoff = (int)((4 * h * ldy + colc) * 4);
 
-        // ---- pass 1: forward values and the pools' winners (bert_amir5.py:627-640) over every row block, d_sg
-        float best_a = -INFINITY, best_b = -INFINITY, ya = 0.0f, yb = 0.0f, acc_sg = 0.0f;
-        int ia = 0, ib = 0;
+        // ---- pass 1: the pools' winners over every row block, d_sg
+        Winners w;
 #pragma unroll 1
         for (int blk = 0; blk < nb; ++blk) {
             float ov[16], dv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rs = 32 * blk + (r & 3) + 8 * (r >> 2);   // this lane's row is rs + 4 h
-                ov[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(orsrc, ovoff, (int)(rs * ldo * 4), 0));
-                dv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(drsrc, dvoff, (int)(rs * ldd * 4), 0));   // (no d_out: an empty resource, zeros)
+                ov[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(orsrc, ovoff, row_soff(blk, r, ldo), 0));
+                dv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(drsrc, dvoff, row_soff(blk, r, ldd), 0));   // (no d_out: zeros)
             }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = 32 * blk + row_of(r, h);
-                const bool valid = row < T;
-                const float y = ov[r] * inv_sg;          // (rows past T: 0)
-                const float va = y * ga, vb = y * gb;
-                if (valid && va > best_a) { best_a = va; ia = row; ya = y; }
-                if (valid && vb > best_b) { best_b = vb; ib = row; yb = y; }
-                acc_sg = fmaf(dv[r], y, acc_sg);
-            }
+            scan_rows(w, k, ov, dv, blk, h, T);
         }
-        {   // the two lane halves hold different rows of the same column: the smaller row wins a tie
-            const float oa = __shfl_xor(best_a, 32), oya = __shfl_xor(ya, 32);
-            const int oia = __shfl_xor(ia, 32);
-            const bool ta = oa > best_a || (oa == best_a && oia < ia);
-            best_a = ta ? oa : best_a; ia = ta ? oia : ia; ya = ta ? oya : ya;
-            const float ob = __shfl_xor(best_b, 32), oyb = __shfl_xor(yb, 32);
-            const int oib = __shfl_xor(ib, 32);
-            const bool tb = ob > best_b || (ob == best_b && oib < ib);
-            best_b = tb ? ob : best_b; ib = tb ? oib : ib; yb = tb ? oyb : yb;
-        }
+        exchange_halves(w);
 
         // ---- pass 2: per source block t, dY (stored unscaled where the adjacency gradient wants it) and D.dY in register order,
         //      then dH[s] += N(s, t) . (D.dY)(t) for every live s
@@ -174,33 +120,31 @@ __global__ __launch_bounds__(256, 2) void gate_pool_backward_weighted_wide_kerne
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[s][r] = 0.0f;
         float bsum = 0.0f;
-        const double sg64 = sg, pa_g64 = (double)dpa * ga, pb_g64 = (double)dpb * gb;
+        const double sg64 = k.sg, pa_g64 = (double)k.dpa * k.ga, pb_g64 = (double)k.dpb * k.gb;
 #pragma unroll 1
         for (int t = 0; t < nb; ++t) {
-            float dv[16], rinv[16];
+            float dv[16], rinv[16], gw[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rs = 32 * t + (r & 3) + 8 * (r >> 2);
-                dv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(drsrc, dvoff, (int)(rs * ldd * 4), 0));
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v4 = *reinterpret_cast<const float4 *>(&sinv[32 * t + 8 * q + 4 * h]);
-                rinv[4 * q] = v4.x; rinv[4 * q + 1] = v4.y; rinv[4 * q + 2] = v4.z; rinv[4 * q + 3] = v4.w;
-            }
-            float gw[16];
+            for (int r = 0; r < 16; ++r) dv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(drsrc, dvoff, row_soff(t, r, ldd), 0));
+            rinv_of_block(sinv, t, h, rinv);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = 32 * t + row_of(r, h);
                 // one rounding: the products are exact in float64, so a pool term that cancels d_out * sg costs no relative accuracy
                 double g64 = (double)dv[r] * sg64;
-                if (d_pa && row == ia && row < T) g64 += pa_g64;
-                if (d_pb && row == ib && row < T) g64 += pb_g64;
+                if (wins_a(k, w, row, T)) g64 += pa_g64;
+                if (wins_b(k, w, row, T)) g64 += pb_g64;
                 const float g = (float)g64;
                 bsum += g;
-                if (dY && cok && row < T)
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g), yrsrc, yvoff, (int)((32 * t + (r & 3) + 8 * (r >> 2)) * ldy * 4), 0);
-                gw[r] = g * rinv[r];                                   // gcn.py:35: the row's own 1 / (rowsum + 1)
+                if (dY && k.cok && row < T) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g), yrsrc, yvoff, row_soff(t, r, ldy), 0);
+                {   // gcn.py:35: the row's own 1 / (rowsum + 1).  Under -ffp-contract=fast the compiler may fuse this product into
+                    // split3's x - p0 (an fma of the unrounded product).  In the builds of this library it does so in the 0/1 kernels
+                    // (all 16 rows) and in part of the weighted one, and never did here; each kernel's bits are pinned by
+                    // tools/backward_digest.py against the build before it.  Here the compiler began to fuse 4 of the 16 rows once the
+                    // split moved into the shared header, so the rounding this kernel always had is written down:
+#pragma clang fp contract(off)
+                    gw[r] = g * rinv[r];
+                }
             }
             bf16x8 pl[3][2];
             split3(gw, pl);
@@ -211,28 +155,17 @@ __global__ __launch_bounds__(256, 2) void gate_pool_backward_weighted_wide_kerne
                 const uint32_t rest = live_t >> (q + 1);
                 bf16x8 nxt[3][2];
                 load6(nxt, rest ? q + 1 + __builtin_ctz(rest) : __builtin_ctz(live_t));
-#define GGCN_NY(P, Q)                                                                                                  \
-                _Pragma("unroll") for (int k = 0; k < 2; ++k) acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur[P][k], pl[Q][k], acc[s], 0, 0, 0)
-                GGCN_NY(2, 0); GGCN_NY(1, 1); GGCN_NY(0, 2);   // 2^-16
-                GGCN_NY(1, 0); GGCN_NY(0, 1);                  // 2^-8
-                GGCN_NY(0, 0);
+                GGCN_MMA_PLANES6(acc[s], cur, pl);
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
-                    for (int k = 0; k < 2; ++k) cur[p][k] = nxt[p][k];
-#undef GGCN_NY
+                    for (int kk = 0; kk < 2; ++kk) cur[p][kk] = nxt[p][kk];
             }
         }
         bsum += __shfl_xor(bsum, 32);
-        acc_sg += __shfl_xor(acc_sg, 32);
-        if (h == 0 && cok) {
-            if (d_bsum) d_bsum[gf] = bsum;
-            if (d_sg) d_sg[gf] = acc_sg;
-            if (d_ga) d_ga[gf] = dpa * ya;
-            if (d_gb) d_gb[gf] = dpb * yb;
-        }
-
-        // ---- dH, one 32-row block at a time: staged, then 16-byte row stores (lane -> row lane >> 3 of eight, columns 4 (lane & 7)..)
+        w.acc_sg += __shfl_xor(w.acc_sg, 32);
+        store_column_grads(k, w, h, bsum, d_bsum, d_sg, d_ga, d_gb);
+        // ---- dH, one 32-row block at a time: store_block36's text in place (through the call the kernel needs 2 more VGPRs)
         const int colq = (lane & 7) * 4;
         float *gbase = dH + (int64_t)b * T * ldh + col0 + colq;
 #pragma unroll
@@ -315,10 +248,8 @@ __global__ __launch_bounds__(256) void graph_operands_wwt_kernel(const int32_t *
                     const float x = dense[t * kMaxT + ((32 * s + s_row + t) & (kMaxT - 1))];
                     bad = bad || !(fabsf(x) < 3.0e38f);                      // (a sum of finite duplicates may overflow)
                     any = any || x != 0.0f;
-                    const __bf16 p0 = (__bf16)x;
-                    const float r1 = x - (float)p0;
-                    const __bf16 p1 = (__bf16)r1;
-                    const __bf16 p2 = (__bf16)(r1 - (float)p1);
+                    __bf16 p0, p1, p2;
+                    planes_of(x, p0, p1, p2);
                     pl[0].u[j] = __builtin_bit_cast(unsigned short, p0);
                     pl[1].u[j] = __builtin_bit_cast(unsigned short, p1);
                     pl[2].u[j] = __builtin_bit_cast(unsigned short, p2);
@@ -368,18 +299,12 @@ int gate_pool_backward_weighted_wide(const float *out, int64_t ldo, const float 
 {
     const char *who = "ggcn_gate_pool_backward_weighted_wide";
     if (!out || !dH || !graph_ops_wwt || !inv) return fail(GGCN_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || T <= 0 || F <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d F=%d must be positive", who, B, T, F);
-    if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32; use ggcn_gate_pool_backward_weighted", who, T);
-    if (T > kMaxT) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 128; use ggcn_gate_pool_backward + ggcn_aggregate_t", who, T);
-    if (ldo < F || ldh < F || (d_out && ldd < F) || (dY && ldy < F)) return fail(GGCN_EINVAL, "%s: leading dimension smaller than F=%d", who, F);
-    int64_t ldmax = ldo > ldh ? ldo : ldh;
-    if (d_out && ldd > ldmax) ldmax = ldd;
-    if (dY && ldy > ldmax) ldmax = ldy;
-    // (whole 32-row blocks: the offsets of the rows past T, which the range check zeroes, must not wrap either)
-    if ((int64_t)32 * ((T + 31) / 32) * ldmax * 4 >= ((int64_t)1 << 31)) return fail(GGCN_EUNSUPPORTED, "%s: a graph's rows exceed 2 GiB", who);
-    if (F % 4 != 0 || ldh % 4 != 0 || !aligned16(dH) || !aligned16(graph_ops_wwt))
-        return fail(GGCN_EUNSUPPORTED, "%s: needs F %% 4 == 0, ldh %% 4 == 0 and 16-byte aligned dH / graph_ops_wwt; use "
-                                       "ggcn_gate_pool_backward + ggcn_aggregate_t", who);
+    const EntryRules rules = {who, false, 33, "ggcn_gate_pool_backward_weighted", kMaxT, "", true,
+                              "F % 4 == 0, ldh % 4 == 0 and 16-byte aligned dH / graph_ops_wwt; use ggcn_gate_pool_backward + ggcn_aggregate_t"};
+    const int64_t ldd_in = d_out ? ldd : F, ldy_in = dY ? ldy : F;   // (an operand that is not there: its leading dimension is not read)
+    if (const int rc = backward_entry_checks(rules, B, T, F, {ldo, ldh, ldd_in, ldy_in}, {ldo, ldh, ldd_in, ldy_in},
+                                             F % 4 == 0 && ldh % 4 == 0 && aligned16(dH) && aligned16(graph_ops_wwt)))
+        return rc;
     const int W = (T + 31) >> 5;
     const char *blocks = static_cast<const char *>(graph_ops_wwt);
     hipLaunchKernelGGL(gate_pool_backward_weighted_wide_kernel, dim3((unsigned)B), dim3(256), 0, st, out, ldo, store_gate, gate_a, gate_b,

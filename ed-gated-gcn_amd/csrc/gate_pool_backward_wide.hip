@@ -4,13 +4,9 @@
 //   dY[t] = d_out[t]*sg + [t = argmax_a] d_pa*ga + [t = argmax_b] d_pb*gb         models/bert_amir5.py:627-640 backwards
 //   dH    = A^T . D . dY,   D = diag(1 / (rowsum(A) + 1))                           models/gcn.py:35,41 backwards (train.py:120)
 //
-// The 32-node form of this launch is gate_pool_backward_mma.hip; its structure is kept: ONE workgroup per graph (its rows are one
-// contiguous block of `out`, `d_out` and dH), four wavefronts that walk the 32-column tiles w, w + 4, ..., lane (c, h) holding, of
-// column c and of every 32-row block, the 16 rows (r & 3) + 8 (r >> 2) + 4 h -- the accumulator's register -> row map and the k
-// order of expand_mask's fragments (expand_mask.h) -- buffer-resource loads whose range check zeroes rows >= T, dH through LDS as 16-byte row
-// stores, winners = the first maximum in ascending row order (strict > inside a lane, whose rows ascend with block and register;
-// the smaller row wins between the two lane halves).  The element math (y read back from `out`, dY, d_sg, d_ga, d_gb, d_bsum in
-// two partial sums per column) is gate_pool_backward_mma_kernel's, line for line.  What differs:
+// The tile is gate_pool_backward_tile.h (its register -> row map is also the k order of expand_mask's fragments, expand_mask.h);
+// the 32-node form of this launch is gate_pool_backward_mma.hip.  One workgroup per graph, four wavefronts that walk the
+// 32-column tiles w, w + 4, ....  This file's own:
 //   * a tile is NB = ceil(T/32) row blocks (2..4), and the pools' winners must be known over all of them before any dY.  Pass 1
 //     walks the blocks of `out` and `d_out` for the winners and d_sg.  Pass 2 reloads d_out per SOURCE block t (L2-hot: the
 //     workgroup read these lines a moment ago; the scalar kernel reads d_out twice as well), forms D.dY, splits it into three bf16
@@ -26,44 +22,20 @@
 //   * 1 / (rowsum + 1) comes from `inv` (ggcn_inv_denominators: float[B*T]) through LDS, zero beyond T.
 //   * no dY output and no max |dH|: an adjacency gradient keeps the two passes, and dX at these lengths is never "scaled".
 //   * no form under gate dropout: ggcn_gate_pool_backward_drop + ggcn_aggregate_t keep that case.
-//   * dH leaves one 32-row block at a time through a 32 x 32 staging tile per wavefront (rows padded to 36 words): 16-byte stores,
-//     eight lanes per 128-byte row segment.
+//   * dH leaves one 32-row block at a time (store_block36).
 // No atomics, a fixed summation order (blocks in ascending t, planes smallest first): bit-identical from run to run.
 // Traffic per layer: out + d_out read, d_out read again (L2), dH written: 3 N F 4 bytes from memory where the two passes move 5.
-// Registers (`make resources`): 222 VGPRs (the compiler keeps the loads of a block in flight next to the four accumulators), no
+// Registers (`make resources`): 207 VGPRs (the compiler keeps the loads of a block in flight next to the four accumulators), no
 // scratch, 21008 bytes of LDS: two workgroups per CU (__launch_bounds__(256, 2); a bound of three spills 100 bytes per lane, of
 // four 312).  rowmask_transpose_wide_kernel: 36 VGPRs, 2 KiB of LDS.
-#include "bf16x3_core.h"
-#include "common.h"
 #include "expand_mask.h"
+#include "gate_pool_backward_tile.h"
 
 namespace ggcn {
 namespace {
 
 using namespace bx3;
-
-constexpr int kMaxT = 128, kMaxNB = kMaxT / 32;
-constexpr int kStageLd = 36;   // words per staged row: 16-byte aligned, and the two lane halves (4 rows apart) miss each other's banks
-
-__device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// v -> three bf16 planes (p0 + p1 + p2 = v to 2^-25) as B-operand fragments of the two k-steps
-__device__ __forceinline__ void split3(const float (&v)[16], bf16x8 (&f)[3][2])
-{
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float x = v[8 * s + e];
-            const __bf16 p0 = (__bf16)x;
-            const float r1 = x - (float)p0;
-            const __bf16 p1 = (__bf16)r1;
-            const float r2 = r1 - (float)p1;
-            f[0][s][e] = p0;
-            f[1][s][e] = p1;
-            f[2][s][e] = (__bf16)r2;
-        }
-}
+using namespace gpb;
 
 __global__ __launch_bounds__(256, 2) void gate_pool_backward_wide_kernel(
     const float *__restrict__ out, int64_t ldo, const float *__restrict__ store_gate, const float *__restrict__ gate_a,
@@ -101,55 +73,18 @@ __global__ __launch_bounds__(256, 2) void gate_pool_backward_wide_kernel(
 
 #pragma unroll 1
     for (int col0 = wave * 32; col0 < F; col0 += 128) {   // wavefront-uniform walk over this wavefront's 32-column tiles
-        const int col = col0 + c;
-        const bool cok = col < F;
-        const int colc = cok ? col : 0;      // (a lane past F works on column 0's data and stores nothing)
-        const int64_t gf = (int64_t)b * F + colc;
-        const float sg = store_gate ? store_gate[gf] : 1.0f;
-        const float inv_sg = store_gate ? (sg != 0.0f ? 1.0f / sg : 0.0f) : 1.0f;
-        const float ga = gate_a ? gate_a[gf] : 1.0f, gb = gate_b ? gate_b[gf] : 1.0f;
-        const float dpa = d_pa ? d_pa[gf] : 0.0f, dpb = d_pb ? d_pb[gf] : 0.0f;
-        // the graph's rows of `out` and `d_out` behind buffer resources that END with its last row: a lane's rows are one lane
-        // offset (its column, its half's 4-row shift) + SCALAR offsets, and rows past T read zeros by the hardware's range check
-        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(out + (int64_t)b * T * ldo), 0,
-                                                                              (int)((((int64_t)T - 1) * ldo + F) * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>((d_out ? d_out : out) + (int64_t)b * T * (d_out ? ldd : ldo)), 0,
-                                                                              d_out ? (int)((((int64_t)T - 1) * ldd + F) * 4) : 0, 0x00020000);
-        const int ovoff = (int)((4 * h * ldo + colc) * 4), dvoff = (int)((4 * h * ldd + colc) * 4);
+        const Column k = column_operands(b, col0 + c, F, store_gate, gate_a, gate_b, d_pa, d_pb);
+        const GraphRows rows(out, ldo, d_out, ldd, b, T, F, h, k.colc);
 
-        // ---- pass 1: forward values and the pools' winners (bert_amir5.py:627-640) over every row block, d_sg
-        float best_a = -INFINITY, best_b = -INFINITY, ya = 0.0f, yb = 0.0f, acc_sg = 0.0f;
-        int ia = 0, ib = 0;
+        // ---- pass 1: the pools' winners over every row block, d_sg
+        Winners w;
 #pragma unroll 1
         for (int blk = 0; blk < nb; ++blk) {
             float ov[16], dv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rs = 32 * blk + (r & 3) + 8 * (r >> 2);   // this lane's row is rs + 4 h
-                ov[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(orsrc, ovoff, (int)(rs * ldo * 4), 0));
-                dv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(drsrc, dvoff, (int)(rs * ldd * 4), 0));   // (no d_out: an empty resource, zeros)
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = 32 * blk + row_of(r, h);
-                const bool valid = row < T;
-                const float y = ov[r] * inv_sg;          // (rows past T: 0)
-                const float va = y * ga, vb = y * gb;
-                if (valid && va > best_a) { best_a = va; ia = row; ya = y; }
-                if (valid && vb > best_b) { best_b = vb; ib = row; yb = y; }
-                acc_sg = fmaf(dv[r], y, acc_sg);
-            }
+            rows.load(blk, ov, dv);
+            scan_rows(w, k, ov, dv, blk, h, T);
         }
-        {   // the two lane halves hold different rows of the same column: the smaller row wins a tie
-            const float oa = __shfl_xor(best_a, 32), oya = __shfl_xor(ya, 32);
-            const int oia = __shfl_xor(ia, 32);
-            const bool ta = oa > best_a || (oa == best_a && oia < ia);
-            best_a = ta ? oa : best_a; ia = ta ? oia : ia; ya = ta ? oya : ya;
-            const float ob = __shfl_xor(best_b, 32), oyb = __shfl_xor(yb, 32);
-            const int oib = __shfl_xor(ib, 32);
-            const bool tb = ob > best_b || (ob == best_b && oib < ib);
-            best_b = tb ? ob : best_b; ib = tb ? oib : ib; yb = tb ? oyb : yb;
-        }
+        exchange_halves(w);
 
         // ---- pass 2: per source block t, dY and D.dY in register order, then dH[s] += A^T(s, t) . (D.dY)(t) for every live s
         f32x16 acc[kMaxNB];
@@ -158,27 +93,15 @@ __global__ __launch_bounds__(256, 2) void gate_pool_backward_wide_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[s][r] = 0.0f;
         float bsum = 0.0f;
-        const float pa_g = dpa * ga, pb_g = dpb * gb;
+        const float pa_g = k.dpa * k.ga, pb_g = k.dpb * k.gb;
 #pragma unroll 1
         for (int t = 0; t < nb; ++t) {
-            float dv[16], rinv[16];
+            float dv[16], rinv[16], gw[16];
+            rows.load_d(t, dv);
+            rinv_of_block(sinv, t, h, rinv);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rs = 32 * t + (r & 3) + 8 * (r >> 2);
-                dv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(drsrc, dvoff, (int)(rs * ldd * 4), 0));
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v4 = *reinterpret_cast<const float4 *>(&sinv[32 * t + 8 * q + 4 * h]);
-                rinv[4 * q] = v4.x; rinv[4 * q + 1] = v4.y; rinv[4 * q + 2] = v4.z; rinv[4 * q + 3] = v4.w;
-            }
-            float gw[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = 32 * t + row_of(r, h);
-                float g = dv[r] * sg;
-                if (d_pa && row == ia && row < T) g += pa_g;
-                if (d_pb && row == ib && row < T) g += pb_g;
+                const float g = dy_row(k, w, dv[r], 32 * t + row_of(r, h), T, pa_g, pb_g);
                 bsum += g;
                 gw[r] = g * rinv[r];                                   // gcn.py:35: the row's own 1 / (deg + 1)
             }
@@ -189,39 +112,16 @@ __global__ __launch_bounds__(256, 2) void gate_pool_backward_wide_kernel(
                 if (!((live >> (4 * s + t)) & 1u)) continue;   // wavefront-uniform: no edge from block t into block s (or s >= nb)
                 bf16x8 af[2];
                 expand_mask(mt[t * kMaxT + 32 * s + c] >> (4 * h), af);
-#pragma unroll
-                for (int p = 2; p >= 0; --p)
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[k], pl[p][k], acc[s], 0, 0, 0);
+                acc[s] = mma_01(af, pl, acc[s]);
             }
         }
         bsum += __shfl_xor(bsum, 32);
-        acc_sg += __shfl_xor(acc_sg, 32);
-        if (h == 0 && cok) {
-            if (d_bsum) d_bsum[gf] = bsum;
-            if (d_sg) d_sg[gf] = acc_sg;
-            if (d_ga) d_ga[gf] = dpa * ya;
-            if (d_gb) d_gb[gf] = dpb * yb;
-        }
-
-        // ---- dH, one 32-row block at a time: staged, then 16-byte row stores (lane -> row lane >> 3 of eight, columns 4 (lane & 7)..)
-        const int colq = (lane & 7) * 4;
-        float *gbase = dH + (int64_t)b * T * ldh + col0 + colq;
+        w.acc_sg += __shfl_xor(w.acc_sg, 32);
+        store_column_grads(k, w, h, bsum, d_bsum, d_sg, d_ga, d_gb);
 #pragma unroll
         for (int s = 0; s < kMaxNB; ++s) {
             if (s >= nb) break;   // wavefront-uniform
-#pragma unroll
-            for (int r = 0; r < 16; ++r) stage[row_of(r, h) * kStageLd + c] = acc[s][r];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const int row = 8 * it + (lane >> 3);
-                const float4 v4 = *reinterpret_cast<const float4 *>(&stage[row * kStageLd + colq]);
-                if (32 * s + row < T && col0 + colq < F) *reinterpret_cast<float4 *>(gbase + (int64_t)(32 * s + row) * ldh) = v4;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (the next block overwrites the staging tile)
-            __builtin_amdgcn_wave_barrier();
+            store_block36(stage, acc[s], s, dH, ldh, b, T, F, col0, lane);
         }
     }   // column tiles
 }
@@ -266,17 +166,12 @@ int gate_pool_backward_wide(const float *out, int64_t ldo, const float *store_ga
 {
     const char *who = "ggcn_gate_pool_backward_wide";
     if (!out || !dH || !rowmask_t || !inv) return fail(GGCN_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || T <= 0 || F <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d F=%d must be positive", who, B, T, F);
-    if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32; use ggcn_gate_pool_backward_mma", who, T);
-    if (T > kMaxT) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 128; use ggcn_gate_pool_backward + ggcn_aggregate_t", who, T);
-    if (ldo < F || ldh < F || (d_out && ldd < F)) return fail(GGCN_EINVAL, "%s: leading dimension smaller than F=%d", who, F);
-    int64_t ldmax = ldo > ldh ? ldo : ldh;
-    if (d_out && ldd > ldmax) ldmax = ldd;
-    // (whole 32-row blocks: the offsets of the rows past T, which the range check zeroes, must not wrap either)
-    if ((int64_t)32 * ((T + 31) / 32) * ldmax * 4 >= ((int64_t)1 << 31)) return fail(GGCN_EUNSUPPORTED, "%s: a graph's rows exceed 2 GiB", who);
-    if (F % 4 != 0 || ldh % 4 != 0 || !aligned16(dH) || !aligned16(rowmask_t))
-        return fail(GGCN_EUNSUPPORTED, "%s: needs F %% 4 == 0, ldh %% 4 == 0 and 16-byte aligned dH / rowmask_t; use "
-                                       "ggcn_gate_pool_backward + ggcn_aggregate_t", who);
+    const EntryRules rules = {who, false, 33, "ggcn_gate_pool_backward_mma", kMaxT, "", true,
+                              "F % 4 == 0, ldh % 4 == 0 and 16-byte aligned dH / rowmask_t; use ggcn_gate_pool_backward + ggcn_aggregate_t"};
+    const int64_t ldd_in = d_out ? ldd : F;   // (no d_out: ldd is not read)
+    if (const int rc = backward_entry_checks(rules, B, T, F, {ldo, ldh, ldd_in}, {ldo, ldh, ldd_in},
+                                             F % 4 == 0 && ldh % 4 == 0 && aligned16(dH) && aligned16(rowmask_t)))
+        return rc;
     hipLaunchKernelGGL(gate_pool_backward_wide_kernel, dim3((unsigned)B), dim3(256), 0, st, out, ldo, store_gate, gate_a, gate_b, d_out,
                        d_out ? ldd : ldo, d_pa, d_pb, rowmask_t, inv, T, F, dH, ldh, d_sg, d_ga, d_gb, d_bsum);
     return check_launch(who);
