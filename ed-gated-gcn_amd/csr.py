@@ -96,6 +96,37 @@ class BatchedCSR:
                                             _capi.stream_of(dev)), entry)
         return None if flagged and int(flag[0].item()) else ops
 
+    def _plane_block(self, slot, plane, entry, weighted):
+        """The per-plane dictionaries of the <= 32-node blocks: ``entry``'s block for ``plane``, built on first use and kept in the
+        dictionary ``slot`` -- a flagged builder's refusal (None) too, so that builder and read-back run once per plane type.  None,
+        and nothing kept, for graphs of more than 32 nodes or a source that is not on the GPU.  ``weighted``: the flagged builders
+        on the CSR arrays; else the row masks."""
+        store = getattr(self, slot)
+        if store is None:
+            store = {}
+            setattr(self, slot, store)
+        if plane not in store:
+            if self.T > 32:      # (before the CSR arrays are looked at: they are materialised on first access)
+                return None
+            source = (self.rowptr, self.colidx, self.vals) if weighted else (self.rowmask,)
+            if source[0] is None or not source[0].is_cuda:
+                return None
+            store[plane] = self._build(entry, "ggcn_graph_operands2_bytes", source, extra=(plane,), flagged=weighted)
+        return store[plane]
+
+    def _flagged_block(self, slot, fits, entry, by_length=False):
+        """Build once per adjacency: the block of the flagged builder ``entry`` (sized by ``entry + "_bytes"``) on the CSR arrays, kept
+        in ``slot``.  None while the graph does not qualify (``fits``: its node range; the arrays on the GPU), which is not cached;
+        a raised flag is remembered as False, so that the builder and its read-back run once."""
+        ops = getattr(self, slot)
+        if ops is None:
+            if not fits or not self.rowptr.is_cuda:
+                return None
+            ops = self._build(entry, entry + "_bytes", (self.rowptr, self.colidx, self.vals), by_length=by_length, flagged=True)
+            ops = False if ops is None else ops
+            setattr(self, slot, ops)
+        return None if ops is False else ops
+
     @property
     def graph_ops(self):
         """uint8 [B * GGCN_GRAPH_OPS_BYTES] or None: what the one-launch layer / block reads per graph of <= 32 nodes
@@ -143,29 +174,14 @@ class BatchedCSR:
         """uint8 [B * GGCN_GRAPH_OPS2_BYTES]: the block's second layer as ONE operand per graph -- (D.A)^2 in the plane type
         of the launch (0 = bf16 pairs for "bf16x3", 1 = fp16 pairs for "f16mx8" / "f16mx6") -- built from the row masks on
         first use (``ggcn_graph_operands2``), one per plane type."""
-        store = self._graph_ops2
-        if store is None:
-            store = self._graph_ops2 = {}
-        if plane not in store:
-            if self.rowmask is None or self.T > 32 or not self.rowmask.is_cuda:
-                return None
-            store[plane] = self._build("ggcn_graph_operands2", "ggcn_graph_operands2_bytes", (self.rowmask,), extra=(plane,))
-        return store[plane]
+        return self._plane_block("_graph_ops2", plane, "ggcn_graph_operands2", weighted=False)
 
     def graph_ops_weighted(self, plane):
         """uint8 [B * GGCN_GRAPH_OPS2_BYTES] or None: a REAL-valued adjacency of graphs of <= 32 nodes as the one-launch
         layer's operand (``ggcn_graph_operands_weighted``: D.A_w as hi / lo parts in the plane type, 0 = bf16 pairs, 1 = fp16
         pairs), built from the CSR arrays on first use.  None when an entry does not fit the plane type (one read-back of
         the builder's flag per adjacency and plane type): that adjacency keeps linear + aggregate."""
-        store = self._graph_ops_w
-        if store is None:
-            store = self._graph_ops_w = {}
-        if plane not in store:
-            if self.T > 32 or not self.rowptr.is_cuda:
-                return None
-            store[plane] = self._build("ggcn_graph_operands_weighted", "ggcn_graph_operands2_bytes", (self.rowptr, self.colidx, self.vals),
-                                       extra=(plane,), flagged=True)
-        return store[plane]
+        return self._plane_block("_graph_ops_w", plane, "ggcn_graph_operands_weighted", weighted=True)
 
     def graph_ops2_weighted(self, plane):
         """uint8 [B * GGCN_GRAPH_OPS2_BYTES] or None: layer 2 of the one-launch block on a REAL-valued adjacency of graphs of
@@ -173,15 +189,7 @@ class BatchedCSR:
         0 = bf16 pairs, 1 = fp16 pairs, and rowsum(D.A_w)), built from the CSR arrays on first use, one per plane type.  None for
         graphs of more than 32 nodes, arrays that are not on the GPU, or when an entry does not fit the plane type or is not finite
         (one read-back of the builder's flag per adjacency and plane type): that adjacency keeps one weighted launch per layer."""
-        store = self._graph_ops2_w
-        if store is None:
-            store = self._graph_ops2_w = {}
-        if plane not in store:
-            if self.T > 32 or not self.rowptr.is_cuda:
-                return None
-            store[plane] = self._build("ggcn_graph_operands2_weighted", "ggcn_graph_operands2_bytes", (self.rowptr, self.colidx, self.vals),
-                                       extra=(plane,), flagged=True)
-        return store[plane]
+        return self._plane_block("_graph_ops2_w", plane, "ggcn_graph_operands2_weighted", weighted=True)
 
     def graph_ops_weighted_wide(self):
         """uint8 [``ggcn_graph_operands_weighted_wide_bytes(B, T)``] or None: a REAL-valued adjacency of graphs of 33..128 nodes
@@ -189,13 +197,7 @@ class BatchedCSR:
         lo bf16 fragments, one form for both split precisions), built from the CSR arrays on first use.  None when an entry is
         not finite (``rowsum + 1 == 0``; one read-back of the builder's flag per adjacency) or the arrays are not on the GPU:
         that adjacency keeps linear + aggregate."""
-        if self._graph_ops_ww is None:
-            if not 32 < self.T <= 128 or not self.rowptr.is_cuda:
-                return None
-            ops = self._build("ggcn_graph_operands_weighted_wide", "ggcn_graph_operands_weighted_wide_bytes",
-                              (self.rowptr, self.colidx, self.vals), by_length=True, flagged=True)
-            self._graph_ops_ww = False if ops is None else ops
-        return None if self._graph_ops_ww is False else self._graph_ops_ww
+        return self._flagged_block("_graph_ops_ww", 32 < self.T <= 128, "ggcn_graph_operands_weighted_wide", by_length=True)
 
     def graph_ops_weighted_t(self):
         """uint8 [``ggcn_graph_operands_weighted_t_bytes(B)``] or None: A_w^T of a REAL-valued adjacency of graphs of <= 32 nodes
@@ -203,13 +205,7 @@ class BatchedCSR:
         (``ggcn_gate_pool_backward_weighted``), built from the CSR arrays on first use -- no transposed CSR.  None for graphs of
         more than 32 nodes, arrays that are not on the GPU, or an entry that is not finite (one read-back of the builder's flag per
         adjacency): that adjacency keeps ``ggcn_gate_pool_backward`` + ``ggcn_aggregate_t``."""
-        if self._graph_ops_wt is None:
-            if self.T > 32 or not self.rowptr.is_cuda:
-                return None
-            ops = self._build("ggcn_graph_operands_weighted_t", "ggcn_graph_operands_weighted_t_bytes",
-                              (self.rowptr, self.colidx, self.vals), flagged=True)
-            self._graph_ops_wt = False if ops is None else ops
-        return None if self._graph_ops_wt is False else self._graph_ops_wt
+        return self._flagged_block("_graph_ops_wt", self.T <= 32, "ggcn_graph_operands_weighted_t")
 
     def graph_ops_weighted_wide_t(self):
         """uint8 [``ggcn_graph_operands_weighted_wide_t_bytes(B, T)``] or None: A_w^T of a REAL-valued adjacency of graphs of
@@ -218,13 +214,7 @@ class BatchedCSR:
         use -- no transposed CSR.  None for graphs of other sizes, arrays that are not on the GPU, or an entry that is not finite
         (one read-back of the builder's flag per adjacency): that adjacency keeps ``ggcn_gate_pool_backward`` +
         ``ggcn_aggregate_t``."""
-        if self._graph_ops_wwt is None:
-            if not 32 < self.T <= 128 or not self.rowptr.is_cuda:
-                return None
-            ops = self._build("ggcn_graph_operands_weighted_wide_t", "ggcn_graph_operands_weighted_wide_t_bytes",
-                              (self.rowptr, self.colidx, self.vals), by_length=True, flagged=True)
-            self._graph_ops_wwt = False if ops is None else ops
-        return None if self._graph_ops_wwt is False else self._graph_ops_wwt
+        return self._flagged_block("_graph_ops_wwt", 32 < self.T <= 128, "ggcn_graph_operands_weighted_wide_t", by_length=True)
 
     @property
     def device(self):

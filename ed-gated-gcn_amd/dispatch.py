@@ -24,9 +24,7 @@ BACKWARD_PASSES = ("mma", "one_pass", "two_pass", "two_pass_drop")
 LAYER_LAUNCHES = LAYER_PATHS + ("weighted_wide", "weighted_drop", "weighted_wide_drop")
 DROPOUT_LAUNCHES = DROPOUT_PATHS + ("weighted_drop", "weighted_wide_drop")
 OVERLAP_LAUNCHES = OVERLAP_PATHS
-BACKWARD_LAUNCHES = BACKWARD_PASSES + ("weighted", "weighted_drop")
-WIDE_BACKWARD_LAUNCHES = ("wide",)                                      # the opt-in one-launch backward of 0/1 graphs of 33..128 nodes
-WEIGHTED_WIDE_BACKWARD_LAUNCHES = ("weighted_wide",)                     # the opt-in one-launch backward of real-valued graphs of 33..128 nodes
+BACKWARD_LAUNCHES = BACKWARD_PASSES + ("weighted", "weighted_drop", "wide", "weighted_wide")   # ... plus the opt-in one-launch backwards
 DX_FORMS = ("bf16", "scaled", "bf16x3", "fp32")                         # the dW forms are these without "scaled"
 BLOCK_PATHS = ("block", "bf16_block", "folded_eval", "bf16_folded_eval", "two_fused", "layers_eval", "layers")
 BLOCK_LAUNCHES = BLOCK_PATHS + ("weighted_block",)                    # the pinned names plus the opt-in block on a real-valued adjacency
@@ -203,10 +201,32 @@ def backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands):
     return passes, ("scaled" if scaled else dw if need_x else None), dw
 
 
-def _weighted_backward_base(layer, csr, F, operands):
-    """What ``takes_weighted_backward`` and ``takes_weighted_backward_drop`` share; the graph's A_w^T operand is asked last."""
-    return bool(getattr(layer, "weighted_backward", False) and not csr.is_binary and csr.T <= 32 and F % 4 == 0
-                and _aligned16(operands) and not _two_pass_forced() and csr.graph_ops_weighted_t() is not None)
+# The opt-in one-launch gate / pool backwards, in the order ``backward_launch`` asks them.  replaces: the plan's pass; option: the
+# layer's attribute; binary: a 0/1 (True) or real-valued adjacency; wide: graphs of 33..128 nodes (False: <= 32); drop: taken under gate
+# dropout, and only there (it then needs B*T*F < 2^32: the hash takes a 32-bit element index); with_adj: taken where an adjacency
+# gradient is wanted too (the launch stores dY); operand: how the graph is asked for its A^T operand (None: refused)
+_OneLaunchBackward = collections.namedtuple("_OneLaunchBackward", "replaces option binary wide drop with_adj operand")
+_ONE_LAUNCH_BACKWARDS = {
+    "weighted": _OneLaunchBackward("two_pass", "weighted_backward", False, False, False, True, lambda c: c.graph_ops_weighted_t()),
+    "weighted_drop": _OneLaunchBackward("two_pass_drop", "weighted_backward", False, False, True, True, lambda c: c.graph_ops_weighted_t()),
+    "wide": _OneLaunchBackward("two_pass", "wide_backward", True, True, False, False, lambda c: c.rowmask_t_wide),
+    "weighted_wide": _OneLaunchBackward("two_pass", "weighted_wide_backward", False, True, False, True,
+                                        lambda c: c.graph_ops_weighted_wide_t()),
+}
+
+
+def _takes_one_launch_backward(row, layer, csr, B, F, dropout, operands):
+    """The one rule of the four ``takes_*_backward`` predicates on a row of the table above, in one order: the option (a layer that predates
+    it is a plain namespace without the attribute) -- FIRST, so that a layer without it reads nothing of the graph or the operands --
+    the dropout side, the adjacency kind, the node range, F % 4 == 0, every operand 16-byte aligned, ``GGCN_BACKWARD_TWO_PASS`` not
+    set, and -- asked once and LAST, so that a refused call builds nothing -- the graph's operand."""
+    if not getattr(layer, row.option, False):
+        return False
+    if (dropout is not None) != row.drop or (row.drop and B * csr.T * F >= 2 ** 32):
+        return False
+    if bool(csr.is_binary) != row.binary or not (32 < csr.T <= 128 if row.wide else csr.T <= 32):
+        return False
+    return F % 4 == 0 and _aligned16(operands) and not _two_pass_forced() and row.operand(csr) is not None
 
 
 def takes_weighted_backward(layer, csr, F, dropout, operands):
@@ -223,7 +243,7 @@ def takes_weighted_backward(layer, csr, F, dropout, operands):
     softmax rows; 416), 68 -> 62 (512 x 24); the whole layer backward 1521 -> 1271, 1881 -> 1295, 230 -> 226, with an adjacency
     gradient 2016 -> 1859, 2407 -> 1914, 300 -> 300.  It stays opt-in: dH differs in the last bits.
     The compiler's report: 165 VGPRs, no scratch, three workgroups per CU."""
-    return dropout is None and _weighted_backward_base(layer, csr, F, operands)
+    return _takes_one_launch_backward(_ONE_LAUNCH_BACKWARDS["weighted"], layer, csr, None, F, dropout, operands)
 
 
 def takes_weighted_backward_drop(layer, csr, B, F, dropout, operands):
@@ -237,7 +257,7 @@ def takes_weighted_backward_drop(layer, csr, B, F, dropout, operands):
     adjacency gradient.  The compiler's report: 219 VGPRs, no scratch, TWO workgroups per CU (under the three-workgroup bound the
     keep factors spill 84 bytes per lane; the form without dropout keeps 165 VGPRs and three workgroups).
     Timings: ``takes_weighted_dropout``."""
-    return dropout is not None and B * csr.T * F < 2 ** 32 and _weighted_backward_base(layer, csr, F, operands)
+    return _takes_one_launch_backward(_ONE_LAUNCH_BACKWARDS["weighted_drop"], layer, csr, B, F, dropout, operands)
 
 
 def takes_wide_backward(layer, csr, B, F, dropout, operands):
@@ -258,11 +278,7 @@ def takes_wide_backward(layer, csr, B, F, dropout, operands):
     58-128, transposed masks 10.  The whole layer backward, cached: 679 -> 549, 773 -> 650, 811 -> 658, 960 -> 854, 188 -> 178.
     No shape lost; WEAK: the small batch (3-5 %).
     The compiler's report: 222 VGPRs, no scratch, 21 KiB of LDS, two workgroups per CU."""
-    if not getattr(layer, "wide_backward", False):
-        return False
-    if not (dropout is None and csr.is_binary and 32 < csr.T <= 128 and F % 4 == 0 and _aligned16(operands) and not _two_pass_forced()):
-        return False
-    return csr.rowmask_t_wide is not None
+    return _takes_one_launch_backward(_ONE_LAUNCH_BACKWARDS["wide"], layer, csr, B, F, dropout, operands)
 
 
 def takes_weighted_wide_backward(layer, csr, F, dropout, operands):
@@ -285,27 +301,18 @@ def takes_weighted_wide_backward(layer, csr, F, dropout, operands):
     the operand 34-38 (sparse), 53-71 (dense).  NEGATIVE: 64 x 100 on a sparse graph LOSES (stage 98 -> 129, backward 214 -> 241);
     on dense rows it wins there too (222 -> 142).
     The compiler's report: 214 VGPRs, no scratch, 19 KiB of LDS, two workgroups per CU."""
-    if not getattr(layer, "weighted_wide_backward", False):
-        return False
-    if not (dropout is None and not csr.is_binary and 32 < csr.T <= 128 and F % 4 == 0 and _aligned16(operands) and not _two_pass_forced()):
-        return False
-    return csr.graph_ops_weighted_wide_t() is not None
+    return _takes_one_launch_backward(_ONE_LAUNCH_BACKWARDS["weighted_wide"], layer, csr, None, F, dropout, operands)
 
 
 def backward_launch(layer, csr, dtype, B, K, F, need_x, need_adj, dropout, operands):
-    """``backward_plan`` with its pass replaced by "weighted" / "weighted_drop" (``BACKWARD_LAUNCHES``), "wide"
-    (``WIDE_BACKWARD_LAUNCHES``) or "weighted_wide" (``WEIGHTED_WIDE_BACKWARD_LAUNCHES``) where the predicates above hold: asked
-    after the plan and only where it says "two_pass" / "two_pass_drop", so the plan's answers stay as pinned; the wide launch only
-    where no adjacency gradient is wanted, the weighted wide one with it as well (it stores dY)."""
+    """``backward_plan`` with its pass replaced by the first opt-in one-launch backward ("weighted", "weighted_drop", "wide",
+    "weighted_wide": ``BACKWARD_LAUNCHES``) that replaces that pass, admits the adjacency gradient where one is wanted (the wide
+    launch does not: it stores no dY) and whose predicate above holds: asked after the plan and only where it says "two_pass" /
+    "two_pass_drop", so the plan's answers stay as pinned."""
     passes, dx, dw = backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands)
-    if passes == "two_pass" and takes_weighted_backward(layer, csr, F, dropout, operands):
-        passes = "weighted"
-    elif passes == "two_pass_drop" and takes_weighted_backward_drop(layer, csr, B, F, dropout, operands):
-        passes = "weighted_drop"
-    elif passes == "two_pass" and not need_adj and takes_wide_backward(layer, csr, B, F, dropout, operands):
-        passes = "wide"
-    elif passes == "two_pass" and takes_weighted_wide_backward(layer, csr, F, dropout, operands):
-        passes = "weighted_wide"
+    for name, row in _ONE_LAUNCH_BACKWARDS.items():
+        if row.replaces == passes and (row.with_adj or not need_adj) and _takes_one_launch_backward(row, layer, csr, B, F, dropout, operands):
+            return name, dx, dw
     return passes, dx, dw
 
 

@@ -93,23 +93,27 @@ _LAYER_LAUNCHES = {   # dispatch.layer_launch's names but "two_launch" (linear +
 }
 _LAYER_LAUNCHES["bf16_wide_drop"] = _LAYER_LAUNCHES["bf16_wide"]
 
-# dispatch.backward_launch's names: the entry, the graph operands after d_pb, what it writes ("dH"; "dY": to memory, for
-# ggcn_aggregate_t; "both": dH, and dY where an adjacency gradient wants it) and what follows d_bsum
+# One gate / pool backward launch of _GatedLayerFunction.backward, by dispatch.backward_launch's names.  graph(csr): the graph operands
+# after d_pb; writes: "dH", "dY" (to memory, for ggcn_aggregate_t) or "both" (dH, and dY where an adjacency gradient wants it); tail: what
+# follows d_bsum
+_BackwardLaunch = collections.namedtuple("_BackwardLaunch", "entry graph writes tail")
 _weighted_t = lambda c: (c.graph_ops_weighted_t(), c.inv_denominators())   # noqa: E731
-_wide_t = lambda c: (c.rowmask_t_wide, c.inv_denominators())   # noqa: E731
 _BACKWARD_LAUNCHES = {
-    "mma": ("ggcn_gate_pool_backward_mma", lambda c: (c.graph_ops, c.graph_ops_t), "dH", ("amax",)),
-    "one_pass": ("ggcn_gate_pool_backward_agg", lambda c: (c.rowmask,), "dH", ("drop", "amax")),
-    "two_pass": ("ggcn_gate_pool_backward", lambda c: (), "dY", ()),
-    "two_pass_drop": ("ggcn_gate_pool_backward_drop", lambda c: (), "dY", ("drop",)),
-    "weighted": ("ggcn_gate_pool_backward_weighted", _weighted_t, "both", ()),
-    "weighted_drop": ("ggcn_gate_pool_backward_weighted_drop", _weighted_t, "both", ("drop",)),
-    "wide": ("ggcn_gate_pool_backward_wide", _wide_t, "dH", ()),
+    "mma": _BackwardLaunch("ggcn_gate_pool_backward_mma", lambda c: (c.graph_ops, c.graph_ops_t), "dH", ("amax",)),
+    "one_pass": _BackwardLaunch("ggcn_gate_pool_backward_agg", lambda c: (c.rowmask,), "dH", ("drop", "amax")),
+    "two_pass": _BackwardLaunch("ggcn_gate_pool_backward", lambda c: (), "dY", ()),
+    "two_pass_drop": _BackwardLaunch("ggcn_gate_pool_backward_drop", lambda c: (), "dY", ("drop",)),
+    "weighted": _BackwardLaunch("ggcn_gate_pool_backward_weighted", _weighted_t, "both", ()),
+    "weighted_drop": _BackwardLaunch("ggcn_gate_pool_backward_weighted_drop", _weighted_t, "both", ("drop",)),
+    "wide": _BackwardLaunch("ggcn_gate_pool_backward_wide", lambda c: (c.rowmask_t_wide, c.inv_denominators()), "dH", ()),
+    "weighted_wide": _BackwardLaunch("ggcn_gate_pool_backward_weighted_wide",
+                                     lambda c: (c.graph_ops_weighted_wide_t(), c.inv_denominators()), "both", ()),
 }
-# dispatch.WEIGHTED_WIDE_BACKWARD_LAUNCHES, a table of its own: consulted where the name is not in the one above
-_WEIGHTED_WIDE_BACKWARD_LAUNCHES = {
-    "weighted_wide": ("ggcn_gate_pool_backward_weighted_wide", lambda c: (c.graph_ops_weighted_wide_t(), c.inv_denominators()), "both", ()),
-}
+
+
+def _opted_in(opt, name):
+    """A boolean opt-in: on when ``opt.ggcn_<name>`` is true or the environment has ``GGCN_<NAME>=1``."""
+    return bool(getattr(opt, "ggcn_" + name, False)) or os.environ.get("GGCN_" + name.upper(), "0") == "1"
 
 
 class _GatedLayerFunction(torch.autograd.Function):
@@ -179,7 +183,7 @@ class _GatedLayerFunction(torch.autograd.Function):
             need_adj = ctx.adj_dtype is not None and need[11]
             operands = (out2, store_gate, gate_a, gate_b, d_out2, d_pa, d_pb, dh, d_sg, d_ga, d_gb, d_bsum)
             launch, dx_form, dw_form = dispatch.backward_launch(layer, csr, text.dtype, B, K, F, need[0], need_adj, ctx.dropout, operands)
-            entry, graph, writes, tail = (_BACKWARD_LAUNCHES if launch in _BACKWARD_LAUNCHES else _WEIGHTED_WIDE_BACKWARD_LAUNCHES)[launch]
+            entry, graph, writes, tail = _BACKWARD_LAUNCHES[launch]
             dh_amax = torch.zeros(1, **f32) if dx_form == "scaled" else None
             dy = torch.empty(B * T, F, **f32) if (writes == "dY" or (writes == "both" and need_adj)) else None
             # "drop": the keep factors of the forward launch, drawn again from (seed, element)
@@ -269,44 +273,19 @@ class GraphConvolution(nn.Module):
         # form on their own (takes_fused_path); set 256 to send graphs of 129..192 nodes there as well.
         self.fused = bool(getattr(opt, "ggcn_fused", True)) and os.environ.get("GGCN_FUSED", "1") != "0"
         self.fused_max_t = int(getattr(opt, "ggcn_fused_max_t", None) or os.environ.get("GGCN_FUSED_MAX_T", "128"))
-        # bfloat16 features, inference: the whole gated block as one launch for graphs of <= 32 nodes (ggcn_block_fused_bf16) and
-        # the folded evaluation of 33..256-node graphs (gated_block.takes_bf16_block_path / takes_bf16_folded_eval_path).  Off by
-        # default: the fold sums in another order than the two layer launches (both inside the parity gate).
-        self.bf16_block = bool(getattr(opt, "ggcn_bf16_block", False)) or os.environ.get("GGCN_BF16_BLOCK", "0") == "1"
+        # The boolean opt-ins, all off by default: each launch sums in another order than the launches it replaces (inside the parity
+        # gate, but not bit-equal).  The predicate named beside each holds its rule and its measurements.
+        self.bf16_block = _opted_in(opt, "bf16_block")                          # dispatch.takes_bf16_block_path / takes_bf16_folded_eval_path
+        self.weighted_backward = _opted_in(opt, "weighted_backward")            # dispatch.takes_weighted_backward / takes_weighted_backward_drop
+        self.weighted_dropout = _opted_in(opt, "weighted_dropout")              # dispatch.takes_weighted_dropout
+        self.weighted_block = _opted_in(opt, "weighted_block")                  # dispatch.takes_weighted_block_path
+        self.wide_backward = _opted_in(opt, "wide_backward")                    # dispatch.takes_wide_backward
+        self.weighted_wide_backward = _opted_in(opt, "weighted_wide_backward")  # dispatch.takes_weighted_wide_backward
         # real-valued adjacency (a soft or learned graph), float32 features: graphs of up to weighted_max_t nodes run as ONE launch.
         # 32 by default (ggcn_layer_fused_weighted); 128 adds graphs of 33..128 nodes (ggcn_layer_fused_weighted_wide,
         # takes_weighted_path has the measurements); larger values mean 128.  Off by default: its sums differ from linear +
         # aggregate's in the last bits (both inside the parity gate).
         self.weighted_max_t = int(getattr(opt, "ggcn_weighted_max_t", None) or os.environ.get("GGCN_WEIGHTED_MAX_T", "32"))
-        # real-valued adjacency of graphs of <= 32 nodes under autograd: gate / pool backward and dH = A_w^T.D.dY as ONE launch on
-        # the matrix cores (ggcn_gate_pool_backward_weighted; dispatch.takes_weighted_backward has the measurements) instead of
-        # ggcn_gate_pool_backward + a transposed CSR + ggcn_aggregate_t.  Off by default: dH's sums differ in the last bits.
-        self.weighted_backward = (bool(getattr(opt, "ggcn_weighted_backward", False))
-                                  or os.environ.get("GGCN_WEIGHTED_BACKWARD", "0") == "1")
-        # real-valued adjacency under the gates' training-mode dropout: the keep factors are drawn inside the weighted launches
-        # (ggcn_layer_fused_weighted_drop / _wide_drop; with weighted_backward also ggcn_gate_pool_backward_weighted_drop) instead of
-        # the call being refused (dispatch.takes_weighted_dropout).  Off by default, like the launches it builds on.
-        self.weighted_dropout = (bool(getattr(opt, "ggcn_weighted_dropout", False))
-                                 or os.environ.get("GGCN_WEIGHTED_DROPOUT", "0") == "1")
-        # real-valued adjacency of graphs of <= 32 nodes, float32 features, inference: the whole gated block as ONE launch
-        # (ggcn_block_fused_weighted; gated_block.takes_weighted_block_path has the measurements) instead of two weighted layer
-        # launches + the regulariser's.  Off by default: the fold's sums differ from the two layer launches' in the last bits (both
-        # inside the parity gate).
-        self.weighted_block = (bool(getattr(opt, "ggcn_weighted_block", False))
-                               or os.environ.get("GGCN_WEIGHTED_BLOCK", "0") == "1")
-        # 0/1 graphs of 33..128 nodes under autograd (LitBank: ORI_ML = 100) without gate dropout: gate / pool backward and
-        # dH = A^T.D.dY as ONE launch on the matrix cores (ggcn_gate_pool_backward_wide; dispatch.takes_wide_backward has the
-        # measurements) instead of ggcn_gate_pool_backward + a transposed CSR + ggcn_aggregate_t.  Under gate dropout the two
-        # passes stay.  Off by default: dH's sums differ in the last bits.
-        self.wide_backward = (bool(getattr(opt, "ggcn_wide_backward", False))
-                              or os.environ.get("GGCN_WIDE_BACKWARD", "0") == "1")
-        # a REAL-valued adjacency of graphs of 33..128 nodes under autograd (a soft or learned graph at LitBank's lengths) without
-        # gate dropout: gate / pool backward and dH = A_w^T.D.dY as ONE launch on the matrix cores
-        # (ggcn_gate_pool_backward_weighted_wide on BatchedCSR.graph_ops_weighted_wide_t; dispatch.takes_weighted_wide_backward)
-        # instead of ggcn_gate_pool_backward + a transposed CSR + ggcn_aggregate_t; dY is stored only for an adjacency gradient.
-        # Separate from weighted_backward, which stays what it is at 33 nodes.  Off by default: dH's sums differ in the last bits.
-        self.weighted_wide_backward = (bool(getattr(opt, "ggcn_weighted_wide_backward", False))
-                                       or os.environ.get("GGCN_WEIGHTED_WIDE_BACKWARD", "0") == "1")
         # dense adjacency handed to forward(): None = let the device detect edge weights (one 4-byte
         # read-back per conversion), True = promise 0/1 entries like the reference's (graph.py:66-74)
         # and stay sync-free, False = always keep the values

@@ -5,7 +5,9 @@ The old compositions (``layer_path``, then ``takes_weighted_dropout``, then the 
 ``_forward_gated``; ``backward_plan``, then one of the two weighted-backward predicates) are written out here, independently of
 ``dispatch.py``, and so are the bodies the two weighted-backward predicates had before they became statements over one private
 predicate.  Graphs are stand-ins that log which operand block they were asked for: the new functions must ask for the same blocks,
-in the same order, as the old sequence of calls.  The refusals are asked of the loaded library with NULL pointers: every check
+in the same order, as the old sequence of calls.  Section 4 does the same for ``backward_launch`` as a loop over one table of the
+four opt-in one-launch backwards: against the four-armed chain over the four predicates' bodies that it replaced, on a joint grid
+of the three options.  The refusals are asked of the loaded library with NULL pointers: every check
 tested here comes before anything is dereferenced or launched."""
 import ctypes
 import importlib.util
@@ -41,7 +43,8 @@ def test_the_tuples():
     assert dispatch.LAYER_LAUNCHES == dispatch.LAYER_PATHS + NEW_LAYER_NAMES
     assert dispatch.DROPOUT_LAUNCHES == dispatch.DROPOUT_PATHS + ("weighted_drop", "weighted_wide_drop")
     assert dispatch.OVERLAP_LAUNCHES == dispatch.OVERLAP_PATHS
-    assert dispatch.BACKWARD_LAUNCHES == dispatch.BACKWARD_PASSES + ("weighted", "weighted_drop")
+    assert dispatch.BACKWARD_LAUNCHES == ("mma", "one_pass", "two_pass", "two_pass_drop", "weighted", "weighted_drop", "wide", "weighted_wide")
+    assert dispatch.BACKWARD_LAUNCHES[:4] == dispatch.BACKWARD_PASSES
 
 
 # ---------------------------------------------------------------- 1. layer_launch
@@ -226,7 +229,7 @@ def test_backward_launch_matches_the_old_composition(monkeypatch):
             seen.add(got[0])
             n += 1
     assert n == 2 ** 10
-    assert seen == set(dispatch.BACKWARD_LAUNCHES)
+    assert seen == set(dispatch.BACKWARD_PASSES) | {"weighted", "weighted_drop"}
 
 
 def test_the_weighted_backward_predicates_answer_as_their_parent_commit_bodies(monkeypatch):
@@ -248,7 +251,93 @@ def test_the_weighted_backward_predicates_answer_as_their_parent_commit_bodies(m
     assert len(answers) == 4                                   # both predicates answer True and False
 
 
-# ---------------------------------------------------------------- 4. the refusals that moved into helpers
+# ---------------------------------------------------------------- 4. backward_launch with all three options: the parent's elif chain
+def _old_takes_wide_backward(layer, csr, B, F, dropout, operands):
+    """The body at the parent commit."""
+    if not getattr(layer, "wide_backward", False):
+        return False
+    if not (dropout is None and csr.is_binary and 32 < csr.T <= 128 and F % 4 == 0
+            and all(t is None or t.data_ptr() % 16 == 0 for t in operands) and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1"):
+        return False
+    return csr.rowmask_t_wide is not None
+
+
+def _old_takes_weighted_wide_backward(layer, csr, F, dropout, operands):
+    """The body at the parent commit."""
+    if not getattr(layer, "weighted_wide_backward", False):
+        return False
+    if not (dropout is None and not csr.is_binary and 32 < csr.T <= 128 and F % 4 == 0
+            and all(t is None or t.data_ptr() % 16 == 0 for t in operands) and os.environ.get("GGCN_BACKWARD_TWO_PASS", "0") != "1"):
+        return False
+    return csr.graph_ops_weighted_wide_t() is not None
+
+
+def _parent_backward_launch(layer, csr, dtype, B, K, F, need_x, need_adj, dropout, operands):
+    """``dispatch.backward_launch`` at the parent commit: the plan, then a four-armed chain over the four predicates."""
+    passes, dx, dw = dispatch.backward_plan(layer, csr, dtype, K, F, need_x, need_adj, dropout, operands)
+    if passes == "two_pass" and _old_takes_weighted_backward(layer, csr, F, dropout, operands):
+        passes = "weighted"
+    elif passes == "two_pass_drop" and _old_takes_weighted_backward_drop(layer, csr, B, F, dropout, operands):
+        passes = "weighted_drop"
+    elif passes == "two_pass" and not need_adj and _old_takes_wide_backward(layer, csr, B, F, dropout, operands):
+        passes = "wide"
+    elif passes == "two_pass" and _old_takes_weighted_wide_backward(layer, csr, F, dropout, operands):
+        passes = "weighted_wide"
+    return passes, dx, dw
+
+
+OPERAND_BLOCKS = ("wt", "mtw", "wwt")
+
+
+def _joint_graph(T, B, binary, masks, ops, log):
+    """A ``BatchedCSR`` stand-in for all three options: the three transposed operands log into ``log`` that they were asked for
+    (``rowmask_t_wide`` is a property, like the real one, and exists only with row masks)."""
+    blk = types.SimpleNamespace(is_cuda=True)
+
+    class Graph:
+        rowmask_t_wide = property(lambda self: (log.append("mtw"), blk if ops and masks else None)[1])
+    g = Graph()
+    g.T, g.B, g.is_binary = T, B, binary
+    g.rowmask = g.graph_ops = g.graph_ops_t = blk if masks else None
+    g.graph_ops_weighted_t = lambda: (log.append("wt"), blk if ops else None)[1]
+    g.graph_ops_weighted_wide_t = lambda: (log.append("wwt"), blk if ops else None)[1]
+    return g
+
+
+def test_backward_launch_with_all_three_options_matches_the_parent_chain(monkeypatch):
+    options = list(itertools.product((False, True), repeat=3))
+    layers = {o: GraphConvolution(H, H, opt=types.SimpleNamespace(ggcn_weighted_backward=o[0], ggcn_wide_backward=o[1],
+                                                                  ggcn_weighted_wide_backward=o[2])) for o in options}
+    for o, layer in layers.items():
+        assert (layer.weighted_backward, layer.wide_backward, layer.weighted_wide_backward) == o
+    seen, n = set(), 0
+    for two_pass in (False, True):
+        monkeypatch.setenv("GGCN_BACKWARD_TWO_PASS", "1" if two_pass else "0")
+        for T, binary, masks, ops, F, drop, offset, need_adj, fits in itertools.product(
+                (1, 32, 33, 128, 129), (False, True), (True, False), (True, False), (4, 30), (None, (0.25, 7, (0, 1, 2))), (0, 4),
+                (False, True), (True, False)):
+            B = -(-2 ** 32 // (T * F)) - (1 if fits else 0)      # B*T*F on both sides of 2^32
+            assert (B * T * F < 2 ** 32) == fits and (B + 1) * T * F >= 2 ** 32
+            for o, layer in layers.items():
+                logs, answers = [], []
+                for launch in (_parent_backward_launch, dispatch.backward_launch):
+                    log = []
+                    operands = (_at(1 << 20, log), None, _at((1 << 20) + offset, log), None)
+                    csr = _joint_graph(T, B, binary, masks, ops, log)
+                    answers.append(launch(layer, csr, torch.float32, B, H, F, True, need_adj, drop, operands))
+                    logs.append(log)
+                what = (o, T, binary, masks, ops, F, drop, offset, two_pass, need_adj, fits)
+                assert answers[1] == answers[0] and answers[1][0] in dispatch.BACKWARD_LAUNCHES, what
+                assert logs[1] == logs[0], what
+                blocks = [a for a in logs[1] if a in OPERAND_BLOCKS]
+                assert len(blocks) <= 1 and not any(a in OPERAND_BLOCKS for a in logs[1][:-1]), what      # asked last, or not at all
+                seen.add(answers[1][0])
+                n += 1
+    assert n == 2 * 5 * 2 ** 8 * 8
+    assert seen == set(dispatch.BACKWARD_LAUNCHES)
+
+
+# ---------------------------------------------------------------- 5. the refusals that moved into helpers
 EINVAL = 1
 P = ctypes.c_void_p(1 << 20)   # non-null, 16-byte aligned, never dereferenced
 DROP_ENTRIES = sorted(n for n, (_, args) in _capi.PROTOTYPES.items() if ctypes.c_float in args and n != "ggcn_dropout_mask")

@@ -78,12 +78,10 @@ def test_declared_bound_exported_and_abi_stays_14():
     assert proto(KERNEL) == proto("ggcn_gate_pool_backward_weighted")
     assert proto(BUILD) == proto("ggcn_graph_operands_weighted_wide") and proto(SIZE) == proto("ggcn_graph_operands_weighted_wide_bytes")
     assert not any(n.startswith(KERNEL + "_") for n in _capi.PROTOTYPES)            # no form under gate dropout
-    assert dispatch.WEIGHTED_WIDE_BACKWARD_LAUNCHES == ("weighted_wide",)
-    assert not set(dispatch.WEIGHTED_WIDE_BACKWARD_LAUNCHES) & (set(dispatch.BACKWARD_LAUNCHES) | set(dispatch.WIDE_BACKWARD_LAUNCHES))
+    assert "weighted_wide" in dispatch.BACKWARD_LAUNCHES and "weighted_wide" not in dispatch.BACKWARD_PASSES
     from ed_gated_gcn_amd import gcn
-    assert set(gcn._WEIGHTED_WIDE_BACKWARD_LAUNCHES) == set(dispatch.WEIGHTED_WIDE_BACKWARD_LAUNCHES)
-    assert not set(gcn._WEIGHTED_WIDE_BACKWARD_LAUNCHES) & set(gcn._BACKWARD_LAUNCHES)
-    row = gcn._WEIGHTED_WIDE_BACKWARD_LAUNCHES["weighted_wide"]
+    assert set(gcn._BACKWARD_LAUNCHES) == set(dispatch.BACKWARD_LAUNCHES)
+    row = gcn._BACKWARD_LAUNCHES["weighted_wide"]
     assert row[0] == KERNEL and row[2:] == ("both", ())
     assert "_graph_ops_wwt" in pkg.BatchedCSR.__slots__
 
@@ -265,7 +263,7 @@ def test_backward_launch_with_the_option_on_differs_only_where_the_rule_says(mon
         else:
             assert got[0] == plan[0] and got[0] in dispatch.BACKWARD_PASSES, what
         seen.add(got[0])
-    assert seen == set(dispatch.BACKWARD_PASSES) | set(dispatch.WEIGHTED_WIDE_BACKWARD_LAUNCHES) | (set(dispatch.WIDE_BACKWARD_LAUNCHES) if wide_too else set())
+    assert seen == set(dispatch.BACKWARD_PASSES) | {"weighted_wide"} | ({"wide"} if wide_too else set())
 
 
 # ---------------------------------------------------------------- the numpy statement of the operand

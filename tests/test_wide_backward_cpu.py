@@ -73,11 +73,10 @@ def test_declared_bound_exported_and_abi_stays_14():
     weighted = proto("ggcn_gate_pool_backward_weighted")
     assert proto(WIDE) == weighted[:16] + weighted[18:]
     assert not any(n.startswith(WIDE + "_") for n in _capi.PROTOTYPES)            # no form under gate dropout
-    assert dispatch.WIDE_BACKWARD_LAUNCHES == ("wide",)
-    assert not set(dispatch.WIDE_BACKWARD_LAUNCHES) & set(dispatch.BACKWARD_LAUNCHES)
+    assert "wide" in dispatch.BACKWARD_LAUNCHES and "wide" not in dispatch.BACKWARD_PASSES
     from ed_gated_gcn_amd import gcn
     assert gcn._BACKWARD_LAUNCHES["wide"][0] == WIDE and gcn._BACKWARD_LAUNCHES["wide"][2:] == ("dH", ())
-    assert set(gcn._BACKWARD_LAUNCHES) == set(dispatch.BACKWARD_LAUNCHES) | set(dispatch.WIDE_BACKWARD_LAUNCHES)
+    assert set(gcn._BACKWARD_LAUNCHES) == set(dispatch.BACKWARD_LAUNCHES)
 
 
 def test_builder_refusals():
@@ -229,7 +228,7 @@ def test_backward_launch_with_the_option_on_differs_only_where_the_rule_says(mon
         else:
             assert got[0] == plan[0] and got[0] in dispatch.BACKWARD_PASSES, what
         seen.add(got[0])
-    assert seen == set(dispatch.BACKWARD_PASSES) | set(dispatch.WIDE_BACKWARD_LAUNCHES)
+    assert seen == set(dispatch.BACKWARD_PASSES) | {"wide"}
 
 
 def test_the_pinned_plan_cases(monkeypatch):
