@@ -23,14 +23,17 @@ def _check(name, t, dims, allow_bf16=False):
 
 def _launch(a, x, swap):
     """y[b] = a[b] @ x[b] (swap=False) or a[b].T @ x[b] (swap=True); a strided, x/y row-contiguous."""
-    lib = _capi.load_library()
     B, R, C = a.shape
     sb, sr, sc = a.stride()
     if swap:
         R, C, sr, sc = C, R, sc, sr
+    D = x.shape[2]
+    if B == 0 or R == 0 or C == 0 or D == 0:
+        # torch.bmm takes empty operands: an empty result, or the empty sum (zeros) when only C is 0; nothing to launch
+        return torch.zeros(B, R, D, dtype=x.dtype, device=x.device)
+    lib = _capi.load_library()
     if x.stride(2) != 1:
         x = x.contiguous()
-    D = x.shape[2]
     y = torch.empty(B, R, D, dtype=x.dtype, device=x.device)
     fn = lib.ggcn_subword_pool_bf16 if x.dtype == torch.bfloat16 else lib.ggcn_subword_pool
     with torch.cuda.device(x.device):
@@ -55,7 +58,8 @@ class _SubwordPool(torch.autograd.Function):
 
 
 def subword_pool(transform, x):
-    """``torch.bmm(transform, x)`` for a sparse ``transform [B,T,L]`` (any strides) and ``x [B,L,D]``."""
+    """``torch.bmm(transform, x)`` for a sparse ``transform [B,T,L]`` (any strides) and ``x [B,L,D]``.  Empty operands are taken
+    as ``torch.bmm`` takes them, without a launch: B, T or D = 0 gives an empty ``[B,T,D]``, L = 0 gives zeros."""
     _check("transform", transform, 3)
     _check("x", x, 3, allow_bf16=True)
     if transform.shape[0] != x.shape[0] or transform.shape[2] != x.shape[1]:

@@ -834,21 +834,7 @@ def test_hipgraph_capture_replays_bit_identically(pkg, dev):
 
 
 # ---------------------------------------------------------------- sub-word pooling
-def _transform_like_reference(B, T, L, rng, ori_ml=None, bert_ml=None):
-    """data_utils.py:749-766: word i covers l_i consecutive sub-word positions starting at offset 1
-    ([CLS] first), each with weight 1/l_i; padded to [ORI_ML, BERT_ML]."""
-    ori_ml, bert_ml = ori_ml or T, bert_ml or L
-    tr = np.zeros((B, ori_ml, bert_ml), dtype=np.float32)
-    for b in range(B):
-        n_words = int(rng.integers(1, T + 1))
-        off = 1
-        for i in range(n_words):
-            l = int(rng.integers(1, 5))
-            if off + l >= L:
-                break
-            tr[b, i, off:off + l] = 1.0 / l
-            off += l
-    return tr
+from oracle.subword_pool_cases import transform_like_reference as _transform_like_reference  # noqa: E402
 
 
 @pytest.mark.parametrize("B,T,L,D,pad", [(4, 31, 60, 9216, True), (3, 7, 300, 1000, False), (2, 5, 9, 37, True),
