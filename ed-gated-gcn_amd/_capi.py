@@ -140,6 +140,7 @@ PROTOTYPES = {
     "ggcn_dense_head_signal": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "ggcn_overlap_workspace_bytes": (c_sz, [c_i32]),
     "ggcn_gate_overlap": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ggcn_bilstm_recurrence": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp]),
 }
 
 ABI_VERSION = 14
@@ -147,6 +148,7 @@ PREC = {"bf16x3": 0, "fp32": 1, "f16mx8": 2, "f16": 3, "f16mx6": 4}
 PACKED = ("bf16x3", "f16mx8", "f16", "f16mx6")  # precisions whose linear reads a ggcn_weight_pack image ("f16": half features only)
 FLAG_WEIGHTED = 1
 RANGE_OVERFLOW, RANGE_WINDOW, RANGE_HIDDEN = 1, 2, 4   # include/ggcn.h ggcn_range_bits
+BILSTM_TILE = 16   # include/ggcn.h GGCN_BILSTM_TILE: sentences per workgroup of ggcn_bilstm_recurrence
 
 
 def has_f16mx6():

@@ -13,7 +13,9 @@ are dropped per
 token like the reference's (``:621-625``); ``opt.ggcn_wide_backward`` reaches ``gc1`` and ``gc2`` through their constructor and
 puts their backward on graphs of 33..128 nodes into one launch each where no gate dropout is active
 (``dispatch.takes_wide_backward``); ``opt.ggcn_weighted_wide_backward`` reaches them the same way and does the same on a
-real-valued adjacency of 33..128 nodes (``dispatch.takes_weighted_wide_backward``).  BERT, the BiLSTM and ``dense`` stay PyTorch-ROCm.
+real-valued adjacency of 33..128 nodes (``dispatch.takes_weighted_wide_backward``); ``opt.ggcn_hip_lstm`` puts the BiLSTM (``:610``) of an inference forward on the HIP
+path (``recurrent.bilstm``: one projection, one recurrence launch).  BERT, ``dense`` and, by default and in training, the BiLSTM
+stay PyTorch-ROCm.
 """
 import os
 
@@ -26,6 +28,7 @@ from .gated_block import gated_gcn_block, takes_block_path
 from .gcn import GraphConvolution
 from .heads import gate_mlps, scores_and_kl
 from .pooling import subword_pool
+from .recurrent import bilstm, takes_hip_lstm
 
 
 class LegacyBertAdapter(nn.Module):
@@ -91,6 +94,11 @@ class GatedGCNEventDetector(nn.Module):
         # + the fixed-order weight products) instead of the two nn.Sequential.  Off by default, for the same reason.
         self.gate_backward = (bool(getattr(opt, "ggcn_gate_backward", False))
                               or os.environ.get("GGCN_GATE_BACKWARD", "0") == "1")
+        # inference: the BiLSTM (:610) as ``bilstm`` (one bf16x3 projection, one recurrence launch) where ``takes_hip_lstm`` holds --
+        # float32 features and no gradient wanted; training and bf16 autocast keep nn.LSTM.  Off by default: the projection's
+        # bf16x3 sums differ from the fp32 GEMM's in the last bits (both inside the forward gate).
+        self.hip_lstm = (bool(getattr(opt, "ggcn_hip_lstm", False))
+                         or os.environ.get("GGCN_HIP_LSTM", "0") == "1")
 
     def _training_gates(self, aspect):
         """``gate1(aspect), gate2(aspect)`` of the training branches: the two nn.Sequential (under bf16 autocast they give bf16)
@@ -180,7 +188,10 @@ class GatedGCNEventDetector(nn.Module):
         x = subword_pool(transform.float(), x)                              # :600 on the HIP path (non-zeros only)
         rows = torch.arange(B, device=x.device)
         anchor_rep = self.dropout(x[rows, anchor])                          # :604-608: the anchor token's row
-        x, _ = self.lstm(x)                                                 # :610
+        if self.hip_lstm and not torch.is_autocast_enabled("cuda") and takes_hip_lstm(x, self.lstm):
+            x = bilstm(x, self.lstm)                                        # :610 on the HIP path (inference, float32, no autocast)
+        else:
+            x, _ = self.lstm(x)                                             # :610
         if x.dtype == torch.float16 and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16:
             # under bf16 autocast the ROCm LSTM still returns float16; the reference's first consumers of x (gc1's matmul,
             # gcn.py:34) cast it to bf16, so the layers are handed that bf16 tensor directly

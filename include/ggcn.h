@@ -721,6 +721,26 @@ int ggcn_scores_head_dweight(const float *logits, int64_t ldl, const float *G, i
                              int B, int H, int C, float *dW, int64_t lddw, float *d_bias, void *workspace,
                              ggcn_stream_t stream);
 
+/* ---- the BiLSTM's recurrence in one launch (inference; models/bert_amir5.py:557,610) ----------------------------------
+ * PyTorch's LSTM, gate order i, f, g, o, with h0 = c0 = 0, one layer, both directions.  G [B*T, ldg] is the input projection
+ * X . [W_ih_f ; W_ih_r]^T (ggcn_linear: columns 0..4hd-1 belong to the forward direction, 4hd..8hd-1 to the reverse one).  For
+ * direction d in {f, r} and sentence b, t running 0..T-1 for f and T-1..0 for r:
+ *     a = G[b*T+t, d*4hd:(d+1)*4hd] + bias_d + h . Whh_d^T
+ *     i, f, o = sigmoid(a[0:hd]), sigmoid(a[hd:2hd]), sigmoid(a[3hd:4hd])        g = tanh(a[2hd:3hd])
+ *     c = f*c + i*g        h = o * tanh(c)        Y[b*T+t, d*hd:(d+1)*hd] = h
+ * Whh_d is [4hd, hd] row-major as weight_hh_l0[_reverse] lies; bias_d [4hd] = b_ih + b_hh, NULL = zeros.  All T rows of every
+ * sentence are run (a padded batch, no lengths).  One launch for all T steps and both directions: a workgroup of 512 threads
+ * takes GGCN_BILSTM_TILE sentences of one direction, Whh_d stays in its registers, h and c never leave the chip.  Exact fp32
+ * FMA chains in a fixed order, no atomics: two calls give the same bits, a sentence's result does not depend on B or on its
+ * place in a tile, and the two directions run the same arithmetic.  sigmoid and tanh saturate to 0 / 1 / +-1 without a NaN for
+ * every finite a.  No synchronisation.
+ * Refusals, all before any launch: NULL G / Whh_f / Whh_r / Y, B or T <= 0, ldg < 8 hd, ldy < 2 hd, Whh_f or Whh_r off 16
+ * bytes -> GGCN_EINVAL; hd != 128 (the reference's hidden_dim) and B*T >= 2^31 -> GGCN_EUNSUPPORTED. */
+#define GGCN_BILSTM_TILE 16
+int ggcn_bilstm_recurrence(const float *G, int64_t ldg, const float *Whh_f, const float *Whh_r,
+                           const float *bias_f, const float *bias_r, float *Y, int64_t ldy, int B, int T, int hd,
+                           ggcn_stream_t stream);
+
 /* ---- range check for GGCN_PREC_F16MX8 (on demand, not on the forward path) ----------------
  * out[0] = max |x| over the finite entries of X [M,K] (fp32, or IEEE half when is_half != 0; ld in
  * elements), out[1] = 1.0f when some entry is NaN or infinite.  f16mx8 needs |x|, |w| < 65504 and keeps
