@@ -583,7 +583,8 @@ int ggcn_lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const
                           float *overlap_partial, uint64_t *stamps, ggcn_stream_t stream)
 {
     const int flags = (getenv("GGCN_LAB_BLOCK8_ROWMAJOR") ? kBlock8RowMajor : 0) | (getenv("GGCN_LAB_BLOCK8_NODMA") ? kBlock8NoDma : 0) |
-                      (getenv("GGCN_LAB_BLOCK8_SAMESLOTS") ? kBlock8SameSlots : 0);   // (the experiment's switches, read per call)
+                      (getenv("GGCN_LAB_BLOCK8_SAMESLOTS") ? kBlock8SameSlots : 0) |
+                      (getenv("GGCN_LAB_BLOCK8_PRIO") ? kBlock8Prio : 0);   // (the experiment's switches, read per call)
     FusedArgs a = {};
     a.X = X; a.ldx = ldx; a.graph_ops = bytes(graph_ops); a.graph_ops2 = bytes(graph_ops2);
     a.stamps = reinterpret_cast<unsigned long long *>(stamps);

@@ -65,7 +65,7 @@ enum BlockKind { kBlockBinary, kBlockWeighted, kBlockBf16 };   // 0/1 adjacency,
 int launch_block(const char *who, FusedArgs &a, BlockKind kind, int precision, hipStream_t st);   // fused_layer.hip
 
 // the eight-wavefront form of the block on the same description (fused_block8.hip)
-constexpr int kBlock8RowMajor = 1, kBlock8NoDma = 2, kBlock8SameSlots = 4;
+constexpr int kBlock8RowMajor = 1, kBlock8NoDma = 2, kBlock8SameSlots = 4, kBlock8Prio = 8;
 bool block8_shape(int B, int T, int K, int F);
 bool block8_takes(const FusedArgs &a);
 int block_fused8(const char *who, FusedArgs &a, int flags, hipStream_t st);

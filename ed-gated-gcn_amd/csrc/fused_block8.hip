@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kB8Threads, 1) void block_fused8_kernel(const Fused
     }
     // whole tiles take the LDS-DMA staging (workgroup-uniform; a.k_steps & 1 carries the launcher's alignment verdict)
     const bool dma = (a.n_wg * BN == F) && (gt0 + 4 <= B) && a.ov_in == nullptr && a.ov_out == nullptr && (a.k_steps & 0x40000000) != 0;
-    const int k_steps = a.k_steps & 0x1fffffff;
+    const int k_steps = a.k_steps & 0x0fffffff;
     if (dma) {
         if (group == 0) stage_epilogue_operands_dma<kLdsBytes>(a, lp, g0, n_wgi, lds, tid);
         else stage_epilogue_operands_dma<kLdsBytes + kEpiLdsBytes>(a, lp, g0, n_wgi, lds, tid);
@@ -98,6 +98,9 @@ __global__ __launch_bounds__(kB8Threads, 1) void block_fused8_kernel(const Fused
     const float bw12 = *reinterpret_cast<const float *>(a.part[1].wpack + pack_bytes);
     const unsigned long long t_loop0 = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     mx8::BufX<float> bx = mx8::make_bufx<float>(a.X, a.ldx, (int64_t)gt0 * T, (int64_t)B * T, rel, tid);
+    // kBlock8Prio: the second-dispatched half of the workgroup -- the W12 group, whose epilogue is the longer one -- above its SIMD
+    // partner in the issue arbitration, once and for the whole launch (the two groups' epilogues then end together: DESIGN.md 5b)
+    if (group == 1 && (a.k_steps & 0x10000000) != 0) __builtin_amdgcn_s_setprio(1);
     // (two instantiations that meet at the same barriers: group 1's staging passes sit behind the stage's LAST two row blocks)
     if (group == 0 || getenv_slot_same(a))
         mx8::mainloop<float, true, true, !FULLT, false, true, 4, false, 2, 0>(arow, avalid, lp.wpack, K, k_steps / 2, 0, nt0, n_tiles_total, lds, acc, 0, 4,
@@ -177,9 +180,23 @@ bool block8_takes(const FusedArgs &a)
     return true;
 }
 
+// hipFuncSetAttribute once per instantiation and device (the call takes a lock of the runtime's and a few microseconds)
+template <typename KERN>
+static bool block8_reserve_lds(KERN kern)
+{
+    static bool done[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    if (dev >= 0 && dev < 64 && done[dev]) return true;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kB8Lds) != hipSuccess) return false;
+    if (dev >= 0 && dev < 64) done[dev] = true;
+    return true;
+}
+
 // who: the entry (ggcn_block_fused through launch_block, or ggcn_lab_block_fused8); a: the block, layer 1 in part[0] and layer 2 in part[1].
 // flags (fused_args.h kBlock8*): ROWMAJOR = a row block's three column slices on one XCD (the product's map: ggcn_block_fused takes
-// this kernel for large batches), else column slices pinned to XCDs; NODMA / SAMESLOTS: lab switches of ggcn_lab_block_fused8
+// this kernel for large batches), else column slices pinned to XCDs; NODMA / SAMESLOTS: lab switches of ggcn_lab_block_fused8; PRIO: the W12
+// group of every workgroup at s_setprio 1 (the product sets it; the lab entry on GGCN_LAB_BLOCK8_PRIO, so one process times both)
 int block_fused8(const char *who, FusedArgs &a, int flags, hipStream_t st)
 {
     LayerPart &l1 = a.part[0], &l2 = a.part[1];
@@ -200,6 +217,7 @@ int block_fused8(const char *who, FusedArgs &a, int flags, hipStream_t st)
     // (bit 30 of k_steps: every gate / bias row this launch reads starts 16-byte aligned -- the LDS-DMA staging may be used)
     if ((a.F % 4 == 0) && block8_dma_aligned(a) && !(flags & kBlock8NoDma)) a.k_steps |= 0x40000000;
     if (flags & kBlock8SameSlots) a.k_steps |= 0x20000000;
+    if (flags & kBlock8Prio) a.k_steps |= 0x10000000;
     a.n_wg = (a.F + BN - 1) / BN;
     const bool fullt = (a.T == 32) && (a.B % 4 == 0);
     const int64_t g_tiles = ((int64_t)a.B + 3) / 4, total = g_tiles * a.n_wg;   // (in 64 bits: B + 3 may not fit an int)
@@ -209,8 +227,7 @@ int block_fused8(const char *who, FusedArgs &a, int flags, hipStream_t st)
 #define GGCN_L8(FT, VS)                                                                                                           \
     do {                                                                                                                          \
         auto kern = block_fused8_kernel<FT, VS>;                                                                                  \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kB8Lds) != hipSuccess) \
-            return fail(GGCN_ELAUNCH, "%s: cannot reserve %d bytes of LDS", who, kB8Lds);                                         \
+        if (!block8_reserve_lds(kern)) return fail(GGCN_ELAUNCH, "%s: cannot reserve %d bytes of LDS", who, kB8Lds);              \
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kB8Threads), kB8Lds, st, a);                                          \
     } while (0)
     if (fullt && vst) GGCN_L8(true, true);

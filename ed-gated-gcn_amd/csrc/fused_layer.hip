@@ -626,10 +626,11 @@ int launch_block(const char *who, FusedArgs &a, BlockKind kind, int precision, h
     if (kind == kBlockBf16 && layer1 && !a.graph_ops) return fail(GGCN_EINVAL, "%s: layer 1 needs the per-graph operand blocks of ggcn_graph_operands", who);
     // large batches, every output, f16mx8: the eight-wavefront workgroup that stages a row block's X planes once for a W1 and a W12
     // column slice (fused_block8.hip: bit-identical results, 2 % less time in steady state from 2048 graphs up; it reads the 0/1 format).
-    // GGCN_BLOCK_FORM=4 (read per call) keeps the four-wavefront kernel: A/B timing, tests.
+    // GGCN_BLOCK_FORM=4 (read per call) keeps the four-wavefront kernel: A/B timing, tests.  kBlock8Prio: the W12 group of every
+    // workgroup at s_setprio 1 (1.4-2 % of the launch in steady state).
     if (kind == kBlockBinary && layer1 && !first.out && !a.stamps && precision == GGCN_PREC_F16MX8 && block8_takes(a)) {
         const char *form = getenv("GGCN_BLOCK_FORM");
-        if (!(form && form[0] == '4')) return block_fused8(who, a, kBlock8RowMajor, st);
+        if (!(form && form[0] == '4')) return block_fused8(who, a, kBlock8RowMajor | kBlock8Prio, st);
     }
     // A NULL mid bias (gc1 without bias) still needs the second aggregation: a vector of zeros cannot be conjured here, so the
     // caller passes one.

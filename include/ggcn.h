@@ -798,7 +798,8 @@ int ggcn_block_fused_form(int B, int T, int K, int F);
  * 16-byte aligned operands, >= 6 rounds of one workgroup per CU or >= 3 whole rounds).  Workgroups of EIGHT wavefronts share a row
  * block's X planes between the W1 and the W12 column tiles of a 256-column slice (no gcn1).  Bit-identical to the four-wavefront
  * kernel; the same argument checks and messages.  Here for tools/block8_timing.py and the tests; the XCD mapping and staging
- * switches of the experiment are read from the environment (GGCN_LAB_BLOCK8_*). */
+ * switches of the experiment are read from the environment (GGCN_LAB_BLOCK8_*; _PRIO: the W12 group of every workgroup at
+ * s_setprio 1, which ggcn_block_fused always sets). */
 int ggcn_lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
                           const void *graph_ops2, const float *bias1, const float *bias_mid, const float *bias2,
                           int B, int T, int K, int F, const float *gate1, const float *gate2, float *x_out, int64_t ld2,

@@ -56,6 +56,47 @@ if os.environ.get("LAB_ONLY") == "8":
 if os.environ.get("LAB_ONLY") == "4":
     for _ in range(int(os.environ.get("LAB_REPS", 60))): run4()
     torch.cuda.synchronize(); sys.exit(0)
+def stamps_of(tag):
+    """phase stamps of the eight-wavefront form (10 ns ticks): per workgroup and group: start, main loop start, main loop end, end"""
+    grid = 8 * ((B // 4 * 3 + 7) // 8) if not os.environ.get("GGCN_LAB_BLOCK8_ROWMAJOR") else 4096
+    st_buf = torch.zeros(grid * 2 * 4, dtype=torch.int64, device=dev)
+    STAMPS[0] = st_buf
+    for _ in range(20): run8()
+    torch.cuda.synchronize()
+    STAMPS[0] = None
+    s = st_buf.view(-1, 2, 4).cpu().double()
+    s = s[s[:, 1, 3] > 0]
+    for gname, gi in (("W1 group ", 0), ("W12 group", 1)):
+        pro = (s[:, gi, 1] - s[:, gi, 0]) * 0.01; loop = (s[:, gi, 2] - s[:, gi, 1]) * 0.01; epi = (s[:, gi, 3] - s[:, gi, 2]) * 0.01
+        print("%s%s per workgroup (us, median): prologue %.2f  main loop %.2f  epilogue %.2f  total %.2f   (n = %d)" %
+              (tag, gname, float(pro.median()), float(loop.median()), float(epi.median()), float(((s[:, gi, 3] - s[:, gi, 0]) * 0.01).median()), s.shape[0]))
+    last = (s[:, 1, 3] > s[:, 0, 3]).double().mean()
+    print("%sthe W12 group finishes last in %.0f %% of the workgroups (median lag %.2f us); kernel span by stamps: %.1f us" %
+          (tag, 100 * float(last), float(((s[:, 1, 3] - s[:, 0, 3]) * 0.01).median()), float((s[:, :, 3].max() - s[:, :, 0].min()) * 0.01)), flush=True)
+if os.environ.get("LAB_FORMS"):   # the lab switches of ggcn_lab_block_fused8 on the product's XCD map, each form ALONE for 1.5 s behind 300
+    import time                   # untimed launches (DESIGN.md 5b), LAB_FORMS rounds of all of them; then each form's phase stamps
+    FORMS = (("plain", ()), ("W12 group at prio 1", ("PRIO",)))
+    os.environ["GGCN_LAB_BLOCK8_ROWMAJOR"] = "1"
+    def switch(on):
+        for k in ("PRIO",): os.environ.pop("GGCN_LAB_BLOCK8_" + k, None)
+        for k in on: os.environ["GGCN_LAB_BLOCK8_" + k] = "1"
+    for rep in range(int(os.environ["LAB_FORMS"])):
+        for name, on in FORMS:
+            switch(on)
+            for _ in range(300): run8()
+            torch.cuda.synchronize()
+            a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t_end, cnt = time.perf_counter() + 1.5, 0
+            a.record()
+            while time.perf_counter() < t_end:
+                for _ in range(100): run8()
+                cnt += 100; torch.cuda.synchronize()
+            e.record(); torch.cuda.synchronize()
+            print("round %d  %-20s %.1f us" % (rep, name, a.elapsed_time(e) / cnt * 1e3), flush=True)
+    for name, on in FORMS:
+        switch(on)
+        stamps_of("%-20s " % name)
+    sys.exit(0)
 if os.environ.get("LAB_ENERGY"):   # each form ALONE for 1.5 s with the board power beside it: the kernels sit at the power cap, and
     import time                    # five-launch interleaved timings (below) mix the two forms' power states
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -87,17 +128,4 @@ for rnd in range(12):
         e1.record(); torch.cuda.synchronize()
         if rnd >= 2: times[name].append(e0.elapsed_time(e1) / 5 * 1e3)
 for name, v in times.items(): print("%-44s median %.1f us  min %.1f" % (name, statistics.median(v), min(v)))
-# phase stamps of the eight-wavefront form (10 ns ticks): per workgroup and group: start, main loop start, main loop end, end
-grid = 8 * ((B // 4 * 3 + 7) // 8) if not os.environ.get("GGCN_LAB_BLOCK8_ROWMAJOR") else 4096
-st_buf = torch.zeros(grid * 2 * 4, dtype=torch.int64, device=dev)
-STAMPS[0] = st_buf
-for _ in range(20): run8()
-torch.cuda.synchronize()
-s = st_buf.view(-1, 2, 4).cpu().double()
-s = s[s[:, 1, 3] > 0]
-for gname, gi in (("W1 group ", 0), ("W12 group", 1)):
-    pro = (s[:, gi, 1] - s[:, gi, 0]) * 0.01; loop = (s[:, gi, 2] - s[:, gi, 1]) * 0.01; epi = (s[:, gi, 3] - s[:, gi, 2]) * 0.01
-    print("%s per workgroup (us, median): prologue %.2f  main loop %.2f  epilogue %.2f  total %.2f   (n = %d)" %
-          (gname, float(pro.median()), float(loop.median()), float(epi.median()), float(((s[:, gi, 3] - s[:, gi, 0]) * 0.01).median()), s.shape[0]))
-span = (s[:, :, 3].max() - s[:, :, 0].min()) * 0.01
-print("kernel span by stamps: %.1f us" % float(span))
+stamps_of("")
