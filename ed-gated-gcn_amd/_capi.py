@@ -136,6 +136,7 @@ PROTOTYPES = {
     "ggcn_layer_fused_h": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                    c_vp, c_i64, c_vp, c_vp, c_vp]),
     "ggcn_block_fused_form": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "ggcn_linear_form": (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32]),
     "ggcn_dense_head": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "ggcn_dense_head_signal": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "ggcn_overlap_workspace_bytes": (c_sz, [c_i32]),
@@ -147,6 +148,9 @@ ABI_VERSION = 14
 PREC = {"bf16x3": 0, "fp32": 1, "f16mx8": 2, "f16": 3, "f16mx6": 4}
 PACKED = ("bf16x3", "f16mx8", "f16", "f16mx6")  # precisions whose linear reads a ggcn_weight_pack image ("f16": half features only)
 FLAG_WEIGHTED = 1
+# include/ggcn.h ggcn_linear_entry / ggcn_linear_form_bits (ggcn_linear_form)
+LINEAR_ENTRY = {"ggcn_linear": 0, "ggcn_linear_h": 1, "ggcn_linear_bf16": 2, "ggcn_linear_out_bf16": 3, "ggcn_linear_scaled": 4}
+FORM_XVEC, FORM_KFULL, FORM_VST, FORM_WVEC = 1, 2, 4, 8
 RANGE_OVERFLOW, RANGE_WINDOW, RANGE_HIDDEN = 1, 2, 4   # include/ggcn.h ggcn_range_bits
 BILSTM_TILE = 16   # include/ggcn.h GGCN_BILSTM_TILE: sentences per workgroup of ggcn_bilstm_recurrence
 

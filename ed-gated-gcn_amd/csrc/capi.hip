@@ -577,6 +577,49 @@ int ggcn_block_fused_form(int B, int T, int K, int F)
     return (block8_shape(B, T, K, F) && !(form && form[0] == '4')) ? 8 : 4;
 }
 
+int ggcn_linear_form(int entry, const void *X, int64_t ldx, const void *W, int64_t ldw, const void *Y, int64_t ldy, int64_t M, int K,
+                     int F, int precision)
+{
+    // the checks of the entry itself in the entry's order, then the launcher's own form function (common.h); no launch, no dereference
+    const char *who = "ggcn_linear_form";
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(X), ya = reinterpret_cast<uintptr_t>(Y);
+    auto split = [&](int x_bytes, bool y_f32) -> int {
+        if (linear_split_grid(M, F) > (int64_t)INT32_MAX) return -fail(GGCN_EUNSUPPORTED, "%s: M too large", who);
+        return linear_split_form(x_bytes, y_f32, X, ldx, Y, ldy, K, F);
+    };
+    switch (entry) {
+        case GGCN_ENTRY_LINEAR:
+            if (int rc = linear_entry_checks(who, !X || !Y, M, K, F, ldx, ldy)) return -rc;
+            if (precision == GGCN_PREC_BF16X3 || precision == GGCN_PREC_F16MX8) return split(4, true);
+            if (precision != GGCN_PREC_FP32) return -fail(GGCN_EINVAL, "%s: ggcn_linear has no precision %d", who, precision);
+            if (!W) return -fail(GGCN_EINVAL, "%s: ggcn_linear(fp32): W is NULL", who);
+            if (ldw < F) return -fail(GGCN_EINVAL, "%s: ggcn_linear(fp32): ldw < F", who);
+            return linear_fp32_form(X, ldx, W, ldw, K, F);
+        case GGCN_ENTRY_LINEAR_H:
+            if (precision != GGCN_PREC_BF16X3 && precision != GGCN_PREC_F16MX8 && precision != GGCN_PREC_F16)
+                return -fail(GGCN_EUNSUPPORTED, "%s: ggcn_linear_h has no precision %d", who, precision);
+            if (int rc = linear_entry_checks(who, !X || !Y, M, K, F, ldx, ldy)) return -rc;
+            if (precision != GGCN_PREC_F16) return split(2, false);
+            if (linear_split_grid(M, F) > (int64_t)INT32_MAX) return -fail(GGCN_EUNSUPPORTED, "%s: M too large", who);
+            return linear_f16_form(X, ldx, K);
+        case GGCN_ENTRY_LINEAR_BF16:
+        case GGCN_ENTRY_LINEAR_OUT_BF16: {
+            const bool out = entry == GGCN_ENTRY_LINEAR_OUT_BF16;   // fp32 X -> bf16 Y; otherwise bf16 X -> fp32 Y
+            if (int rc = linear_entry_checks(who, !X || !Y, M, K, F, ldx, ldy)) return -rc;
+            if (xa % (out ? 4 : 2) || ya % (out ? 2 : 4)) return -fail(GGCN_EINVAL, "%s: X / Y not aligned to their element size", who);
+            return split(out ? 4 : 2, !out);
+        }
+        case GGCN_ENTRY_LINEAR_SCALED:
+            if (!X || !Y) return -fail(GGCN_EINVAL, "%s: null pointer", who);
+            if (M <= 0 || K <= 0 || F <= 0 || ldx < K || ldy < F) return -fail(GGCN_EINVAL, "%s: M=%lld K=%d F=%d", who, (long long)M, K, F);
+            if (!linear_scaled_takes(static_cast<const float *>(X), ldx, static_cast<const float *>(Y), ldy, K, F))
+                return -fail(GGCN_EUNSUPPORTED, "%s: ggcn_linear_scaled needs K %% 32 == 0, F %% 4 == 0 and 16-byte aligned rows", who);
+            return split(4, true);
+        default:
+            return -fail(GGCN_EINVAL, "%s: unknown entry %d", who, entry);
+    }
+}
+
 int ggcn_lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
                           const void *graph_ops2, const float *bias1, const float *bias_mid, const float *bias2, int B, int T, int K, int F,
                           const float *gate1, const float *gate2, float *x_out, int64_t ld2, float *x1, float *y1, float *pool_out,

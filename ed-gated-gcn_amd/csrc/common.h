@@ -40,6 +40,14 @@ int rowmask_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t sb,
 int linear_fp32(const float *X, int64_t ldx, const float *W, int64_t ldw, float *Y, int64_t ldy,
                 int64_t M, int K, int F, hipStream_t st);
 
+// Which kernel form a linear launcher takes, as ggcn_linear_form_bits (ggcn_linear_form answers with these, and the launchers
+// themselves dispatch on them: one rule).  A bit is only set where the form that needs it is taken: KFULL implies XVEC, VST both.
+// x_bytes: sizeof of X's element; y_f32: Y is float32 (the staged row stores exist for it alone).
+int linear_split_form(int x_bytes, bool y_f32, const void *X, int64_t ldx, const void *Y, int64_t ldy, int K, int F);   // linear_split.hip: launch_linear
+int linear_f16_form(const void *X, int64_t ldx, int K);                                                                // linear_split.hip: launch_linear_f16
+int linear_fp32_form(const void *X, int64_t ldx, const void *W, int64_t ldw, int K, int F);                            // linear_fp32.hip
+int64_t linear_split_grid(int64_t M, int F);   // workgroups of the split / fp16 kernels (refused beyond INT32_MAX)
+
 size_t weight_pack_bytes(int K, int F, int precision);
 int weight_pack(const float *W, int64_t ldw, int K, int F, int precision, bool transposed, void *wpack, hipStream_t st);
 int linear_packed(const float *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy,

@@ -144,11 +144,19 @@ __global__ __launch_bounds__(256) void linear_fp32_kernel(
 
 }  // namespace
 
-int linear_fp32(const float *X, int64_t ldx, const float *W, int64_t ldw, float *Y, int64_t ldy,
-                int64_t M, int K, int F, hipStream_t st)
+// the form rule of linear_fp32 (common.h; ggcn_linear_form): X and W take their 16-byte loads independently
+int linear_fp32_form(const void *X, int64_t ldx, const void *W, int64_t ldw, int K, int F)
 {
     const bool avec = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(X);
     const bool bvec = (F % 4 == 0) && (ldw % 4 == 0) && aligned16(W);
+    return (avec ? GGCN_FORM_XVEC : 0) | (bvec ? GGCN_FORM_WVEC : 0);
+}
+
+int linear_fp32(const float *X, int64_t ldx, const float *W, int64_t ldw, float *Y, int64_t ldy,
+                int64_t M, int K, int F, hipStream_t st)
+{
+    const int form = linear_fp32_form(X, ldx, W, ldw, K, F);
+    const bool avec = form & GGCN_FORM_XVEC, bvec = form & GGCN_FORM_WVEC;
     const int64_t by = (M + BM - 1) / BM;
     if (by > 65535) {
         // grid.y limit: split the rows into chunks of 65535 tiles

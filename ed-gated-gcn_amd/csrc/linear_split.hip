@@ -373,12 +373,12 @@ int launch_linear_f16(const __half *X, int64_t ldx, const void *wpack, __half *Y
 {
     if (!wpack) return fail(GGCN_EINVAL, "ggcn_linear_h(f16): wpack is NULL (ggcn_weight_pack with GGCN_PREC_F16MX8)");
     if (!aligned16(wpack)) return fail(GGCN_EINVAL, "ggcn_linear_h(f16): wpack must be 16-byte aligned");
-    const bool avec = (K % 8 == 0) && (ldx % 8 == 0) && aligned16(X);
-    const bool kfull = (K % f16::BK2 == 0);
+    const int form = linear_f16_form(X, ldx, K);
+    const bool avec = form & GGCN_FORM_XVEC, kfull = form & GGCN_FORM_KFULL;
     const int records = round_up(K, BK) / BK;
     const int64_t m_tiles = (M + BM - 1) / BM;
     const int n_wg = (F + BN - 1) / BN;
-    const int64_t grid = grid_for(m_tiles, n_wg);
+    const int64_t grid = linear_split_grid(M, F);
     if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "ggcn_linear_h(f16): M too large");
     const char *wp = static_cast<const char *>(wpack);
 #define GGCN_LAUNCH(AV, KF)                                                                                           \
@@ -397,17 +397,15 @@ int launch_linear(const ET *X, int64_t ldx, const void *wpack, YT *Y, int64_t ld
 {
     if (!wpack) return fail(GGCN_EINVAL, "ggcn_linear(bf16x3): wpack is NULL (call ggcn_weight_pack first)");
     if (!aligned16(wpack)) return fail(GGCN_EINVAL, "ggcn_linear(bf16x3): wpack must be 16-byte aligned");
-    constexpr int EPT = Geom<ET>::EPT;
-    // (the fast shapes address a tile's 128 rows with 32-bit byte offsets from its first row: buffer loads)
-    const bool avec = (K % EPT == 0) && (ldx % EPT == 0) && aligned16(X) && (int64_t)ldx * (int64_t)sizeof(ET) * 257 < ((int64_t)1 << 31);
-    const bool kfull = (K % BK == 0);
+    static_assert(Geom<ET>::EPT == 16 / (int)sizeof(ET), "linear_split_form derives the elements per 16-byte load from sizeof");
+    const int form = linear_split_form((int)sizeof(ET), std::is_same<YT, float>::value, X, ldx, Y, ldy, K, F);
+    const bool avec = form & GGCN_FORM_XVEC, kfull = form & GGCN_FORM_KFULL, vst = form & GGCN_FORM_VST;
     const int k_steps = round_up(K, BK) / KSTEP;
     const int64_t m_tiles = (M + BM - 1) / BM;
     const int n_wg = (F + BN - 1) / BN;
-    const int64_t grid = grid_for(m_tiles, n_wg);
+    const int64_t grid = linear_split_grid(M, F);
     if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "ggcn_linear(bf16x3): M too large");
     const char *wp = static_cast<const char *>(wpack);
-    const bool vst = std::is_same<YT, float>::value && (F % 4 == 0) && (ldy % 4 == 0) && aligned16(Y);
 #define GGCN_LAUNCH(AV, KF, VS)                                                                                     \
     hipLaunchKernelGGL((linear_split_kernel<SCH, ET, AV, KF, VS && std::is_same<YT, float>::value, false, YT>), dim3((unsigned)grid), \
                        dim3(kThreads), 0, st, X, ldx, wp, Y, ldy, M, K, F, (int)m_tiles, n_wg, k_steps)
@@ -456,6 +454,28 @@ int pack_trailer(const float *W, int64_t ldw, int K, int F, bool transposed, cha
 }
 
 }  // namespace
+
+// ---- the form rules of launch_linear and launch_linear_f16 (common.h; ggcn_linear_form) ----
+int linear_split_form(int x_bytes, bool y_f32, const void *X, int64_t ldx, const void *Y, int64_t ldy, int K, int F)
+{
+    const int ept = 16 / x_bytes;   // Geom<ET>::EPT
+    // (the fast shapes address a tile's 128 rows with 32-bit byte offsets from its first row: buffer loads)
+    const bool avec = (K % ept == 0) && (ldx % ept == 0) && aligned16(X) && ldx * (int64_t)x_bytes * 257 < ((int64_t)1 << 31);
+    const bool kfull = (K % BK == 0);
+    const bool vst = y_f32 && (F % 4 == 0) && (ldy % 4 == 0) && aligned16(Y);
+    if (!avec) return 0;
+    if (!kfull) return GGCN_FORM_XVEC;
+    return GGCN_FORM_XVEC | GGCN_FORM_KFULL | (vst ? GGCN_FORM_VST : 0);
+}
+
+int linear_f16_form(const void *X, int64_t ldx, int K)
+{
+    const bool avec = (K % 8 == 0) && (ldx % 8 == 0) && aligned16(X);
+    const bool kfull = (K % f16::BK2 == 0);
+    return !avec ? 0 : GGCN_FORM_XVEC | (kfull ? GGCN_FORM_KFULL : 0);
+}
+
+int64_t linear_split_grid(int64_t M, int F) { return grid_for((M + BM - 1) / BM, (F + BN - 1) / BN); }
 
 size_t weight_pack_bytes(int K, int F, int precision)
 {
@@ -535,7 +555,7 @@ int linear_packed(const float *X, int64_t ldx, const void *wpack, float *Y, int6
 // derived on the device from *amax.  Fast shapes only (K % 32 == 0, F % 4 == 0, 16-byte aligned rows); the caller keeps bf16x3 otherwise.
 bool linear_scaled_takes(const float *X, int64_t ldx, const float *Y, int64_t ldy, int K, int F)
 {
-    return (K % BK == 0) && (ldx % 4 == 0) && aligned16(X) && (int64_t)ldx * 4 * 257 < ((int64_t)1 << 31) && (F % 4 == 0) && (ldy % 4 == 0) && aligned16(Y);
+    return linear_split_form(4, true, X, ldx, Y, ldy, K, F) == (GGCN_FORM_XVEC | GGCN_FORM_KFULL | GGCN_FORM_VST);
 }
 int linear_scaled(const float *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F, const float *amax,
                   hipStream_t st)
@@ -548,7 +568,7 @@ int linear_scaled(const float *X, int64_t ldx, const void *wpack, float *Y, int6
     const int k_steps = round_up(K, BK) / KSTEP;
     const int64_t m_tiles = (M + BM - 1) / BM;
     const int n_wg = (F + BN - 1) / BN;
-    const int64_t grid = grid_for(m_tiles, n_wg);
+    const int64_t grid = linear_split_grid(M, F);
     if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "ggcn_linear_scaled: M too large");
     hipLaunchKernelGGL((linear_split_kernel<1, float, true, true, true, true>), dim3((unsigned)grid), dim3(kThreads), 0, st, X, ldx,
                        static_cast<const char *>(wpack), Y, ldy, M, K, F, (int)m_tiles, n_wg, k_steps, amax);

@@ -793,6 +793,38 @@ int ggcn_debug_mfma_calibrate(int n_wg, int stages, uint64_t *stamps, float *sin
  * GGCN_BLOCK_FORM=4 in the environment (read per call) keeps the four-wavefront kernel. */
 int ggcn_block_fused_form(int B, int T, int K, int F);
 
+/* Which kernel form a dense linear entry takes for these operands: a host-only query that launches nothing and looks at the
+ * pointer VALUES for their alignment only (nothing is dereferenced; W is looked at for GGCN_PREC_FP32 alone, `precision` by the
+ * entries that have one).  The launchers dispatch on the very function that answers here.  Returns a set of
+ * ggcn_linear_form_bits, or -ggcn_status where the entry would refuse the call (the weight image, which the query does not see,
+ * taken as valid):
+ *   split kernels (ggcn_linear bf16x3 / f16mx8, ggcn_linear_h bf16x3 / f16mx8, ggcn_linear_bf16, ggcn_linear_out_bf16),
+ *   tile 128 rows x 256 columns, 32 k per stage:
+ *     XVEC              16-byte X loads: K and ldx multiples of 16 / sizeof(x), X 16-byte aligned, and
+ *                       ldx * sizeof(x) * 257 < 2^31 (a tile's rows are addressed by 32-bit byte offsets from its first row)
+ *     XVEC|KFULL        and K % 32 == 0: no k guard in the main loop
+ *     XVEC|KFULL|VST    and float32 Y with F, ldy multiples of 4, Y 16-byte aligned: 16-byte row stores through LDS
+ *     0                 element loads, guarded stores
+ *     ggcn_linear_scaled takes XVEC|KFULL|VST or refuses.
+ *   fp16 kernel (ggcn_linear_h, GGCN_PREC_F16), 64 k per stage: XVEC (K, ldx % 8 == 0, aligned), XVEC|KFULL (K % 64 == 0), 0.
+ *   fp32 kernel (ggcn_linear, GGCN_PREC_FP32), tile 128 x 128, 16 k per stage: XVEC (K, ldx % 4 == 0, X aligned) and WVEC
+ *   (F, ldw % 4 == 0, W aligned) independently; beyond 65535 row tiles the launcher walks the rows in slices of 65535 tiles. */
+enum ggcn_linear_entry {
+    GGCN_ENTRY_LINEAR = 0,          /* ggcn_linear */
+    GGCN_ENTRY_LINEAR_H = 1,        /* ggcn_linear_h */
+    GGCN_ENTRY_LINEAR_BF16 = 2,     /* ggcn_linear_bf16 */
+    GGCN_ENTRY_LINEAR_OUT_BF16 = 3, /* ggcn_linear_out_bf16 */
+    GGCN_ENTRY_LINEAR_SCALED = 4    /* ggcn_linear_scaled */
+};
+enum ggcn_linear_form_bits {
+    GGCN_FORM_XVEC = 1,   /* 16-byte X loads */
+    GGCN_FORM_KFULL = 2,  /* whole k stages */
+    GGCN_FORM_VST = 4,    /* 16-byte row stores through LDS */
+    GGCN_FORM_WVEC = 8    /* 16-byte W loads (the fp32 kernel) */
+};
+int ggcn_linear_form(int entry, const void *X, int64_t ldx, const void *W, int64_t ldw, const void *Y, int64_t ldy, int64_t M,
+                     int K, int F, int precision);
+
 /* The eight-wavefront kernel of the block called directly (fused_block8.hip): the kernel ggcn_block_fused itself runs for large
  * batches (the rule of ggcn_block_fused_form above: every output, GGCN_PREC_F16MX8, T <= 32, K % 32 == 0, F a multiple of 256,
  * 16-byte aligned operands, >= 6 rounds of one workgroup per CU or >= 3 whole rounds).  Workgroups of EIGHT wavefronts share a row

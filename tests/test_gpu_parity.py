@@ -174,7 +174,8 @@ def test_gated_block_vs_oracle(pkg, dev, precision, fused, B, T, H, padded):
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3", "f16mx8"])
 @pytest.mark.parametrize("M,K,F", [(256, 768, 768), (1000, 300, 300), (33, 17, 5), (513, 768, 34), (7, 9216, 256)])
 def test_linear_vs_float64(pkg, dev, precision, M, K, F):
-    """gcn.py:34 alone, against a float64 product (odd shapes hit every edge/tail path)."""
+    """gcn.py:34 alone, against a float64 product (odd shapes hit every edge/tail path).
+    Every kernel form by name, hostile strides and per-element gates: tests/test_gpu_linear.py."""
     rng = np.random.default_rng(M + K + F)
     x = rng.standard_normal((M, K)).astype(np.float32)
     w, _ = __import__("ed_gated_gcn_amd").synth.layer_params(K, F, seed=3)
