@@ -21,8 +21,6 @@
 #include "bf16x3_core.h"
 #include "common.h"
 
-#include <cstdlib>
-
 namespace ggcn {
 namespace {
 
@@ -424,13 +422,10 @@ struct TnPlan { int m_tiles, n_wg, n_splits; int64_t chunk_rows; size_t slab_byt
 // 128 x 256 tile).  A pure function of the shape: ggcn_dweight_workspace_bytes and ggcn_dweight can never disagree.
 bool tn_big_tile(int64_t N, int K, int F)
 {
-    bool big = K % T2_B == 0 && F % T2_B == 0 && N >= 65536;
-#ifdef GGCN_LAB_DW   // lab builds only (tools/labbuild.sh "-DGGCN_LAB_DW"): GGCN_DW_TILE=128 / 256 picks the tile per call
-    if (const char *e = getenv("GGCN_DW_TILE")) big = K % T2_B == 0 && F % T2_B == 0 && atoi(e) == 256;
-#endif
-    return big;
+    return K % T2_B == 0 && F % T2_B == 0 && N >= 65536;
 }
 
+// A pure function of (N, K, F) as well: ggcn_dweight_workspace_bytes and ggcn_dweight can never disagree about the slabs.
 TnPlan tn_plan(int64_t N, int K, int F)
 {
     TnPlan p;
@@ -442,10 +437,6 @@ TnPlan tn_plan(int64_t N, int K, int F)
     if (s < 8) s = 8;                  // (more tiles than slots: eight chunks, several rounds)
     const int64_t max_s = (N + 511) / 512;   // at least 512 node rows per chunk
     if (s > max_s) s = max_s;
-#ifdef GGCN_LAB_DW   // lab builds only (tools/dw_timing.py through tools/labbuild.sh "-DGGCN_LAB_DW"): the product plan is a pure
-                     // function of (N, K, F), so ggcn_dweight_workspace_bytes and ggcn_dweight can never disagree about the slabs
-    if (const char *e = getenv("GGCN_LAB_DW_SPLITS")) s = atoi(e);
-#endif
     if (s < 1) s = 1;
     p.n_splits = (int)s;
     const int64_t rows = (N + s - 1) / s;

@@ -169,7 +169,6 @@ __device__ __forceinline__ void mainloop(const float *__restrict__ xtile, uint32
         // 2- to 4-way bank conflicts) cost 67 us of a 700 us launch, so the lanes trade halves through DPP -- the even lane
         // takes the whole xl block, the odd lane the whole xh block -- and each stores its block and its scale as two
         // conflict-free 16-byte writes.
-        if constexpr (((GGCN_LAB_OFF) & 4) != 0) { asm volatile("" :: "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[3]), "v"(q[4]), "v"(q[5])); return; }
         uint32_t recv[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -268,9 +267,8 @@ __device__ __forceinline__ void mainloop(const float *__restrict__ xtile, uint32
         f16x8 ah[3];
         i32x8 aq[2];
         int sa[2];
-        constexpr bool SPLIT = !((GGCN_LAB_OFF) & 2);
         SplitState sp;
-        if constexpr (SPLIT) split_read(sp, buf ^ 1);   // (the last stage splits a repeat of itself: nobody reads it)
+        split_read(sp, buf ^ 1);   // (the last stage splits a repeat of itself: nobody reads it)
         read_h1(buf, 0, 0, ah[0]);
         read_h1(buf, 1, 0, ah[1]);
         GGCN_SB6();
@@ -283,16 +281,15 @@ __device__ __forceinline__ void mainloop(const float *__restrict__ xtile, uint32
             acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i % 3], b0[0], acc[i][0], 0, 0, 0);
             acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i % 3], b0[1], acc[i][1], 0, 0, 0);
             GGCN_SB6();
-            if constexpr (!((GGCN_LAB_OFF) & 1)) issue_piece(i, st + 2, buf);  // one DMA piece per row block (RAW[buf] was split a stage ago)
-            if constexpr (SPLIT) {   // the split of stage st + 1, a piece behind every MFMA pair
-                if (i == 0) split_scale(sp);
-                if (i == 1) split_pairs(sp, 0, 2);
-                if (i == 2) { split_pairs(sp, 2, 2); split_store_h(sp, buf ^ 1, 0); }
-                if (i == 3) split_pairs(sp, 4, 2);
-            }
+            issue_piece(i, st + 2, buf);  // one DMA piece per row block (RAW[buf] was split a stage ago)
+            // the split of stage st + 1, a piece behind every MFMA pair
+            if (i == 0) split_scale(sp);
+            if (i == 1) split_pairs(sp, 0, 2);
+            if (i == 2) { split_pairs(sp, 2, 2); split_store_h(sp, buf ^ 1, 0); }
+            if (i == 3) split_pairs(sp, 4, 2);
             GGCN_SB6();
         }
-        if constexpr (!((GGCN_LAB_OFF) & 16)) load_bf0(st + 1, b0);
+        load_bf0(st + 1, b0);
         GGCN_SB6();
         // ---- k-step 1 (fragment t = 4 + i sits in ah[(4 + i) % 3]) ----
 #pragma unroll
@@ -303,13 +300,11 @@ __device__ __forceinline__ void mainloop(const float *__restrict__ xtile, uint32
             acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[(4 + i) % 3], b1[0], acc[i][0], 0, 0, 0);
             acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[(4 + i) % 3], b1[1], acc[i][1], 0, 0, 0);
             GGCN_SB6();
-            if constexpr (SPLIT) {
-                if (i == 0) { split_pairs(sp, 6, 2); split_store_h(sp, buf ^ 1, 1); }
-                if (i == 1) split_convert(sp, buf ^ 1);
-                GGCN_SB6();
-            }
+            if (i == 0) { split_pairs(sp, 6, 2); split_store_h(sp, buf ^ 1, 1); }
+            if (i == 1) split_convert(sp, buf ^ 1);
+            GGCN_SB6();
         }
-        if constexpr (!((GGCN_LAB_OFF) & 16)) load_bf1(st + 1, b1);
+        load_bf1(st + 1, b1);
         GGCN_SB6();
         // ---- fp6 corrections ----
 #pragma unroll
@@ -320,7 +315,7 @@ __device__ __forceinline__ void mainloop(const float *__restrict__ xtile, uint32
             if (i + 2 < 4) read_q(buf, i + 2, aq[i & 1], sa[i & 1]);
             GGCN_SB6();
         }
-        if constexpr (!((GGCN_LAB_OFF) & 16)) load_bq(st + 1, bm);
+        load_bq(st + 1, bm);
         __syncthreads();
     };
     int st = 0;

@@ -39,7 +39,6 @@
 // 23 % fewer W bytes through L2 for 16 VALU per stage: fused layer -2 %, plain linear -3 %.
 #pragma once
 #include "bf16x3_core.h"
-#include "lab_hooks.h"
 
 namespace ggcn {
 namespace mx8 {
@@ -167,8 +166,6 @@ __device__ __forceinline__ int q_lds_off(int row, int chunk)
 }
 
 #define GGCN_SB() __builtin_amdgcn_sched_barrier(0)
-// timing-only elimination ladder (lab_hooks.h: GGCN_LAB_OFF, 0 in the product build)
-#define GGCN_ON(bit) constexpr (!((GGCN_LAB_OFF) & (bit)))
 
 // RBLK: only the first `nblk` of this wavefront's four 32-row blocks hold nodes (wavefront-uniform run-time count: the second
 // row group of a 256-row graph slot, fused_layer.hip wide8) -- the MFMAs of the others are skipped, their rows stay zero.
@@ -200,11 +197,6 @@ __device__ __forceinline__ BufX<AT> make_bufx(const AT *X, int64_t ldx, int64_t 
 // NB (fp32 rows: one staging pass = one 32-row block): only the first NB of this wavefront's four blocks exist at all -- the
 // staging passes, fragment reads and MFMAs of the others are not compiled in (the second row group of a 129..224-node graph
 // in a 256-row slot, fused_wide8.hip): their LDS rows are never written or read, their accumulators stay zero.
-// W2 (GGCN_LAB_W2, lab): a second register set for W's fp16 fragments -- the next stage's are asked for at the TOP of a
-// stage (a whole stage of lead) instead of behind its first MX MFMA (7 MFMAs of lead).
-#ifndef GGCN_LAB_W2
-#define GGCN_LAB_W2 0
-#endif
 // XS (ggcn_linear_scaled: the backward's dX): every value is multiplied by the power of two `xscale` before it is split -- rows
 // whose magnitudes lie anywhere in the fp32 range (gradients) are brought to |x| < 256 first; the caller undoes it at the store.
 // XP (fused_block8.hip, the block's large-batch kernel): this thread STAGES only XP of the tile's passes -- pass0, pass0 + 1, ... in the slots 0 ..
@@ -394,9 +386,7 @@ __device__ __forceinline__ void mainloop(const AT *const (&arow)[Geom<AT>::NP], 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    constexpr bool W2 = (GGCN_LAB_W2) != 0;
-    f16x8 bset0[W2 ? 2 : 1][RN], bset1[W2 ? 2 : 1][RN];   // fp16 fragments of the two k-steps: [register set][column tile]
-    f16x8 (&b0)[RN] = bset0[0], (&b1)[RN] = bset1[0];
+    f16x8 b0[RN], b1[RN];   // fp16 fragments of the two k-steps: [column tile]
     i32x4 bq[RN];  // fp8(wl) of the stage
     i32x4 bw[RN];  // fp8(wh) of the stage (GGCN_WH8_STORED)
     int sq[RN];
@@ -428,92 +418,61 @@ __device__ __forceinline__ void mainloop(const AT *const (&arow)[Geom<AT>::NP], 
     //                                        of the next block's fragments (one slot ahead of use)
     //   slots 4-7 (block i): 2 MX  MFMAs   | the fp16 B fragments of the next stage, LDS reads
     // The MX operand of B is loaded at the top of its stage (used from slot 4 on).
-    // ladder: operands the switched-off steps would have produced (dead code when GGCN_LAB_OFF == 0)
-    f16x8 lab_h[2];
-    i32x8 lab_q;
-    i32x8 lab_bm[RN];
-    if constexpr ((GGCN_LAB_OFF) != 0) {
-        read_h(0, 0, lab_h);
-        read_q(0, 0, lab_q);
-        load_bq(kstage(0), bq, sq);
-        if constexpr (GGCN_WH8_STORED) load_wh8(kstage(0), bw);
-#pragma unroll
-        for (int j = 0; j < RN; ++j) {
-            const i32x4 w = GGCN_WH8_STORED ? bw[j] : wh8_of(b0[j], b1[j], sq[j]);
-            lab_bm[j] = i32x8{w[0], w[1], w[2], w[3], bq[j][0], bq[j][1], bq[j][2], bq[j][3]};
-        }
-    }
     auto stage = [&](int st, auto bufc) {
         constexpr int buf = decltype(bufc)::value;
         const int k_next1 = kstage(st + 1) * BK;
         const int ka = kstage(st + 2) * BK;
         f16x8 ah[2][2];
         i32x8 aq[2];
-        if GGCN_ON(8) read_h(buf, 0, ah[0]); else { ah[0][0] = lab_h[0]; ah[0][1] = lab_h[1]; }
-        if GGCN_ON(16) { load_bq(kstage(st), bq, sq); if constexpr (GGCN_WH8_STORED) load_wh8(kstage(st), bw); }
-        // W2: this stage's fragments live in set `buf` (stage parity = buffer parity); the next stage's are asked for now, BEHIND
-        // this stage's bq (vmcnt retires in order: the MX phase's wait for bq must not wait for them)
-        f16x8 (&b0)[RN] = bset0[W2 ? buf : 0], (&b1)[RN] = bset1[W2 ? buf : 0];
-        if constexpr (W2) { if GGCN_ON(16) load_bf(kstage(st + 1), bset0[buf ^ 1], bset1[buf ^ 1]); }
+        read_h(buf, 0, ah[0]);
+        load_bq(kstage(st), bq, sq);
+        if constexpr (GGCN_WH8_STORED) load_wh8(kstage(st), bw);
         GGCN_SB();
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            if GGCN_ON(8) {
-                if (i < NB - 1) read_h(buf, i + 1, ah[(i + 1) & 1]);
-                else read_q(buf, 0, aq[0]);
-            } else {
-                if (i < NB - 1) { ah[(i + 1) & 1][0] = lab_h[0]; ah[(i + 1) & 1][1] = lab_h[1]; }
-                else aq[0] = lab_q;
-            }
+            const bool stages_here = i - SLOT0 >= 0 && i - SLOT0 < NP && i - SLOT0 < XP;   // staging pass i - SLOT0 sits behind this slot
+            if (i < NB - 1) read_h(buf, i + 1, ah[(i + 1) & 1]);
+            else read_q(buf, 0, aq[0]);
             GGCN_SB();
             if (!RBLK || i < nblk) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i & 1][0], b0[0], acc[i][0], 0, 0, 0);
             GGCN_SB();
-            if GGCN_ON(2) { if (i - SLOT0 >= 0 && i - SLOT0 < NP && i - SLOT0 < GGCN_LAB_XPASSES && i - SLOT0 < XP) split_pass(i - SLOT0, k_next1); }
+            if (stages_here) split_pass(i - SLOT0, k_next1);
             GGCN_SB();
             if (!RBLK || i < nblk) acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i & 1][0], b0[1], acc[i][1], 0, 0, 0);
             GGCN_SB();
-            if GGCN_ON(4) { if (i - SLOT0 >= 0 && i - SLOT0 < NP && i - SLOT0 < GGCN_LAB_XPASSES && i - SLOT0 < XP) write_pass(buf ^ 1, i - SLOT0); }
-            else { _Pragma("unroll") for (int q = 0; q < NQ; ++q) asm volatile("" :: "v"(sp[q].h01), "v"(sp[q].h23), "v"(sp[q].l8), "v"(sp[q].h8)); }
+            if (stages_here) write_pass(buf ^ 1, i - SLOT0);
             GGCN_SB();
             if (!RBLK || i < nblk) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i & 1][1], b1[0], acc[i][0], 0, 0, 0);
             GGCN_SB();
-            if GGCN_ON(1) { if (i - SLOT0 >= 0 && i - SLOT0 < NP && i - SLOT0 < GGCN_LAB_XPASSES && i - SLOT0 < XP) load_a_pass(i - SLOT0, ka); }
-            else { if (i < NP) { _Pragma("unroll") for (int c = 0; c < EPT; ++c) asm volatile("" : "+v"(ra[i][c])); } }
+            if (stages_here) load_a_pass(i - SLOT0, ka);
             GGCN_SB();
             if (!RBLK || i < nblk) acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i & 1][1], b1[1], acc[i][1], 0, 0, 0);
             GGCN_SB();
         }
         // the MX operand of W = {fp8(wh) made here from the fp16 fragments, fp8(wl) as loaded}; b0/b1 are
-        // dead afterwards and take the next stage's fragments.  The second column tile's converts sit behind the first
-        // tile's first MX MFMA (GGCN_LAB_WH8 = 0: both tiles' converts in front of the MX phase, the round-2 order)
+        // dead afterwards and take the next stage's fragments.  Both tiles' converts sit in front of the MX phase
+        // (the second tile's behind the first tile's first MX MFMA was no gain: DESIGN.md).
         i32x8 bm[RN];
-        auto make_bm = [&](int j) {
-            if GGCN_ON(32) {
-                i32x4 w;
-                if constexpr (GGCN_WH8_STORED) w = bw[j];
-                else w = wh8_of(b0[j], b1[j], sq[j]);
-                bm[j] = i32x8{w[0], w[1], w[2], w[3], bq[j][0], bq[j][1], bq[j][2], bq[j][3]};
-            } else {
-                bm[j] = lab_bm[j];
-            }
-        };
-        make_bm(0);
-        if constexpr (!(GGCN_LAB_WH8)) make_bm(1);
+#pragma unroll
+        for (int j = 0; j < RN; ++j) {
+            i32x4 w;
+            if constexpr (GGCN_WH8_STORED) w = bw[j];
+            else w = wh8_of(b0[j], b1[j], sq[j]);
+            bm[j] = i32x8{w[0], w[1], w[2], w[3], bq[j][0], bq[j][1], bq[j][2], bq[j][3]};
+        }
         GGCN_SB();
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            if GGCN_ON(8) { if (i < NB - 1) read_q(buf, i + 1, aq[(i + 1) & 1]); }
-            else { if (i < NB - 1) aq[(i + 1) & 1] = lab_q; }
+            if (i < NB - 1) read_q(buf, i + 1, aq[(i + 1) & 1]);
             GGCN_SB();
-            if (!RBLK || i < nblk) acc[i][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aq[i & 1], bm[0], acc[i][0], GGCN_LAB_MXFMT, GGCN_LAB_MXFMT, 0, scale_a, 0, sq[0]);
+            if (!RBLK || i < nblk) acc[i][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aq[i & 1], bm[0], acc[i][0], 0, 0, 0, scale_a, 0, sq[0]);
             GGCN_SB();
-            if constexpr (GGCN_LAB_WH8) { if (i == 0) make_bm(1); }
-            if constexpr (!W2) { if GGCN_ON(16) { if (i == 0) load_bf(kstage(st + 1), b0, b1); } }  // b0/b1 are dead: the fp16 MFMAs of this stage are all issued
+            if (i == 0) load_bf(kstage(st + 1), b0, b1);   // b0/b1 are dead: the fp16 MFMAs of this stage are all issued
             GGCN_SB();
-            if (!RBLK || i < nblk) acc[i][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aq[i & 1], bm[1], acc[i][1], GGCN_LAB_MXFMT, GGCN_LAB_MXFMT, 0, scale_a, 0, sq[1]);
+            if (!RBLK || i < nblk) acc[i][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(aq[i & 1], bm[1], acc[i][1], 0, 0, 0, scale_a, 0, sq[1]);
             GGCN_SB();
         }
-        if GGCN_ON(64) __syncthreads();
+        __syncthreads();
     };
     int st = 0;
     for (; st + 1 < stages; st += 2) {
@@ -526,7 +485,6 @@ __device__ __forceinline__ void mainloop(const AT *const (&arow)[Geom<AT>::NP], 
     else range_verdict(amax);
 }
 #undef GGCN_SB
-#undef GGCN_ON
 
 }  // namespace mx8
 }  // namespace ggcn

@@ -55,17 +55,6 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused6_kernel(c
     const uint32_t xtile_bytes = (uint32_t)(((rows_left < 128 ? rows_left : 128) - 1) * a.ldx * 4 + (int64_t)K * 4);
     float amax;
     mx6::mainloop<!FULLT>(xtile, xtile_bytes, aoff, (uint32_t)(16 * a.ldx * 4), uvalid, lp.wpack, K, a.k_steps / 2, nt0, n_tiles_total, lds, acc, &amax);
-    if constexpr (((GGCN_LAB_OFF) & 128) != 0) {   // ladder: no epilogue
-        float sacc = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < RN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += acc[i][j][r];
-        if (sacc == 123.456f && lp.pool_a) lp.pool_a[tid] = sacc;
-        return;
-    }
     // everything the epilogue derives from the thread id is derived AFTER the loop (the asm makes the id opaque): hipcc
     // otherwise computes those per-lane offsets and pointers up front and keeps ~25 registers alive across a loop that
     // has none to spare

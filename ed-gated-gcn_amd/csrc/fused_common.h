@@ -5,7 +5,6 @@
 #include "f16mx8_core.h"
 #include "expand_mask.h"
 #include "fused_args.h"
-#include "lab_hooks.h"
 
 namespace ggcn {
 
@@ -44,15 +43,10 @@ __device__ __forceinline__ void split2(const f32x16 &acc, bf16x8 (&frag)[2][2])
         }
 }
 
-// the [N,F] output leaves in 16-byte pieces; GGCN_LAB_NT_STORE (lab_hooks.h) makes them non-temporal
+// the [N,F] output leaves in 16-byte pieces
 __device__ __forceinline__ void store_out4(float *p, const float4 &v)
 {
-#if GGCN_LAB_NT_STORE
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4 *>(p));
-#else
     *reinterpret_cast<float4 *>(p) = v;
-#endif
 }
 
 // the same with the non-temporal hint always: the eight-wavefront kernel (129..256-node graphs) re-reads a graph's X rows
@@ -458,7 +452,7 @@ __device__ __forceinline__ void epilogue(const FusedArgs &a, const LayerPart &lp
 #pragma unroll
                 for (int p = 1; p >= 0; --p)
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) { if constexpr (!((GGCN_LAB_EPI) & 2)) y[j] = P::mma(afv[s], hf[p][s], y[j]); else y[j][s] += (float)hf[p][s][0]; }
+                    for (int s = 0; s < 2; ++s) y[j] = P::mma(afv[s], hf[p][s], y[j]);
             }
         }
         // per row: the factor of the aggregate and what is added to it.  A layer: 1 / (rowsum + 1) and the bias (gcn.py:41,43);
@@ -549,13 +543,12 @@ __device__ __forceinline__ void epilogue(const FusedArgs &a, const LayerPart &lp
                 const int row = 4 * it + (lane >> 4);
                 const float4 v4 = *reinterpret_cast<const float4 *>(&stage_lds[row * 64 + (colq ^ (32 * ((row >> 2) & 1)))]);
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                if ((FULLT || row < T) && gcol < F && !((GGCN_LAB_EPI) & 1))   // (GGCN_LAB_EPI 1: timing build without the stores)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v4), orsrc, voff, 4 * it * ldo * 4, (GGCN_LAB_NT_STORE) ? 2 : 0);
+                if ((FULLT || row < T) && gcol < F)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v4), orsrc, voff, 4 * it * ldo * 4, 0);
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
-        if (i == 0) GGCN_TRACE(7);
     }
 }
 

@@ -196,7 +196,7 @@ template <int SCH, bool AVEC, bool KFULL, bool FULLT, bool VST, bool STAMP = fal
 __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(const FusedArgs a)
 {
     static_assert(std::is_same<XT, float>::value || (SCH == 0 && !STAMP), "bf16 features: the bf16x3 main loop");
-    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes + kEpiLdsBytes + GGCN_LAB_LDS_PAD];
+    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes + kEpiLdsBytes];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
     // bert_amir5.py:638 for the launch BEFORE this one on the stream: block 0 adds the per-(graph,
     // 64-column group) partial dot products that launch left in ov_in, in a fixed order
@@ -218,8 +218,6 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(co
         n_wgi = slot % a.n_wg;
         if (g_tile >= a.g_tiles) return;
     }
-    GGCN_TRACE_IDS();
-    GGCN_TRACE(3);
     // the part this workgroup's column tiles belong to (workgroup-uniform: scalar selects)
     const LayerPart &lp = a.part[second ? 1 : 0];
     const char *__restrict__ wpack = lp.wpack;
@@ -245,7 +243,6 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(co
         arow[i] = fused_x<XT>(a) + node * a.ldx;
     }
 
-#if !GGCN_LAB_NO_DMA_STAGE
     // Round 5: whole tiles with aligned rows bring the epilogue's operands to LDS by LDS-DMA (stage_epilogue_operands_dma,
     // fused_common.h: no registers, no wait in front of the main loop) -- block 618.3 -> 608.6 us, a 512-graph shard 83.0 -> 82.1 us
     // in the same process, bit-identical (found on the eight-wavefront experiment, fused_block8.hip, where the register form of the
@@ -254,13 +251,8 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(co
                            ((reinterpret_cast<uintptr_t>(lp.store_gate) | reinterpret_cast<uintptr_t>(lp.pool_gate_a) | reinterpret_cast<uintptr_t>(lp.pool_gate_b) |
                              reinterpret_cast<uintptr_t>(lp.bias) | reinterpret_cast<uintptr_t>(lp.mid)) & 15u) == 0;
     if (dma_stage) stage_epilogue_operands_dma<kLdsBytes>(a, lp, g0, n_wgi, lds, tid);
-    else
-#else
-    constexpr bool dma_stage = false;
-#endif
-    stage_epilogue_operands<kLdsBytes>(a, lp, g0, n_wgi, lds, tid);   // g0 = gt0: one wavefront row
+    else stage_epilogue_operands<kLdsBytes>(a, lp, g0, n_wgi, lds, tid);   // g0 = gt0: one wavefront row
     f32x16 acc[4][RN];
-    GGCN_TRACE(4);
     unsigned long long stamp_c = 0, stamp_w = 0;
     if constexpr (STAMP) {
         stamp_c = __builtin_readcyclecounter();
@@ -288,7 +280,6 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(co
         if (dma_stage) dma_range_verdict<kLdsBytes>(amax, wpack, (int64_t)n_tiles_total * (a.k_steps / 2) * mx8::STAGE_PACK_BYTES, lds, tid & 63);
         else fused_range_verdict<kLdsBytes>(amax, wpack, (int64_t)n_tiles_total * (a.k_steps / 2) * mx8::STAGE_PACK_BYTES, lds, true);
     }
-    GGCN_TRACE(5);
     if constexpr (STAMP) {
         asm volatile("" :: "v"(acc[3][RN - 1][15]));   // the loop's last MFMA has retired
         const unsigned long long c1 = __builtin_readcyclecounter(), w1 = __builtin_amdgcn_s_memrealtime();
@@ -296,17 +287,6 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(co
             a.stamps[2 * (size_t)blockIdx.x] = c1 - stamp_c;
             a.stamps[2 * (size_t)blockIdx.x + 1] = w1 - stamp_w;
         }
-    }
-    if constexpr (((GGCN_LAB_OFF) & 128) != 0) {   // ladder: no epilogue (the accumulators only have to stay live)
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < RN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s += acc[i][j][r];
-        if (s == 123.456f && lp.pool_a) lp.pool_a[tid] = s;
-        return;
     }
     // `mid` and `out` are workgroup-uniform run-time facts (the W1 / W12 tiles of the block): four straight-line
     // epilogues instead of scalar branches inside one -- a branch per tile ends the basic block, and nothing (the
@@ -321,7 +301,6 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_kernel(co
         if (lp.out) epilogue<SCH, FULLT, VST, false, true>(a, lp, acc, g0, nt0, n_tiles_total, lds, tid);
         else epilogue<SCH, FULLT, VST, false, false>(a, lp, acc, g0, nt0, n_tiles_total, lds, tid);
     }
-    GGCN_TRACE(6);
 }
 
 
@@ -458,7 +437,7 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, b
     const bool kfull = (a.K % BK == 0);
     a.k_steps = round_up(a.K, BK) / KSTEP;
     a.n_wg = (a.F + BN - 1) / BN;
-    if (a.T > 32) {   // 64-, 128- or 256-row graph slots: layer_fused_wide_kernel
+    if (a.T > 32) {   // 64- or 128-row graph slots: layer_fused_wide_kernel; 256-row slots: layer_fused_wide8_kernel
         const int sb = a.T <= 64 ? 2 : a.T <= 128 ? 4 : 8;
         const int gpt = sb == 2 ? 2 : 1;   // graphs per workgroup
         const int64_t gt = ((int64_t)a.B + gpt - 1) / gpt;
@@ -468,7 +447,7 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, b
         const bool fast = avec && kfull;
         // (bf16 features: a launch without `out` stores no rows: the vector-store form is as good as any, and it is the fast shape's only form)
         const bool vstw = vst || (a.Xb && !any_out);
-        if (sb == 8 && (a.Xb || !GGCN_LAB_WIDE_SB8)) return launch_fused_wide8(who, a, precision, fast, vstw, gridw, st);   // 129..256 nodes: eight wavefronts per graph
+        if (sb == 8) return launch_fused_wide8(who, a, precision, fast, vstw, gridw, st);   // 129..256 nodes: eight wavefronts per graph
         return launch_fused_wide(who, a, precision, sb, fast, vstw, gridw, st);
     }
     const int64_t g_tiles = ((int64_t)a.B + 4 * WM - 1) / (4 * WM);
@@ -525,7 +504,6 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, b
     return check_launch(who);
 }
 
-GGCN_TRACE_READER
 
 int csr_rowmask(const int32_t *rowptr, const int32_t *colidx, int B, int T, uint32_t *rowmask, hipStream_t st)
 {

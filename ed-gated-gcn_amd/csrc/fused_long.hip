@@ -23,7 +23,6 @@
 // `hidden` at config 4 is gone).  One workgroup per CU, two wavefronts per SIMD -- the occupancy of the two-launch
 // linear.
 #include "f16mx8_core.h"
-#include "lab_hooks.h"
 
 namespace ggcn {
 namespace {
@@ -54,25 +53,9 @@ static_assert(kOffLut + 16 * 8 <= kDmaLds, "the epilogue's LDS map must fit wher
 constexpr int kCodeZero = LR << 2;
 
 #define GGCN_SB() __builtin_amdgcn_sched_barrier(0)
-// timing-only switches of the MFMA neighbour sums (lab builds; wrong results): 1 no MFMAs, 2 no transposed reads, 4 no row
-// stores, 8 no selection fragments, 16 no normalise / pools / stores at all
-#ifndef GGCN_LAB_LONG
-#define GGCN_LAB_LONG 0
-#endif
-// timing-only switches of the main loop's fill (lab builds; wrong results): 1 all ten pieces of the next stage at the top of the
-// stage, 2 no W pieces, 4 no X pieces, 8 only the first four X pieces, 16 no MFMAs / fragment reads, 32 X in half-line pieces
-#ifndef GGCN_LAB_LONG_MAIN
-#define GGCN_LAB_LONG_MAIN 0
-#endif
-#ifndef GGCN_LAB_LONG_AUX
-#define GGCN_LAB_LONG_AUX 2     // cache policy of the row stores (buffer intrinsic aux: 1 sc0, 2 nt, 16 sc1)
-#endif
-#ifndef GGCN_LAB_LONG_XAUX
-#define GGCN_LAB_LONG_XAUX 0    // ... of the X pieces' LDS-DMA loads
-#endif
-#ifndef GGCN_LAB_LONG_WAUX
-#define GGCN_LAB_LONG_WAUX 0    // ... of the W pieces' LDS-DMA loads
-#endif
+// cache policy of the row stores (buffer intrinsic aux: 1 sc0, 2 nt, 16 sc1).  Non-temporal: plain stores allocated a workgroup's
+// 128 KiB of output in its XCD's L2 and evicted the X rows the graph's other column tiles were about to read (kernel -20 us)
+constexpr int kRowStoreAux = 2;
 
 // hidden tile: row r at r * 256 B (LC * 2).  Lane sums (weighted edges, > kIdxCapL edges): plain -- their reads are
 // conflict-free by the ORDER in which a lane takes its two chunks (see there); an XOR keyed on the row would break exactly
@@ -133,7 +116,6 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
     const int n_tiles_total = (F + NT - 1) / NT;
     const int stages = K / LBK;             // the launcher guarantees K % 64 == 0
 
-    GGCN_LT(0);
     // ---- the graph's CSR ----
     const int e_base = a.rowptr[node0];
     const int nnz_g = a.rowptr[node0 + T] - e_base;
@@ -179,31 +161,22 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
         const int bdst = 2 * kDmaA + ((wave >> 1) * 4 + 2 * (wave & 1)) * 1024;
         auto issue_piece = [&](int t, int st, int buf) {   // t = 0..7: X piece t; 8, 9: the two k-steps of this wavefront's W record
             st = st < stages ? st : stages - 1;
-            if (((GGCN_LAB_LONG_MAIN) & 2) && t >= 8) return;
-            if (((GGCN_LAB_LONG_MAIN) & 4) && t < 8) return;
-            if (((GGCN_LAB_LONG_MAIN) & 8) && t >= 4 && t < 8) return;
-            if (((GGCN_LAB_LONG_MAIN) & 32) && t < 8) {   // half-line pieces: 16 rows x 64 B, the k-low halves first (t < 4), the k-high halves later
-                const int row = 128 * (t & 3) + 16 * wave + (lane >> 2);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.X + (node0 + row) * a.ldx + 8 * ((lane & 3) + 4 * (t >> 2)) + st * LBK),
-                                                 (__attribute__((address_space(3))) void *)(lds + buf * kDmaA + (64 * t + 8 * wave) * 128), 16, 0, GGCN_LAB_LONG_XAUX);
-            } else if (t < 8) {
+            if (t < 8) {
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(asrc[t] + st * LBK),
-                                                 (__attribute__((address_space(3))) void *)(lds + buf * kDmaA + (64 * t + 8 * wave) * 128), 16, 0, GGCN_LAB_LONG_XAUX);
+                                                 (__attribute__((address_space(3))) void *)(lds + buf * kDmaA + (64 * t + 8 * wave) * 128), 16, 0, 0);
             } else {
                 int rec = 2 * st + (wave & 1);
                 rec = rec < a.records ? rec : a.records - 1;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(bsrc + (int64_t)rec * mx8::STAGE_PACK_BYTES + (t - 8) * 1024),
-                                                 (__attribute__((address_space(3))) void *)(lds + bdst + buf * kDmaB + (t - 8) * 1024), 16, 0, GGCN_LAB_LONG_WAUX);
+                                                 (__attribute__((address_space(3))) void *)(lds + bdst + buf * kDmaB + (t - 8) * 1024), 16, 0, 0);
             }
         };
         const int sw = ((lane & 31) >> 1) & 7;
         const int aoff = (128 * rg + (lane & 31)) * 128;
         auto read_a = [&](int buf, int s, int i, f16x8 &af) {
-            if ((GGCN_LAB_LONG_MAIN) & 128) { asm volatile("" : "+v"(af)); return; }
             af = *reinterpret_cast<const f16x8 *>(lds + buf * kDmaA + aoff + i * 4096 + (((2 * s + khalf) ^ sw) << 4));
         };
         auto read_b = [&](int buf, int s, f16x8 (&bf)[RN]) {
-            if ((GGCN_LAB_LONG_MAIN) & 256) { asm volatile("" : "+v"(bf[0]), "+v"(bf[1])); return; }
 #pragma unroll
             for (int j = 0; j < RN; ++j)
                 bf[j] = *reinterpret_cast<const f16x8 *>(lds + 2 * kDmaA + buf * kDmaB + ((2 * cg + j) * 4 + s) * 1024 + 16 * lane);
@@ -218,16 +191,6 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
             constexpr int buf = decltype(bufc)::value;
             constexpr int AH = 2;     // X fragment reads run two steps (of 2 MFMAs) ahead of their use, W fragments of a k-step three
             f16x8 af[AH + 1], bf[2][RN];
-            if ((GGCN_LAB_LONG_MAIN) & 1) {
-#pragma unroll
-                for (int t = 0; t < 10; ++t) issue_piece(t, st + 1, buf ^ 1);
-            }
-            if ((GGCN_LAB_LONG_MAIN) & 16) {
-#pragma unroll
-                for (int t = 0; t < 10; ++t) issue_piece(t, st + 1, buf ^ 1);
-                __syncthreads();
-                return;
-            }
             read_b(buf, 0, bf[0]);
 #pragma unroll
             for (int t = 0; t < AH; ++t) read_a(buf, t >> 2, t & 3, af[t]);
@@ -242,13 +205,12 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
                     GGCN_SB();
                     acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t % (AH + 1)], bf[s4 & 1][0], acc[i][0], 0, 0, 0);
                     GGCN_SB();
-                    if (t < 10 && !((GGCN_LAB_LONG_MAIN) & 1)) issue_piece(t, st + 1, buf ^ 1);
+                    if (t < 10) issue_piece(t, st + 1, buf ^ 1);
                     GGCN_SB();
                     acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t % (AH + 1)], bf[s4 & 1][1], acc[i][1], 0, 0, 0);
                     GGCN_SB();
                 }
-            if ((GGCN_LAB_LONG_MAIN) & 64) asm volatile("s_waitcnt vmcnt(10)\n\ts_barrier" ::: "memory");   // timing of a ring one stage deeper: waits for the pieces of the stage BEFORE
-            else __syncthreads();
+            __syncthreads();
         };
         int st = 0;
         for (; st + 1 < stages; st += 2) {
@@ -273,7 +235,6 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
                     make_uint2(((tid & 1) ? 0x3C00u : 0u) | ((tid & 2) ? 0x3C000000u : 0u), ((tid & 4) ? 0x3C00u : 0u) | ((tid & 8) ? 0x3C000000u : 0u));
         }
     }
-    GGCN_LT(1);
     // ---- 2. hidden -> fp16 -> the LDS tile [512][128] over the stage buffers ----
     // Lane pairs (l, l ^ 1) hold neighbouring columns of the same rows: they swap one register of every pair (r, r + 1)
     // so that the even lane stores columns (c, c + 1) of row(r) and the odd lane those of row(r + 1) as ONE dword each:
@@ -304,7 +265,6 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
     if (tid < 16) *reinterpret_cast<uint4 *>(lds + kTile + 16 * tid) = make_uint4(0u, 0u, 0u, 0u);   // row LR
     __syncthreads();
 
-    GGCN_LT(2);
     // ---- 3. neighbour sums out of the tile, normalise, bias, gates, stores, pools ----
     // 8 lanes x 2 chunks of 16 B cover a row of the tile: a wavefront works on 8 destination rows at once and every
     // per-edge instruction (id, mask, address) serves 16 columns.  Lane (q8, cl) owns chunks cl + 8 par and
@@ -475,7 +435,6 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
                 for (int j = 1; j < 4; ++j) { ga[0][j] = ga[0][0] ^ (j << 6); ga[1][j] = ga[1][0] ^ (j << 6); }
             };
             auto gather = [&](f16x8 (&bf)[4]) {
-                if ((GGCN_LAB_LONG) & 2) return;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     union { f16x8 v; s16x4 h[2]; } u;
@@ -485,7 +444,6 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
                 }
             };
             auto select = [&](f16x8 &sel) {
-                if ((GGCN_LAB_LONG) & 8) return;
                 const int clo = min(max(rl, 0), 8), chi = min(max(rh, clo), 8);
                 unsigned mask;
                 asm("v_bfm_b32 %0, %1, %2" : "=v"(mask) : "v"(chi - clo), "v"(clo));     // ((1 << width) - 1) << offset
@@ -509,20 +467,20 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
             auto step = [&](int k, auto cur_c) {
                 constexpr int cur = decltype(cur_c)::value;
                 GGCN_SB();
-                if (!((GGCN_LAB_LONG) & 1)) sum[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sel[cur], bf[cur][0], sum[0], 0, 0, 0);
+                sum[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sel[cur], bf[cur][0], sum[0], 0, 0, 0);
                 GGCN_SB();
                 gather(bf[cur ^ 1]);
                 GGCN_SB();
-                if (!((GGCN_LAB_LONG) & 1)) sum[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sel[cur], bf[cur][1], sum[1], 0, 0, 0);
+                sum[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sel[cur], bf[cur][1], sum[1], 0, 0, 0);
                 GGCN_SB();
                 select(sel[cur ^ 1]);
                 GGCN_SB();
-                if (!((GGCN_LAB_LONG) & 1)) sum[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sel[cur], bf[cur][2], sum[2], 0, 0, 0);
+                sum[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sel[cur], bf[cur][2], sum[2], 0, 0, 0);
                 GGCN_SB();
                 addresses(n0, n1);
                 n0 = cp[16 * (k + 3)]; n1 = cp[16 * (k + 3) + 4];
                 GGCN_SB();
-                if (!((GGCN_LAB_LONG) & 1)) sum[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sel[cur], bf[cur][3], sum[3], 0, 0, 0);
+                sum[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sel[cur], bf[cur][3], sum[3], 0, 0, 0);
                 GGCN_SB();
             };
             int ks = 0;
@@ -561,26 +519,25 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
                                 asm("v_max3_f32 %0, %0, %1, %2" : "+v"(pmx[j]) : "v"(a0), "v"(a1));
                                 asm("v_min3_f32 %0, %0, %1, %2" : "+v"(pmn[j]) : "v"(i0), "v"(i1));
                             }
-                            if constexpr (OUT && !((GGCN_LAB_LONG) & 4)) {
+                            if constexpr (OUT) {
                                 const __half2 mine = __floats2half2_rn(v0 * gj[j], v1 * gj[j]);     // (row r, row r + 1) of column m
                                 const unsigned mu = __builtin_bit_cast(unsigned, mine);
                                 const unsigned pu = (unsigned)__builtin_amdgcn_mov_dpp((int)mu, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
                                 o[jj] = __builtin_amdgcn_perm(pu, mu, selp);
                             }
                         }
-                        if constexpr (OUT && !((GGCN_LAB_LONG) & 4)) {
+                        if constexpr (OUT) {
                             // the two column blocks trade halves: afterwards one register holds rows (r, r + 1) of the lower lanes'
                             // row set for BOTH blocks -- 128 contiguous bytes per row and store instruction, whole lines -- and
                             // the other the upper lanes' row set (4 rows further)
                             const auto sw = __builtin_amdgcn_permlane32_swap(o[0], o[1], false, false);
                             const int so = s_row + (int)((8 * (r >> 2) + (r & 3)) * ldo * 2);
-                            __builtin_amdgcn_raw_buffer_store_b32(sw[0], orsrc, lane_off2[jp], so, GGCN_LAB_LONG_AUX);
-                            __builtin_amdgcn_raw_buffer_store_b32(sw[1], orsrc, lane_off2[jp], so + (int)(4 * ldo * 2), GGCN_LAB_LONG_AUX);
+                            __builtin_amdgcn_raw_buffer_store_b32(sw[0], orsrc, lane_off2[jp], so, kRowStoreAux);
+                            __builtin_amdgcn_raw_buffer_store_b32(sw[1], orsrc, lane_off2[jp], so + (int)(4 * ldo * 2), kRowStoreAux);
                         }
                     }
             };
             const bool whole = R0 + 32 <= T;        // wavefront-uniform
-            if ((GGCN_LAB_LONG) & 16) { pmx[0] = fmaxf(pmx[0], sum[0][0] + sum[1][0] + sum[2][0] + sum[3][0]); continue; }
             if (whole) { if (a.out) finish(std::true_type{}, std::true_type{}); else finish(std::true_type{}, std::false_type{}); }
             else { if (a.out) finish(std::false_type{}, std::true_type{}); else finish(std::false_type{}, std::false_type{}); }
         }
@@ -602,8 +559,6 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
     if (mma) rows_mma();
     else if (staged) rows(std::true_type{});
     else rows(std::false_type{});
-    GGCN_LT(3);
-    GGCN_LT_WAVE7(7);
     // pools (bert_amir5.py:635-640): max_t (v_t * gate) = gate * (gate >= 0 ? max_t v_t : min_t v_t), exactly
     if (a.pool_a || a.pool_b) {
         // max / min over the 8 row groups of the wavefront (lanes l, l ^ 8, l ^ 16, l ^ 32 hold the same chunk pair only
@@ -629,9 +584,7 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
                     s_red[(1 * 16 + 2 * wave + par) * LC + 8 * ch[h] + k] = vmin[h][k];
                 }
         }
-        GGCN_LT(5);
         __syncthreads();
-        GGCN_LT(6);
         if (tid < LC && ct * LC + tid < F) {
             float mx = s_red[tid], mn = s_red[16 * LC + tid];
 #pragma unroll
@@ -651,13 +604,10 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
             if (a.pool_b) a.pool_b[g] = pgb * (pgb >= 0.0f ? mx : mn);
         }
     }
-    GGCN_LT(4);
 }
 #undef GGCN_SB
 
 }  // namespace
-
-GGCN_LT_READER
 
 int layer_fused_h(const void *X, int64_t ldx, const void *wpack, const int32_t *rowptr, const int32_t *colidx,
                   const float *vals, const float *bias, int B, int T, int K, int F, const float *store_gate,

@@ -24,7 +24,7 @@ namespace {
 template <int SCH, bool AVEC, bool KFULL, bool FULLT, bool VST>
 __global__ __launch_bounds__(kThreads, kWavesPerSimd) void layer_fused_weighted_drop_kernel(const FusedArgs a)
 {
-    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes + kEpiLdsBytes + GGCN_LAB_LDS_PAD];
+    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes + kEpiLdsBytes];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
     int g_tile, n_wgi;
     if (!tile_of_block(blockIdx.x, a.g_tiles, a.n_wg, g_tile, n_wgi)) return;
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void graph_operands2_w_kernel(const int32_t *_
 template <int SCH, bool AVEC, bool KFULL, bool FULLT, bool VST>
 __global__ __launch_bounds__(kThreads, kWavesPerSimd) void block_fused_weighted_kernel(const FusedArgs a)
 {
-    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes + kEpiLdsBytes + GGCN_LAB_LDS_PAD];
+    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes + kEpiLdsBytes];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
     int g_tile, n_wgi;
     bool second = false;

@@ -5,8 +5,8 @@
 namespace ggcn {
 namespace {
 
-// ---- graphs of 33..256 nodes (LitBank: ORI_ML = 100, constant.py:227; ACE cased: ORI_ML = 231, constant.py:267)
-// in the same one launch per layer ----
+// ---- graphs of 33..128 nodes (LitBank: ORI_ML = 100, constant.py:227) in the same one launch per layer; graphs of 129..256
+// nodes (ACE cased: ORI_ML = 231, constant.py:267) take layer_fused_wide8_kernel (fused_wide8.hip) ----
 // A graph occupies SB = 2 or 4 consecutive 32-row blocks of a wavefront's 128-row tile (64- or 128-row slot;
 // T in 65..96 takes the 128-row slot), its adjacency is SB x SB blocks of 32 x 32 bits (row masks of
 // ceil(T/32) words), and the neighbour sum of output block io is
@@ -14,11 +14,6 @@ namespace {
 // with every hidden[ii] taken from the accumulator tiles as in the 32-node kernel.  All accumulators are first
 // split into their two bf16 planes IN PLACE (same register count), then each output block is produced,
 // normalised, gated, pooled and stored.  One part only (the two-layer block form stays with T <= 32).
-// SB = 8 (T in 129..256), the FIRST form of the 256-row slot, kept behind GGCN_LAB_WIDE_SB8 for comparison: the workgroup
-// runs the main loop TWICE (rows 0-127, then 128-255 of its graph) and keeps the first half's planes in registers
-// meanwhile -- 256 registers of planes in the epilogue, so it is built for one wavefront per SIMD and the main loop runs
-// at its lone-wavefront speed: measured 4-18 % SLOWER than linear + aggregate at T = 231 (tools/wide_timing.py).  The
-// launcher takes layer_fused_wide8_kernel (below: eight wavefronts, both halves in flight) for these graphs.
 // DROP (training, bert_amir5.py:621-625): the three gates are dropped per (token, feature) -- keep factors from the
 // counter-based hash of dropout_hash.h, the same ones ggcn_gate_pool_backward_drop and ggcn_dropout_mask draw -- and the
 // pools maximise the gated, kept values themselves (every element has its own factor: no max / min shortcut).
@@ -35,18 +30,18 @@ namespace {
 // requested as soon as the last column tile's lo products have issued and the hi fragments after its hi products: the
 // element-wise work and stores of that tile and the next row's first products run under them.
 // WEIGHTED && DROP (ggcn_layer_fused_weighted_wide_drop): both of the above -- the keep factors only touch what follows y.
-// wide_one_wave: the instantiations compiled WITHOUT the two-wavefronts-per-SIMD bound.  SB = 8 (the lab form above), and one more: WEIGHTED && DROP with the general f16mx8 main loop at
+// wide_one_wave: the one instantiation compiled WITHOUT the two-wavefronts-per-SIMD bound.  WEIGHTED && DROP with the general f16mx8 main loop at
 // SB = 4 spills 8 bytes per lane under it -- 64 registers of fragments, 128 of planes and the pools' running maxima leave nothing
 // for the hash; an opaque lane id after the main loop and a 32-bit element index left one register spilled.  Unbound it takes
 // 253 VGPRs + 128 AGPRs and no scratch: ONE wavefront per SIMD, for the slow-shape form (K % 32 != 0 or rows off 16 bytes) of
 // 65..128-node graphs under dropout in f16mx8 alone.  The fast shapes and every bf16x3 form keep two.  Its speed is not measured.
-constexpr bool wide_one_wave(int sch, bool avec, int sb, bool drop, bool weighted) { return sb == 8 || (weighted && drop && sch == 1 && sb == 4 && !avec); }
+constexpr bool wide_one_wave(int sch, bool avec, int sb, bool drop, bool weighted) { return weighted && drop && sch == 1 && sb == 4 && !avec; }
 template <int SCH, bool AVEC, bool KFULL, bool VST, int SB, bool DROP = false, typename XT = float, bool WEIGHTED = false>
 __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHTED) ? 1 : kWavesPerSimd) void layer_fused_wide_kernel(const FusedArgs a)
 {
-    static_assert(SB == 2 || SB == 4 || SB == 8, "a graph slot is 64, 128 or 256 rows");
-    static_assert(!WEIGHTED || (SB != 8 && std::is_same<XT, float>::value), "real-valued adjacency: float32 features, 64- and 128-row slots");
-    static_assert(std::is_same<XT, float>::value || (SCH == 0 && SB != 8), "bf16 features: the bf16x3 main loop, 64- and 128-row slots");
+    static_assert(SB == 2 || SB == 4, "a graph slot is 64 or 128 rows");
+    static_assert(!WEIGHTED || std::is_same<XT, float>::value, "real-valued adjacency: float32 features");
+    static_assert(std::is_same<XT, float>::value || SCH == 0, "bf16 features: the bf16x3 main loop");
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
     if (a.ov_in && blockIdx.x == 0) reduce_partials(a.ov_in, B * ((F + 63) / 64), B, a.ov_out, reinterpret_cast<float *>(lds));
@@ -59,8 +54,7 @@ __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHT
     float *__restrict__ ov_partial = lp.ov_partial;
     const int ldo = lp.ldo;
     constexpr int S = 32 * SB;                     // rows per graph slot
-    constexpr int GPT = SB >= 4 ? 1 : 4 / SB;      // graphs per workgroup
-    constexpr int HALVES = SB == 8 ? 2 : 1;        // 128-row passes through the main loop
+    constexpr int GPT = 4 / SB;                    // graphs per workgroup
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -73,14 +67,17 @@ __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHT
 
     constexpr int NP = Geom<XT>::NP;
     // every accumulator tile -> its two bf16 planes (B-operand fragments of the aggregation MFMAs), in place
-    bf16x8 hf[4 * HALVES][RN][2][2];
+    bf16x8 hf[4][RN][2][2];
+    // hidden = X . W, then split.  The ONE-TRIP loop is deliberate: this body once ran per 128-row half of a 256-row slot, and as a
+    // plain block the compiler orders the code around the main loop differently -- every instantiation moves by a few instructions.
+    // Kept so that the device code stays byte-identical; whoever next changes this kernel's code may make it a block.
 #pragma unroll
-    for (int hh = 0; hh < HALVES; ++hh) {
+    for (int once = 0; once < 1; ++once) {
         const XT *arow[NP];
         bool avalid[NP];
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const int row = stage_row<XT>(i) + 128 * hh;
+            const int row = stage_row<XT>(i);
             const int g = g0 + row / S, r = row % S;
             avalid[i] = (g < B) && (r < T);
             const int64_t node = avalid[i] ? (int64_t)g * T + r : 0;
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHT
                 int rel[NP];
 #pragma unroll
                 for (int i = 0; i < NP; ++i) {
-                    const int row = stage_row<float>(i) + 128 * hh;
+                    const int row = stage_row<float>(i);
                     rel[i] = avalid[i] ? (row / S) * T + row % S : -1;
                 }
                 bx = mx8::make_bufx<float>(a.X, a.ldx, (int64_t)g0 * T, (int64_t)B * T, rel, tid);
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHT
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < RN; ++j) split2(acc[i][j], hf[4 * hh + i][j]);
+            for (int j = 0; j < RN; ++j) split2(acc[i][j], hf[i][j]);
     }
 
     const int c = lane & 31, h = lane >> 5;
@@ -176,10 +173,8 @@ __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHT
         for (int s = 0; s < GPT; ++s) {
             const int g = g0 + s;
             if (g >= B) break;  // workgroup-uniform
-            // this lane's adjacency rows: node 32*io + (lane & 31), word ii; SB <= 4: for the whole graph (one
-            // latency), SB = 8: one output block ahead (64 words would not stay in registers)
-            constexpr int MB = SB == 8 ? 2 : SB;
-            uint32_t mw[MB][SB];
+            // this lane's adjacency rows: node 32*io + (lane & 31), word ii, for the whole graph (one latency)
+            uint32_t mw[SB][SB];
             auto load_masks = [&](int io, uint32_t (&m)[SB]) {
                 const int node = 32 * io + c;
                 const bool ok = node < T;
@@ -192,8 +187,6 @@ __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHT
             };
             if constexpr (WEIGHTED) {
                 if (s == 0) fetch_w(g, 0, 0), fetch_w(g, 0, 1);   // (later graphs: requested under the previous graph's last block row)
-            } else if constexpr (SB == 8) {
-                load_masks(0, mw[0]);
             } else {
 #pragma unroll
                 for (int io = 0; io < SB; ++io) load_masks(io, mw[io]);
@@ -205,9 +198,6 @@ __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHT
             for (int io = 0; io < SB; ++io) {
                 const int node0 = 32 * io;
                 if (node0 >= T) break;  // workgroup-uniform: block of padding rows
-                const int mi = SB == 8 ? (io & 1) : io;
-                if constexpr (SB == 8)
-                    if (io + 1 < SB) load_masks(io + 1, mw[(io + 1) & 1]);   // rows past T read as zeros
                 bf16x8 af[WEIGHTED ? 1 : SB][2];
                 float rinv[16];
                 if constexpr (WEIGHTED) {
@@ -217,8 +207,8 @@ __global__ __launch_bounds__(kThreads, wide_one_wave(SCH, AVEC, SB, DROP, WEIGHT
                     int deg = 0;
 #pragma unroll
                     for (int ii = 0; ii < SB; ++ii) {
-                        deg += __popc(mw[mi][ii]);
-                        expand_mask(mw[mi][ii] >> (4 * h), af[ii]);
+                        deg += __popc(mw[io][ii]);
+                        expand_mask(mw[io][ii] >> (4 * h), af[ii]);
                     }
                     const float inv = 1.0f / (float)(deg + 1);                  // gcn.py:35
 #pragma unroll
@@ -433,9 +423,6 @@ int launch_fused_wide(const char *who, const FusedArgs &a, int precision, int sb
 #undef GGCN_LAUNCHWB
         return check_launch(who);
     }
-#if GGCN_LAB_WIDE_SB8
-    if (sb == 8) { if (precision == GGCN_PREC_F16MX8) GGCN_PICKW(1, 8); else GGCN_PICKW(0, 8); return check_launch(who); }
-#endif
     if (sb != 2 && sb != 4) return fail(GGCN_EUNSUPPORTED, "%s: no %d-row graph slot in this build", who, 32 * sb);
     if (precision == GGCN_PREC_F16MX8) { if (sb == 2) GGCN_PICKW(1, 2); else GGCN_PICKW(1, 4); }
     else { if (sb == 2) GGCN_PICKW(0, 2); else GGCN_PICKW(0, 4); }

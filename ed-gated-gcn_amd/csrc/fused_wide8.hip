@@ -12,32 +12,31 @@ __device__ __forceinline__ float vminf_raw(float x, float y) { float d; asm("v_m
 // ---- graphs of 129..256 nodes, two wavefronts per SIMD: EIGHT wavefronts per (graph, 256 columns) -----------------------
 // Wavefront (rg, cg) = rows 128 rg .. + 127 of the graph's 256-row slot x columns 64 cg .. + 63: the two row groups run
 // the SAME main loop side by side on their own stage buffers (thread ids taken mod 256 inside the loop), so the loop keeps
-// the two-wavefronts-per-SIMD speed of the 32-node kernel instead of the lone wavefront of the SB = 8 form above, and no
-// half of the graph waits in registers.  A neighbour sum needs hidden rows of BOTH row groups, so the accumulators go to
+// the two-wavefronts-per-SIMD speed of the 32-node kernel instead of the lone wavefront of a first form that ran it twice
+// and kept one half of the graph waiting in registers.  A neighbour sum needs hidden rows of BOTH row groups, so the accumulators go to
 // LDS per 32-column tile -- as an fp32 tile [256 rows][32 columns] per column group, 128 KiB over the dead stage buffers --
 // and the sums run over per-row EDGE LISTS (made once per workgroup from the row masks) with 8 lanes x 16 B per row, 8
 // source rows in flight: exact fp32 sums, ~5 LDS reads + 20 adds per row of a parse.  160 KiB of LDS, one workgroup per CU.
 // Measured (tools/wide_timing.py, f16mx8, 512 x 231 x 768): 399 us against 498 us for linear + aggregate (507 us for the
 // lone-wavefront form); 228 us of it is the main loop (timing build without the epilogue), the rest runs under nothing:
-// with one workgroup per CU the phases are serial.  The FIRST form of this epilogue (GGCN_LAB_WIDE8_DENSE: bf16 plane
+// with one workgroup per CU the phases are serial.  The FIRST form of this epilogue (removed; DESIGN.md: bf16 plane
 // fragments exchanged through LDS, dense 32 x 32 adjacency blocks on the MFMAs, mask words expanded into operands, empty
 // blocks skipped) took 456 us: 8 x 4 MFMAs and ~100 VALU of expansion per block against a handful of edges per row.
 constexpr int kW8Threads = 512;
-constexpr int kW8Ex = 8 * 16 * 1024;          // per wavefront: 4 row blocks x (2 planes x 2 k-steps) x 1 KiB
+constexpr int kW8Ex = 8 * 16 * 1024;          // four column groups x fp32 tile [256 rows][32 columns], over the dead stage buffers
 constexpr int kW8Cap = 16;                   // source ids per row kept in LDS (rows with more neighbours walk their mask words)
-constexpr int kW8Stage = 4096;                // per wavefront: 32 rows x 32 columns of output on their way to 16-byte stores
+constexpr int kW8Stage = 4096;                // per wavefront, behind the tiles: the pools' meeting place (first 4 KiB), then the edge lists
 constexpr int kW8Lds = kW8Ex + 8 * kW8Stage;  // 160 KiB
 constexpr int kW8ListBytes = GGCN_EDGE_LISTS_BYTES;   // ids 8192 + degrees 1024 + reciprocals 1024 + zero row 128, padded to 11 KiB
 static_assert(4096 + kW8ListBytes <= 8 * kW8Stage, "the lists' LDS image lies behind both row groups' stage buffers");
 static_assert(2 * kLdsBytes <= kW8Ex && kW8Lds <= 160 * 1024, "the stage buffers of both row groups lie under the exchange area");
 
 // DROP (training, bert_amir5.py:621-625): per-(token, feature) keep factors of the three gates (dropout_hash.h), the pools
-// maximise the gated, kept values (edge-list epilogue only).
+// maximise the gated, kept values.
 // XT: element type of the features -- float, or __bf16 (a.Xb; bf16x3 image, two MFMAs per product: bf16x3_core.h).
 template <int SCH, bool AVEC, bool KFULL, bool VST, bool DROP = false, typename XT = float>
 __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const FusedArgs a)
 {
-    static_assert(!(DROP && GGCN_LAB_WIDE8_DENSE), "gate dropout lives in the edge-list epilogue");
     static_assert(std::is_same<XT, float>::value || SCH == 0, "bf16 features: the bf16x3 main loop");
     extern __shared__ __attribute__((aligned(16))) char lds8[];
     const int B = a.B, T = a.T, K = a.K, F = a.F;
@@ -72,16 +71,15 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
     // ---- the edge lists of the graph's rows (what the epilogue's neighbour sums walk), made BEFORE the main loop: their LDS
     // lies behind both row groups' stage buffers, and the row masks' trip from global memory hides under the loop's first
     // stages instead of standing between the loop and the epilogue ----
-    if constexpr (!GGCN_LAB_WIDE8_DENSE) {
-      if (a.graph_ops) {
-          // ggcn_graph_edge_lists made the lists once per adjacency tensor: the block IS the LDS image (ids, degrees, reciprocals, the
-          // zero row), 11 pieces of 1 KiB brought in by LDS-DMA -- no registers, no instructions beyond the 1-2 issues per wavefront;
-          // they land under the main loop's first stages (its per-stage vmcnt(0) + barrier cover them long before the epilogue)
-          const char *blk = a.graph_ops + (int64_t)g * kW8ListBytes;
-          for (int piece = wave; piece < kW8ListBytes / 1024; piece += 8)
-              __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(blk + piece * 1024 + lane * 16),
-                                               (__attribute__((address_space(3))) void *)(lds8 + kW8Ex + 4096 + piece * 1024), 16, 0, 0);
-      } else {
+    if (a.graph_ops) {
+        // ggcn_graph_edge_lists made the lists once per adjacency tensor: the block IS the LDS image (ids, degrees, reciprocals, the
+        // zero row), 11 pieces of 1 KiB brought in by LDS-DMA -- no registers, no instructions beyond the 1-2 issues per wavefront;
+        // they land under the main loop's first stages (its per-stage vmcnt(0) + barrier cover them long before the epilogue)
+        const char *blk = a.graph_ops + (int64_t)g * kW8ListBytes;
+        for (int piece = wave; piece < kW8ListBytes / 1024; piece += 8)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(blk + piece * 1024 + lane * 16),
+                                             (__attribute__((address_space(3))) void *)(lds8 + kW8Ex + 4096 + piece * 1024), 16, 0, 0);
+    } else {
         unsigned short *s_ids = reinterpret_cast<unsigned short *>(lds8 + kW8Ex + 4096);   // [256 rows][kW8Cap]
         int *s_deg = reinterpret_cast<int *>(lds8 + kW8Ex + 4096 + 256 * kW8Cap * 2);      // [256]
         float *s_inv = reinterpret_cast<float *>(lds8 + kW8Ex + 4096 + 256 * kW8Cap * 2 + 1024);   // [256] 1 / (deg + 1)
@@ -93,7 +91,10 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
             uint32_t mwd[8];
 #pragma unroll
             for (int wi = 0; wi < 8; ++wi) {
-                const bool ok = row < T && wi < W && !((GGCN_LAB_OFF) & 32);   // (timing build: no masks, empty lists)
+                // (as a branch, not `row < T && wi < W` as a value: the general bf16x3 instantiation's address arithmetic is
+                // selected differently from the two spellings, and the device code is to stay byte-identical)
+                bool ok = false;
+                if (row < T && wi < W) ok = true;
                 const uint32_t v = a.rowmask[ok ? ((int64_t)g * T + row) * W + wi : 0];
                 mwd[wi] = ok ? v : 0u;
             }
@@ -114,7 +115,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
             s_inv[row] = 1.0f / (float)(deg + 1);                               // gcn.py:35
             if (tid < 32) reinterpret_cast<float *>(lds8 + zero_off)[tid] = 0.0f;
         }
-      }
     }
 
     // ---- hidden = X . W for both row groups at once ----
@@ -163,202 +163,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
                 mx8::mainloop<float, AVEC, KFULL, true, false, BUF, 4>(arow, avalid, lp.wpack, K, a.k_steps / 2, 0, nt0, n_tiles_total, stage, acc, 0, 4, nullptr, &bx);
         }
     }
-    if constexpr (GGCN_LAB_WIDE8_DENSE) {
-    // every accumulator tile -> its two bf16 planes (B-operand fragments of the aggregation MFMAs), in place
-    bf16x8 hf[4][RN][2][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < RN; ++j) split2(acc[i][j], hf[i][j]);
-
-    const int c = lane & 31, h = lane >> 5;
-    float vb[RN], vsg[RN], vga[RN], vgb[RN];
-    bool col_ok[RN];
-    {
-        const float *dummy = a.X;
-        const float *pb = bias ? bias : dummy, *psg = store_gate ? store_gate : dummy;
-        const float *pga = pool_gate_a ? pool_gate_a : dummy, *pgb = pool_gate_b ? pool_gate_b : dummy;
-#pragma unroll
-        for (int j = 0; j < RN; ++j) {
-            const int gn = (nt0 + j) * NT + c;
-            col_ok[j] = gn < F;
-            const int gnc = col_ok[j] ? gn : 0;
-            const int64_t at = (int64_t)g * F + gnc;
-            vb[j] = bias ? pb[gnc] : 0.0f;
-            vsg[j] = store_gate ? psg[at] : 1.0f;
-            vga[j] = pool_gate_a ? pga[at] : 1.0f;
-            vgb[j] = pool_gate_b ? pgb[at] : 1.0f;
-        }
-    }
-    // this lane's adjacency rows of output block io (node 32 io + c), one block ahead of their use; words past the graph
-    // and rows past T read as zeros
-    auto load_masks = [&](int io, uint32_t (&m)[8]) {
-        const int node = 32 * io + c;
-        const bool ok = node < T;
-#pragma unroll
-        for (int ii = 0; ii < 8; ++ii) {
-            const bool okw = ok && ii < W;
-            const uint32_t v = a.rowmask[okw ? ((int64_t)g * T + node) * W + ii : 0];
-            m[ii] = okw ? v : 0u;
-        }
-    };
-    uint32_t mw[2][8];
-    load_masks(4 * rg, mw[0]);
-    float *stage_lds = reinterpret_cast<float *>(lds8 + kW8Ex + wave * kW8Stage);
-    const int perm_base = 16 * h;
-    const int lane_off = 4 * h * ldo + c;
-    float vmax[RN], vmin[RN];
-#pragma unroll
-    for (int j = 0; j < RN; ++j) { vmax[j] = -INFINITY; vmin[j] = INFINITY; }
-
-    auto tiles = [&](auto has_out) {
-        constexpr bool vst = VST && decltype(has_out)::value;
-        constexpr bool direct_store = !VST && decltype(has_out)::value;
-#pragma unroll
-        for (int j = 0; j < RN; ++j) {
-            __syncthreads();   // the fragments of column tile j - 1 (j = 0: the last stage's operand planes) have been read
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks)
-                        *reinterpret_cast<bf16x8 *>(lds8 + (((wave * 4 + i) * 2 + p) * 2 + ks) * 1024 + lane * 16) = hf[i][j][p][ks];
-            __syncthreads();
-            const bool tile_ok = nt0 + j < n_tiles_total;   // wavefront-uniform: column tile past F
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int t = 4 * j + i, io = 4 * rg + i, node0 = 32 * io;
-                // the next block's masks (wraps to this wavefront's first block for the second column tile)
-                if (t + 1 < 4 * RN) load_masks(4 * rg + ((i + 1) & 3), mw[(t + 1) & 1]);
-                if (node0 >= T || !tile_ok) continue;   // wavefront-uniform: a block of padding rows (no barrier below)
-                const uint32_t (&m)[8] = mw[t & 1];
-                int deg = 0;
-#pragma unroll
-                for (int ii = 0; ii < 8; ++ii) deg += __popc(m[ii]);
-                const float inv = 1.0f / (float)(deg + 1);                  // gcn.py:35
-                f32x16 y;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) y[r] = 0.0f;
-                // The four operand fragments of block ii + 1 are asked for before block ii's MFMAs (an empty block's are read in
-                // vain): read just in front of their use, every pair of MFMAs waited out an LDS round trip.
-                auto frag_src = [&](int ii) { return lds8 + ((((ii >> 2) * 4 + cg) * 4 + (ii & 3)) * 4) * 1024 + lane * 16; };
-                bf16x8 fr[2][4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) fr[0][q] = *reinterpret_cast<const bf16x8 *>(frag_src(0) + q * 1024);
-#pragma unroll
-                for (int ii = 0; ii < 8; ++ii) {
-                    if (32 * ii >= T) break;   // workgroup-uniform: source blocks of padding rows
-                    if (ii + 1 < 8) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) fr[(ii + 1) & 1][q] = *reinterpret_cast<const bf16x8 *>(frag_src(ii + 1) + q * 1024);
-                    }
-                    // a block without an edge adds nothing (dependency arcs are mostly short: away from the diagonal most
-                    // blocks of a parse are empty); wavefront-uniform
-                    if (__builtin_amdgcn_ballot_w64(m[ii] != 0u) == 0) continue;
-                    bf16x8 af[2];
-                    if constexpr (((GGCN_LAB_OFF) & 32) != 0) {   // (timing build: no expansion)
-                        union { bf16x8 v; uint32_t w[4]; } u;
-                        u.w[0] = u.w[1] = u.w[2] = u.w[3] = m[ii] & 0x3F803F80u;
-                        af[0] = af[1] = u.v;
-                    } else
-                    expand_mask(m[ii] >> (4 * h), af);   // once per block: both planes use it (small plane first)
-#pragma unroll
-                    for (int p = 1; p >= 0; --p)
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks)
-                            if constexpr (!((GGCN_LAB_OFF) & 64))
-                                y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], fr[ii & 1][2 * p + ks], y, 0, 0, 0);   // gcn.py:41
-                }
-                float rinv[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row0 = (r & 3) + 8 * (r >> 2);
-                    rinv[r] = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_base + 4 * row0, __float_as_int(inv)));
-                }
-                float *tile = decltype(has_out)::value ? out + ((int64_t)g * T + node0) * ldo + (nt0 + j) * NT : nullptr;
-                auto finish = [&](auto whole_c) {   // whole: all 32 rows of the block are nodes (wavefront-uniform) -- no row test
-                    constexpr bool WHOLE = decltype(whole_c)::value;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row0 = (r & 3) + 8 * (r >> 2);  // this lane's row is row0 + 4h
-                        const float v = y[r] * rinv[r] + vb[j];   // gcn.py:41,43
-                        if (vst) stage_lds[(row0 + 4 * h) * 32 + c] = v * vsg[j];
-                        if (WHOLE || node0 + row0 + 4 * h < T) {
-                            if (direct_store && col_ok[j]) tile[lane_off + row0 * ldo] = v * vsg[j];
-                            vmax[j] = vmaxf_raw(vmax[j], v);
-                            vmin[j] = vminf_raw(vmin[j], v);
-                        }
-                    }
-                };
-                if constexpr (((GGCN_LAB_OFF) & 16) != 0) {   // (timing build: nothing behind the neighbour sums)
-                    asm volatile("" :: "v"(y[0]), "v"(y[5]), "v"(y[10]), "v"(y[15]), "v"(rinv[3]));
-                    continue;
-                }
-                if (node0 + 32 <= T) finish(std::true_type{});
-                else finish(std::false_type{});
-                if (vst) {   // 32 rows x 128 B leave as 16 B per lane: 8 rows per instruction
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    const int colq = (lane & 7) * 4;
-                    const int gcol = (nt0 + j) * NT + colq;
-#pragma unroll
-                    for (int it = 0; it < 4; ++it) {
-                        const int row = 8 * it + (lane >> 3);
-                        const float4 v4 = *reinterpret_cast<const float4 *>(&stage_lds[row * 32 + colq]);
-                        if (node0 + row < T && gcol < F) store_out4_stream(tile + row * ldo + colq, v4);
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                }
-            }
-        }
-    };
-    if constexpr (!((GGCN_LAB_OFF) & 128)) {
-        if (out) tiles(std::true_type{});
-        else tiles(std::false_type{});
-    } else {
-        asm volatile("" :: "v"(hf[0][0][0][0]), "v"(hf[3][1][1][1]), "v"(hf[1][0][1][0]), "v"(hf[2][1][0][1]));
-    }
-
-    // pools of the graph: max over ALL its rows (bert_amir5.py:635-640) -- the two row groups meet in LDS
-    if (pool_a || pool_b || lp.ov_partial) {
-        float *pl = reinterpret_cast<float *>(lds8 + kW8Ex);   // [wavefront][max / min][column tile][32] over the store staging
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < RN; ++j) {
-            const float mx = fmaxf(vmax[j], upper_half_to_lower(vmax[j]));
-            const float mn = fminf(vmin[j], upper_half_to_lower(vmin[j]));
-            if (h == 0) {
-                pl[((wave * 2 + 0) * RN + j) * 32 + c] = mx;
-                pl[((wave * 2 + 1) * RN + j) * 32 + c] = mn;
-            }
-        }
-        __syncthreads();
-        if (rg == 0) {
-            float dot = 0.0f;
-#pragma unroll
-            for (int j = 0; j < RN; ++j) {
-                if (nt0 + j >= n_tiles_total) break;
-                const float mx = fmaxf(pl[((wave * 2 + 0) * RN + j) * 32 + c], pl[(((wave + 4) * 2 + 0) * RN + j) * 32 + c]);
-                const float mn = fminf(pl[((wave * 2 + 1) * RN + j) * 32 + c], pl[(((wave + 4) * 2 + 1) * RN + j) * 32 + c]);
-                if (h == 0 && col_ok[j]) {
-                    const int gn = (nt0 + j) * NT + c;
-                    const float pa = vga[j] * (vga[j] >= 0.0f ? mx : mn), pb = vgb[j] * (vgb[j] >= 0.0f ? mx : mn);
-                    if (pool_a) pool_a[(int64_t)g * F + gn] = pa;
-                    if (pool_b) pool_b[(int64_t)g * F + gn] = pb;
-                    dot = fmaf(pa, pb, dot);
-                }
-            }
-            if (lp.ov_partial && nt0 < n_tiles_total) {
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) dot += __shfl_xor(dot, d);
-                if (lane == 0) lp.ov_partial[(int64_t)g * ((F + 63) / 64) + (nt0 >> 1)] = dot;
-            }
-        }
-    }
-
-    } else {
     // ---- neighbour sums over the EDGES, out of an fp32 tile in LDS (gcn.py:41) ----------------------------------------
     // Per 32-column tile j every wavefront writes its accumulators, as they are, into its column group's tile
     // [256 rows][32 columns] fp32 (4 x 32 KiB over the dead stage buffers).  Then 8 lanes x 16 B cover a row: a wavefront
@@ -411,7 +215,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
         pre_c[j] = lp.pre ? lp.pre[gn < F ? gn : 0] : 0.0f;
     }
     const int tile_lane = cg * (256 * 128) + 16 * cl, zero_lane = zero_off + 16 * cl;
-    const int n_steps = ((GGCN_LAB_OFF) & 16) ? 1 : 16;   // (timing build: one row step only)
     const bool full_slot = T == 256;
 #pragma unroll
     for (int j = 0; j < RN; ++j) {
@@ -440,7 +243,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
         int deg_n = s_deg[8 * rg + q8];
         float inv_n = s_inv[8 * rg + q8];
         uint4 idq_n = *reinterpret_cast<const uint4 *>(s_ids + (8 * rg + q8) * kW8Cap);
-        for (int it = 0; it < n_steps; ++it) {
+        for (int it = 0; it < 16; ++it) {
             const int step = 2 * it + rg;
             if (8 * step >= T) break;   // wavefront-uniform: only padding rows from here on
             const int row = 8 * step + q8;
@@ -497,7 +300,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
                         vmin[j][k] = vminf_raw(vmin[j][k], v);
                     }
                 }
-                if (out && !((GGCN_LAB_OFF) & 8)) {   // (timing build: no stores)
+                if (out) {
                     float *dst = out + ((int64_t)g * T + row) * ldo + col0;
                     if constexpr (VST) {
                         if (cok[j][0]) store_out4_stream(dst, make_float4(o4[0], o4[1], o4[2], o4[3]));
@@ -515,7 +318,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
     }
     // pools of the graph: max over ALL its rows (bert_amir5.py:635-640): across the 8 row classes of the wavefront (lanes 8
     // apart), then the two row groups meet in LDS
-    if ((pool_a || pool_b || lp.ov_partial) && !((GGCN_LAB_OFF) & 64)) {   // (timing build: no pools)
+    if (pool_a || pool_b || lp.ov_partial) {
 #pragma unroll
         for (int j = 0; j < RN; ++j)
 #pragma unroll
@@ -562,7 +365,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void layer_fused_wide8_kernel(const 
                 if (lane == 0) lp.ov_partial[(int64_t)g * ((F + 63) / 64) + (nt0 >> 1)] = dot;
             }
         }
-    }
     }
 }
 
@@ -621,7 +423,7 @@ int launch_fused_wide8(const char *who, const FusedArgs &a, int precision, bool 
     } while (0)
 #define GGCN_LAUNCH8(SC, AV, KF, VS)                                            \
     do {                                                                        \
-        if (a.drop.thr != 0 && !GGCN_LAB_WIDE8_DENSE) GGCN_LAUNCH8D(SC, AV, KF, VS, !GGCN_LAB_WIDE8_DENSE); \
+        if (a.drop.thr != 0) GGCN_LAUNCH8D(SC, AV, KF, VS, true);               \
         else GGCN_LAUNCH8D(SC, AV, KF, VS, false);                              \
     } while (0)
 #define GGCN_PICK8(SC)                                      \
@@ -639,9 +441,7 @@ int launch_fused_wide8(const char *who, const FusedArgs &a, int precision, bool 
             return fail(GGCN_ELAUNCH, "%s: cannot reserve %d bytes of LDS", who, kW8Lds);                                 \
         hipLaunchKernelGGL(kern, dim3((unsigned)gridw), dim3(kW8Threads), kW8Lds, st, a);                                 \
     } while (0)
-        constexpr bool kDrop8 = !GGCN_LAB_WIDE8_DENSE;
-        if (a.drop.thr != 0 && !kDrop8) return fail(GGCN_EUNSUPPORTED, "%s: gate dropout lives in the edge-list epilogue", who);
-        if (a.drop.thr != 0) { if (fast && vst) GGCN_LAUNCH8B(true, true, true, kDrop8); else GGCN_LAUNCH8B(false, false, false, kDrop8); }
+        if (a.drop.thr != 0) { if (fast && vst) GGCN_LAUNCH8B(true, true, true, true); else GGCN_LAUNCH8B(false, false, false, true); }
         else { if (fast && vst) GGCN_LAUNCH8B(true, true, true, false); else GGCN_LAUNCH8B(false, false, false, false); }
 #undef GGCN_LAUNCH8B
         return check_launch(who);

@@ -11,7 +11,7 @@ dev = torch.device("cuda:0")
 N, K, F = int(os.environ.get("LAB_N", 131072)), 768, 768
 x = torch.randn(N, K, device=dev)
 g = torch.randn(N, F, device=dev) * 1e-3
-ws = torch.empty(4 * lib.ggcn_dweight_workspace_bytes(N, K, F, 0), dtype=torch.uint8, device=dev)   # (room for more chunks: LAB_SPLITS)
+ws = torch.empty(4 * lib.ggcn_dweight_workspace_bytes(N, K, F, 0), dtype=torch.uint8, device=dev)
 dw = {}
 def run(name):
     out = dw.setdefault(name, torch.empty(K, F, device=dev))
@@ -19,8 +19,6 @@ def run(name):
 def mode(name):
     if name == "transpose": os.environ["GGCN_DWEIGHT_TRANSPOSE"] = "1"
     else: os.environ.pop("GGCN_DWEIGHT_TRANSPOSE", None)
-    if "@" in name: os.environ["GGCN_LAB_DW_SPLITS"] = name.split("@")[1]
-    else: os.environ.pop("GGCN_LAB_DW_SPLITS", None)
 for name in ("tn", "transpose"):
     mode(name); run(name)
 torch.cuda.synchronize()
@@ -29,8 +27,6 @@ for name in ("tn", "transpose"):
     print("%-10s max|err| vs float64 (64 rows of dW): %.3g  (|dW| ~ %.3g)" % (name, float((dw[name][:64] - ref).abs().max()), float(ref.abs().max())))
 print("tn vs transpose max|diff| %.3g" % float((dw["tn"] - dw["transpose"]).abs().max()))
 times = {"tn": [], "transpose": []}
-for sp in os.environ.get("LAB_SPLITS", "").split(","):
-    if sp: times["tn@" + sp] = []
 for rnd in range(8):
     for name in times:
         mode(name)

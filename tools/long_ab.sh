@@ -1,14 +1,12 @@
 #!/bin/bash
 # config 4 through the one-launch long-graph layer: MFMA neighbour sums (default) against the lane sums of round 3
-# (GGCN_LONG_LANE_SUMS=1), same box, back to back; phase timeline of the lab trace build if present.
+# (GGCN_LONG_LANE_SUMS=1), same box, back to back.
 set -u
 O=gpurun_out/r4; mkdir -p $O
 TAG=${1:-ab}
-if [ -f tools/_lab/libggcn_ltrace.so ]; then python tools/long_trace.py > $O/long_trace_$TAG.txt 2>&1; fi
 python bench.py --config 4 --steps 200 --warmup 20 > $O/c4_mma_$TAG.json 2>$O/c4_mma_$TAG.err || exit 1
 GGCN_LONG_LANE_SUMS=1 python bench.py --config 4 --steps 200 --warmup 20 > $O/c4_lane_$TAG.json 2>$O/c4_lane_$TAG.err || exit 1
 python bench.py --config 4 --steps 200 --warmup 20 > $O/c4_mma2_$TAG.json 2>$O/c4_mma2_$TAG.err || exit 1
-[ -f $O/long_trace_$TAG.txt ] && cat $O/long_trace_$TAG.txt
 python - <<PY
 import json
 for n in ("mma","lane","mma2"):
