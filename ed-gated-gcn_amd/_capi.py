@@ -142,6 +142,9 @@ PROTOTYPES = {
     "ggcn_overlap_workspace_bytes": (c_sz, [c_i32]),
     "ggcn_gate_overlap": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ggcn_bilstm_recurrence": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp]),
+    "ggcn_bilstm_recurrence_save": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                            c_vp]),
+    "ggcn_bilstm_recurrence_backward": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp]),
 }
 
 ABI_VERSION = 14

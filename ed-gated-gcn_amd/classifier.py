@@ -14,8 +14,9 @@ token like the reference's (``:621-625``); ``opt.ggcn_wide_backward`` reaches ``
 puts their backward on graphs of 33..128 nodes into one launch each where no gate dropout is active
 (``dispatch.takes_wide_backward``); ``opt.ggcn_weighted_wide_backward`` reaches them the same way and does the same on a
 real-valued adjacency of 33..128 nodes (``dispatch.takes_weighted_wide_backward``); ``opt.ggcn_hip_lstm`` puts the BiLSTM (``:610``) of an inference forward on the HIP
-path (``recurrent.bilstm``: one projection, one recurrence launch).  BERT, ``dense`` and, by default and in training, the BiLSTM
-stay PyTorch-ROCm.
+path (``recurrent.bilstm``: one projection, one recurrence launch), and ``opt.ggcn_hip_lstm_backward`` that of a training step
+(``recurrent.bilstm_train``: the saving forward and a one-launch backward, float32, no autocast).  BERT, ``dense`` and, by default,
+the BiLSTM stay PyTorch-ROCm.
 """
 import os
 
@@ -28,7 +29,7 @@ from .gated_block import gated_gcn_block, takes_block_path
 from .gcn import GraphConvolution
 from .heads import gate_mlps, scores_and_kl
 from .pooling import subword_pool
-from .recurrent import bilstm, takes_hip_lstm
+from .recurrent import bilstm, bilstm_train, takes_hip_lstm, takes_hip_lstm_train, lstm_wants_grad
 
 
 class LegacyBertAdapter(nn.Module):
@@ -99,6 +100,11 @@ class GatedGCNEventDetector(nn.Module):
         # bf16x3 sums differ from the fp32 GEMM's in the last bits (both inside the forward gate).
         self.hip_lstm = (bool(getattr(opt, "ggcn_hip_lstm", False))
                          or os.environ.get("GGCN_HIP_LSTM", "0") == "1")
+        # training: the BiLSTM (:610) as the differentiable ``bilstm_train`` (the projection, the saving recurrence launch, one
+        # backward launch + the fixed-order weight products) where a gradient is wanted and ``takes_hip_lstm_train`` holds;
+        # bf16 autocast and the CPU keep nn.LSTM.  Independent of ``hip_lstm``; off by default, for the same reason.
+        self.hip_lstm_backward = (bool(getattr(opt, "ggcn_hip_lstm_backward", False))
+                                  or os.environ.get("GGCN_HIP_LSTM_BACKWARD", "0") == "1")
 
     def _training_gates(self, aspect):
         """``gate1(aspect), gate2(aspect)`` of the training branches: the two nn.Sequential (under bf16 autocast they give bf16)
@@ -190,6 +196,9 @@ class GatedGCNEventDetector(nn.Module):
         anchor_rep = self.dropout(x[rows, anchor])                          # :604-608: the anchor token's row
         if self.hip_lstm and not torch.is_autocast_enabled("cuda") and takes_hip_lstm(x, self.lstm):
             x = bilstm(x, self.lstm)                                        # :610 on the HIP path (inference, float32, no autocast)
+        elif (self.hip_lstm_backward and not torch.is_autocast_enabled("cuda") and takes_hip_lstm_train(x, self.lstm)
+              and lstm_wants_grad(x, self.lstm)):
+            x = bilstm_train(x, self.lstm)                                  # :610 on the HIP path (training, float32, no autocast)
         else:
             x, _ = self.lstm(x)                                             # :610
         if x.dtype == torch.float16 and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16:

@@ -1,5 +1,6 @@
-"""The classifier's BiLSTM (``models/bert_amir5.py:557,610``: ``nn.LSTM(9216, 128, bidirectional, batch_first)``) on the HIP path
-in inference: ONE input projection and ONE recurrence launch.
+"""The classifier's BiLSTM (``models/bert_amir5.py:557,610``: ``nn.LSTM(9216, 128, bidirectional, batch_first)``) on the HIP path:
+in inference ONE input projection and ONE recurrence launch (``bilstm``), in training the same two in their saving form and a
+one-launch backward (``bilstm_train``).
 
 * the projection ``G = X . [W_ih_f ; W_ih_r]^T`` (``[B*T, I] x [I, 8 hd]``) is the library's ``ggcn_linear`` at precision bf16x3
   (full fp32 range, no range flag) on a ``ggcn_weight_pack`` image of the two ``weight_ih`` matrices stacked: 1024 x I row-major is
@@ -7,9 +8,16 @@ in inference: ONE input projection and ONE recurrence launch.
 * the recurrence is ``ggcn_bilstm_recurrence``: all T steps and both directions in one launch, ``W_hh`` resident in registers,
   ``h`` and ``c`` on the chip, exact fp32.
 
-Forward only.  A call that wants a gradient raises; the classifier takes this path with ``opt.ggcn_hip_lstm`` /
+``bilstm`` is forward only.  A call that wants a gradient raises; the classifier takes this path with ``opt.ggcn_hip_lstm`` /
 ``GGCN_HIP_LSTM=1`` where ``takes_hip_lstm`` holds and keeps ``nn.LSTM`` everywhere else (training, bf16 autocast).  No CPU
 fallback: CPU tensors raise.
+
+``bilstm_train`` is the differentiable form (``x`` and all eight parameters): ``ggcn_bilstm_recurrence_save`` writes the
+activated gates over ``G`` and keeps ``c`` and the ``h`` each step read; the backward is ONE ``ggcn_bilstm_recurrence_backward``
+launch (all T steps, both directions, time walked backwards, ``dc`` and the recurrent ``dh`` on the chip) whose ``dG`` feeds the
+library's fixed-order products: ``ggcn_dweight`` for ``[W_ih_f ; W_ih_r]`` and the two ``W_hh``, ``ggcn_colsum`` for the biases,
+``ggcn_linear`` for ``dX`` -- each skipped where no gradient is wanted.  The classifier takes it in training with
+``opt.ggcn_hip_lstm_backward`` / ``GGCN_HIP_LSTM_BACKWARD=1`` where ``takes_hip_lstm_train`` holds (off by default).
 """
 import torch
 
@@ -43,19 +51,24 @@ def _params(lstm):
     return [getattr(lstm, name, None) for name in PARAMS]
 
 
-def _wants_grad(x, lstm):
+def lstm_wants_grad(x, lstm):
+    """A call on ``x`` and ``lstm`` wants a gradient: grad is enabled and ``x`` or a parameter of the module requires one."""
     return torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in _params(lstm)))
 
 
-def takes_hip_lstm(x, lstm):
-    """``bilstm(x, lstm)`` would run: the conditions of its raises as a predicate (no side effect; CPU tensors answer False)."""
+def takes_hip_lstm_train(x, lstm):
+    """``bilstm_train(x, lstm)`` would run: the conditions of its raises as a predicate (no side effect; CPU tensors answer
+    False).  Nothing about gradients: ``bilstm_train`` serves a call with and without one."""
     if not (isinstance(x, torch.Tensor) and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32):
         return False
     if _module_problem(lstm) is not None or x.shape[2] != lstm.input_size:
         return False
-    if any(p is not None and p.device != x.device for p in _params(lstm)):
-        return False
-    return not _wants_grad(x, lstm)
+    return not any(p is not None and p.device != x.device for p in _params(lstm))
+
+
+def takes_hip_lstm(x, lstm):
+    """``bilstm(x, lstm)`` would run: the conditions of its raises as a predicate (no side effect; CPU tensors answer False)."""
+    return takes_hip_lstm_train(x, lstm) and not lstm_wants_grad(x, lstm)
 
 
 def _operands(lstm, lib, st):
@@ -77,11 +90,8 @@ def _operands(lstm, lib, st):
     return cached[1]
 
 
-def bilstm(x, lstm):
-    """``lstm(x)[0]`` for ``x [B,T,I]`` float32 on the GPU and the classifier's ``nn.LSTM``: ``[B,T,2*128]`` float32, contiguous,
-    from one ``ggcn_linear`` (bf16x3) and one ``ggcn_bilstm_recurrence`` launch; zero initial state, every one of the T rows run
-    (the reference passes the padded batch).  The weight image, the two summed biases and the ``W_hh`` copies are cached on the
-    module and rebuilt when a parameter changes.  ``B == 0`` or ``T == 0`` gives an empty tensor without a launch."""
+def _check(x, lstm, forward_only):
+    """The raises of ``bilstm`` (``forward_only``) and of ``bilstm_train``, in one order and with one set of texts."""
     if not isinstance(x, torch.Tensor) or x.dim() != 3:
         raise TypeError("x must be a 3-d tensor")
     if x.dtype != torch.float32:
@@ -91,13 +101,21 @@ def bilstm(x, lstm):
         raise RuntimeError(problem)
     if x.shape[2] != lstm.input_size:
         raise RuntimeError("x %s does not match lstm.input_size %d" % (tuple(x.shape), lstm.input_size))
-    if _wants_grad(x, lstm):
+    if forward_only and lstm_wants_grad(x, lstm):
         raise RuntimeError("bilstm is forward only: a gradient through the LSTM stays nn.LSTM (call it under torch.no_grad())")
     if not x.is_cuda:
         raise RuntimeError("x is on %s: the HIP path has no CPU fallback" % x.device)
     for name, p in zip(PARAMS, _params(lstm)):
         if p is not None and p.device != x.device:
             raise RuntimeError("lstm.%s is on %s, x on %s: the HIP path has no CPU fallback" % (name, p.device, x.device))
+
+
+def bilstm(x, lstm):
+    """``lstm(x)[0]`` for ``x [B,T,I]`` float32 on the GPU and the classifier's ``nn.LSTM``: ``[B,T,2*128]`` float32, contiguous,
+    from one ``ggcn_linear`` (bf16x3) and one ``ggcn_bilstm_recurrence`` launch; zero initial state, every one of the T rows run
+    (the reference passes the padded batch).  The weight image, the two summed biases and the ``W_hh`` copies are cached on the
+    module and rebuilt when a parameter changes.  ``B == 0`` or ``T == 0`` gives an empty tensor without a launch."""
+    _check(x, lstm, forward_only=True)
     B, T, I = x.shape
     dev = x.device
     y = torch.empty(B, T, 2 * HIDDEN, dtype=torch.float32, device=dev)
@@ -114,3 +132,132 @@ def bilstm(x, lstm):
         _capi.check(lib.ggcn_bilstm_recurrence(_capi.ptr(g), 8 * HIDDEN, _capi.ptr(whh_f), _capi.ptr(whh_r), _capi.ptr(bias_f),
                                                _capi.ptr(bias_r), _capi.ptr(y), 2 * HIDDEN, B, T, HIDDEN, st), "ggcn_bilstm_recurrence")
     return y
+
+
+def _dx_operand(lstm, lib, st):
+    """The ``ggcn_weight_pack`` image of ``[W_ih_f ; W_ih_r]`` as the ``[K = 8 hd, F = I]`` matrix it is (``transposed=0``): the
+    operand of ``dX = dG . [W_ih_f ; W_ih_r]``.  Cached on the module under ``_operands``' key, built only when ``x`` wants a
+    gradient."""
+    ps = _params(lstm)
+    key = tuple(None if p is None else (p.data_ptr(), tensor_version(p), p.device) for p in ps)
+    cached = getattr(lstm, "_ggcn_lstm_dx", None)
+    if cached is None or cached[0] != key:
+        I = lstm.input_size
+        prec = _capi.PREC["bf16x3"]
+        wcat = torch.cat([ps[0].detach(), ps[4].detach()], dim=0).contiguous()
+        pack = torch.empty(lib.ggcn_weight_pack_bytes(8 * HIDDEN, I, prec), dtype=torch.uint8, device=wcat.device)
+        _capi.check(lib.ggcn_weight_pack(_capi.ptr(wcat), I, 8 * HIDDEN, I, prec, 0, _capi.ptr(pack), st), "ggcn_weight_pack")
+        cached = (key, pack)
+        lstm._ggcn_lstm_dx = cached
+    return cached[1]
+
+
+class _BilstmTrain(torch.autograd.Function):
+    """``bilstm`` under autograd: the projection, then ``ggcn_bilstm_recurrence_save`` in place on ``G`` (the bits of
+    ``bilstm``'s ``y``); the backward is one ``ggcn_bilstm_recurrence_backward`` launch and, for what wants a gradient, the
+    library's fixed-order products on its ``dG``."""
+
+    @staticmethod
+    def forward(ctx, x, lstm, *params):
+        B, T, I = x.shape
+        dev = x.device
+        ctx.lstm, ctx.dims = lstm, (B, T, I)
+        y = torch.empty(B, T, 2 * HIDDEN, dtype=torch.float32, device=dev)
+        if B == 0 or T == 0:
+            return y
+        lib = _capi.load_library()
+        ptr = _capi.ptr
+        x2 = _rows2d(x.detach())
+        with torch.cuda.device(dev):
+            st = _capi.stream_of(dev)
+            pack, whh_f, whh_r, bias_f, bias_r = _operands(lstm, lib, st)
+            g = torch.empty(B * T, 8 * HIDDEN, dtype=torch.float32, device=dev)
+            c = torch.empty(B * T, 2 * HIDDEN, dtype=torch.float32, device=dev)
+            hprev = torch.empty(B * T, 2 * HIDDEN, dtype=torch.float32, device=dev)
+            _capi.check(lib.ggcn_linear(ptr(x2), x2.stride(0), None, 0, ptr(pack), ptr(g), 8 * HIDDEN, B * T, I, 8 * HIDDEN,
+                                        _capi.PREC["bf16x3"], st), "ggcn_linear")
+            _capi.check(lib.ggcn_bilstm_recurrence_save(ptr(g), 8 * HIDDEN, ptr(whh_f), ptr(whh_r), ptr(bias_f), ptr(bias_r), ptr(y),
+                                                        2 * HIDDEN, B, T, HIDDEN, ptr(g), ptr(c), ptr(hprev), st),
+                        "ggcn_bilstm_recurrence_save")
+        # what the backward reads of the module, under autograd's version check: W_hh always, the two W_ih only where dX is formed
+        w_ih = (params[0], params[4]) if ctx.needs_input_grad[0] else ()
+        ctx.save_for_backward(x2, g, c, hprev, whh_f, whh_r, *w_ih)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        B, T, I = ctx.dims
+        lstm = ctx.lstm
+        need_x, need = ctx.needs_input_grad[0], list(ctx.needs_input_grad[2:])
+        ps = _params(lstm)
+        need = [n and p is not None for n, p in zip(need, ps)]
+        if B == 0 or T == 0:
+            dev = dy.device
+            return (torch.zeros(B, T, I, dtype=torch.float32, device=dev) if need_x else None, None,
+                    *(torch.zeros_like(p) if n else None for n, p in zip(need, ps)))
+        x2, g, c, hprev, whh_f, whh_r = ctx.saved_tensors[:6]     # (raises if a saved weight was updated in place since the forward)
+        lib = _capi.load_library()
+        ptr = _capi.ptr
+        dev = g.device
+        rows, W = B * T, 8 * HIDDEN
+        bx3 = _capi.PREC["bf16x3"]
+        # the entry takes rows with a leading dimension, no batch stride: an expanded or strided dY (a loss's gradient is often an
+        # expanded scalar) is copied to [B*T, 2 hd] here, a contiguous one is handed over as it lies
+        dy2 = dy.float().contiguous().view(rows, 2 * HIDDEN)
+        grads = [None] * 8
+        with torch.cuda.device(dev):
+            st = _capi.stream_of(dev)
+            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)   # noqa: E731
+            dg = new(rows, W)
+            _capi.check(lib.ggcn_bilstm_recurrence_backward(ptr(dy2), dy2.stride(0), ptr(g), W, ptr(c), ptr(whh_f), ptr(whh_r),
+                                                            ptr(dg), W, B, T, HIDDEN, st), "ggcn_bilstm_recurrence_backward")
+
+            def product(xcols, K, dh, ldh, F):        # dW [K,F] = dG[:, xcols:xcols+K]^T . dh
+                dw = new(K, F)
+                ws = torch.empty(max(16, lib.ggcn_dweight_workspace_bytes(rows, K, F, bx3)), dtype=torch.uint8, device=dev)
+                _capi.check(lib.ggcn_dweight(ptr(dg[:, xcols:]), W, ptr(dh), ldh, rows, K, F, ptr(dw), F, bx3, ptr(ws), st), "ggcn_dweight")
+                return dw
+
+            if need[0] or need[4]:                    # d[W_ih_f ; W_ih_r], already in nn.LSTM layout
+                dwih = product(0, W, x2, x2.stride(0), I)
+                if need[0] and need[4]:               # the two halves of one buffer: disjoint rows
+                    grads[0], grads[4] = dwih[:W // 2], dwih[W // 2:]
+                else:                                 # one half alone gets storage of its own, not a hold on the whole product
+                    grads[0 if need[0] else 4] = (dwih[:W // 2] if need[0] else dwih[W // 2:]).clone()
+            for d in (0, 1):
+                if need[4 * d + 1]:                   # dW_hh_d = da_d^T . Hprev_d
+                    grads[4 * d + 1] = product(d * 4 * HIDDEN, 4 * HIDDEN, hprev[:, d * HIDDEN:], 2 * HIDDEN, HIDDEN)
+            if any(need[i] for i in (2, 3, 6, 7)):    # both biases of a direction receive the column sums of its da
+                db = new(W)
+                ws = torch.empty(max(16, lib.ggcn_colsum_workspace_bytes(W)), dtype=torch.uint8, device=dev)
+                _capi.check(lib.ggcn_colsum(ptr(dg), W, rows, W, ptr(db), ptr(ws), st), "ggcn_colsum")
+                for i in (2, 3, 6, 7):                # a copy each: b_ih.grad and b_hh.grad must not share memory (autograd
+                    if need[i]:                       # accumulates and optimizers clip in place)
+                        grads[i] = (db[:W // 2] if i < 4 else db[W // 2:]).clone()
+            dx = None
+            if need_x:                                # dX = dG . [W_ih_f ; W_ih_r]
+                dx = new(B, T, I)
+                _capi.check(lib.ggcn_linear(ptr(dg), W, None, 0, ptr(_dx_operand(lstm, lib, st)), ptr(dx), I, rows, W, I, bx3, st),
+                            "ggcn_linear")
+        return (dx, None, *grads)
+
+
+def bilstm_train(x, lstm):
+    """``lstm(x)[0]`` as ``bilstm`` gives it, differentiable in ``x`` and in all eight parameters of the module.
+
+    With grad enabled and ``x`` or a parameter requiring a gradient the call goes through ``_BilstmTrain``: the same bf16x3
+    projection, ``ggcn_bilstm_recurrence_save`` in place on ``G`` (the same ``y`` bits; the activated gates, ``c`` and the ``h``
+    each step read are kept: ``[B*T, 8 hd + 2 hd + 2 hd]`` floats), and a backward of one ``ggcn_bilstm_recurrence_backward``
+    launch plus, each only where a gradient is wanted, three ``ggcn_dweight`` (``[W_ih_f ; W_ih_r]`` in one, the two ``W_hh``),
+    one ``ggcn_colsum`` (the biases) and one ``ggcn_linear`` (``dX``, on a second cached image), all bf16x3 / fixed order.
+    Without a gradient wanted it is ``bilstm`` and saves nothing.  The raises are ``bilstm``'s, without the one on gradients;
+    ``B == 0`` or ``T == 0`` gives an empty result and zero gradients without a launch.  Every gradient has storage of its own
+    (``bias_ih`` and ``bias_hh`` receive equal values in two buffers).  A ``dY`` that is not contiguous (an expanded scalar, a
+    slice) is copied to ``[B*T, 2 hd]`` first: the backward entry takes a leading dimension, no batch stride; a time-sliced ``x``
+    is copied likewise, as in ``bilstm``.  The classifier takes it in training
+    with ``opt.ggcn_hip_lstm_backward`` / ``GGCN_HIP_LSTM_BACKWARD=1``."""
+    _check(x, lstm, forward_only=False)
+    if not lstm_wants_grad(x, lstm):
+        return bilstm(x, lstm)
+    return _BilstmTrain.apply(x, lstm, *_params(lstm))

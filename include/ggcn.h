@@ -741,6 +741,39 @@ int ggcn_bilstm_recurrence(const float *G, int64_t ldg, const float *Whh_f, cons
                            const float *bias_f, const float *bias_r, float *Y, int64_t ldy, int B, int T, int hd,
                            ggcn_stream_t stream);
 
+/* ---- the BiLSTM's recurrence under autograd: saving forward, backward in one launch (training through bert_amir5.py:610) ----
+ * ggcn_bilstm_recurrence_save: ggcn_bilstm_recurrence's launch and arguments plus three outputs.  gates [B*T, ldg] receives the
+ * activated i, f, g, o of every step and direction in the column layout of G; gates == G is allowed (each thread overwrites the
+ * one element it has read: one [B*T, 8hd] buffer serves both).  C [B*T, 2hd] contiguous receives the cell state after each step,
+ * Hprev [B*T, 2hd] contiguous the h each step read (zeros at a direction's first step: t = 0 forward, t = T-1 reverse), both in
+ * the column layout of Y.  Y is the plain entry's bit for bit: one step body serves both kernels.  The refusals are
+ * ggcn_bilstm_recurrence's, plus NULL gates / C / Hprev; the bias pointers stay optional.
+ *
+ * ggcn_bilstm_recurrence_backward: from dY [B*T, lddy] (the gradient of Y), the saved gates [B*T, ldg] and C, all T steps and both
+ * directions in ONE launch, each direction's time walked backwards.  Per sentence and direction, with dh = dY[b,t,d] + dh_rec and
+ * a carried dc (both zero at the start):
+ *     tc = tanh(c_t)    do = dh*tc         dc += dh*o*(1-tc^2)
+ *     di = dc*g         dg = dc*i          df = dc*c_{t-1}          dc <- dc*f
+ *     da = [ di*i(1-i) | df*f(1-f) | dg*(1-g^2) | do*o(1-o) ]  -> dG[b*T+t, d*4hd:(d+1)*4hd]        dh_rec = da . Whh_d
+ * c_{t-1} is read from C (zero at the direction's first step), i(1-i) and the like are taken from the stored float32 gates,
+ * tanh(c) is recomputed.  dG [B*T, lddg] is the gradient of G + bias: from it, with the library's fixed-order products,
+ *     d[W_ih_f ; W_ih_r] [8hd, I] = ggcn_dweight(X = dG, K = 8hd, dH = x, F = I)           already in nn.LSTM layout
+ *     dW_hh_d [4hd, hd] = ggcn_dweight(X = dG + d*4hd, K = 4hd, dH = Hprev + d*hd, F = hd)
+ *     d bias_f | d bias_r = ggcn_colsum(dG, lddg, B*T, 8hd)        (b_ih and b_hh both receive it)
+ *     dX = dG . [W_ih_f ; W_ih_r] = ggcn_linear on the ggcn_weight_pack(transposed = 0) image of the [8hd, I] stack
+ * Grid and workgroup as the forward's; a thread keeps a 128-long COLUMN piece of Whh_d in registers, da sits in LDS, the four
+ * quarter sums of dh_rec are added in a fixed order, dc and dh_rec never leave the chip.  Exact fp32 FMA chains, no atomics: two
+ * calls give the same bits, a sentence's result does not depend on B or on its place in a tile, and the two directions run the
+ * same arithmetic.  No synchronisation.  Refusals, all before any launch: NULL dY / gates / C / Whh_f / Whh_r / dG, B or T <= 0,
+ * lddy < 2 hd, ldg or lddg < 8 hd, Whh_f or Whh_r off 16 bytes, dG overlapping gates (dG is a buffer of its own, so that a second
+ * backward can read the gates again) -> GGCN_EINVAL; hd != 128 and B*T >= 2^31 -> GGCN_EUNSUPPORTED. */
+int ggcn_bilstm_recurrence_save(const float *G, int64_t ldg, const float *Whh_f, const float *Whh_r,
+                                const float *bias_f, const float *bias_r, float *Y, int64_t ldy, int B, int T, int hd,
+                                float *gates, float *C, float *Hprev, ggcn_stream_t stream);
+int ggcn_bilstm_recurrence_backward(const float *dY, int64_t lddy, const float *gates, int64_t ldg, const float *C,
+                                    const float *Whh_f, const float *Whh_r, float *dG, int64_t lddg, int B, int T, int hd,
+                                    ggcn_stream_t stream);
+
 /* ---- range check for GGCN_PREC_F16MX8 (on demand, not on the forward path) ----------------
  * out[0] = max |x| over the finite entries of X [M,K] (fp32, or IEEE half when is_half != 0; ld in
  * elements), out[1] = 1.0f when some entry is NaN or infinite.  f16mx8 needs |x|, |w| < 65504 and keeps

@@ -7,7 +7,14 @@ first step; the forms take turns window group by window group, so a drift of the
 the largest difference of the two forms' outputs.  Last line: one evaluation step of the classifier without an encoder with
 ``ggcn_hip_lstm`` off and on.
 
-usage: bilstm_timing.py [output file]   (writes profiles/bilstm_timing.txt by default)"""
+``--train``: the TRAINING step of the BiLSTM alone, forward + backward with ``dX`` off as in the reference (BERT is frozen,
+train.py:44): ``nn.LSTM`` under autograd against ``recurrent.bilstm_train``, and the plain recurrence launch, the saving one and the backward
+launch each by itself, on the same shapes in one process.  Every step of both forms begins with an in-place update of ``weight_ih_l0``
+and drops the gradients, so the HIP form packs its weight image every step, as after an optimizer step.  Beside the time: the
+largest difference of the two forms' gradients, relative to the gradient's largest entry.
+
+usage: bilstm_timing.py [--train] [output file]   (writes profiles/bilstm_timing.txt, with --train
+profiles/bilstm_backward_timing.txt, by default)"""
 import os
 import statistics
 import sys
@@ -90,7 +97,81 @@ def classifier_step(dev, B=256, words=31, pieces=65, classes=34):
             "   | logits, on against off: max|diff| %.3g" % (B, words, fmt(res["off"]), fmt(res["on"]), diff))
 
 
+def train_main(path):
+    assert torch.cuda.is_available(), "a timing needs the GPU"
+    dev = torch.device("cuda:0")
+    lib = pkg.load_library()
+    lines = ["# %s; the BiLSTM's training step alone (forward + backward, dX off, float32, features %d wide), us per step: median "
+             "(min..max) over %d windows, each form alone in its windows, the forms taking turns" % (
+                 torch.cuda.get_device_name(0), I, (GROUPS - SKIP) * WINDOWS)]
+    torch.manual_seed(0)
+    lstm = torch.nn.LSTM(I, recurrent.HIDDEN, bidirectional=True, batch_first=True, num_layers=1).to(dev)
+    for p in lstm.parameters():
+        if p.dim() > 1:
+            torch.nn.init.xavier_uniform_(p)
+    H8, H2 = 8 * recurrent.HIDDEN, 2 * recurrent.HIDDEN
+    ptr = _capi.ptr
+    for B, T in SHAPES:
+        x = torch.randn(B, T, I, device=dev)
+        dy = torch.randn(B, T, H2, device=dev)
+
+        def begin():
+            lstm.zero_grad(set_to_none=True)
+            with torch.no_grad():
+                lstm.weight_ih_l0.add_(0.0)          # moves the version counter: the cached image is rebuilt
+
+        def torch_form():
+            begin()
+            lstm(x)[0].backward(dy)
+
+        def hip_form():
+            begin()
+            pkg.bilstm_train(x, lstm).backward(dy)
+
+        torch_form()
+        ref = {n: p.grad.clone() for n, p in lstm.named_parameters()}
+        hip_form()
+        diff = max(float((p.grad - ref[n]).abs().max()) / (float(ref[n].abs().max()) + 1e-30) for n, p in lstm.named_parameters())
+        st = _capi.stream_of(dev)
+        pack, whh_f, whh_r, bias_f, bias_r = recurrent._operands(lstm, lib, st)
+        g = torch.empty(B * T, H8, device=dev)
+        _capi.check(lib.ggcn_linear(ptr(x.view(B * T, I)), I, None, 0, ptr(pack), ptr(g), H8, B * T, I, H8, _capi.PREC["bf16x3"], st), "ggcn_linear")
+        saved, dg = torch.empty(B * T, H8, device=dev), torch.empty(B * T, H8, device=dev)
+        y, c, hprev = (torch.empty(B * T, H2, device=dev) for _ in range(3))
+
+        def save():            # (gates in a buffer of their own here, so that every call reads the same G)
+            _capi.check(lib.ggcn_bilstm_recurrence_save(ptr(g), H8, ptr(whh_f), ptr(whh_r), ptr(bias_f), ptr(bias_r), ptr(y), H2, B, T,
+                                                        recurrent.HIDDEN, ptr(saved), ptr(c), ptr(hprev), st), "ggcn_bilstm_recurrence_save")
+
+        def plain():           # the inference launch, for the cost of the three stores
+            _capi.check(lib.ggcn_bilstm_recurrence(ptr(g), H8, ptr(whh_f), ptr(whh_r), ptr(bias_f), ptr(bias_r), ptr(y), H2, B, T,
+                                                   recurrent.HIDDEN, st), "ggcn_bilstm_recurrence")
+
+        def backward():
+            _capi.check(lib.ggcn_bilstm_recurrence_backward(ptr(dy), H2, ptr(saved), H8, ptr(c), ptr(whh_f), ptr(whh_r), ptr(dg), H8, B, T,
+                                                            recurrent.HIDDEN, st), "ggcn_bilstm_recurrence_backward")
+
+        save()
+        reps = 3 if B * T >= 50000 else 10
+        res = take_turns({"nn.LSTM": torch_form, "bilstm_train": hip_form, "plain launch": plain, "save launch": save,
+                          "backward launch": backward}, reps)
+        line = "B=%d T=%d: " % (B, T) + "   ".join("%s %s" % (n, fmt(v)) for n, v in res.items())
+        line += "   | nn.LSTM / bilstm_train %.2f   | gradients, bilstm_train against nn.LSTM: max|diff| / max|grad| %.3g" % (
+            statistics.median(res["nn.LSTM"]) / statistics.median(res["bilstm_train"]), diff)
+        print(line, flush=True)
+        lines.append(line)
+        del x, dy, g, saved, dg, y, c, hprev, ref
+        lstm.zero_grad(set_to_none=True)
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
+    if "--train" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--train"]
+        return train_main(rest[0] if rest else os.path.join(ROOT, "profiles", "bilstm_backward_timing.txt"))
     path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "bilstm_timing.txt")
     assert torch.cuda.is_available(), "a timing needs the GPU"
     dev = torch.device("cuda:0")
