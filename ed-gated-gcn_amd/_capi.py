@@ -76,6 +76,10 @@ PROTOTYPES = {
                                   c_i32, c_i32, c_i32, c_i32, c_vp]),
     "ggcn_subword_pool_bf16": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
                                        c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "ggcn_subword_pool_layers": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                         c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "ggcn_subword_pool_layers_form": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                              c_i32, c_i32, c_i32, c_i32]),
     "ggcn_linear_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
     "ggcn_linear_out_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
     "ggcn_layer_fused_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
@@ -156,6 +160,7 @@ LINEAR_ENTRY = {"ggcn_linear": 0, "ggcn_linear_h": 1, "ggcn_linear_bf16": 2, "gg
 FORM_XVEC, FORM_KFULL, FORM_VST, FORM_WVEC = 1, 2, 4, 8
 RANGE_OVERFLOW, RANGE_WINDOW, RANGE_HIDDEN = 1, 2, 4   # include/ggcn.h ggcn_range_bits
 BILSTM_TILE = 16   # include/ggcn.h GGCN_BILSTM_TILE: sentences per workgroup of ggcn_bilstm_recurrence
+POOL_MAX_LAYERS = 16   # include/ggcn.h GGCN_POOL_MAX_LAYERS: layers per ggcn_subword_pool_layers launch
 
 
 def has_f16mx6():

@@ -15,7 +15,8 @@ puts their backward on graphs of 33..128 nodes into one launch each where no gat
 (``dispatch.takes_wide_backward``); ``opt.ggcn_weighted_wide_backward`` reaches them the same way and does the same on a
 real-valued adjacency of 33..128 nodes (``dispatch.takes_weighted_wide_backward``); ``opt.ggcn_hip_lstm`` puts the BiLSTM (``:610``) of an inference forward on the HIP
 path (``recurrent.bilstm``: one projection, one recurrence launch), and ``opt.ggcn_hip_lstm_backward`` that of a training step
-(``recurrent.bilstm_train``: the saving forward and a one-launch backward, float32, no autocast).  BERT, ``dense`` and, by default,
+(``recurrent.bilstm_train``: the saving forward and a one-launch backward, float32, no autocast); ``opt.ggcn_pool_layers`` pools
+BERT's layer outputs as the list they come in (``pooling.subword_pool_layers``: one launch, no ``torch.cat`` of ``:596``).  BERT, ``dense`` and, by default,
 the BiLSTM stay PyTorch-ROCm.
 """
 import os
@@ -28,7 +29,7 @@ from . import dispatch
 from .gated_block import gated_gcn_block, takes_block_path
 from .gcn import GraphConvolution
 from .heads import gate_mlps, scores_and_kl
-from .pooling import subword_pool
+from .pooling import subword_pool, subword_pool_layers
 from .recurrent import bilstm, bilstm_train, takes_hip_lstm, takes_hip_lstm_train, lstm_wants_grad
 
 
@@ -105,6 +106,11 @@ class GatedGCNEventDetector(nn.Module):
         # bf16 autocast and the CPU keep nn.LSTM.  Independent of ``hip_lstm``; off by default, for the same reason.
         self.hip_lstm_backward = (bool(getattr(opt, "ggcn_hip_lstm_backward", False))
                                   or os.environ.get("GGCN_HIP_LSTM_BACKWARD", "0") == "1")
+        # the sub-word pooling (:600) straight from BERT's list of layer outputs: ``subword_pool_layers`` pools every layer into its
+        # own columns in one launch instead of ``torch.cat`` (:596, a full [B,L,9216] copy) + ``subword_pool``.  Same bits, forward
+        # and backward, float32 and bf16; taken where the layers are a list or tuple of GPU tensors.  Off by default.
+        self.pool_layers = (bool(getattr(opt, "ggcn_pool_layers", False))
+                            or os.environ.get("GGCN_POOL_LAYERS", "0") == "1")
 
     def _training_gates(self, aspect):
         """``gate1(aspect), gate2(aspect)`` of the training branches: the two nn.Sequential (under bf16 autocast they give bf16)
@@ -190,8 +196,11 @@ class GatedGCNEventDetector(nn.Module):
         if isinstance(adj, torch.Tensor):
             adj = adj[:, :T, :T]
         x, pooled = self.bert(ids, seg, output_all_encoded_layers=True)     # :591
-        x = torch.cat(x[-self.n_layer:], dim=-1)                            # :596
-        x = subword_pool(transform.float(), x)                              # :600 on the HIP path (non-zeros only)
+        if self.pool_layers and isinstance(x, (list, tuple)) and all(torch.is_tensor(t) and t.is_cuda for t in x[-self.n_layer:]):
+            x = subword_pool_layers(transform.float(), x[-self.n_layer:])   # :596 + :600 in one launch, no [B,L,9216] copy
+        else:
+            x = torch.cat(x[-self.n_layer:], dim=-1)                        # :596
+            x = subword_pool(transform.float(), x)                          # :600 on the HIP path (non-zeros only)
         rows = torch.arange(B, device=x.device)
         anchor_rep = self.dropout(x[rows, anchor])                          # :604-608: the anchor token's row
         if self.hip_lstm and not torch.is_autocast_enabled("cuda") and takes_hip_lstm(x, self.lstm):

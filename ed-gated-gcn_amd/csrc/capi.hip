@@ -777,6 +777,21 @@ int ggcn_subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, 
     return subword_pool(A, sa_b, sa_r, sa_c, X, x_batch, ldx, Y, y_batch, ldy, B, R, C, D, as_stream(stream));
 }
 
+int ggcn_subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                             int is_bf16, int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C,
+                             int Dl, ggcn_stream_t stream)
+{
+    return subword_pool_layers(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, Y, y_batch, ldy, B, R, C, Dl,
+                               as_stream(stream));
+}
+
+int ggcn_subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers,
+                                  int n_layers, int is_bf16, int64_t x_batch, int64_t ldx, const void *Y, int64_t y_batch,
+                                  int64_t ldy, int B, int R, int C, int Dl)
+{
+    return subword_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, Y, y_batch, ldy, B, R, C, Dl);
+}
+
 int ggcn_absmax(const void *X, int is_half, int64_t ld, int64_t M, int K, float *out, ggcn_stream_t stream)
 {
     return absmax(X, is_half, ld, M, K, out, as_stream(stream));

@@ -89,6 +89,13 @@ int subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const
                  int64_t ldx, float *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, hipStream_t st);
 int subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *X, int64_t x_batch,
                       int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, hipStream_t st);
+// every layer of `layers` (a host array) into its own Dl columns of Y, one launch; ..._form: 1 vector / 0 scalar / -status, host only
+int subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                        int is_bf16, int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C,
+                        int Dl, hipStream_t st);
+int subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                             int is_bf16, int64_t x_batch, int64_t ldx, const void *Y, int64_t y_batch, int64_t ldy, int B, int R,
+                             int C, int Dl);
 int csr_rowmask(const int32_t *rowptr, const int32_t *colidx, int B, int T, uint32_t *rowmask, hipStream_t st);
 int graph_operands(const uint32_t *rowmask, int B, int T, void *ops, hipStream_t st);
 int graph_edge_lists(const uint32_t *rowmask, int B, int T, void *lists, hipStream_t st);   // fused_wide8.hip

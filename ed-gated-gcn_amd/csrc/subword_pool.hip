@@ -10,6 +10,9 @@
 // pass (dX = A^T . dY) is the same launch with the two strides swapped.
 // XT = __bf16 (ggcn_subword_pool_bf16, x from BERT under bf16 autocast): X and Y in bf16, the sums in fp32, Y rounded to
 // nearest even once -- what torch.bmm gives under autocast.
+// ggcn_subword_pool_layers reads x where BERT left it: the 12 layer outputs of bert_amir5.py:596, before their `torch.cat`, each
+// pooled into its own 768 columns of Y by ONE launch -- the same compaction and the same two loop bodies, so a layer's columns
+// are bit for bit those of ggcn_subword_pool on that layer alone, and the 9216-wide copy is never made.
 #include "common.h"
 
 namespace ggcn {
@@ -31,72 +34,137 @@ __device__ __forceinline__ void store4(__bf16 *p, const float4 &v)
     *reinterpret_cast<bf16x4_t *>(p) = bf16x4_t{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
 }
 
-template <bool VEC, typename XT = float>
-__global__ __launch_bounds__(256) void subword_pool_kernel(const float *__restrict__ A, int64_t sa_b, int64_t sa_r,
-                                                          int64_t sa_c, const XT *__restrict__ X,
-                                                          int64_t x_batch, int64_t ldx, XT *__restrict__ Y,
-                                                          int64_t y_batch, int64_t ldy, int R, int C, int D)
+// What a workgroup keeps of its row of A: the non-zeros as (column, value) pairs, ascending column.
+struct alignas(16) RowLds {   // (16-byte aligned: the loops read four pairs with one ds_read_b128 each)
+    alignas(16) int idx[kMaxCols];
+    alignas(16) float val[kMaxCols];
+    int wave[4];
+    int total;
+};
+
+// Compact the non-zeros of the row `arow` (C columns, sa_c elements apart) into `s`, ascending column, 256 columns per round.
+// Called by all 256 threads; returns the number kept (the same in every thread, `s` is complete on return).
+__device__ __forceinline__ int compact_row(RowLds &s, const float *__restrict__ arow, int64_t sa_c, int C)
 {
-    __shared__ int s_idx[kMaxCols];
-    __shared__ float s_val[kMaxCols];
-    __shared__ int s_wave[4];
-    __shared__ int s_total;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x / R, r = blockIdx.x % R;
-    const float *arow = A + b * sa_b + r * sa_r;
-    if (tid == 0) s_total = 0;
+    if (tid == 0) s.total = 0;
     __syncthreads();
-    // ---- compact the non-zeros of row (b, r), ascending column, 256 columns per round ----
     for (int c0 = 0; c0 < C; c0 += 256) {
         const int c = c0 + tid;
         const float v = c < C ? arow[c * sa_c] : 0.0f;
         const bool nz = v != 0.0f;
         const unsigned long long m = __ballot(nz);
         const int before = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wave] = __popcll(m);
+        if (lane == 0) s.wave[wave] = __popcll(m);
         __syncthreads();
-        int off = s_total;
-        for (int w = 0; w < wave; ++w) off += s_wave[w];
+        int off = s.total;
+        for (int w = 0; w < wave; ++w) off += s.wave[w];
         if (nz) {
-            s_idx[off + before] = c;
-            s_val[off + before] = v;
+            s.idx[off + before] = c;
+            s.val[off + before] = v;
         }
         __syncthreads();
-        if (tid == 0) s_total += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        if (tid == 0) s.total += s.wave[0] + s.wave[1] + s.wave[2] + s.wave[3];
         __syncthreads();
     }
-    const int n = s_total;
+    return s.total;
+}
+
+// The two loop bodies: one thread, four adjacent features (vector form) or one (scalar form) of the n kept rows of xb,
+// from 0, one fmaf per kept entry in ascending column.
+template <typename XT>
+__device__ __forceinline__ float4 pooled4(const RowLds &s, int n, const XT *__restrict__ xb, int64_t ldx, int f)
+{
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int e = 0;
+    for (; e + 1 < n; e += 2) {  // two rows in flight
+        const float4 x0 = load4(xb + (int64_t)s.idx[e] * ldx + f);
+        const float4 x1 = load4(xb + (int64_t)s.idx[e + 1] * ldx + f);
+        const float v0 = s.val[e], v1 = s.val[e + 1];
+        acc.x = fmaf(v0, x0.x, acc.x); acc.y = fmaf(v0, x0.y, acc.y);
+        acc.z = fmaf(v0, x0.z, acc.z); acc.w = fmaf(v0, x0.w, acc.w);
+        acc.x = fmaf(v1, x1.x, acc.x); acc.y = fmaf(v1, x1.y, acc.y);
+        acc.z = fmaf(v1, x1.z, acc.z); acc.w = fmaf(v1, x1.w, acc.w);
+    }
+    if (e < n) {
+        const float4 x0 = load4(xb + (int64_t)s.idx[e] * ldx + f);
+        const float v0 = s.val[e];
+        acc.x = fmaf(v0, x0.x, acc.x); acc.y = fmaf(v0, x0.y, acc.y);
+        acc.z = fmaf(v0, x0.z, acc.z); acc.w = fmaf(v0, x0.w, acc.w);
+    }
+    return acc;
+}
+
+template <typename XT>
+__device__ __forceinline__ float pooled1(const RowLds &s, int n, const XT *__restrict__ xb, int64_t ldx, int f)
+{
+    float acc = 0.0f;
+    for (int e = 0; e < n; ++e) acc = fmaf(s.val[e], (float)xb[(int64_t)s.idx[e] * ldx + f], acc);
+    return acc;
+}
+
+template <bool VEC, typename XT = float>
+__global__ __launch_bounds__(256) void subword_pool_kernel(const float *__restrict__ A, int64_t sa_b, int64_t sa_r,
+                                                          int64_t sa_c, const XT *__restrict__ X,
+                                                          int64_t x_batch, int64_t ldx, XT *__restrict__ Y,
+                                                          int64_t y_batch, int64_t ldy, int R, int C, int D)
+{
+    __shared__ RowLds s;
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / R, r = blockIdx.x % R;
+    const int n = compact_row(s, A + b * sa_b + r * sa_r, sa_c, C);
     const XT *xb = X + b * x_batch;
     XT *yrow = Y + b * y_batch + (int64_t)r * ldy;
-    const int f = blockIdx.y * kSlab + tid * 4;
     if (VEC) {
+        const int f = blockIdx.y * kSlab + tid * 4;
         if (f >= D) return;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        int e = 0;
-        for (; e + 1 < n; e += 2) {  // two rows in flight
-            const float4 x0 = load4(xb + (int64_t)s_idx[e] * ldx + f);
-            const float4 x1 = load4(xb + (int64_t)s_idx[e + 1] * ldx + f);
-            const float v0 = s_val[e], v1 = s_val[e + 1];
-            acc.x = fmaf(v0, x0.x, acc.x); acc.y = fmaf(v0, x0.y, acc.y);
-            acc.z = fmaf(v0, x0.z, acc.z); acc.w = fmaf(v0, x0.w, acc.w);
-            acc.x = fmaf(v1, x1.x, acc.x); acc.y = fmaf(v1, x1.y, acc.y);
-            acc.z = fmaf(v1, x1.z, acc.z); acc.w = fmaf(v1, x1.w, acc.w);
-        }
-        if (e < n) {
-            const float4 x0 = load4(xb + (int64_t)s_idx[e] * ldx + f);
-            const float v0 = s_val[e];
-            acc.x = fmaf(v0, x0.x, acc.x); acc.y = fmaf(v0, x0.y, acc.y);
-            acc.z = fmaf(v0, x0.z, acc.z); acc.w = fmaf(v0, x0.w, acc.w);
-        }
-        store4(yrow + f, acc);
+        store4(yrow + f, pooled4(s, n, xb, ldx, f));
     } else {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int fq = blockIdx.y * kSlab + q * 256 + tid;  // coalesced scalar form
             if (fq >= D) continue;
-            float acc = 0.0f;
-            for (int e = 0; e < n; ++e) acc = fmaf(s_val[e], (float)xb[(int64_t)s_idx[e] * ldx + fq], acc);
-            yrow[fq] = (XT)acc;
+            yrow[fq] = (XT)pooled1(s, n, xb, ldx, fq);
+        }
+    }
+}
+
+// All layers of BERT in one launch (ggcn_subword_pool_layers): Y[b, r, l*Dl + f] = sum_c A[b,r,c] * X_l[b,c,f].  The layers'
+// base pointers travel in the kernel's argument block; nothing is written to device memory for them.
+struct LayerPtrs {
+    const void *p[GGCN_POOL_MAX_LAYERS];
+};
+
+constexpr int kUnit = 256;  // features per wavefront: 64 lanes x 4
+
+// One workgroup per (b, r, four units); a unit is 256 adjacent features of ONE layer, so a wavefront's layer is uniform and
+// at Dl = 768 (three units a layer) every lane of every wavefront has work.  units = ceil(Dl / 256), per layer.
+template <bool VEC, typename XT>
+__global__ __launch_bounds__(256) void subword_pool_layers_kernel(const float *__restrict__ A, int64_t sa_b, int64_t sa_r,
+                                                                 int64_t sa_c, const LayerPtrs layers, int n_layers,
+                                                                 int64_t x_batch, int64_t ldx, XT *__restrict__ Y,
+                                                                 int64_t y_batch, int64_t ldy, int R, int C, int Dl, int units)
+{
+    __shared__ RowLds s;
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x / R, r = blockIdx.x % R;
+    const int n = compact_row(s, A + b * sa_b + r * sa_r, sa_c, C);
+    const int u = __builtin_amdgcn_readfirstlane((int)(blockIdx.y * 4 + (threadIdx.x >> 6)));   // this wavefront's unit
+    const int l = u / units;
+    if (l >= n_layers) return;
+    const int f0 = (u - l * units) * kUnit;
+    const XT *xb = static_cast<const XT *>(layers.p[l]) + b * x_batch;
+    XT *yrow = Y + b * y_batch + (int64_t)r * ldy + (int64_t)l * Dl;
+    if (VEC) {
+        const int f = f0 + lane * 4;
+        if (f >= Dl) return;
+        store4(yrow + f, pooled4(s, n, xb, ldx, f));
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int fq = f0 + q * 64 + lane;  // coalesced scalar form
+            if (fq >= Dl) continue;
+            yrow[fq] = (XT)pooled1(s, n, xb, ldx, fq);
         }
     }
 }
@@ -146,6 +214,74 @@ int subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, 
         hipLaunchKernelGGL((subword_pool_kernel<false, __bf16>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, X, x_batch, ldx, Y,
                            y_batch, ldy, R, C, D);
     return check_launch("ggcn_subword_pool_bf16");
+}
+
+// 1 = vector form, 0 = scalar form, -ggcn_status (message set) where ggcn_subword_pool_layers refuses.  Host only: reads the
+// n_layers entries of `layers` and nothing behind any device pointer.  The launcher dispatches on this answer.
+int subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                             int is_bf16, int64_t x_batch, int64_t ldx, const void *Y, int64_t y_batch, int64_t ldy, int B, int R,
+                             int C, int Dl)
+{
+    const char *who = "ggcn_subword_pool_layers";
+    (void)sa_b; (void)sa_r; (void)sa_c;
+    if (!A || !layers || !Y) return -fail(GGCN_EINVAL, "%s: null pointer", who);
+    if (n_layers < 1) return -fail(GGCN_EINVAL, "%s: n_layers=%d must be positive", who, n_layers);
+    if (n_layers > GGCN_POOL_MAX_LAYERS)
+        return -fail(GGCN_EUNSUPPORTED, "%s: n_layers=%d > %d layers a launch (split the layers into groups of %d, each into its own columns of Y)",
+                     who, n_layers, GGCN_POOL_MAX_LAYERS, GGCN_POOL_MAX_LAYERS);
+    for (int l = 0; l < n_layers; ++l)
+        if (!layers[l]) return -fail(GGCN_EINVAL, "%s: layers[%d] is a null pointer", who, l);
+    if (B <= 0 || R <= 0 || C <= 0 || Dl <= 0)
+        return -fail(GGCN_EINVAL, "%s: B=%d R=%d C=%d Dl=%d must be positive", who, B, R, C, Dl);
+    if (C > kMaxCols) return -fail(GGCN_EUNSUPPORTED, "%s: C=%d > %d columns", who, C, kMaxCols);
+    if (ldx < Dl || ldy < (int64_t)n_layers * Dl) return -fail(GGCN_EINVAL, "%s: leading dimension too small", who);
+    if ((int64_t)B * R > (int64_t)INT32_MAX) return -fail(GGCN_EUNSUPPORTED, "%s: too many rows", who);
+    const uintptr_t elem = is_bf16 ? 2 : 4, wide = is_bf16 ? 8 : 16;   // (8-byte loads and stores of four bf16)
+    if (reinterpret_cast<uintptr_t>(A) % 4 || reinterpret_cast<uintptr_t>(Y) % elem)
+        return -fail(GGCN_EINVAL, "%s: A or Y not aligned to its element", who);
+    bool vec = (Dl % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (x_batch % 4 == 0) && (y_batch % 4 == 0) &&
+               (reinterpret_cast<uintptr_t>(Y) % wide == 0);
+    for (int l = 0; l < n_layers; ++l) {
+        if (reinterpret_cast<uintptr_t>(layers[l]) % elem)
+            return -fail(GGCN_EINVAL, "%s: layers[%d] not aligned to its element", who, l);
+        vec = vec && (reinterpret_cast<uintptr_t>(layers[l]) % wide == 0);
+    }
+    const int64_t units = ((int64_t)Dl + kUnit - 1) / kUnit;
+    if ((n_layers * units + 3) / 4 > 65535)
+        return -fail(GGCN_EUNSUPPORTED, "%s: n_layers=%d Dl=%d needs more than 65535 workgroups a row", who, n_layers, Dl);
+    return vec ? 1 : 0;
+}
+
+namespace {
+template <typename XT>
+void launch_layers(bool vec, const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const LayerPtrs &ptrs, int n_layers,
+                   int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int Dl, hipStream_t st)
+{
+    const int units = (Dl + kUnit - 1) / kUnit;
+    const dim3 grid((unsigned)(B * R), (unsigned)((n_layers * units + 3) / 4));
+    if (vec)
+        hipLaunchKernelGGL((subword_pool_layers_kernel<true, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
+                           x_batch, ldx, static_cast<XT *>(Y), y_batch, ldy, R, C, Dl, units);
+    else
+        hipLaunchKernelGGL((subword_pool_layers_kernel<false, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
+                           x_batch, ldx, static_cast<XT *>(Y), y_batch, ldy, R, C, Dl, units);
+}
+}  // namespace
+
+int subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                        int is_bf16, int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C,
+                        int Dl, hipStream_t st)
+{
+    const int form = subword_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, Y, y_batch, ldy, B, R,
+                                              C, Dl);
+    if (form < 0) return -form;
+    LayerPtrs ptrs = {};
+    for (int l = 0; l < n_layers; ++l) ptrs.p[l] = layers[l];
+    if (is_bf16)
+        launch_layers<__bf16>(form == 1, A, sa_b, sa_r, sa_c, ptrs, n_layers, x_batch, ldx, Y, y_batch, ldy, B, R, C, Dl, st);
+    else
+        launch_layers<float>(form == 1, A, sa_b, sa_r, sa_c, ptrs, n_layers, x_batch, ldx, Y, y_batch, ldy, B, R, C, Dl, st);
+    return check_launch("ggcn_subword_pool_layers");
 }
 
 }  // namespace ggcn

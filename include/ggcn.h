@@ -894,6 +894,28 @@ int ggcn_subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t s
                            const void *X, int64_t x_batch, int64_t ldx,
                            void *Y, int64_t y_batch, int64_t ldy,
                            int B, int R, int C, int D, ggcn_stream_t stream);
+/* The same straight from BERT's layer list (bert_amir5.py:596 concatenates the 12 layer outputs only to pool them at :600):
+ *   Y[b, r, l*Dl + f] = sum_c A[b,r,c] * X_l[b,c,f],  l = 0..n_layers-1, ONE launch, no concatenated copy of x.
+ * layers: a HOST array of n_layers device pointers (read during the call, passed to the kernel by value in its argument
+ * block: capture-safe); every layer is [B,C,Dl] with the SAME x_batch and ldx (elements), float32 or, with is_bf16 != 0,
+ * bfloat16 (then Y is bfloat16 too: fp32 sums, one RNE in the store).  A, its element strides, C <= 2048, "non-zeros only,
+ * ascending c": as ggcn_subword_pool.  Layer l's columns of Y are bit for bit what ggcn_subword_pool / _bf16 write for
+ * that layer alone (D = Dl, Y + l*Dl).  Y row r of batch b starts at Y + b*y_batch + r*ldy, ldy >= n_layers*Dl.
+ * The vector form is taken when Dl, ldx, ldy, x_batch and y_batch are multiples of 4 and Y and every layer pointer are
+ * aligned to 16 bytes (8 for bfloat16); otherwise the whole launch takes the scalar form (same bits).
+ * GGCN_EINVAL: a NULL A, layers, Y or layers[l]; n_layers < 1; B, R, C or Dl <= 0; ldx < Dl; ldy < n_layers*Dl; a pointer
+ * not aligned to its element.  GGCN_EUNSUPPORTED: n_layers > GGCN_POOL_MAX_LAYERS (split the layers into groups, each into
+ * its own columns of Y); C > 2048; B*R > INT32_MAX; a grid dimension past 65535.  All before any launch. */
+#define GGCN_POOL_MAX_LAYERS 16
+int ggcn_subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
+                             const void *const *layers, int n_layers, int is_bf16, int64_t x_batch, int64_t ldx,
+                             void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int Dl, ggcn_stream_t stream);
+/* host-only: 1 = vector form, 0 = scalar form, -ggcn_status where the entry would refuse (ggcn_last_error names
+ * ggcn_subword_pool_layers); launches nothing and dereferences nothing on the device.  The launcher dispatches on the
+ * function that answers here. */
+int ggcn_subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
+                                  const void *const *layers, int n_layers, int is_bf16, int64_t x_batch, int64_t ldx,
+                                  const void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int Dl);
 
 /* ---- bfloat16 features (training and inference under torch.autocast(dtype=torch.bfloat16)) ----------------------
  * X (the layer's input) in bfloat16; weights, bias, gates, `out`, pools and dW stay float32, dX is bfloat16 -- the
