@@ -29,6 +29,7 @@ from . import dispatch
 from .gated_block import gated_gcn_block, takes_block_path
 from .gcn import GraphConvolution
 from .heads import gate_mlps, scores_and_kl
+from .hostops import _opted_in, cached
 from .pooling import subword_pool, subword_pool_layers
 from .recurrent import bilstm, bilstm_train, takes_hip_lstm, takes_hip_lstm_train, lstm_wants_grad
 
@@ -90,27 +91,22 @@ class GatedGCNEventDetector(nn.Module):
         # training: the scores / kl head (:645-648) as the differentiable ``scores_and_kl`` (one forward launch pair, one backward
         # launch + the weight product) instead of the reference's PyTorch ops.  Off by default: its sums differ from those ops'
         # in the last bits (both inside the gradient gate).
-        self.head_backward = (bool(getattr(opt, "ggcn_head_backward", False))
-                              or os.environ.get("GGCN_HEAD_BACKWARD", "0") == "1")
+        self.head_backward = _opted_in(opt, "head_backward")
         # training: the gate MLPs (:562-571) as the differentiable ``gate_mlps`` (the saving forward launch, one backward launch
         # + the fixed-order weight products) instead of the two nn.Sequential.  Off by default, for the same reason.
-        self.gate_backward = (bool(getattr(opt, "ggcn_gate_backward", False))
-                              or os.environ.get("GGCN_GATE_BACKWARD", "0") == "1")
+        self.gate_backward = _opted_in(opt, "gate_backward")
         # inference: the BiLSTM (:610) as ``bilstm`` (one bf16x3 projection, one recurrence launch) where ``takes_hip_lstm`` holds --
         # float32 features and no gradient wanted; training and bf16 autocast keep nn.LSTM.  Off by default: the projection's
         # bf16x3 sums differ from the fp32 GEMM's in the last bits (both inside the forward gate).
-        self.hip_lstm = (bool(getattr(opt, "ggcn_hip_lstm", False))
-                         or os.environ.get("GGCN_HIP_LSTM", "0") == "1")
+        self.hip_lstm = _opted_in(opt, "hip_lstm")
         # training: the BiLSTM (:610) as the differentiable ``bilstm_train`` (the projection, the saving recurrence launch, one
         # backward launch + the fixed-order weight products) where a gradient is wanted and ``takes_hip_lstm_train`` holds;
         # bf16 autocast and the CPU keep nn.LSTM.  Independent of ``hip_lstm``; off by default, for the same reason.
-        self.hip_lstm_backward = (bool(getattr(opt, "ggcn_hip_lstm_backward", False))
-                                  or os.environ.get("GGCN_HIP_LSTM_BACKWARD", "0") == "1")
+        self.hip_lstm_backward = _opted_in(opt, "hip_lstm_backward")
         # the sub-word pooling (:600) straight from BERT's list of layer outputs: ``subword_pool_layers`` pools every layer into its
         # own columns in one launch instead of ``torch.cat`` (:596, a full [B,L,9216] copy) + ``subword_pool``.  Same bits, forward
         # and backward, float32 and bf16; taken where the layers are a list or tuple of GPU tensors.  Off by default.
-        self.pool_layers = (bool(getattr(opt, "ggcn_pool_layers", False))
-                            or os.environ.get("GGCN_POOL_LAYERS", "0") == "1")
+        self.pool_layers = _opted_in(opt, "pool_layers")
 
     def _training_gates(self, aspect):
         """``gate1(aspect), gate2(aspect)`` of the training branches: the two nn.Sequential (under bf16 autocast they give bf16)
@@ -149,18 +145,18 @@ class GatedGCNEventDetector(nn.Module):
         key = tuple(None if q is None else (q.data_ptr(), tensor_version(q)) for q in ps)
         if any(k is not None and k[1] is None for k in key):
             return "bf16x3"
-        if self._proved is None or self._proved[0] != key:
-            with torch.no_grad():
-                w1, w2 = self.gc1.weight.detach().float(), self.gc2.weight.detach().float()
-                b1 = torch.zeros_like(w1[0]) if self.gc1.bias is None else self.gc1.bias.detach().float()
-                c1 = w1.abs().sum(0)
-                m1 = (c1 + b1.abs()).max()
-                w12 = w1 @ w2
-                bound = torch.stack([m1.new_tensor(1.0), m1, m1 * w2.abs().sum(0).max(),
-                                     (w12.abs().sum(0) + (b1 @ w2).abs()).max()]).max()
-                ok = bool(torch.isfinite(bound)) and float(bound) < self.F16_RANGE_MARGIN
-            self._proved = (key, ok, float(m1))
-        _, ok, m1 = self._proved
+
+        @torch.no_grad()
+        def prove():
+            w1, w2 = self.gc1.weight.detach().float(), self.gc2.weight.detach().float()
+            b1 = torch.zeros_like(w1[0]) if self.gc1.bias is None else self.gc1.bias.detach().float()
+            c1 = w1.abs().sum(0)
+            m1 = (c1 + b1.abs()).max()
+            w12 = w1 @ w2
+            bound = torch.stack([m1.new_tensor(1.0), m1, m1 * w2.abs().sum(0).max(),
+                                 (w12.abs().sum(0) + (b1 @ w2).abs()).max()]).max()
+            return bool(torch.isfinite(bound)) and float(bound) < self.F16_RANGE_MARGIN, float(m1)
+        ok, m1 = cached(self, "_proved", key, prove)   # (its own key: no device in it, and never one without a version -- above)
         if ok and not (m1 <= self.F16MX8_WINDOW):
             # gcn1 may leave the window: fine only where no main loop ever splits it -- the one-launch block, which runs only
             # without autograd (gated_gcn_block takes two launches when a gradient is wanted: gc2's main loop splits gcn1)

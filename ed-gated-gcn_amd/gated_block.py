@@ -18,8 +18,8 @@ launch that also applies the gate and the max over tokens.
 """
 import torch
 
-from . import _capi, dispatch, range_guard
-from .csr import BatchedCSR, tensor_version
+from . import _capi, dispatch, hostops, range_guard
+from .csr import BatchedCSR
 from .dispatch import (takes_bf16_block_path, takes_bf16_folded_eval_path, takes_block_path, takes_folded_eval_path,  # noqa: F401
                        takes_weighted_block_path)
 from .gcn import _require_gate, _rows2d
@@ -51,14 +51,8 @@ def _block_operands(gc1, gc2, lib, st, precision=None):
     linear (a k-ordered fp32 FMA chain): they are parameters folded once per weight update, not activations."""
     w1, w2, b1 = gc1.weight, gc2.weight, gc1.bias
     precision = precision or gc1.precision
-    prec = _capi.PREC[precision]
-    key = (w1.data_ptr(), tensor_version(w1), w2.data_ptr(), tensor_version(w2), None if b1 is None else (b1.data_ptr(), tensor_version(b1)),
-           w1.device, prec)
-    store = getattr(gc2, "_block_ops", None)
-    if not isinstance(store, dict):
-        store = gc2._block_ops = {}   # one entry per precision (like _packed_weight): an eval / train switch of the classifier folds nothing again
-    cached = store.get(prec)
-    if cached is None or cached[0] != key:
+
+    def fold():
         K, F1, F2 = gc1.in_features, gc1.out_features, gc2.out_features
         dev = w1.device
         w1c, w2c = w1.detach().contiguous(), w2.detach().contiguous()
@@ -70,11 +64,11 @@ def _block_operands(gc1, gc2, lib, st, precision=None):
             b1c = b1.detach().contiguous()
             _capi.check(lib.ggcn_linear(_capi.ptr(b1c), F1, _capi.ptr(w2c), F2, None, _capi.ptr(mid), F2, 1, F1, F2,
                                         _capi.PREC["fp32"], st), "ggcn_linear(b1.W2)")
-        pack12 = torch.empty(lib.ggcn_weight_pack_bytes(K, F2, prec), dtype=torch.uint8, device=dev)
-        _capi.check(lib.ggcn_weight_pack(_capi.ptr(w12), F2, K, F2, prec, 0, _capi.ptr(pack12), st), "ggcn_weight_pack(W12)")
-        cached = (key, pack12, mid)
-        store[prec] = cached
-    return gc1._packed_weight(lib, st, precision=precision), cached[1], cached[2]
+        return hostops.weight_pack(lib, st, w12, F2, K, F2, precision, False, tag="(W12)"), mid
+
+    # one entry per precision (like _packed_weight): an eval / train switch of the classifier folds nothing again
+    pack12, mid = hostops.cached(gc2, "_block_ops", hostops.param_key(w1, w2, b1), fold, slot=_capi.PREC[precision])
+    return gc1._packed_weight(lib, st, precision=precision), pack12, mid
 
 
 def _folded_eval(x, csr, gate2, gc1, gc2, want_x):

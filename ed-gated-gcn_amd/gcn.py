@@ -17,8 +17,9 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _capi, dispatch, range_guard
-from .csr import BatchedCSR, cached_from_dense, tensor_version
+from . import _capi, dispatch, hostops, range_guard
+from .csr import BatchedCSR, cached_from_dense
+from .hostops import _opted_in, f32_rows
 from .dispatch import BF16_PRECISIONS  # noqa: F401  (its home is dispatch.py; imported from here too)
 
 
@@ -111,11 +112,6 @@ _BACKWARD_LAUNCHES = {
 }
 
 
-def _opted_in(opt, name):
-    """A boolean opt-in: on when ``opt.ggcn_<name>`` is true or the environment has ``GGCN_<NAME>=1``."""
-    return bool(getattr(opt, "ggcn_" + name, False)) or os.environ.get("GGCN_" + name.upper(), "0") == "1"
-
-
 class _GatedLayerFunction(torch.autograd.Function):
     """One gated layer under autograd (``train.py:115-121`` trains through gc1/gc2 and the gates).
 
@@ -161,14 +157,7 @@ class _GatedLayerFunction(torch.autograd.Function):
             return (None,) * 12
         lib = _capi.load_library()
         (B, T, K), F, dev = text.shape, layer.out_features, text.device
-
-        def f32c(t, shape):
-            if t is None:
-                return None
-            t = t.reshape(shape)
-            return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-        d_out2, d_pa, d_pb = f32c(d_out, (B * T, F)), f32c(d_pa, (B, F)), f32c(d_pb, (B, F))
+        d_out2, d_pa, d_pb = f32_rows(d_out, (B * T, F)), f32_rows(d_pa, (B, F)), f32_rows(d_pb, (B, F))
         out2 = out.reshape(-1, F)
         ptr = _capi.ptr
         with torch.cuda.device(dev):
@@ -206,45 +195,31 @@ class _GatedLayerFunction(torch.autograd.Function):
                 if ctx.adj_dtype != torch.float32:
                     d_adj = d_adj.to(ctx.adj_dtype)
             dx = dw = db = None
-            if dx_form is not None:
-                dx = torch.empty(B * T, K, dtype=torch.bfloat16 if dx_form == "bf16" else torch.float32, device=dev)
-                if dx_form == "bf16":   # bfloat16 features: dX in bf16 (the reference's gradient dtype under autocast), rounded in the store
-                    pack_t = layer._packed_weight(lib, st, transposed=True)
-                    _capi.check(lib.ggcn_linear_out_bf16(ptr(dh), F, ptr(pack_t), ptr(dx), K, B * T, F, K, st), "ggcn_linear_out_bf16(dX)")
-                elif dx_form == "scaled":
+            if dx_form in ("bf16", "bf16x3"):
+                # gradients can be far below fp16's range (f16mx8 would flush them): dX takes the bf16x3 linear, which keeps the fp32
+                # exponent range; bfloat16 features: dX in bf16 (the reference's gradient dtype under autocast), rounded in the store
+                dx = hostops.linear_packed(lib, st, dh, F, layer._packed_weight(lib, st, transposed=True), B * T, F, K,
+                                           out_dtype=torch.bfloat16 if dx_form == "bf16" else torch.float32, tag="(dX)").view(B, T, K)
+            elif dx_form is not None:
+                dx = torch.empty(B, T, K, **f32)
+                if dx_form == "scaled":
                     pack_t = layer._packed_weight(lib, st, transposed=True, precision="f16mx8")
                     _capi.check(lib.ggcn_linear_scaled(ptr(dh), F, ptr(pack_t), ptr(dx), K, B * T, F, K, ptr(dh_amax), st),
                                 "ggcn_linear_scaled(dX)")
-                elif dx_form == "bf16x3":
-                    # gradients can be far below fp16's range (f16mx8 would flush them): dX always takes
-                    # the bf16x3 linear, which keeps the fp32 exponent range
-                    pack_t = layer._packed_weight(lib, st, transposed=True)
-                    _capi.check(lib.ggcn_linear(ptr(dh), F, None, 0, ptr(pack_t), ptr(dx), K, B * T, F, K, _capi.PREC["bf16x3"], st),
-                                "ggcn_linear(dX)")
                 else:   # exact-fp32 mode: W^T as a plain matrix, transposed once per weight update
-                    key = (weight.data_ptr(), tensor_version(weight), weight.device)
-                    if getattr(layer, "_wt_key", None) != key:
-                        layer._wt, layer._wt_key = weight.detach().t().contiguous(), key
-                    _capi.check(lib.ggcn_linear(ptr(dh), F, ptr(layer._wt), K, None, ptr(dx), K, B * T, F, K, _capi.PREC["fp32"], st),
+                    wt = hostops.cached(layer, "_wt", hostops.param_key(weight), lambda: weight.detach().t().contiguous())
+                    _capi.check(lib.ggcn_linear(ptr(dh), F, ptr(wt), K, None, ptr(dx), K, B * T, F, K, _capi.PREC["fp32"], st),
                                 "ggcn_linear(dX)")
-                dx = dx.view(B, T, K)
             if need[1]:
                 x2d = _rows2d(text)
-                dw = torch.empty(K, F, **f32)
                 if dw_form == "bf16":
-                    ws = torch.empty(lib.ggcn_dweight_bf16_workspace_bytes(B * T, K, F), dtype=torch.uint8, device=dev)
-                    _capi.check(lib.ggcn_dweight_bf16(ptr(x2d), x2d.stride(0), ptr(dh), F, B * T, K, F, ptr(dw), F, ptr(ws), st),
-                                "ggcn_dweight_bf16")
+                    dw = hostops.dweight_bf16(lib, st, x2d, x2d.stride(0), dh, F, B * T, K, F)
                 else:
                     # split-precision layers: bf16x3 on the forward's main loop (fp32 exponent range, ~1e-5);
                     # precision "fp32": the exact fp32 MFMA form, which wants 16-byte aligned rows
-                    ws = torch.empty(lib.ggcn_dweight_workspace_bytes(B * T, K, F, _capi.PREC[dw_form]), dtype=torch.uint8, device=dev)
-                    _capi.check(lib.ggcn_dweight(ptr(x2d), x2d.stride(0), ptr(dh), F, B * T, K, F, ptr(dw), F, _capi.PREC[dw_form],
-                                                 ptr(ws), st), "ggcn_dweight")
+                    dw = hostops.dweight(lib, st, x2d, x2d.stride(0), dh, F, B * T, K, F, dw_form)
             if d_bsum is not None:   # db = sum_rows dY: per-graph sums from the pass above, added over the graphs
-                db = torch.empty(F, **f32)
-                ws = torch.empty(lib.ggcn_colsum_workspace_bytes(F), dtype=torch.uint8, device=dev)
-                _capi.check(lib.ggcn_colsum(ptr(d_bsum), F, B, F, ptr(db), ptr(ws), st), "ggcn_colsum")
+                db = hostops.colsum(lib, st, d_bsum, F, B, F)
         return dx, dw, db, d_sg, d_ga, d_gb, None, None, None, None, None, d_adj
 
 
@@ -290,8 +265,6 @@ class GraphConvolution(nn.Module):
         # read-back per conversion), True = promise 0/1 entries like the reference's (graph.py:66-74)
         # and stay sync-free, False = always keep the values
         self.binary_adj = getattr(opt, "ggcn_binary_adj", None)
-        self._pack = None
-        self._pack_key = None
 
     def extra_repr(self):
         return "in_features=%d, out_features=%d, bias=%s, precision=%s" % (
@@ -306,21 +279,9 @@ class GraphConvolution(nn.Module):
         # the transposed image serves the backward's dX linear: bf16x3 (full range) unless the caller names f16mx8 (the scaled form)
         name = precision or (self.precision if not transposed else "bf16x3")
         name = name if (name in _capi.PACKED and (not transposed or name == "f16mx8")) else "bf16x3"
-        prec = _capi.PREC[name]
-        key = (w.data_ptr(), tensor_version(w), w.device)
-        slot = (name, bool(transposed))
-        if not isinstance(self._pack, dict):
-            self._pack, self._pack_key = {}, {}
-        if self._pack.get(slot) is None or self._pack_key.get(slot) != key:
-            K, F = (self.out_features, self.in_features) if transposed else (self.in_features, self.out_features)
-            pack = torch.empty(lib.ggcn_weight_pack_bytes(K, F, prec), dtype=torch.uint8, device=w.device)
-            wc = w.detach()
-            if not wc.is_contiguous():
-                wc = wc.contiguous()
-            _capi.check(lib.ggcn_weight_pack(_capi.ptr(wc), self.out_features, K, F, prec, 1 if transposed else 0,
-                                             _capi.ptr(pack), stream), "ggcn_weight_pack")
-            self._pack[slot], self._pack_key[slot] = pack, key
-        return self._pack[slot]
+        K, F = (self.out_features, self.in_features) if transposed else (self.in_features, self.out_features)
+        return hostops.cached(self, "_pack", hostops.param_key(w), slot=(name, bool(transposed)), build=lambda: hostops.weight_pack(
+            lib, stream, w.detach().contiguous(), self.out_features, K, F, name, transposed))
 
     def kernel_precision(self, x2d=None, csr=None):
         """The arithmetic a launch really uses: "f16mx6" is taken by the one-launch layer / block for graphs of <= 32

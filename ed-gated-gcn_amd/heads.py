@@ -15,26 +15,21 @@ classifier takes them in training with ``opt.ggcn_head_backward`` / ``GGCN_HEAD_
 """
 import torch
 
-from . import _capi
-from .csr import tensor_version
+from . import _capi, hostops
 from .gcn import _rows2d
 
 
 def _transposed(linear, lib, st):
     """[in,out] copy of an nn.Linear weight, rebuilt when the weight changes."""
     w = linear.weight
-    key = (w.data_ptr(), tensor_version(w), w.device)
-    cached = getattr(linear, "_ggcn_wt", None)
-    if cached is None or cached[0] != key:
-        wc = w.detach()
-        if not wc.is_contiguous():
-            wc = wc.contiguous()
+
+    def build():
+        wc = w.detach().contiguous()
         wt = torch.empty(wc.shape[1], wc.shape[0], dtype=torch.float32, device=w.device)
         _capi.check(lib.ggcn_transpose(_capi.ptr(wc), wc.shape[0], wc.shape[1], wc.stride(0), _capi.ptr(wt), st),
                     "ggcn_transpose")
-        cached = (key, wt)
-        linear._ggcn_wt = cached
-    return cached[1]
+        return wt
+    return hostops.cached(linear, "_ggcn_wt", hostops.param_key(w), build)
 
 
 def _gate_linears(seq):
@@ -92,11 +87,10 @@ class _GateMlps(torch.autograd.Function):
         need = [n and (i % 2 == 0 or ctx.has_bias[i // 2]) for i, n in enumerate(need)]
         if not need_a and not any(need):
             return none
-        dg1, dg2 = (None if g is None else g.float().contiguous() for g in (dg1, dg2))
+        dg1, dg2 = hostops.f32_rows(dg1), hostops.f32_rows(dg2)
         lib = _capi.load_library()
         dev = a.device
         ptr = _capi.ptr
-        fp32 = _capi.PREC["fp32"]
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
             new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)   # noqa: E731
@@ -109,11 +103,7 @@ class _GateMlps(torch.autograd.Function):
 
             def product(x_col, K, other, ld_other):
                 """``Z[:, x_col : x_col + K]^T . other`` -> ``[K, H]``, rows = the Linear's outputs: nn.Linear's layout."""
-                dw = new(K, H)
-                ws = torch.empty(max(16, lib.ggcn_dweight_workspace_bytes(B, K, H, fp32)), dtype=torch.uint8, device=dev)
-                _capi.check(lib.ggcn_dweight(ptr(Z[:, x_col:]), ldz, ptr(other), ld_other, B, K, H, ptr(dw), H, fp32, ptr(ws), st),
-                            "ggcn_dweight")
-                return dw
+                return hostops.dweight(lib, st, Z[:, x_col:], ldz, other, ld_other, B, K, H, "fp32")
 
             grads = [None] * 8
             s = Z[:, 4 * Hp:] if Z is not None else None
@@ -128,9 +118,7 @@ class _GateMlps(torch.autograd.Function):
                 if need[4 * g + 2]:
                     grads[4 * g + 2] = product((2 + g) * Hp, H, hid, H)
             if need[1] or need[3] or need[5] or need[7]:
-                db = new(4 * Hp)
-                ws = torch.empty(lib.ggcn_colsum_workspace_bytes(4 * Hp), dtype=torch.uint8, device=dev)
-                _capi.check(lib.ggcn_colsum(ptr(Z), ldz, B, 4 * Hp, ptr(db), ptr(ws), st), "ggcn_colsum")
+                db = hostops.colsum(lib, st, Z, ldz, B, 4 * Hp)
                 for i, group in ((1, 0), (3, 2), (5, 1), (7, 3)):    # Z's groups: dz1_A | dz1_B | dz2_A | dz2_B
                     if need[i]:
                         grads[i] = db[group * Hp:group * Hp + H]
@@ -233,8 +221,7 @@ class _ScoresAndKl(torch.autograd.Function):
         need_b = need_b and bias is not None
         if g_scores is None and g_kl is None:
             return None, None, None, None, None, None
-        g_scores = None if g_scores is None else g_scores.float().contiguous()
-        g_kl = None if g_kl is None else g_kl.float().contiguous()
+        g_scores, g_kl = hostops.f32_rows(g_scores), hostops.f32_rows(g_kl)
         lib = _capi.load_library()
         dev = x2.device
         ptr = _capi.ptr

@@ -21,8 +21,7 @@ library's fixed-order products: ``ggcn_dweight`` for ``[W_ih_f ; W_ih_r]`` and t
 """
 import torch
 
-from . import _capi
-from .csr import tensor_version
+from . import _capi, hostops
 from .gcn import _rows2d
 
 HIDDEN = 128                    # the kernel's hd (the reference hard-codes hidden_dim = 128, bert_amir5.py:551)
@@ -74,20 +73,16 @@ def takes_hip_lstm(x, lstm):
 def _operands(lstm, lib, st):
     """``(pack of [W_ih_f ; W_ih_r], W_hh_f, W_hh_r, bias_f, bias_r)`` cached on the module, rebuilt when a parameter changes."""
     ps = _params(lstm)
-    key = tuple(None if p is None else (p.data_ptr(), tensor_version(p), p.device) for p in ps)
-    cached = getattr(lstm, "_ggcn_lstm", None)
-    if cached is None or cached[0] != key:
+
+    def build():
         wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r = (None if p is None else p.detach() for p in ps)
         I = lstm.input_size
-        prec = _capi.PREC["bf16x3"]
         wcat = torch.cat([wih_f, wih_r], dim=0).contiguous()                     # [8 hd, I]: the [F,K] matrix of transposed=1
-        pack = torch.empty(lib.ggcn_weight_pack_bytes(I, 8 * HIDDEN, prec), dtype=torch.uint8, device=wcat.device)
-        _capi.check(lib.ggcn_weight_pack(_capi.ptr(wcat), I, I, 8 * HIDDEN, prec, 1, _capi.ptr(pack), st), "ggcn_weight_pack")
+        pack = hostops.weight_pack(lib, st, wcat, I, I, 8 * HIDDEN, "bf16x3", True)
         bias_f = None if bih_f is None else (bih_f + bhh_f).contiguous()
         bias_r = None if bih_r is None else (bih_r + bhh_r).contiguous()
-        cached = (key, (pack, whh_f.contiguous(), whh_r.contiguous(), bias_f, bias_r))
-        lstm._ggcn_lstm = cached
-    return cached[1]
+        return pack, whh_f.contiguous(), whh_r.contiguous(), bias_f, bias_r
+    return hostops.cached(lstm, "_ggcn_lstm", hostops.param_key(*ps), build)
 
 
 def _check(x, lstm, forward_only):
@@ -126,9 +121,7 @@ def bilstm(x, lstm):
     with torch.cuda.device(dev):
         st = _capi.stream_of(dev)
         pack, whh_f, whh_r, bias_f, bias_r = _operands(lstm, lib, st)
-        g = torch.empty(B * T, 8 * HIDDEN, dtype=torch.float32, device=dev)
-        _capi.check(lib.ggcn_linear(_capi.ptr(x2), x2.stride(0), None, 0, _capi.ptr(pack), _capi.ptr(g), 8 * HIDDEN, B * T, I, 8 * HIDDEN,
-                                    _capi.PREC["bf16x3"], st), "ggcn_linear")
+        g = hostops.linear_packed(lib, st, x2, x2.stride(0), pack, B * T, I, 8 * HIDDEN)
         _capi.check(lib.ggcn_bilstm_recurrence(_capi.ptr(g), 8 * HIDDEN, _capi.ptr(whh_f), _capi.ptr(whh_r), _capi.ptr(bias_f),
                                                _capi.ptr(bias_r), _capi.ptr(y), 2 * HIDDEN, B, T, HIDDEN, st), "ggcn_bilstm_recurrence")
     return y
@@ -139,17 +132,9 @@ def _dx_operand(lstm, lib, st):
     operand of ``dX = dG . [W_ih_f ; W_ih_r]``.  Cached on the module under ``_operands``' key, built only when ``x`` wants a
     gradient."""
     ps = _params(lstm)
-    key = tuple(None if p is None else (p.data_ptr(), tensor_version(p), p.device) for p in ps)
-    cached = getattr(lstm, "_ggcn_lstm_dx", None)
-    if cached is None or cached[0] != key:
-        I = lstm.input_size
-        prec = _capi.PREC["bf16x3"]
-        wcat = torch.cat([ps[0].detach(), ps[4].detach()], dim=0).contiguous()
-        pack = torch.empty(lib.ggcn_weight_pack_bytes(8 * HIDDEN, I, prec), dtype=torch.uint8, device=wcat.device)
-        _capi.check(lib.ggcn_weight_pack(_capi.ptr(wcat), I, 8 * HIDDEN, I, prec, 0, _capi.ptr(pack), st), "ggcn_weight_pack")
-        cached = (key, pack)
-        lstm._ggcn_lstm_dx = cached
-    return cached[1]
+    I = lstm.input_size
+    return hostops.cached(lstm, "_ggcn_lstm_dx", hostops.param_key(*ps), lambda: hostops.weight_pack(
+        lib, st, torch.cat([ps[0].detach(), ps[4].detach()], dim=0).contiguous(), I, 8 * HIDDEN, I, "bf16x3", False))
 
 
 class _BilstmTrain(torch.autograd.Function):
@@ -171,11 +156,9 @@ class _BilstmTrain(torch.autograd.Function):
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
             pack, whh_f, whh_r, bias_f, bias_r = _operands(lstm, lib, st)
-            g = torch.empty(B * T, 8 * HIDDEN, dtype=torch.float32, device=dev)
+            g = hostops.linear_packed(lib, st, x2, x2.stride(0), pack, B * T, I, 8 * HIDDEN)
             c = torch.empty(B * T, 2 * HIDDEN, dtype=torch.float32, device=dev)
             hprev = torch.empty(B * T, 2 * HIDDEN, dtype=torch.float32, device=dev)
-            _capi.check(lib.ggcn_linear(ptr(x2), x2.stride(0), None, 0, ptr(pack), ptr(g), 8 * HIDDEN, B * T, I, 8 * HIDDEN,
-                                        _capi.PREC["bf16x3"], st), "ggcn_linear")
             _capi.check(lib.ggcn_bilstm_recurrence_save(ptr(g), 8 * HIDDEN, ptr(whh_f), ptr(whh_r), ptr(bias_f), ptr(bias_r), ptr(y),
                                                         2 * HIDDEN, B, T, HIDDEN, ptr(g), ptr(c), ptr(hprev), st),
                         "ggcn_bilstm_recurrence_save")
@@ -201,10 +184,9 @@ class _BilstmTrain(torch.autograd.Function):
         ptr = _capi.ptr
         dev = g.device
         rows, W = B * T, 8 * HIDDEN
-        bx3 = _capi.PREC["bf16x3"]
         # the entry takes rows with a leading dimension, no batch stride: an expanded or strided dY (a loss's gradient is often an
         # expanded scalar) is copied to [B*T, 2 hd] here, a contiguous one is handed over as it lies
-        dy2 = dy.float().contiguous().view(rows, 2 * HIDDEN)
+        dy2 = hostops.f32_rows(dy, (rows, 2 * HIDDEN))
         grads = [None] * 8
         with torch.cuda.device(dev):
             st = _capi.stream_of(dev)
@@ -214,10 +196,7 @@ class _BilstmTrain(torch.autograd.Function):
                                                             ptr(dg), W, B, T, HIDDEN, st), "ggcn_bilstm_recurrence_backward")
 
             def product(xcols, K, dh, ldh, F):        # dW [K,F] = dG[:, xcols:xcols+K]^T . dh
-                dw = new(K, F)
-                ws = torch.empty(max(16, lib.ggcn_dweight_workspace_bytes(rows, K, F, bx3)), dtype=torch.uint8, device=dev)
-                _capi.check(lib.ggcn_dweight(ptr(dg[:, xcols:]), W, ptr(dh), ldh, rows, K, F, ptr(dw), F, bx3, ptr(ws), st), "ggcn_dweight")
-                return dw
+                return hostops.dweight(lib, st, dg[:, xcols:], W, dh, ldh, rows, K, F, "bf16x3")
 
             if need[0] or need[4]:                    # d[W_ih_f ; W_ih_r], already in nn.LSTM layout
                 dwih = product(0, W, x2, x2.stride(0), I)
@@ -229,17 +208,13 @@ class _BilstmTrain(torch.autograd.Function):
                 if need[4 * d + 1]:                   # dW_hh_d = da_d^T . Hprev_d
                     grads[4 * d + 1] = product(d * 4 * HIDDEN, 4 * HIDDEN, hprev[:, d * HIDDEN:], 2 * HIDDEN, HIDDEN)
             if any(need[i] for i in (2, 3, 6, 7)):    # both biases of a direction receive the column sums of its da
-                db = new(W)
-                ws = torch.empty(max(16, lib.ggcn_colsum_workspace_bytes(W)), dtype=torch.uint8, device=dev)
-                _capi.check(lib.ggcn_colsum(ptr(dg), W, rows, W, ptr(db), ptr(ws), st), "ggcn_colsum")
+                db = hostops.colsum(lib, st, dg, W, rows, W)
                 for i in (2, 3, 6, 7):                # a copy each: b_ih.grad and b_hh.grad must not share memory (autograd
                     if need[i]:                       # accumulates and optimizers clip in place)
                         grads[i] = (db[:W // 2] if i < 4 else db[W // 2:]).clone()
             dx = None
             if need_x:                                # dX = dG . [W_ih_f ; W_ih_r]
-                dx = new(B, T, I)
-                _capi.check(lib.ggcn_linear(ptr(dg), W, None, 0, ptr(_dx_operand(lstm, lib, st)), ptr(dx), I, rows, W, I, bx3, st),
-                            "ggcn_linear")
+                dx = hostops.linear_packed(lib, st, dg, W, _dx_operand(lstm, lib, st), rows, W, I).view(B, T, I)
         return (dx, None, *grads)
 
 

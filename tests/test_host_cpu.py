@@ -51,6 +51,48 @@ def test_binding_covers_every_declared_symbol_and_abi_matches():
     assert lib.ggcn_overlap_workspace_bytes(4096) == 4096 * 4
 
 
+CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
+
+
+def _ctype(decl, name):
+    """The ctypes type of one parameter (or result) declaration of include/ggcn.h; a type this table does not know fails."""
+    if "*" in decl or re.search(r"\bggcn_stream_t\b", decl):
+        return ctypes.c_void_p
+    words = [w for w in re.findall(r"\w+", decl) if w not in ("const", "unsigned", "signed")]
+    assert words and words[0] in CTYPE_OF, "%s: no ctypes type known for %r" % (name, decl.strip())
+    return CTYPE_OF[words[0]]
+
+
+def _declared_prototypes():
+    """{name: (result declaration, [parameter declarations])} of every ``ret name(args);`` of the header, comments stripped."""
+    src = open(os.path.join(ROOT, "include", "ggcn.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    protos = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(ggcn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in protos, "%s is declared twice" % name
+        args = args.strip()
+        protos[name] = (ret, [] if args in ("", "void") else args.split(","))
+    return protos
+
+
+def test_binding_argument_types_match_the_header():
+    """``_capi.PROTOTYPES`` against ``include/ggcn.h``, parameter by parameter: an ``int64_t`` leading dimension bound as ``c_int``
+    would otherwise show only as a wrong result or a fault on the GPU.  Every entry of the header is parsed (none left out), and
+    a parameter type the mapping does not know fails the test."""
+    protos = _declared_prototypes()
+    assert sorted(protos) == _declared_functions() == sorted(_capi.PROTOTYPES)
+    for name, (ret, args) in protos.items():
+        res, argtypes = _capi.PROTOTYPES[name]
+        want_res = ctypes.c_char_p if re.fullmatch(r"\s*const\s+char\s*\*\s*", ret) else _ctype(ret, name)
+        assert res is want_res, "%s returns %r, bound as %s" % (name, ret.strip(), res.__name__)
+        want = [_ctype(a, name) for a in args]
+        assert len(argtypes) == len(want), "%s takes %d arguments, bound with %d" % (name, len(want), len(argtypes))
+        for i, (got, w, a) in enumerate(zip(argtypes, want, args)):
+            assert got is w, "%s argument %d (%s): bound as %s, the header says %s" % (name, i, a.strip(), got.__name__, w.__name__)
+
+
 def test_bad_arguments_return_codes_not_crashes():
     lib = pkg.load_library()
     rc = lib.ggcn_linear(None, 8, None, 8, None, None, 8, 4, 8, 8, 0, None)
