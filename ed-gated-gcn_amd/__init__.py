@@ -12,6 +12,9 @@ Public surface (mirrors the reference interface for this path):
 * ``BatchedCSR``        -- many sentence graphs as one block-diagonal CSR.
 * ``subword_pool``      -- ``models/bert_amir5.py:600``: ``bmm(transform, x)`` on the non-zeros only.
 * ``subword_pool_layers`` -- the same on BERT's list of layer outputs, without the ``torch.cat`` of ``:596``: one launch, same bits.
+* ``anchor_pool_layers`` -- the baselines' step (``models/bert_ed.py:46-62``, ``models/bertdm.py:164-198``): from that list to the
+  anchor word's row and the two masked max-pools in one launch; ``anchor_pool_formula`` is its second half as PyTorch ops.
+* ``AnchorEventDetector`` / ``DynamicMultiPoolEventDetector`` -- the baselines ``BertED`` and ``BertDM`` around it.
 * ``bilstm``            -- ``models/bert_amir5.py:610``: the BiLSTM forward in inference, one projection and one recurrence launch.
 * ``bilstm_train``      -- the same line under autograd: the saving forward and a one-launch backward (``x`` and all eight parameters).
 
@@ -23,10 +26,11 @@ from ._capi import lib_path, load_library  # noqa: F401
 from .csr import BatchedCSR  # noqa: F401
 from .gcn import GraphConvolution  # noqa: F401
 from .gated_block import gated_gcn_block  # noqa: F401
-from .pooling import subword_pool, subword_pool_layers  # noqa: F401
+from .pooling import anchor_pool_formula, anchor_pool_layers, subword_pool, subword_pool_layers  # noqa: F401
 from .heads import dense_head, gate_mlps, scores_and_kl  # noqa: F401
 from .recurrent import bilstm, bilstm_train, takes_hip_lstm, takes_hip_lstm_train  # noqa: F401
 from .classifier import GatedGCNEventDetector, GatedGCNEventDetector54, GCNEventDetectorNoGate, LegacyBertAdapter  # noqa: F401
+from .classifier import AnchorEventDetector, DynamicMultiPoolEventDetector  # noqa: F401
 
-__all__ = ["GraphConvolution", "gated_gcn_block", "BatchedCSR", "subword_pool", "subword_pool_layers", "gate_mlps", "scores_and_kl", "bilstm", "takes_hip_lstm", "bilstm_train", "takes_hip_lstm_train", "GatedGCNEventDetector", "GatedGCNEventDetector54", "GCNEventDetectorNoGate", "LegacyBertAdapter",
+__all__ = ["GraphConvolution", "gated_gcn_block", "BatchedCSR", "subword_pool", "subword_pool_layers", "anchor_pool_layers", "anchor_pool_formula", "AnchorEventDetector", "DynamicMultiPoolEventDetector", "gate_mlps", "scores_and_kl", "bilstm", "takes_hip_lstm", "bilstm_train", "takes_hip_lstm_train", "GatedGCNEventDetector", "GatedGCNEventDetector54", "GCNEventDetectorNoGate", "LegacyBertAdapter",
            "load_library", "lib_path"]

@@ -18,6 +18,10 @@ path (``recurrent.bilstm``: one projection, one recurrence launch), and ``opt.gg
 (``recurrent.bilstm_train``: the saving forward and a one-launch backward, float32, no autocast); ``opt.ggcn_pool_layers`` pools
 BERT's layer outputs as the list they come in (``pooling.subword_pool_layers``: one launch, no ``torch.cat`` of ``:596``).  BERT, ``dense`` and, by default,
 the BiLSTM stay PyTorch-ROCm.
+
+The two baselines of ``train.py:268-282`` are here too: ``AnchorEventDetector`` = ``BertED`` (``models/bert_ed.py:13-69``) and
+``DynamicMultiPoolEventDetector`` = ``BertDM`` (``models/bertdm.py:104-201``), around ``pooling.anchor_pool_layers`` (one launch
+from BERT's layer list to what their final linear reads).
 """
 import os
 
@@ -29,8 +33,8 @@ from . import dispatch
 from .gated_block import gated_gcn_block, takes_block_path
 from .gcn import GraphConvolution
 from .heads import gate_mlps, scores_and_kl
-from .hostops import _opted_in, cached
-from .pooling import subword_pool, subword_pool_layers
+from .hostops import _opted_in, _unless_opted_out, cached
+from .pooling import anchor_pool_formula, anchor_pool_layers, subword_pool, subword_pool_layers
 from .recurrent import bilstm, bilstm_train, takes_hip_lstm, takes_hip_lstm_train, lstm_wants_grad
 
 
@@ -310,3 +314,91 @@ class GatedGCNEventDetector54(GatedGCNEventDetector):
 class GCNEventDetectorNoGate(GatedGCNEventDetector):
     """``BertAmir55NoGate`` (``models/bert_amir5.py:654-752``)."""
     VARIANT = "55nogate"
+
+
+class _AnchorBaseline(nn.Module):
+    """What the two baselines of ``train.py:268-282`` share: BERT's layers -> sub-words pooled into words -> the anchor word's
+    row and, for ``bertdm``, the two masked max-pools.  Where BERT returns a list or tuple of GPU tensors none of which requires
+    grad (the reference freezes BERT, ``train.py:43-44``) the whole step is ONE launch, ``anchor_pool_layers``: in training as
+    in inference, float32 and bf16, capturable.  Everywhere else -- a fine-tuned BERT, a tensor in place of the list,
+    ``opt.ggcn_anchor_pool = False`` (or ``GGCN_ANCHOR_POOL=0``) -- it is the composed path: ``subword_pool_layers`` (a list of
+    GPU tensors) or ``torch.cat`` + ``subword_pool``, then ``anchor_pool_formula``, the reference's PyTorch ops; differentiable,
+    and the same bits."""
+    SIDES = False
+
+    def _setup(self, bert, opt, n_layer):
+        self.device = getattr(opt, "device", None)
+        self.bert = bert
+        self.n_layer = n_layer
+        self.dropout = nn.Dropout(opt.dropout)
+        self.anchor_pool = _unless_opted_out(opt, "anchor_pool")
+
+    def _anchor_parts(self, inputs):
+        """``(anchor_rep [B,n*Dl] in BERT's dtype, pooled [B,2*n*Dl] float32)``; ``pooled`` is None for ``bert_ed``, and where the
+        one launch already wrote the two side by side with no dropout to come between them (then the first is all of
+        ``[B,3*n*Dl]``)."""
+        L = int(inputs["cls_text_sep_length"].max())                        # one host sync, as bert_ed.py:30-31 / bertdm.py:148-149
+        T = int(inputs["sentence_length"].max())
+        ids = inputs["cls_text_sep_indices"][:, :L]
+        seg = inputs["cls_text_sep_segments_ids"][:, :L]
+        transform = inputs["transform"][:, :T, :L].float()
+        anchor = inputs["anchor_index"].long()
+        x, _ = self.bert(ids, seg, output_all_encoded_layers=True)          # bert_ed.py:42 / bertdm.py:161
+        listed = isinstance(x, (list, tuple))
+        if listed:
+            x = x[-self.n_layer:]
+        on_gpu = listed and all(torch.is_tensor(t) and t.is_cuda for t in x)
+        length = None
+        if self.SIDES:
+            # (lengths kept on the host -- pinned, no sync at the two lines above -- are copied over without one)
+            length = inputs["sentence_length"].long().to(anchor.device, non_blocking=True)
+        if self.anchor_pool and on_gpu and not any(t.requires_grad for t in x):
+            z = anchor_pool_layers(transform, x, anchor, length, sides=self.SIDES)      # one launch, no [B,T,n*Dl]
+            if not self.SIDES:
+                return z, None
+            if not (self.training and self.dropout.p > 0):
+                return z, None               # no dropout between the parts: z IS the concatenation of bertdm.py:198, bit for bit
+            w = z.shape[1] // 3
+            # (a bf16 value is exact in float32, and back; contiguous, so that dropout draws the mask it draws on the composed row)
+            return z[:, :w].to(x[0].dtype).contiguous(), z[:, w:]
+        if on_gpu:
+            v = subword_pool_layers(transform, x)                           # no torch.cat of bert_ed.py:46 / bertdm.py:164
+        else:
+            v = subword_pool(transform, torch.cat(x, dim=-1) if listed else x)          # bert_ed.py:46,50 / bertdm.py:164,166
+        if not self.SIDES:
+            return anchor_pool_formula(v, anchor, sides=False), None        # bert_ed.py:55-62
+        return anchor_pool_formula(v, anchor, length, sides=True)           # bertdm.py:170-194
+
+
+class AnchorEventDetector(_AnchorBaseline):
+    """``BertED`` (``models/bert_ed.py:13-69``, ``--model bert_ed``): the anchor word's pooled row of the 12 BERT layers,
+    dropout, ``fc``.  (With bf16 layers the launch's float32 row is converted back by one small elementwise kernel.)  Loads a reference ``state_dict`` unchanged (``bert.*``, ``fc``); ``forward(inputs) -> (logits, 0, 0,
+    None)``."""
+
+    def __init__(self, bert, opt):
+        super().__init__()
+        self._setup(bert, opt, 12)                                          # bert_ed.py:17-21
+        self.hidden_dim = getattr(opt, "hidden_dim", None)
+        self.fc = nn.Linear(768 * self.n_layer, opt.polarities_dim)         # :22
+
+    def forward(self, inputs):
+        anchor_rep, _ = self._anchor_parts(inputs)
+        return self.fc(self.dropout(anchor_rep)), 0, 0, None                # :65-69
+
+
+class DynamicMultiPoolEventDetector(_AnchorBaseline):
+    """``BertDM`` (``models/bertdm.py:104-201``, ``--model bertdm``, dynamic multi-pooling): over the last ``opt.n_layer`` BERT
+    layers the anchor word's row, the max-pool over the words up to and including the anchor and the one over the words after
+    it, dropout on the anchor part and on the concatenation, ``dense``.  Loads a reference ``state_dict`` unchanged (``bert.*``,
+    ``dense``; the reference's ``self.m`` is a plain attribute, not a buffer); ``forward(inputs) -> (logits, 0.0, 0.0, 0.0)``."""
+    SIDES = True
+
+    def __init__(self, bert, opt):
+        super().__init__()
+        self._setup(bert, opt, opt.n_layer)                                 # bertdm.py:108-111
+        self.dense = nn.Linear(opt.n_layer * opt.bert_dim * 3, opt.polarities_dim)      # :112
+
+    def forward(self, inputs):
+        anchor_rep, pooled = self._anchor_parts(inputs)
+        x = anchor_rep if pooled is None else torch.cat((self.dropout(anchor_rep), pooled), 1)      # :197-198
+        return self.dense(self.dropout(x)), 0.0, 0.0, 0.0                   # :199-201

@@ -792,6 +792,22 @@ int ggcn_subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, in
     return subword_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, Y, y_batch, ldy, B, R, C, Dl);
 }
 
+int ggcn_anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                            int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
+                            float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl, ggcn_stream_t stream)
+{
+    return anchor_pool_layers(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, anchor, length, sides, Z, ldz, z_section,
+                              B, R, C, Dl, as_stream(stream));
+}
+
+int ggcn_anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                                 int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
+                                 const float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl)
+{
+    return anchor_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, anchor, length, sides, Z, ldz,
+                                   z_section, B, R, C, Dl);
+}
+
 int ggcn_absmax(const void *X, int is_half, int64_t ld, int64_t M, int K, float *out, ggcn_stream_t stream)
 {
     return absmax(X, is_half, ld, M, K, out, as_stream(stream));

@@ -96,6 +96,13 @@ int subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c
 int subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
                              int is_bf16, int64_t x_batch, int64_t ldx, const void *Y, int64_t y_batch, int64_t ldy, int B, int R,
                              int C, int Dl);
+// the anchor's pooled row and, with sides, the two masked max-pools of bertdm.py:176-185 per sentence, one launch; ..._form as above
+int anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                       int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides, float *Z,
+                       int64_t ldz, int64_t z_section, int B, int R, int C, int Dl, hipStream_t st);
+int anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                            int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
+                            const float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl);
 int csr_rowmask(const int32_t *rowptr, const int32_t *colidx, int B, int T, uint32_t *rowmask, hipStream_t st);
 int graph_operands(const uint32_t *rowmask, int B, int T, void *ops, hipStream_t st);
 int graph_edge_lists(const uint32_t *rowmask, int B, int T, void *lists, hipStream_t st);   // fused_wide8.hip

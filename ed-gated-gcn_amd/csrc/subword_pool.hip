@@ -13,6 +13,8 @@
 // ggcn_subword_pool_layers reads x where BERT left it: the 12 layer outputs of bert_amir5.py:596, before their `torch.cat`, each
 // pooled into its own 768 columns of Y by ONE launch -- the same compaction and the same two loop bodies, so a layer's columns
 // are bit for bit those of ggcn_subword_pool on that layer alone, and the 9216-wide copy is never made.
+// ggcn_anchor_pool_layers serves the baselines bert_ed / bertdm, which keep of all pooled rows only the anchor's and two masked
+// max-pools: one launch from the layer list to [B, 3*n*Dl], the pooled rows held in registers and never stored.
 #include "common.h"
 
 namespace ggcn {
@@ -169,6 +171,93 @@ __global__ __launch_bounds__(256) void subword_pool_layers_kernel(const float *_
     }
 }
 
+// The baselines' step (ggcn_anchor_pool_layers; models/bert_ed.py:46-62, models/bertdm.py:164-198): of the pooled rows
+// v[b, r, :] above only the anchor's row and, with `sides`, the two masked max-pools of bertdm.py:176-185 leave the launch.
+// One workgroup per (sentence, four units) walks the sentence's rows in ascending r: the compaction and the pooled values of
+// subword_pool_layers_kernel row by row, a select into the anchor registers, an update of one of the two running maxima; it
+// stores 3 x (its features) floats once, after the loop.  No atomics, one fixed order: [B, R, n*Dl] never exists.
+__device__ __forceinline__ float nan_max(float m, float t) { return (t > m || t != t) ? t : m; }   // torch.max: a NaN stays
+
+template <bool VEC, typename XT>
+__global__ __launch_bounds__(256) void anchor_pool_layers_kernel(const float *__restrict__ A, int64_t sa_b, int64_t sa_r,
+                                                                int64_t sa_c, const LayerPtrs layers, int n_layers,
+                                                                int64_t x_batch, int64_t ldx, const int64_t *__restrict__ anchor,
+                                                                const int64_t *__restrict__ length, int sides,
+                                                                float *__restrict__ Z, int64_t ldz, int64_t z_section, int R, int C,
+                                                                int Dl, int units)
+{
+    __shared__ RowLds s;
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x;
+    // read once, clamped (an index outside its range never reaches A or a layer) and uniform: the loop below holds barriers
+    const int64_t a64 = anchor[b];
+    const int a = __builtin_amdgcn_readfirstlane((int)(a64 < 0 ? 0 : (a64 > R - 1 ? R - 1 : a64)));
+    int n = 0;
+    if (sides) {                                                    // (sides == 0: `length` is never touched)
+        const int64_t n64 = length[b];
+        n = __builtin_amdgcn_readfirstlane((int)(n64 < 0 ? 0 : (n64 > R ? R : n64)));
+    }
+    const int r_first = sides ? 0 : a, r_last = (sides && n - 1 > a) ? n - 1 : a;
+    const int u = __builtin_amdgcn_readfirstlane((int)(blockIdx.y * 4 + (threadIdx.x >> 6)));   // this wavefront's unit
+    const int l = u / units;
+    const bool wave_live = l < n_layers;     // a wavefront past the last unit stays for the barriers of every compaction
+    const int f0 = wave_live ? (u - l * units) * kUnit : 0;
+    const XT *xb = static_cast<const XT *>(layers.p[wave_live ? l : 0]) + b * x_batch;
+    int f[4];
+    bool live[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        f[q] = VEC ? f0 + lane * 4 + q : f0 + q * 64 + lane;        // (scalar form: coalesced, as subword_pool_layers_kernel)
+        live[q] = wave_live && f[q] < Dl;
+    }
+    const float left0 = a < R - 1 ? 1.0f : -INFINITY;               // a masked word right of the anchor contributes 0 + 1
+    float anc[4], left[4], right[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) anc[q] = 0.0f, left[q] = left0, right[q] = 1.0f;
+    for (int r = r_first; r <= r_last; ++r) {
+        const int cnt = compact_row(s, A + b * sa_b + r * sa_r, sa_c, C);
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (VEC) {
+            if (live[0]) {                                          // (Dl % 4 == 0: four features live or none)
+                const float4 p = pooled4(s, cnt, xb, ldx, f[0]);
+                v[0] = p.x, v[1] = p.y, v[2] = p.z, v[3] = p.w;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (live[q]) v[q] = pooled1(s, cnt, xb, ldx, f[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float w = (float)(XT)v[q];                        // bf16 layers: the one rounding of the pooled value
+            const float t = w + 1.0f;
+            if (r == a) anc[q] = w;
+            if (r <= a) left[q] = nan_max(left[q], t);
+            else right[q] = nan_max(right[q], t);                   // a < r < n by the loop's bounds
+        }
+        __syncthreads();   // compact_row's result is read after its last barrier; the next call clears it first
+    }
+    float *zrow = Z + b * ldz + (int64_t)l * Dl;
+    if (VEC) {
+        if (!live[0]) return;
+        store4(zrow + f[0], make_float4(anc[0], anc[1], anc[2], anc[3]));
+        if (sides) {
+            store4(zrow + z_section + f[0], make_float4(left[0] - 1.0f, left[1] - 1.0f, left[2] - 1.0f, left[3] - 1.0f));
+            store4(zrow + 2 * z_section + f[0], make_float4(right[0] - 1.0f, right[1] - 1.0f, right[2] - 1.0f, right[3] - 1.0f));
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (!live[q]) continue;
+            zrow[f[q]] = anc[q];
+            if (sides) {
+                zrow[z_section + f[q]] = left[q] - 1.0f;
+                zrow[2 * z_section + f[q]] = right[q] - 1.0f;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 int subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const float *X, int64_t x_batch,
@@ -282,6 +371,85 @@ int subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c
     else
         launch_layers<float>(form == 1, A, sa_b, sa_r, sa_c, ptrs, n_layers, x_batch, ldx, Y, y_batch, ldy, B, R, C, Dl, st);
     return check_launch("ggcn_subword_pool_layers");
+}
+
+// 1 = vector form, 0 = scalar form, -ggcn_status (message set) where ggcn_anchor_pool_layers refuses.  Host only, as
+// subword_pool_layers_form; its vector / scalar rule with Z, ldz and (with sides) z_section in the place of Y, y_batch and ldy.
+int anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                            int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
+                            const float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl)
+{
+    const char *who = "ggcn_anchor_pool_layers";
+    (void)sa_b; (void)sa_r; (void)sa_c;
+    if (!A || !layers || !anchor || !Z) return -fail(GGCN_EINVAL, "%s: null pointer", who);
+    if (sides && !length) return -fail(GGCN_EINVAL, "%s: length is a null pointer with sides", who);
+    if (n_layers < 1) return -fail(GGCN_EINVAL, "%s: n_layers=%d must be positive", who, n_layers);
+    if (n_layers > GGCN_POOL_MAX_LAYERS)
+        return -fail(GGCN_EUNSUPPORTED, "%s: n_layers=%d > %d layers a launch (split the layers into groups of %d, each into its own columns of Z)",
+                     who, n_layers, GGCN_POOL_MAX_LAYERS, GGCN_POOL_MAX_LAYERS);
+    for (int l = 0; l < n_layers; ++l)
+        if (!layers[l]) return -fail(GGCN_EINVAL, "%s: layers[%d] is a null pointer", who, l);
+    if (B <= 0 || R <= 0 || C <= 0 || Dl <= 0)
+        return -fail(GGCN_EINVAL, "%s: B=%d R=%d C=%d Dl=%d must be positive", who, B, R, C, Dl);
+    if (C > kMaxCols) return -fail(GGCN_EUNSUPPORTED, "%s: C=%d > %d columns", who, C, kMaxCols);
+    const int64_t width = (int64_t)n_layers * Dl;
+    if (sides && z_section < width)
+        return -fail(GGCN_EINVAL, "%s: z_section=%lld < n_layers*Dl=%lld", who, (long long)z_section, (long long)width);
+    if (ldx < Dl || ldz < width || (sides && (ldz - width) / 2 < z_section))
+        return -fail(GGCN_EINVAL, "%s: leading dimension too small", who);
+    // (this grid is (B, units) and would take more; kept so that whatever this entry accepts the composed path,
+    // ggcn_subword_pool_layers on the same A, accepts too)
+    if ((int64_t)B * R > (int64_t)INT32_MAX) return -fail(GGCN_EUNSUPPORTED, "%s: too many rows", who);
+    const uintptr_t elem = is_bf16 ? 2 : 4, wide = is_bf16 ? 8 : 16;   // (8-byte loads of four bf16; Z is float32)
+    if (reinterpret_cast<uintptr_t>(A) % 4 || reinterpret_cast<uintptr_t>(Z) % 4 || reinterpret_cast<uintptr_t>(anchor) % 8 ||
+        (sides && reinterpret_cast<uintptr_t>(length) % 8))
+        return -fail(GGCN_EINVAL, "%s: A, Z, anchor or length not aligned to its element", who);
+    bool vec = (Dl % 4 == 0) && (ldx % 4 == 0) && (x_batch % 4 == 0) && (ldz % 4 == 0) && (!sides || z_section % 4 == 0) && aligned16(Z);
+    for (int l = 0; l < n_layers; ++l) {
+        if (reinterpret_cast<uintptr_t>(layers[l]) % elem)
+            return -fail(GGCN_EINVAL, "%s: layers[%d] not aligned to its element", who, l);
+        vec = vec && (reinterpret_cast<uintptr_t>(layers[l]) % wide == 0);
+    }
+    const int64_t units = ((int64_t)Dl + kUnit - 1) / kUnit;
+    if ((n_layers * units + 3) / 4 > 65535)
+        return -fail(GGCN_EUNSUPPORTED, "%s: n_layers=%d Dl=%d needs more than 65535 workgroups a sentence", who, n_layers, Dl);
+    return vec ? 1 : 0;
+}
+
+namespace {
+template <typename XT>
+void launch_anchor(bool vec, const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const LayerPtrs &ptrs, int n_layers,
+                   int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides, float *Z, int64_t ldz,
+                   int64_t z_section, int B, int R, int C, int Dl, hipStream_t st)
+{
+    const int units = (Dl + kUnit - 1) / kUnit;
+    const dim3 grid((unsigned)B, (unsigned)((n_layers * units + 3) / 4));
+    if (vec)
+        hipLaunchKernelGGL((anchor_pool_layers_kernel<true, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
+                           x_batch, ldx, anchor, length, sides, Z, ldz, z_section, R, C, Dl, units);
+    else
+        hipLaunchKernelGGL((anchor_pool_layers_kernel<false, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
+                           x_batch, ldx, anchor, length, sides, Z, ldz, z_section, R, C, Dl, units);
+}
+}  // namespace
+
+int anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                       int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides, float *Z,
+                       int64_t ldz, int64_t z_section, int B, int R, int C, int Dl, hipStream_t st)
+{
+    const int form = anchor_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, anchor, length, sides, Z,
+                                             ldz, z_section, B, R, C, Dl);
+    if (form < 0) return -form;
+    LayerPtrs ptrs = {};
+    for (int l = 0; l < n_layers; ++l) ptrs.p[l] = layers[l];
+    const int on = sides != 0;
+    if (is_bf16)
+        launch_anchor<__bf16>(form == 1, A, sa_b, sa_r, sa_c, ptrs, n_layers, x_batch, ldx, anchor, length, on, Z, ldz, z_section,
+                              B, R, C, Dl, st);
+    else
+        launch_anchor<float>(form == 1, A, sa_b, sa_r, sa_c, ptrs, n_layers, x_batch, ldx, anchor, length, on, Z, ldz, z_section,
+                             B, R, C, Dl, st);
+    return check_launch("ggcn_anchor_pool_layers");
 }
 
 }  // namespace ggcn

@@ -18,6 +18,11 @@ def _opted_in(opt, name):
     return bool(getattr(opt, "ggcn_" + name, False)) or os.environ.get("GGCN_" + name.upper(), "0") == "1"
 
 
+def _unless_opted_out(opt, name):
+    """A boolean that is on by default: off when ``opt.ggcn_<name>`` is set and false or the environment has ``GGCN_<NAME>=0``."""
+    return bool(getattr(opt, "ggcn_" + name, True)) and os.environ.get("GGCN_" + name.upper(), "1") != "0"
+
+
 def param_key(*tensors):
     """``(data_ptr, version, device)`` per tensor, None for an absent one: what a cache of something derived from them keys on.
     An in-place update moves the version, a re-assigned ``.data`` the pointer."""

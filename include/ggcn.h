@@ -916,6 +916,40 @@ int ggcn_subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t
 int ggcn_subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
                                   const void *const *layers, int n_layers, int is_bf16, int64_t x_batch, int64_t ldx,
                                   const void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int Dl);
+/* The step of the baselines bert_ed / bertdm (models/bert_ed.py:46-62, models/bertdm.py:164-198) in ONE launch, from BERT's
+ * layer list to what the final linear reads.  With v[b, r, l*Dl + f] = sum_c A[b,r,c] * X_l[b,c,f] exactly as
+ * ggcn_subword_pool_layers forms it (float32 FMAs in ascending c from 0; bfloat16 layers: one RNE to bfloat16),
+ * a = clamp(anchor[b], 0, R-1) and n = clamp(length[b], 0, R), for j = 0..n_layers*Dl-1:
+ *   Z[b, j]               = v[b, a, j]                                                  (the anchor word's row)
+ *   Z[b, z_section + j]   = max(m0, max_{r <= a}    (v[b,r,j] + 1.0f)) - 1.0f,  m0 = 1.0f if a < R-1, else -inf
+ *   Z[b, 2*z_section + j] = max(1.0f, max_{a < r < n} (v[b,r,j] + 1.0f)) - 1.0f
+ * the last two only with sides != 0.  This is bertdm.py:176-185 bit for bit: it multiplies by a 0/1 mask, adds ones, takes the
+ * max and subtracts ones, so a masked word contributes exactly 1.0f and every value goes through the rounding of v + 1.  A
+ * NaN in a row that is pooled propagates, as torch.max's.  Masked rows are never read: the one divergence is a masked row
+ * that is not finite, which the reference turns into NaN (inf * 0) and this entry ignores.  [B, R, n_layers*Dl] is never
+ * formed; the rows are walked in ascending r without atomics, so a sentence gives the same bits alone as in a batch.
+ * anchor, length: int64 [B] on the device, read by the kernel (no host read: capture-safe) and clamped there; length may be
+ * NULL with sides == 0 and is then never touched.  Z: float32 always (a bfloat16 value is exact in it), row b at Z + b*ldz;
+ * z_section (elements) is the distance between the three parts, so that a group of GGCN_POOL_MAX_LAYERS layers can write
+ * into its own columns of a wider Z.  A, layers, x_batch, ldx, C <= 2048: as ggcn_subword_pool_layers.  The vector form is
+ * taken when Dl, ldx, x_batch, ldz and (with sides) z_section are multiples of 4, Z is aligned to 16 bytes and every layer
+ * pointer to 16 (8 for bfloat16); otherwise the whole launch takes the scalar form (same bits).
+ * GGCN_EINVAL: a NULL A, layers, layers[l], anchor or Z; a NULL length with sides; n_layers < 1; B, R, C or Dl <= 0; with
+ * sides z_section < n_layers*Dl; ldx < Dl; ldz < n_layers*Dl + (sides ? 2*z_section : 0); a pointer not aligned to its
+ * element.  GGCN_EUNSUPPORTED: n_layers > GGCN_POOL_MAX_LAYERS; C > 2048; B*R > INT32_MAX; more than 65535 workgroups a
+ * sentence.  All before any launch. */
+int ggcn_anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
+                            const void *const *layers, int n_layers, int is_bf16, int64_t x_batch, int64_t ldx,
+                            const int64_t *anchor, const int64_t *length, int sides,
+                            float *Z, int64_t ldz, int64_t z_section,
+                            int B, int R, int C, int Dl, ggcn_stream_t stream);
+/* host-only: 1 = vector form, 0 = scalar form, -ggcn_status where the entry would refuse (ggcn_last_error names
+ * ggcn_anchor_pool_layers); launches nothing and dereferences nothing on the device. */
+int ggcn_anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
+                                 const void *const *layers, int n_layers, int is_bf16, int64_t x_batch, int64_t ldx,
+                                 const int64_t *anchor, const int64_t *length, int sides,
+                                 const float *Z, int64_t ldz, int64_t z_section,
+                                 int B, int R, int C, int Dl);
 
 /* ---- bfloat16 features (training and inference under torch.autocast(dtype=torch.bfloat16)) ----------------------
  * X (the layer's input) in bfloat16; weights, bias, gates, `out`, pools and dW stay float32, dX is bfloat16 -- the
