@@ -16,6 +16,7 @@ Public surface (mirrors the reference interface for this path):
   anchor word's row and the two masked max-pools in one launch; ``anchor_pool_formula`` is its second half as PyTorch ops.
 * ``AnchorEventDetector`` / ``DynamicMultiPoolEventDetector`` -- the baselines ``BertED`` and ``BertDM`` around it.
 * ``bilstm``            -- ``models/bert_amir5.py:610``: the BiLSTM forward in inference, one projection and one recurrence launch.
+* ``bilstm_layers``     -- ``:596,600,610`` in two launches: the projection pools BERT's layer list in its own loader (no ``[B,T,9216]``), then the recurrence.
 * ``bilstm_train``      -- the same line under autograd: the saving forward and a one-launch backward (``x`` and all eight parameters).
 
 All compute is in ``libggcn_hip.so`` (hand-written HIP for gfx950, C ABI in
@@ -28,9 +29,9 @@ from .gcn import GraphConvolution  # noqa: F401
 from .gated_block import gated_gcn_block  # noqa: F401
 from .pooling import anchor_pool_formula, anchor_pool_layers, subword_pool, subword_pool_layers  # noqa: F401
 from .heads import dense_head, gate_mlps, scores_and_kl  # noqa: F401
-from .recurrent import bilstm, bilstm_train, takes_hip_lstm, takes_hip_lstm_train  # noqa: F401
+from .recurrent import bilstm, bilstm_layers, bilstm_train, takes_hip_lstm, takes_hip_lstm_layers, takes_hip_lstm_train  # noqa: F401
 from .classifier import GatedGCNEventDetector, GatedGCNEventDetector54, GCNEventDetectorNoGate, LegacyBertAdapter  # noqa: F401
 from .classifier import AnchorEventDetector, DynamicMultiPoolEventDetector  # noqa: F401
 
-__all__ = ["GraphConvolution", "gated_gcn_block", "BatchedCSR", "subword_pool", "subword_pool_layers", "anchor_pool_layers", "anchor_pool_formula", "AnchorEventDetector", "DynamicMultiPoolEventDetector", "gate_mlps", "scores_and_kl", "bilstm", "takes_hip_lstm", "bilstm_train", "takes_hip_lstm_train", "GatedGCNEventDetector", "GatedGCNEventDetector54", "GCNEventDetectorNoGate", "LegacyBertAdapter",
+__all__ = ["GraphConvolution", "gated_gcn_block", "BatchedCSR", "subword_pool", "subword_pool_layers", "anchor_pool_layers", "anchor_pool_formula", "AnchorEventDetector", "DynamicMultiPoolEventDetector", "gate_mlps", "scores_and_kl", "bilstm", "takes_hip_lstm", "bilstm_train", "takes_hip_lstm_train", "bilstm_layers", "takes_hip_lstm_layers", "GatedGCNEventDetector", "GatedGCNEventDetector54", "GCNEventDetectorNoGate", "LegacyBertAdapter",
            "load_library", "lib_path"]

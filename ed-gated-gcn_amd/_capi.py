@@ -84,6 +84,10 @@ PROTOTYPES = {
                                         c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "ggcn_anchor_pool_layers_form": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32,
                                              c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "ggcn_linear_pooled_layers": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64,
+                                          c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "ggcn_linear_pooled_layers_form": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i64,
+                                               c_i32, c_i32, c_i32, c_i32, c_i32]),
     "ggcn_linear_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
     "ggcn_linear_out_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
     "ggcn_layer_fused_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,

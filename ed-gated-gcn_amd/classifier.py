@@ -16,7 +16,8 @@ puts their backward on graphs of 33..128 nodes into one launch each where no gat
 real-valued adjacency of 33..128 nodes (``dispatch.takes_weighted_wide_backward``); ``opt.ggcn_hip_lstm`` puts the BiLSTM (``:610``) of an inference forward on the HIP
 path (``recurrent.bilstm``: one projection, one recurrence launch), and ``opt.ggcn_hip_lstm_backward`` that of a training step
 (``recurrent.bilstm_train``: the saving forward and a one-launch backward, float32, no autocast); ``opt.ggcn_pool_layers`` pools
-BERT's layer outputs as the list they come in (``pooling.subword_pool_layers``: one launch, no ``torch.cat`` of ``:596``).  BERT, ``dense`` and, by default,
+BERT's layer outputs as the list they come in (``pooling.subword_pool_layers``: one launch, no ``torch.cat`` of ``:596``), and ``opt.ggcn_lstm_layers`` lets the BiLSTM's projection of an
+inference forward read that list itself (``recurrent.bilstm_layers``: the pooled words ``[B,T,9216]`` are never formed).  BERT, ``dense`` and, by default,
 the BiLSTM stay PyTorch-ROCm.
 
 The two baselines of ``train.py:268-282`` are here too: ``AnchorEventDetector`` = ``BertED`` (``models/bert_ed.py:13-69``) and
@@ -35,7 +36,7 @@ from .gcn import GraphConvolution
 from .heads import gate_mlps, scores_and_kl
 from .hostops import _opted_in, _unless_opted_out, cached
 from .pooling import anchor_pool_formula, anchor_pool_layers, subword_pool, subword_pool_layers
-from .recurrent import bilstm, bilstm_train, takes_hip_lstm, takes_hip_lstm_train, lstm_wants_grad
+from .recurrent import LAYERS_MIN_ROWS, bilstm, bilstm_layers, bilstm_train, takes_hip_lstm, takes_hip_lstm_layers, takes_hip_lstm_train, lstm_wants_grad
 
 
 class LegacyBertAdapter(nn.Module):
@@ -111,6 +112,15 @@ class GatedGCNEventDetector(nn.Module):
         # own columns in one launch instead of ``torch.cat`` (:596, a full [B,L,9216] copy) + ``subword_pool``.  Same bits, forward
         # and backward, float32 and bf16; taken where the layers are a list or tuple of GPU tensors.  Off by default.
         self.pool_layers = _opted_in(opt, "pool_layers")
+        # inference: the BiLSTM's input projection straight from BERT's list of layer outputs (``bilstm_layers``: the projection's
+        # loader pools the layers where they lie) and the anchor word's row from ``anchor_pool_layers``: the pooled words
+        # [B,T,9216] are never formed either.  Taken where ``takes_hip_lstm_layers`` holds (float32 layers on the GPU, no gradient
+        # wanted, no autocast); everything else keeps the paths above.  ``bilstm``'s bits; independent of ``hip_lstm`` and
+        # ``pool_layers``.  Off by default.  Below ``lstm_layers_min_rows`` rows B*T (``opt.ggcn_lstm_layers_min_rows`` /
+        # ``GGCN_LSTM_LAYERS_MIN_ROWS``; default ``recurrent.LAYERS_MIN_ROWS``, the measured break-even) the path is not taken: it
+        # is slower there and only saves memory; 0 takes it at every size.
+        self.lstm_layers = _opted_in(opt, "lstm_layers")
+        self.lstm_layers_min_rows = int(getattr(opt, "ggcn_lstm_layers_min_rows", os.environ.get("GGCN_LSTM_LAYERS_MIN_ROWS", LAYERS_MIN_ROWS)))
 
     def _training_gates(self, aspect):
         """``gate1(aspect), gate2(aspect)`` of the training branches: the two nn.Sequential (under bf16 autocast they give bf16)
@@ -196,6 +206,15 @@ class GatedGCNEventDetector(nn.Module):
         if isinstance(adj, torch.Tensor):
             adj = adj[:, :T, :T]
         x, pooled = self.bert(ids, seg, output_all_encoded_layers=True)     # :591
+        if self.lstm_layers and isinstance(x, (list, tuple)) and not torch.is_autocast_enabled("cuda"):
+            tf, layers = transform.float(), x[-self.n_layer:]
+        else:
+            tf = layers = None
+        if layers is not None and takes_hip_lstm_layers(tf, layers, self.lstm, self.lstm_layers_min_rows):
+            # :596 + :600 + :604-610 in three launches: neither [B,L,9216] nor [B,T,9216] is formed (inference, float32)
+            anchor_rep = self.dropout(anchor_pool_layers(tf, layers, anchor.long(), None, sides=False))
+            x = bilstm_layers(tf, layers, self.lstm)
+            return self._after_lstm(x, anchor_rep, pooled, anchor, adj, dist, torch.arange(B, device=x.device))
         if self.pool_layers and isinstance(x, (list, tuple)) and all(torch.is_tensor(t) and t.is_cuda for t in x[-self.n_layer:]):
             x = subword_pool_layers(transform.float(), x[-self.n_layer:])   # :596 + :600 in one launch, no [B,L,9216] copy
         else:
@@ -210,6 +229,11 @@ class GatedGCNEventDetector(nn.Module):
             x = bilstm_train(x, self.lstm)                                  # :610 on the HIP path (training, float32, no autocast)
         else:
             x, _ = self.lstm(x)                                             # :610
+        return self._after_lstm(x, anchor_rep, pooled, anchor, adj, dist, rows)
+
+    def _after_lstm(self, x, anchor_rep, pooled, anchor, adj, dist, rows):
+        """``forward`` from the BiLSTM's output on (``:615-648``)."""
+        B, T = x.shape[0], x.shape[1]
         if x.dtype == torch.float16 and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16:
             # under bf16 autocast the ROCm LSTM still returns float16; the reference's first consumers of x (gc1's matmul,
             # gcn.py:34) cast it to bf16, so the layers are handed that bf16 tensor directly

@@ -808,6 +808,20 @@ int ggcn_anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int
                                    z_section, B, R, C, Dl);
 }
 
+int ggcn_linear_pooled_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                              int64_t x_batch, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int B, int R, int C, int Dl,
+                              int F, ggcn_stream_t stream)
+{
+    return linear_pooled_layers(A, sa_b, sa_r, sa_c, layers, n_layers, x_batch, ldx, wpack, Y, ldy, B, R, C, Dl, F, as_stream(stream));
+}
+
+int ggcn_linear_pooled_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                                   int64_t x_batch, int64_t ldx, const void *wpack, const float *Y, int64_t ldy, int B, int R, int C,
+                                   int Dl, int F)
+{
+    return linear_pooled_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, x_batch, ldx, wpack, Y, ldy, B, R, C, Dl, F);
+}
+
 int ggcn_absmax(const void *X, int is_half, int64_t ld, int64_t M, int K, float *out, ggcn_stream_t stream)
 {
     return absmax(X, is_half, ld, M, K, out, as_stream(stream));

@@ -103,6 +103,13 @@ int anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
 int anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
                             int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
                             const float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl);
+// the bf16x3 linear on the pooled layers, the pooled words never stored (linear_pooled.hip); ..._form: 1 taken / -status, host only
+int linear_pooled_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                         int64_t x_batch, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int B, int R, int C, int Dl, int F,
+                         hipStream_t st);
+int linear_pooled_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                              int64_t x_batch, int64_t ldx, const void *wpack, const float *Y, int64_t ldy, int B, int R, int C,
+                              int Dl, int F);
 int csr_rowmask(const int32_t *rowptr, const int32_t *colidx, int B, int T, uint32_t *rowmask, hipStream_t st);
 int graph_operands(const uint32_t *rowmask, int B, int T, void *ops, hipStream_t st);
 int graph_edge_lists(const uint32_t *rowmask, int B, int T, void *lists, hipStream_t st);   // fused_wide8.hip

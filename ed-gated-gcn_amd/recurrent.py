@@ -19,9 +19,11 @@ library's fixed-order products: ``ggcn_dweight`` for ``[W_ih_f ; W_ih_r]`` and t
 ``ggcn_linear`` for ``dX`` -- each skipped where no gradient is wanted.  The classifier takes it in training with
 ``opt.ggcn_hip_lstm_backward`` / ``GGCN_HIP_LSTM_BACKWARD=1`` where ``takes_hip_lstm_train`` holds (off by default).
 """
+import ctypes
+
 import torch
 
-from . import _capi, hostops
+from . import _capi, hostops, pooling
 from .gcn import _rows2d
 
 HIDDEN = 128                    # the kernel's hd (the reference hard-codes hidden_dim = 128, bert_amir5.py:551)
@@ -236,3 +238,121 @@ def bilstm_train(x, lstm):
     if not lstm_wants_grad(x, lstm):
         return bilstm(x, lstm)
     return _BilstmTrain.apply(x, lstm, *_params(lstm))
+
+
+# ---- the projection straight from BERT's layer list ------------------------------------------------------------
+
+def layers_want_grad(layers, lstm):
+    """A call on ``layers`` and ``lstm`` wants a gradient: grad is enabled and a layer or a parameter of the module requires one."""
+    return torch.is_grad_enabled() and (any(x.requires_grad for x in layers)
+                                        or any(p is not None and p.requires_grad for p in _params(lstm)))
+
+
+def _check_layers_call(transform, layers, lstm):
+    """The raises of ``bilstm_layers``: first those that need no device (the module, the layer list, the gradient), with
+    ``bilstm``'s texts where they apply, then ``pooling._check_layers`` (CPU tensors, shapes, devices, the transform)."""
+    problem = _module_problem(lstm)
+    if problem is not None:
+        raise RuntimeError(problem)
+    if not isinstance(layers, (list, tuple)) or len(layers) == 0 or not all(
+            isinstance(x, torch.Tensor) and x.dim() == 3 for x in layers):
+        raise TypeError("layers must be a non-empty list or tuple of 3-d tensors")
+    if len(layers) > pooling.MAX_LAYERS:
+        raise RuntimeError("bilstm_layers takes at most %d layers in its one projection launch, got %d (pool them with "
+                           "subword_pool_layers and call bilstm)" % (pooling.MAX_LAYERS, len(layers)))
+    for i, x in enumerate(layers):
+        if x.dtype != torch.float32:
+            raise RuntimeError("layers[%d] must be float32, got %s (bf16 layers: subword_pool_layers, then nn.LSTM under "
+                               "autocast)" % (i, x.dtype))
+    width = sum(x.shape[2] for x in layers)
+    if width != lstm.input_size:
+        raise RuntimeError("layers of %d columns in all do not match lstm.input_size %d" % (width, lstm.input_size))
+    if layers_want_grad(layers, lstm):
+        raise RuntimeError("bilstm_layers is forward only: a gradient through the LSTM stays nn.LSTM (call it under torch.no_grad())")
+    pooling._check_layers("bilstm_layers", transform, layers)
+    dev = layers[0].device
+    for name, p in zip(PARAMS, _params(lstm)):
+        if p is not None and p.device != dev:
+            raise RuntimeError("lstm.%s is on %s, layers on %s: the HIP path has no CPU fallback" % (name, p.device, dev))
+
+
+def _pooled_args(transform, layers, real):
+    """The argument list of ``ggcn_linear_pooled_layers(_form)`` up to ``wpack``, and what must stay alive during the call.
+    ``real=False`` (the predicate): layers that do not share their strides are not copied; the form is asked about the
+    contiguous copies ``bilstm_layers`` would make (the allocator's alignment, contiguous strides)."""
+    B, R, C = transform.shape
+    Dl = layers[0].shape[2]
+    x0 = layers[0]
+    if real:
+        layers, x_batch, ldx = pooling._one_layout(list(layers))
+        addrs = [x.data_ptr() for x in layers]
+    elif x0.stride(2) != 1 or x0.stride(1) < Dl or any(x.stride() != x0.stride() for x in layers):
+        x_batch, ldx, addrs = C * Dl, Dl, [256] * len(layers)
+    else:
+        x_batch, ldx, addrs = x0.stride(0), x0.stride(1), [x.data_ptr() for x in layers]
+    ptrs = (ctypes.c_void_p * len(addrs))(*addrs)            # host array, read during the call
+    sb, sr, sc = transform.stride()
+    return (_capi.ptr(transform), sb, sr, sc, ptrs, len(addrs), x_batch, ldx), (B, R, C, Dl), layers
+
+
+# Rows B*T from which on ``takes_hip_lstm_layers`` answers True by default: the smallest row count at which the one projection
+# launch was measured not slower than ``subword_pool_layers`` + ``ggcn_linear`` (4096 x 32; it lost at 256 x 31 and 32 x 31, where the
+# grid does not fill the chip twice and nothing hides the loader's latency: profiles/lstm_layers_timing.txt, DESIGN 4.23).
+LAYERS_MIN_ROWS = 4096 * 32
+
+
+def takes_hip_lstm_layers(transform, layers, lstm, min_rows=None):
+    """``bilstm_layers(transform, layers, lstm)`` would run and is worth taking: the conditions of its raises, the answer of
+    ``ggcn_linear_pooled_layers_form`` and the measured row-count floor (``min_rows``, None: ``LAYERS_MIN_ROWS``; 0 for the
+    memory saving at any size -- ``bilstm_layers`` itself runs at every size) as a predicate.  No side effect (nothing is copied,
+    packed or launched); False for CPU tensors, bf16 layers, more than 16 layers, a layer that requires grad and a wanted
+    gradient."""
+    try:
+        if any(isinstance(x, torch.Tensor) and x.requires_grad for x in layers):
+            return False
+        _check_layers_call(transform, layers, lstm)
+    except (TypeError, RuntimeError):
+        return False
+    B, R, C = transform.shape
+    if B == 0 or R == 0 or C == 0:
+        return True                                          # served without the launch
+    if B * R < (LAYERS_MIN_ROWS if min_rows is None else min_rows):
+        return False
+    head, (B, R, C, Dl), _ = _pooled_args(transform, layers, real=False)
+    F = 8 * HIDDEN
+    fake = ctypes.c_void_p(256)                              # the form reads no device memory: an aligned stand-in for wpack and Y
+    return _capi.load_library().ggcn_linear_pooled_layers_form(*head, fake, fake, F, B, R, C, Dl, F) > 0
+
+
+def bilstm_layers(transform, layers, lstm):
+    """``bilstm(subword_pool_layers(transform, layers), lstm)`` bit for bit, without the pooled words: ``[B,T,2*128]`` float32
+    from ONE ``ggcn_linear_pooled_layers`` launch -- the bf16x3 projection on the module's cached image whose loader pools
+    BERT's layers where they lie, so that neither ``[B,L,n*Dl]`` nor ``[B,T,n*Dl]`` exists -- and one ``ggcn_bilstm_recurrence``
+    launch.  ``transform [B,T,L]`` float32 with any strides, ``layers``: 1..16 float32 tensors ``[B,L,Dl]`` of one shape and
+    device with ``n*Dl == lstm.input_size``; layers that do not share their strides are made contiguous first.  Forward only: a
+    wanted gradient raises, as do CPU tensors; the module's raises are ``bilstm``'s.  A layout the launch has no form for
+    (``Dl % 32 != 0``, rows off 16 bytes) raises with the library's message, which names the composed pair;
+    ``takes_hip_lstm_layers`` is the predicate.  ``B == 0`` or ``T == 0`` gives an empty tensor and ``L == 0`` the LSTM of zeros,
+    without the projection launch."""
+    _check_layers_call(transform, layers, lstm)
+    B, T, C = transform.shape
+    dev = layers[0].device
+    F = 8 * HIDDEN
+    y = torch.empty(B, T, 2 * HIDDEN, dtype=torch.float32, device=dev)
+    if B == 0 or T == 0:
+        return y
+    lib = _capi.load_library()
+    with torch.cuda.device(dev):
+        st = _capi.stream_of(dev)
+        pack, whh_f, whh_r, bias_f, bias_r = _operands(lstm, lib, st)
+        if C == 0:
+            g = torch.zeros(B * T, F, dtype=torch.float32, device=dev)       # the empty sums
+        else:
+            g = torch.empty(B * T, F, dtype=torch.float32, device=dev)
+            head, (B, T, C, Dl), keep = _pooled_args(transform, [x.detach() for x in layers], real=True)
+            _capi.check(lib.ggcn_linear_pooled_layers(*head, _capi.ptr(pack), _capi.ptr(g), F, B, T, C, Dl, F, st),
+                        "ggcn_linear_pooled_layers")
+            del keep
+        _capi.check(lib.ggcn_bilstm_recurrence(_capi.ptr(g), F, _capi.ptr(whh_f), _capi.ptr(whh_r), _capi.ptr(bias_f),
+                                               _capi.ptr(bias_r), _capi.ptr(y), 2 * HIDDEN, B, T, HIDDEN, st), "ggcn_bilstm_recurrence")
+    return y

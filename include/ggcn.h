@@ -950,6 +950,32 @@ int ggcn_anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int
                                  const int64_t *anchor, const int64_t *length, int sides,
                                  const float *Z, int64_t ldz, int64_t z_section,
                                  int B, int R, int C, int Dl);
+/* The bf16x3 linear on pooled layers: the BiLSTM's input projection (bert_amir5.py:610) read straight from BERT's layer list,
+ *   Y[b*R + r, f] = sum_l sum_k ( sum_c A[b,r,c] * X_l[b,c,k] ) * W[l*Dl + k, f],   ONE launch,
+ * so that neither the concatenation [B,C,n_layers*Dl] nor the pooled words [B,R,n_layers*Dl] exist.  A, its three element
+ * strides, layers (a HOST array of float32 device pointers, read during the call and passed by value: capture-safe), x_batch,
+ * ldx, C <= 2048: as ggcn_subword_pool_layers.  wpack: the ggcn_weight_pack(GGCN_PREC_BF16X3) image of the
+ * [K = n_layers*Dl, F] matrix W.  Y: float32, row b*R + r at Y + (b*R + r)*ldy; no bias.
+ * Arithmetic: a pooled value is formed as ggcn_subword_pool_layers forms it (from 0.0f, one float32 FMA per non-zero of the
+ * row of A in ascending c; an absent entry is skipped, so a NaN in a row of X that no row of A selects does not arrive), then
+ * split and multiplied as ggcn_linear(GGCN_PREC_BF16X3) does: Y is bit for bit that entry on the output of
+ * ggcn_subword_pool_layers.  A row of A with any number of non-zeros is taken (rows beyond the loader's fast capacity are
+ * slower, not different).
+ * GGCN_EINVAL: a NULL A, layers, layers[l], wpack or Y; n_layers < 1; B, R, C, Dl or F <= 0; ldx < Dl; ldy < F; a pointer not
+ * aligned to its element; wpack off 16 bytes.  GGCN_EUNSUPPORTED: n_layers > GGCN_POOL_MAX_LAYERS; C > 2048;
+ * B*R > INT32_MAX; more k-steps than ggcn_weight_pack takes (n_layers*Dl > 1048560); and the layouts the kernel has no form
+ * for -- Dl % 32 != 0; ldx, x_batch, F or ldy not a multiple of 4; a layer or Y off 16 bytes -- for which the caller takes
+ * ggcn_subword_pool_layers and ggcn_linear.  All before any launch. */
+int ggcn_linear_pooled_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
+                              const void *const *layers, int n_layers, int64_t x_batch, int64_t ldx,
+                              const void *wpack, float *Y, int64_t ldy,
+                              int B, int R, int C, int Dl, int F, ggcn_stream_t stream);
+/* host-only: 1 = the launch is taken, -ggcn_status where the entry would refuse (ggcn_last_error names
+ * ggcn_linear_pooled_layers); launches nothing and dereferences nothing on the device. */
+int ggcn_linear_pooled_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
+                                   const void *const *layers, int n_layers, int64_t x_batch, int64_t ldx,
+                                   const void *wpack, const float *Y, int64_t ldy,
+                                   int B, int R, int C, int Dl, int F);
 
 /* ---- bfloat16 features (training and inference under torch.autocast(dtype=torch.bfloat16)) ----------------------
  * X (the layer's input) in bfloat16; weights, bias, gates, `out`, pools and dW stay float32, dX is bfloat16 -- the
