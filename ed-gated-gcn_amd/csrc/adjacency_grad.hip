@@ -192,10 +192,16 @@ __global__ __launch_bounds__(256) void adjacency_grad_kernel(
 }
 
 }  // namespace
+}  // namespace ggcn
 
-int adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64_t ldh, const float *inv, const int32_t *rowptr,
-                   const int32_t *colidx, const float *vals, int B, int T, int F, float *d_adj, hipStream_t st)
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64_t ldh, const float *inv, const int32_t *rowptr,
+                        const int32_t *colidx, const float *vals, int B, int T, int F, float *d_adj, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_adjacency_grad";
     if (!dY) return fail(GGCN_EINVAL, "%s: dY is NULL", who);
     if (!hidden) return fail(GGCN_EINVAL, "%s: hidden is NULL", who);
@@ -234,4 +240,4 @@ int adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64_t ld
     return check_launch(who);
 }
 
-}  // namespace ggcn
+}  // extern "C"

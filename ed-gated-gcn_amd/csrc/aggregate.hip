@@ -738,12 +738,18 @@ int check_args(const void *Hd, int64_t ldh, const int32_t *rowptr, const int32_t
 }
 
 }  // namespace
+}  // namespace ggcn
 
-int aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,
-              const float *vals, const float *bias, int B, int T, int F, const float *store_gate,
-              const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-              float *pool_a, float *pool_b, hipStream_t st)
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,
+                   const float *vals, const float *bias, int B, int T, int F, const float *store_gate,
+                   const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
+                   float *pool_a, float *pool_b, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (int rc = check_args(Hd, ldh, rowptr, colidx, B, T, F, out, ldo, pool_a, pool_b)) return rc;
     const bool vec = (F % 4 == 0) && (ldh % 4 == 0) && aligned16(Hd) && (!out || ((ldo % 4 == 0) && aligned16(out))) &&
                      side_aligned(bias, store_gate, pool_gate_a, pool_gate_b);
@@ -754,9 +760,10 @@ int aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t
                             pool_gate_b, out, ldo, pool_a, pool_b, st);
 }
 
-int aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int K,
-                   float *Z, int64_t ldz, hipStream_t st)
+int ggcn_aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int K,
+                        float *Z, int64_t ldz, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_aggregate_bf16";
     if (!X || !rowptr || !colidx) return fail(GGCN_EINVAL, "%s: null input pointer", who);
     if (!Z) return fail(GGCN_EINVAL, "%s: null output pointer", who);
@@ -775,10 +782,11 @@ int aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int3
     return launch_bf16<1>(x, ldx, rowptr, colidx, vals, B, T, K, Z, ldz, st);
 }
 
-int aggregate_t(const float *G, int64_t ldg, const int32_t *rowptr_t, const int32_t *colidx_t,
-                const float *vals_t, const float *src_scale, int B, int T, int F, float *out, int64_t ldo,
-                hipStream_t st)
+int ggcn_aggregate_t(const float *G, int64_t ldg, const int32_t *rowptr_t, const int32_t *colidx_t,
+                     const float *vals_t, const float *src_scale, int B, int T, int F, float *out, int64_t ldo,
+                     ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (int rc = check_args(G, ldg, rowptr_t, colidx_t, B, T, F, out, ldo, nullptr, nullptr)) return rc;
     if (!src_scale || !out) return fail(GGCN_EINVAL, "ggcn_aggregate_t: null pointer");
     const bool vec = (F % 4 == 0) && (ldg % 4 == 0) && aligned16(G) && (ldo % 4 == 0) && aligned16(out);
@@ -786,18 +794,20 @@ int aggregate_t(const float *G, int64_t ldg, const int32_t *rowptr_t, const int3
                : launch_t<1>(G, ldg, rowptr_t, colidx_t, vals_t, src_scale, B, T, F, out, ldo, st);
 }
 
-int inv_denominators(const int32_t *rowptr, const float *vals, int64_t n, float *inv, hipStream_t st)
+int ggcn_inv_denominators(const int32_t *rowptr, const float *vals, int64_t n, float *inv, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!rowptr || !inv || n <= 0) return fail(GGCN_EINVAL, "ggcn_inv_denominators: bad argument");
     hipLaunchKernelGGL(inv_denominator_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rowptr, vals, n, inv);
     return check_launch("ggcn_inv_denominators");
 }
 
-int aggregate_h(const void *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,
-                const float *vals, const float *bias, int B, int T, int F, const float *store_gate,
-                const float *pool_gate_a, const float *pool_gate_b, void *out, int64_t ldo,
-                float *pool_a, float *pool_b, hipStream_t st)
+int ggcn_aggregate_h(const void *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,
+                     const float *vals, const float *bias, int B, int T, int F, const float *store_gate,
+                     const float *pool_gate_a, const float *pool_gate_b, void *out, int64_t ldo,
+                     float *pool_a, float *pool_b, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (int rc = check_args(Hd, ldh, rowptr, colidx, B, T, F, out, ldo, pool_a, pool_b)) return rc;
     const __half *h = static_cast<const __half *>(Hd);
     __half *o = static_cast<__half *>(out);
@@ -828,4 +838,4 @@ int aggregate_h(const void *Hd, int64_t ldh, const int32_t *rowptr, const int32_
                              pool_gate_b, o, ldo, pool_a, pool_b, st);
 }
 
-}  // namespace ggcn
+}  // extern "C"

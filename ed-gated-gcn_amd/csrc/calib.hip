@@ -112,13 +112,20 @@ __global__ __launch_bounds__(256, 2) void mfma_calib_kernel(int stages, unsigned
 }
 
 }  // namespace
+}  // namespace ggcn
 
-int mfma_calibrate(int n_wg, int stages, unsigned long long *stamps, float *sink, hipStream_t st)
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_debug_mfma_calibrate(int n_wg, int stages, uint64_t *stamps64, float *sink, ggcn_stream_t stream)
 {
+    unsigned long long *stamps = reinterpret_cast<unsigned long long *>(stamps64);
+    const hipStream_t st = as_stream(stream);
     if (n_wg <= 0 || stages <= 0 || stages > (1 << 20))
         return fail(GGCN_EINVAL, "ggcn_debug_mfma_calibrate: n_wg=%d stages=%d must be positive", n_wg, stages);
     hipLaunchKernelGGL(mfma_calib_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, stages, stamps, sink);
     return check_launch("ggcn_debug_mfma_calibrate");
 }
 
-}  // namespace ggcn
+}  // extern "C"

@@ -1,6 +1,11 @@
 // extern "C" surface of libggcn_hip.so -- see include/ggcn.h for the contract.
 // Argument checking lives here and in the per-kernel launchers; nothing in this
 // library allocates, frees, copies to the host or synchronises.
+// Defined here: the entries that have checks, a dispatch between launchers or a description (FusedArgs, DropSpec) of their own --
+// the one-launch layers and blocks, the ggcn_linear* family and ggcn_linear_form, ggcn_dweight, the gate / pool backward entries that
+// share a launcher, ggcn_dense_head[_signal], the *_bytes computed inline, ggcn_block_fused_form and ggcn_range_flag with its registry
+// -- and the library's own (ggcn_abi_version, ggcn_has_f16mx6, ggcn_last_error).  Every other entry IS its launcher: it is defined
+// extern "C" beside its kernels, at the end of that .hip file.
 // The one-launch entries (ggcn_layer_fused*, ggcn_block_fused*, ggcn_lab_block_fused8, ggcn_debug_block_fused_stamped) check here
 // only what is their own -- the graph sizes they take, the operands only they have, what must be looked at before it narrows into a
 // field -- and write their arguments into a FusedArgs (fused_args.h) by name.  Everything else is checked once, on that description:
@@ -25,6 +30,30 @@ int fail(int code, const char *fmt, ...)
     vsnprintf(error_buffer(), 512, fmt, ap);
     va_end(ap);
     return code;
+}
+
+namespace {
+// The readers of the f16mx8 range flag, one per translation unit that holds a copy (GGCN_RANGE_FLAG_TU, f16mx8_core.h).  They
+// register while the library loads, in no order this file may rely on: hence a function-local static, and no allocation.
+constexpr int kMaxRangeFlagReaders = 16;
+struct RangeFlagReaders {
+    RangeFlagReader reader[kMaxRangeFlagReaders];
+    int count;
+    bool overflow;   // a registration found the array full: every ggcn_range_flag call says so
+};
+RangeFlagReaders &registered_readers()
+{
+    static RangeFlagReaders r = {};
+    return r;
+}
+}  // namespace
+
+int register_range_flag_reader(RangeFlagReader reader)
+{
+    RangeFlagReaders &r = registered_readers();
+    if (r.count < kMaxRangeFlagReaders) r.reader[r.count++] = reader;
+    else r.overflow = true;
+    return r.count;
 }
 
 }  // namespace ggcn
@@ -91,53 +120,9 @@ int ggcn_has_f16mx6(void)
 
 const char *ggcn_last_error(void) { return error_buffer(); }
 
-size_t ggcn_csr_workspace_bytes(int64_t n_rows) { return csr_workspace_bytes(n_rows); }
-
-int ggcn_csr_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t stride_b,
-                        int64_t stride_r, int64_t stride_c, int32_t *rowptr, int32_t *colidx,
-                        float *vals, int64_t capacity, uint32_t *rowmask, int32_t *flags,
-                        void *workspace, ggcn_stream_t stream)
-{
-    return csr_from_dense(adj, adj_dtype, B, T, stride_b, stride_r, stride_c, rowptr, colidx, vals,
-                          capacity, rowmask, flags, workspace, as_stream(stream));
-}
-
-int ggcn_csr_transpose(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T,
-                       int32_t *rowptr_t, int32_t *colidx_t, float *vals_t, void *workspace, ggcn_stream_t stream)
-{
-    return csr_transpose(rowptr, colidx, vals, B, T, rowptr_t, colidx_t, vals_t, workspace, as_stream(stream));
-}
-
-int ggcn_rowmask_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t stride_b, int64_t stride_r,
-                            int64_t stride_c, uint32_t *rowmask, int32_t *flags, ggcn_stream_t stream)
-{
-    return rowmask_from_dense(adj, adj_dtype, B, T, stride_b, stride_r, stride_c, rowmask, flags, as_stream(stream));
-}
-
-int ggcn_csr_rowmask(const int32_t *rowptr, const int32_t *colidx, int B, int T, uint32_t *rowmask,
-                     ggcn_stream_t stream)
-{
-    return csr_rowmask(rowptr, colidx, B, T, rowmask, as_stream(stream));
-}
-
 size_t ggcn_graph_operands_bytes(int B) { return B > 0 ? (size_t)B * GGCN_GRAPH_OPS_BYTES : 0; }
 size_t ggcn_graph_operands2_bytes(int B) { return B > 0 ? (size_t)B * GGCN_GRAPH_OPS2_BYTES : 0; }
-int ggcn_graph_operands2(const uint32_t *rowmask, int B, int T, int plane, void *graph_ops2, ggcn_stream_t stream)
-{
-    return graph_operands2(rowmask, B, T, plane, graph_ops2, as_stream(stream));
-}
-
 size_t ggcn_graph_edge_lists_bytes(int B) { return B > 0 ? (size_t)B * GGCN_EDGE_LISTS_BYTES : 0; }
-
-int ggcn_graph_edge_lists(const uint32_t *rowmask, int B, int T, void *lists, ggcn_stream_t stream)
-{
-    return graph_edge_lists(rowmask, B, T, lists, as_stream(stream));
-}
-
-int ggcn_graph_operands(const uint32_t *rowmask, int B, int T, void *graph_ops, ggcn_stream_t stream)
-{
-    return graph_operands(rowmask, B, T, graph_ops, as_stream(stream));
-}
 
 int ggcn_layer_fused(const float *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops,
                      const float *bias, int B, int T, int K, int F, const float *store_gate,
@@ -176,12 +161,6 @@ int ggcn_layer_fused_prebias(const float *X, int64_t ldx, const void *wpack, con
     return launch_fused(who, a, precision, as_stream(stream));
 }
 
-int ggcn_graph_operands_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane,
-                                 void *graph_opsw, int32_t *flag, ggcn_stream_t stream)
-{
-    return graph_operands_weighted(rowptr, colidx, vals, B, T, plane, graph_opsw, flag, as_stream(stream));
-}
-
 int ggcn_layer_fused_weighted(const float *X, int64_t ldx, const void *wpack, const void *graph_opsw, const float *bias,
                               const float *zero_mid, int B, int T, int K, int F, const float *store_gate,
                               const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo, float *pool_a,
@@ -204,14 +183,6 @@ int ggcn_layer_fused_weighted(const float *X, int64_t ldx, const void *wpack, co
     l.wpack = bytes(wpack); l.bias = bias; l.mid = zero_mid; l.store_gate = store_gate; l.pool_gate_a = pool_gate_a; l.pool_gate_b = pool_gate_b;
     l.out = out; l.ldo = (int)ldo; l.pool_a = pool_a; l.pool_b = pool_b; l.ov_partial = overlap_partial;
     return launch_fused(who, a, precision, as_stream(stream));
-}
-
-size_t ggcn_graph_operands_weighted_wide_bytes(int B, int T) { return graph_operands_weighted_wide_bytes(B, T); }
-
-int ggcn_graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *graph_opsww,
-                                      int32_t *flag, ggcn_stream_t stream)
-{
-    return graph_operands_weighted_wide(rowptr, colidx, vals, B, T, graph_opsww, flag, as_stream(stream));
 }
 
 int ggcn_layer_fused_weighted_wide(const float *X, int64_t ldx, const void *wpack, const void *graph_opsww, const float *bias,
@@ -309,12 +280,6 @@ int ggcn_block_fused(const float *X, int64_t ldx, const void *wpack1, const void
     return launch_block(who, a, kBlockBinary, precision, as_stream(stream));
 }
 
-int ggcn_graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane,
-                                  void *graph_ops2w, int32_t *flag, ggcn_stream_t stream)
-{
-    return graph_operands2_weighted(rowptr, colidx, vals, B, T, plane, graph_ops2w, flag, as_stream(stream));
-}
-
 int ggcn_block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_opsw,
                               const void *graph_ops2w, const float *bias1, const float *bias_mid, const float *bias2,
                               const float *zero_mid, int B, int T, int K, int F, const float *gate1, const float *gate2, float *gcn1,
@@ -335,38 +300,6 @@ int ggcn_block_fused_weighted(const float *X, int64_t ldx, const void *wpack1, c
     l2.wpack = bytes(wpack12); l2.bias = bias2; l2.mid = bias_mid; l2.store_gate = gate2; l2.pool_gate_a = gate2;
     l2.out = x_out; l2.ldo = (int)ld2; l2.pool_a = pool_out;
     return launch_block(who, a, kBlockWeighted, precision, as_stream(stream));
-}
-
-int ggcn_overlap_reduce(const float *partials, int B, int F, float *xy, ggcn_stream_t stream)
-{
-    return overlap_reduce(partials, B, F, xy, as_stream(stream));
-}
-
-size_t ggcn_weight_pack_bytes(int K, int F, int precision) { return weight_pack_bytes(K, F, precision); }
-
-int ggcn_weight_pack(const float *W, int64_t ldw, int K, int F, int precision, int transposed, void *wpack,
-                     ggcn_stream_t stream)
-{
-    return weight_pack(W, ldw, K, F, precision, transposed != 0, wpack, as_stream(stream));
-}
-
-int ggcn_aggregate_t(const float *G, int64_t ldg, const int32_t *rowptr_t, const int32_t *colidx_t,
-                     const float *vals_t, const float *src_scale, int B, int T, int F, float *out, int64_t ldo,
-                     ggcn_stream_t stream)
-{
-    return aggregate_t(G, ldg, rowptr_t, colidx_t, vals_t, src_scale, B, T, F, out, ldo, as_stream(stream));
-}
-
-int ggcn_inv_denominators(const int32_t *rowptr, const float *vals, int64_t n_rows, float *inv,
-                          ggcn_stream_t stream)
-{
-    return inv_denominators(rowptr, vals, n_rows, inv, as_stream(stream));
-}
-
-int ggcn_adjacency_grad(const float *dY, int64_t ldy, const float *hidden, int64_t ldh, const float *inv, const int32_t *rowptr,
-                        const int32_t *colidx, const float *vals, int B, int T, int F, float *d_adj, ggcn_stream_t stream)
-{
-    return adjacency_grad(dY, ldy, hidden, ldh, inv, rowptr, colidx, vals, B, T, F, d_adj, as_stream(stream));
 }
 
 int ggcn_linear(const float *X, int64_t ldx, const float *W, int64_t ldw, const void *wpack, float *Y,
@@ -496,21 +429,6 @@ int ggcn_block_fused_bf16(const void *X, int64_t ldx, const void *wpack1, const 
     return launch_block(who, a, kBlockBf16, GGCN_PREC_BF16X3, as_stream(stream));
 }
 
-int ggcn_aggregate_bf16(const void *X, int64_t ldx, const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T,
-                        int K, float *Z, int64_t ldz, ggcn_stream_t stream)
-{
-    return aggregate_bf16(X, ldx, rowptr, colidx, vals, B, T, K, Z, ldz, as_stream(stream));
-}
-
-int ggcn_aggregate(const float *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,
-                   const float *vals, const float *bias, int B, int T, int F, const float *store_gate,
-                   const float *pool_gate_a, const float *pool_gate_b, float *out, int64_t ldo,
-                   float *pool_a, float *pool_b, ggcn_stream_t stream)
-{
-    return aggregate(Hd, ldh, rowptr, colidx, vals, bias, B, T, F, store_gate, pool_gate_a, pool_gate_b,
-                     out, ldo, pool_a, pool_b, as_stream(stream));
-}
-
 int ggcn_linear_h(const void *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy, int64_t M, int K, int F,
                   int precision, ggcn_stream_t stream)
 {
@@ -518,24 +436,6 @@ int ggcn_linear_h(const void *X, int64_t ldx, const void *wpack, void *Y, int64_
         return fail(GGCN_EUNSUPPORTED, "ggcn_linear_h: precision %d (use bf16x3, f16mx8 or f16)", precision);
     if (int rc = linear_entry_checks("ggcn_linear_h", !X || !Y, M, K, F, ldx, ldy)) return rc;
     return linear_packed_h(X, ldx, wpack, Y, ldy, M, K, F, precision, as_stream(stream));
-}
-
-int ggcn_aggregate_h(const void *Hd, int64_t ldh, const int32_t *rowptr, const int32_t *colidx,
-                     const float *vals, const float *bias, int B, int T, int F, const float *store_gate,
-                     const float *pool_gate_a, const float *pool_gate_b, void *out, int64_t ldo,
-                     float *pool_a, float *pool_b, ggcn_stream_t stream)
-{
-    return aggregate_h(Hd, ldh, rowptr, colidx, vals, bias, B, T, F, store_gate, pool_gate_a, pool_gate_b, out,
-                       ldo, pool_a, pool_b, as_stream(stream));
-}
-
-int ggcn_layer_fused_h(const void *X, int64_t ldx, const void *wpack, const int32_t *rowptr, const int32_t *colidx,
-                       const float *vals, const float *bias, int B, int T, int K, int F, const float *store_gate,
-                       const float *pool_gate_a, const float *pool_gate_b, void *out, int64_t ldo, float *pool_a,
-                       float *pool_b, ggcn_stream_t stream)
-{
-    return layer_fused_h(X, ldx, wpack, rowptr, colidx, vals, bias, B, T, K, F, store_gate, pool_gate_a, pool_gate_b,
-                         out, ldo, pool_a, pool_b, as_stream(stream));
 }
 
 int ggcn_gate_pool_backward(const float *out, int64_t ldo, const float *store_gate, const float *gate_a,
@@ -641,28 +541,6 @@ int ggcn_lab_block_fused8(const float *X, int64_t ldx, const void *wpack1, const
     return block_fused8("ggcn_lab_block_fused8", a, flags, as_stream(stream));
 }
 
-int ggcn_rowmask_transpose(const uint32_t *rowmask, int B, int T, uint32_t *rowmask_t, ggcn_stream_t stream)
-{
-    return rowmask_transpose(rowmask, B, T, rowmask_t, as_stream(stream));
-}
-
-int ggcn_gate_pool_backward_mma(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
-                                const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops,
-                                const void *graph_ops_t, int B, int T, int F, float *dH, int64_t ldh, float *d_sg, float *d_ga,
-                                float *d_gb, float *d_bsum, float *dh_amax, ggcn_stream_t stream)
-{
-    return gate_pool_backward_mma(out, ldo, store_gate, gate_a, gate_b, d_out, ldd, d_pa, d_pb, graph_ops, graph_ops_t, B, T, F, dH, ldh,
-                                  d_sg, d_ga, d_gb, d_bsum, dh_amax, as_stream(stream));
-}
-
-size_t ggcn_graph_operands_weighted_t_bytes(int B) { return graph_operands_weighted_t_bytes(B); }
-
-int ggcn_graph_operands_weighted_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *graph_ops_wt,
-                                   int32_t *flag, ggcn_stream_t stream)
-{
-    return graph_operands_weighted_t(rowptr, colidx, vals, B, T, graph_ops_wt, flag, as_stream(stream));
-}
-
 int ggcn_gate_pool_backward_weighted(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
                                      const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wt,
                                      const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
@@ -670,43 +548,6 @@ int ggcn_gate_pool_backward_weighted(const float *out, int64_t ldo, const float 
 {
     return gate_pool_backward_weighted(out, ldo, store_gate, gate_a, gate_b, d_out, ldd, d_pa, d_pb, graph_ops_wt, inv, B, T, F, dH, ldh,
                                        dY, ldy, d_sg, d_ga, d_gb, d_bsum, as_stream(stream));
-}
-
-int ggcn_rowmask_transpose_wide(const uint32_t *rowmask, int B, int T, uint32_t *rowmask_t, ggcn_stream_t stream)
-{
-    return rowmask_transpose_wide(rowmask, B, T, rowmask_t, as_stream(stream));
-}
-
-int ggcn_gate_pool_backward_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
-                                 const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const uint32_t *rowmask_t,
-                                 const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *d_sg, float *d_ga, float *d_gb,
-                                 float *d_bsum, ggcn_stream_t stream)
-{
-    return gate_pool_backward_wide(out, ldo, store_gate, gate_a, gate_b, d_out, ldd, d_pa, d_pb, rowmask_t, inv, B, T, F, dH, ldh, d_sg,
-                                   d_ga, d_gb, d_bsum, as_stream(stream));
-}
-
-size_t ggcn_graph_operands_weighted_wide_t_bytes(int B, int T) { return graph_operands_weighted_wide_t_bytes(B, T); }
-
-int ggcn_graph_operands_weighted_wide_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *graph_ops_wwt,
-                                        int32_t *flag, ggcn_stream_t stream)
-{
-    return graph_operands_weighted_wide_t(rowptr, colidx, vals, B, T, graph_ops_wwt, flag, as_stream(stream));
-}
-
-int ggcn_gate_pool_backward_weighted_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
-                                          const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wwt,
-                                          const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
-                                          float *d_ga, float *d_gb, float *d_bsum, ggcn_stream_t stream)
-{
-    return gate_pool_backward_weighted_wide(out, ldo, store_gate, gate_a, gate_b, d_out, ldd, d_pa, d_pb, graph_ops_wwt, inv, B, T, F, dH,
-                                            ldh, dY, ldy, d_sg, d_ga, d_gb, d_bsum, as_stream(stream));
-}
-
-int ggcn_linear_scaled(const float *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F,
-                       const float *amax, ggcn_stream_t stream)
-{
-    return linear_scaled(X, ldx, wpack, Y, ldy, M, K, F, amax, as_stream(stream));
 }
 
 int ggcn_layer_fused_drop(const float *X, int64_t ldx, const void *wpack, const uint32_t *rowmask, const void *graph_ops,
@@ -727,18 +568,6 @@ int ggcn_layer_fused_drop(const float *X, int64_t ldx, const void *wpack, const 
     return launch_fused(who, a, precision, as_stream(stream));
 }
 
-int ggcn_dropout_mask(int64_t rows, int F, float p, uint64_t seed, int stream_id, float *mask, ggcn_stream_t stream)
-{
-    return dropout_mask(rows, F, p, seed, stream_id, mask, as_stream(stream));
-}
-
-size_t ggcn_colsum_workspace_bytes(int F) { return colsum_workspace_bytes(F); }
-
-int ggcn_colsum(const float *X, int64_t ld, int64_t M, int F, float *out, void *workspace, ggcn_stream_t stream)
-{
-    return colsum(X, ld, M, F, out, workspace, as_stream(stream));
-}
-
 size_t ggcn_dweight_workspace_bytes(int64_t n_rows, int K, int F, int precision)
 {
     return precision == GGCN_PREC_FP32 ? dweight_workspace_bytes(n_rows, K, F) : dweight_bx3_workspace_bytes(n_rows, K, F);
@@ -752,86 +581,6 @@ int ggcn_dweight(const float *X, int64_t ldx, const float *dH, int64_t ldg, int6
     if (precision != GGCN_PREC_BF16X3)
         return fail(GGCN_EUNSUPPORTED, "ggcn_dweight: precision %d (gradients need fp32 range: use bf16x3 or fp32)", precision);
     return dweight_bx3(X, ldx, dH, ldg, n_rows, K, F, dW, lddw, workspace, as_stream(stream));
-}
-
-size_t ggcn_dweight_bf16_workspace_bytes(int64_t n_rows, int K, int F) { return dweight_bf16_workspace_bytes(n_rows, K, F); }
-
-int ggcn_dweight_bf16(const void *X, int64_t ldx, const float *dH, int64_t ldg, int64_t n_rows, int K, int F, float *dW,
-                      int64_t lddw, void *workspace, ggcn_stream_t stream)
-{
-    if (X && reinterpret_cast<uintptr_t>(X) % 2) return fail(GGCN_EINVAL, "ggcn_dweight_bf16: X not 2-byte aligned");
-    return dweight_bf16(X, ldx, dH, ldg, n_rows, K, F, dW, lddw, workspace, as_stream(stream));
-}
-
-int ggcn_subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *X, int64_t x_batch,
-                           int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D,
-                           ggcn_stream_t stream)
-{
-    return subword_pool_bf16(A, sa_b, sa_r, sa_c, X, x_batch, ldx, Y, y_batch, ldy, B, R, C, D, as_stream(stream));
-}
-
-int ggcn_subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const float *X, int64_t x_batch,
-                      int64_t ldx, float *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D,
-                      ggcn_stream_t stream)
-{
-    return subword_pool(A, sa_b, sa_r, sa_c, X, x_batch, ldx, Y, y_batch, ldy, B, R, C, D, as_stream(stream));
-}
-
-int ggcn_subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                             int is_bf16, int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C,
-                             int Dl, ggcn_stream_t stream)
-{
-    return subword_pool_layers(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, Y, y_batch, ldy, B, R, C, Dl,
-                               as_stream(stream));
-}
-
-int ggcn_subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers,
-                                  int n_layers, int is_bf16, int64_t x_batch, int64_t ldx, const void *Y, int64_t y_batch,
-                                  int64_t ldy, int B, int R, int C, int Dl)
-{
-    return subword_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, Y, y_batch, ldy, B, R, C, Dl);
-}
-
-int ggcn_anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                            int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
-                            float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl, ggcn_stream_t stream)
-{
-    return anchor_pool_layers(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, anchor, length, sides, Z, ldz, z_section,
-                              B, R, C, Dl, as_stream(stream));
-}
-
-int ggcn_anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                                 int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
-                                 const float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl)
-{
-    return anchor_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, anchor, length, sides, Z, ldz,
-                                   z_section, B, R, C, Dl);
-}
-
-int ggcn_linear_pooled_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                              int64_t x_batch, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int B, int R, int C, int Dl,
-                              int F, ggcn_stream_t stream)
-{
-    return linear_pooled_layers(A, sa_b, sa_r, sa_c, layers, n_layers, x_batch, ldx, wpack, Y, ldy, B, R, C, Dl, F, as_stream(stream));
-}
-
-int ggcn_linear_pooled_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                                   int64_t x_batch, int64_t ldx, const void *wpack, const float *Y, int64_t ldy, int B, int R, int C,
-                                   int Dl, int F)
-{
-    return linear_pooled_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, x_batch, ldx, wpack, Y, ldy, B, R, C, Dl, F);
-}
-
-int ggcn_absmax(const void *X, int is_half, int64_t ld, int64_t M, int K, float *out, ggcn_stream_t stream)
-{
-    return absmax(X, is_half, ld, M, K, out, as_stream(stream));
-}
-
-int ggcn_debug_poison_lds(uint32_t pattern, ggcn_stream_t stream) { return poison_lds(pattern, as_stream(stream)); }
-
-int ggcn_debug_mfma_calibrate(int n_wg, int stages, uint64_t *stamps, float *sink, ggcn_stream_t stream)
-{
-    return mfma_calibrate(n_wg, stages, reinterpret_cast<unsigned long long *>(stamps), sink, as_stream(stream));
 }
 
 int ggcn_debug_block_fused_stamped(const float *X, int64_t ldx, const void *wpack1, const void *wpack12, const void *graph_ops,
@@ -858,73 +607,14 @@ int ggcn_debug_block_fused_stamped(const float *X, int64_t ldx, const void *wpac
 int ggcn_range_flag(uint32_t *flag, int clear, ggcn_stream_t stream)
 {
     if (!flag) return fail(GGCN_EINVAL, "ggcn_range_flag: null flag pointer");
+    const RangeFlagReaders &r = registered_readers();
+    if (r.overflow)
+        return fail(GGCN_EINVAL, "ggcn_range_flag: more than %d translation units registered a reader of the range flag (kMaxRangeFlagReaders)",
+                    kMaxRangeFlagReaders);
     // one copy of the flag per translation unit that holds an f16mx8 main loop
-    int rc = range_flag_linear(flag, clear, as_stream(stream));
-    rc = rc ? rc : range_flag_fused(flag, clear, as_stream(stream));
-    rc = rc ? rc : range_flag_wide(flag, clear, as_stream(stream));
-    rc = rc ? rc : range_flag_wide8(flag, clear, as_stream(stream));
-    rc = rc ? rc : range_flag_block8(flag, clear, as_stream(stream));
-    rc = rc ? rc : range_flag_weighted_drop(flag, clear, as_stream(stream));
-#ifdef GGCN_WITH_F16MX6
-    rc = rc ? rc : range_flag_fused6(flag, clear, as_stream(stream));
-#endif
+    int rc = GGCN_OK;
+    for (int i = 0; i < r.count && !rc; ++i) rc = r.reader[i](flag, clear, as_stream(stream));
     return rc;
-}
-
-int ggcn_transpose(const float *W, int rows, int cols, int64_t ldw, float *Wt, ggcn_stream_t stream)
-{
-    return transpose_f32(W, rows, cols, ldw, Wt, as_stream(stream));
-}
-
-int ggcn_gate_mlp(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a,
-                  const float *w2t_a, const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b,
-                  const float *w2t_b, const float *b2_b, float *gate_b, ggcn_stream_t stream)
-{
-    return gate_mlp(aspect, lda, B, H, w1t_a, b1_a, w2t_a, b2_a, gate_a, w1t_b, b1_b, w2t_b, b2_b, gate_b, as_stream(stream));
-}
-
-int ggcn_gate_mlp_save(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a,
-                       const float *w2t_a, const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b,
-                       const float *w2t_b, const float *b2_b, float *gate_b, float *hid_a, float *hid_b, ggcn_stream_t stream)
-{
-    return gate_mlp_save(aspect, lda, B, H, w1t_a, b1_a, w2t_a, b2_a, gate_a, w1t_b, b1_b, w2t_b, b2_b, gate_b, hid_a, hid_b,
-                         as_stream(stream));
-}
-
-int ggcn_gate_mlp_backward(const float *aspect, int64_t lda, int B, int H, const float *w1_a, const float *w2_a, const float *hid_a,
-                           const float *gate_a, const float *d_gate_a, const float *w1_b, const float *w2_b, const float *hid_b,
-                           const float *gate_b, const float *d_gate_b, float *d_aspect, int64_t ldda, float *Z, int64_t ldz,
-                           ggcn_stream_t stream)
-{
-    return gate_mlp_backward(aspect, lda, B, H, w1_a, w2_a, hid_a, gate_a, d_gate_a, w1_b, w2_b, hid_b, gate_b, d_gate_b, d_aspect, ldda,
-                             Z, ldz, as_stream(stream));
-}
-
-int ggcn_scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
-                     const float *fc_weight, int64_t ldw, const float *fc_bias, const float *dist, int64_t ldd, int B,
-                     int T, int H, int C, float *scores, int64_t ld_scores, float *kl_part, ggcn_stream_t stream)
-{
-    return scores_head(X, ldx, aspect, lda, logits, ldl, fc_weight, ldw, fc_bias, dist, ldd, B, T, H, C, scores, ld_scores,
-                       kl_part, as_stream(stream));
-}
-
-int ggcn_scores_head_backward(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
-                              const float *fc_weight, int64_t ldw, const float *fc_bias, const float *dist, int64_t ldd,
-                              const float *scores, int64_t ld_scores, const float *kl_part, const float *g_scores, int64_t ld_gs,
-                              const float *g_kl, int B, int T, int H, int C, float *dX, int64_t lddx, float *d_aspect, int64_t ldda,
-                              float *d_logits, int64_t lddl, float *G, int64_t ldg, float *dc0, ggcn_stream_t stream)
-{
-    return scores_head_backward(X, ldx, aspect, lda, logits, ldl, fc_weight, ldw, fc_bias, dist, ldd, scores, ld_scores, kl_part,
-                                g_scores, ld_gs, g_kl, B, T, H, C, dX, lddx, d_aspect, ldda, d_logits, lddl, G, ldg, dc0,
-                                as_stream(stream));
-}
-
-size_t ggcn_scores_head_dweight_workspace_bytes(int B, int H, int C) { return scores_head_dweight_workspace_bytes(B, H, C); }
-
-int ggcn_scores_head_dweight(const float *logits, int64_t ldl, const float *G, int64_t ldg, const float *dc0, int B, int H, int C,
-                             float *dW, int64_t lddw, float *d_bias, void *workspace, ggcn_stream_t stream)
-{
-    return scores_head_dweight(logits, ldl, G, ldg, dc0, B, H, C, dW, lddw, d_bias, workspace, as_stream(stream));
 }
 
 int ggcn_dense_head(const float *pooled, int64_t ldp, const float *Wt, int64_t ldw, const float *bias, int B, int H, int C,
@@ -939,14 +629,6 @@ int ggcn_dense_head_signal(const float *pooled, int64_t ldp, const float *Wt, in
 {
     if (!signal) return fail(GGCN_EINVAL, "ggcn_dense_head_signal: null signal words (ggcn_dense_head is the plain form)");
     return dense_head(pooled, ldp, Wt, ldw, bias, B, H, C, logits, ldl, overlap_partials, F_block, xy, as_stream(stream), signal);
-}
-
-size_t ggcn_overlap_workspace_bytes(int B) { return overlap_workspace_bytes(B); }
-
-int ggcn_gate_overlap(const float *x1, const float *y1, int B, int F, float *xy, void *workspace,
-                      ggcn_stream_t stream)
-{
-    return gate_overlap(x1, y1, B, F, xy, workspace, as_stream(stream));
 }
 
 }  // extern "C"

@@ -277,10 +277,16 @@ __global__ __launch_bounds__(256) void csr_transpose_kernel(const int32_t *__res
 }
 
 }  // namespace
+}  // namespace ggcn
 
-int csr_transpose(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int32_t *rowptr_t,
-                  int32_t *colidx_t, float *vals_t, void *workspace, hipStream_t st)
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_csr_transpose(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int32_t *rowptr_t,
+                       int32_t *colidx_t, float *vals_t, void *workspace, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!rowptr || !colidx || !rowptr_t || !colidx_t || !workspace) return fail(GGCN_EINVAL, "ggcn_csr_transpose: null pointer");
     if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_csr_transpose: B=%d T=%d must be positive", B, T);
     if ((vals != nullptr) != (vals_t != nullptr))
@@ -290,16 +296,17 @@ int csr_transpose(const int32_t *rowptr, const int32_t *colidx, const float *val
     return check_launch("ggcn_csr_transpose");
 }
 
-size_t csr_workspace_bytes(int64_t n_rows)
+size_t ggcn_csr_workspace_bytes(int64_t n_rows)
 {
     if (n_rows < 0) return 0;
     const int64_t tiles = (n_rows + kScanTile - 1) / kScanTile;
     return (size_t)(tiles > 0 ? tiles : 1) * sizeof(int32_t);
 }
 
-int rowmask_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t sb, int64_t sr, int64_t sc,
-                       uint32_t *rowmask, int32_t *flags, hipStream_t st)
+int ggcn_rowmask_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t sb, int64_t sr, int64_t sc,
+                            uint32_t *rowmask, int32_t *flags, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!adj || !rowmask) return fail(GGCN_EINVAL, "ggcn_rowmask_from_dense: null pointer");
     if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_rowmask_from_dense: B=%d T=%d must be positive", B, T);
     if (T > GGCN_MASK_MAX_T)
@@ -315,10 +322,11 @@ int rowmask_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t sb,
     }
 }
 
-int csr_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t sb, int64_t sr, int64_t sc,
-                   int32_t *rowptr, int32_t *colidx, float *vals, int64_t capacity, uint32_t *rowmask,
-                   int32_t *flags, void *workspace, hipStream_t st)
+int ggcn_csr_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t sb, int64_t sr, int64_t sc,
+                        int32_t *rowptr, int32_t *colidx, float *vals, int64_t capacity, uint32_t *rowmask,
+                        int32_t *flags, void *workspace, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (rowmask && T > GGCN_MASK_MAX_T)
         return fail(GGCN_EUNSUPPORTED, "ggcn_csr_from_dense: row masks need T <= %d, got T=%d", GGCN_MASK_MAX_T, T);
     if (!adj || !rowptr || !colidx || !workspace)
@@ -339,4 +347,4 @@ int csr_from_dense(const void *adj, int adj_dtype, int B, int T, int64_t sb, int
     }
 }
 
-}  // namespace ggcn
+}  // extern "C"

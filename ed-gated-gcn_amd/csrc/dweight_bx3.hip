@@ -190,7 +190,13 @@ int dweight_bx3(const float *X, int64_t ldx, const float *G, int64_t ldg, int64_
     return check_launch("ggcn_dweight(bf16x3)");
 }
 
-size_t dweight_bf16_workspace_bytes(int64_t N, int K, int F)
+}  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
+
+size_t ggcn_dweight_bf16_workspace_bytes(int64_t N, int K, int F)
 {
     if (N <= 0 || K <= 0 || F <= 0) return 0;
     const Plan p = plan_for(N, K, F, sizeof(__bf16));
@@ -199,9 +205,11 @@ size_t dweight_bf16_workspace_bytes(int64_t N, int K, int F)
 
 // bf16 features: the transposed form above with Xt in bf16 -- its rows go to LDS as the single hi plane of the main loop (two
 // MFMAs per product); dH keeps its hi/lo image, so the bound is the fp32 ggcn_dweight's
-int dweight_bf16(const void *Xv, int64_t ldx, const float *G, int64_t ldg, int64_t N, int K, int F, float *dW,
-                 int64_t lddw, void *workspace, hipStream_t st)
+int ggcn_dweight_bf16(const void *Xv, int64_t ldx, const float *G, int64_t ldg, int64_t N, int K, int F, float *dW,
+                      int64_t lddw, void *workspace, ggcn_stream_t stream)
 {
+    if (Xv && reinterpret_cast<uintptr_t>(Xv) % 2) return fail(GGCN_EINVAL, "ggcn_dweight_bf16: X not 2-byte aligned");
+    const hipStream_t st = as_stream(stream);
     const __bf16 *X = static_cast<const __bf16 *>(Xv);
     if (!X || !G || !dW || !workspace) return fail(GGCN_EINVAL, "ggcn_dweight_bf16: null pointer");
     if (N <= 0 || K <= 0 || F <= 0) return fail(GGCN_EINVAL, "ggcn_dweight_bf16: N=%lld K=%d F=%d must be positive", (long long)N, K, F);
@@ -229,4 +237,4 @@ int dweight_bf16(const void *Xv, int64_t ldx, const float *G, int64_t ldg, int64
     return check_launch("ggcn_dweight_bf16");
 }
 
-}  // namespace ggcn
+}  // extern "C"

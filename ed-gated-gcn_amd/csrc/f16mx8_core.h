@@ -71,7 +71,8 @@ constexpr int SCALE_XL = 127 - XL_SHIFT, SCALE_XH = 127;
 // Sticky range flag: f16mx8 needs |x| < 65504 on its fp32 inputs (larger values saturate in the fp16 plane: MODE.FP16_OVFL).
 // Every main loop keeps the running maximum of |x| it splits (one v_max3 per two values) and ORs 1 into this word when it
 // reaches fp16's largest finite value -- one atomic, only when hit.  One copy per translation unit that includes this file
-// (no relocatable device code); ggcn_range_flag (capi.hip) reads / clears all of them.
+// (no relocatable device code).  A file that makes verdicts expands GGCN_RANGE_FLAG_TU(name) once: that defines the copy's reader and
+// registers it, when the library is loaded, with ggcn_range_flag (capi.hip), which reads / clears every registered copy.
 // Bits of the flag (ggcn.h GGCN_RANGE_*): 1 = a value reached 65504 (fp16 saturates: results wrong); 2 = a value left the
 // window |x| <= 448 in which the fp8 correction is exact to its format (beyond it the correction saturates and the product
 // falls to plain fp16 accuracy, 2^-12 relative: outside the 1e-4 parity gate); 4 = the one-launch layer of graphs of
@@ -88,7 +89,7 @@ __device__ __forceinline__ void range_verdict(float amax, float hb_scale = 0.0f,
     if (amax * hb_scale + hb_add >= kHalfMax) bits |= 4u;
     if (bits) atomicOr(&g_range_flag, bits);
 }
-// this translation unit's copy of the flag: OR it into *dst (device memory), clear on request
+// this translation unit's copy of the flag: OR it into *dst (device memory), clear on request; the reader registers itself
 #define GGCN_RANGE_FLAG_TU(fn)                                                                          \
     namespace {                                                                                         \
     __global__ void fn##_kernel(unsigned int *dst, int clear)                                           \
@@ -97,11 +98,12 @@ __device__ __forceinline__ void range_verdict(float amax, float hb_scale = 0.0f,
         if (v) atomicOr(dst, v);                                                                        \
         if (clear) mx8::g_range_flag = 0u;                                                              \
     }                                                                                                   \
-    }                                                                                                   \
     int fn(unsigned int *dst, int clear, hipStream_t st)                                                \
     {                                                                                                   \
         hipLaunchKernelGGL(fn##_kernel, dim3(1), dim3(1), 0, st, dst, clear);                           \
         return check_launch("ggcn_range_flag");                                                         \
+    }                                                                                                   \
+    [[maybe_unused]] const int fn##_registered = register_range_flag_reader(fn);                        \
     }
 // The packed weight images end in a 16-byte trailer: float[0] = max_f sum_k |w[k,f]| (ggcn_weight_pack), the factor of the
 // hidden-value bound above.

@@ -504,77 +504,6 @@ int launch_fused(const char *who, FusedArgs &a, int precision, hipStream_t st, b
     return check_launch(who);
 }
 
-
-int csr_rowmask(const int32_t *rowptr, const int32_t *colidx, int B, int T, uint32_t *rowmask, hipStream_t st)
-{
-    if (!rowptr || !colidx || !rowmask) return fail(GGCN_EINVAL, "ggcn_csr_rowmask: null pointer");
-    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_csr_rowmask: B=%d T=%d must be positive", B, T);
-    if (T > GGCN_MASK_MAX_T)
-        return fail(GGCN_EUNSUPPORTED, "ggcn_csr_rowmask: T=%d > %d (row masks cover graphs of at most %d nodes)", T, GGCN_MASK_MAX_T, GGCN_MASK_MAX_T);
-    const int64_t n = (int64_t)B * T;
-    hipLaunchKernelGGL(rowmask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rowptr, colidx, n, T,
-                       rowmask);
-    return check_launch("ggcn_csr_rowmask");
-}
-
-__global__ __launch_bounds__(256) void dropout_mask_kernel(int64_t n, int F, DropSpec d, int sel, float *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = drop_keep(drop_hash((uint32_t)i, d.seed_lo, d.seed_hi), sel, d.thr, d.scale);
-}
-
-int dropout_mask(int64_t rows, int F, float p, uint64_t seed, int sel, float *out, hipStream_t st)
-{
-    if (!out) return fail(GGCN_EINVAL, "ggcn_dropout_mask: null pointer");
-    if (rows <= 0 || F <= 0 || sel < 0 || sel > 2 || !(p >= 0.0f && p < 1.0f))
-        return fail(GGCN_EINVAL, "ggcn_dropout_mask: rows=%lld F=%d sel=%d p=%g", (long long)rows, F, sel, (double)p);
-    const int64_t n = rows * F;
-    if (n >= ((int64_t)1 << 32)) return fail(GGCN_EUNSUPPORTED, "ggcn_dropout_mask: rows*F must fit 32 bits");
-    const DropSpec d = make_drop_spec(p, seed, 0, 0, 0);
-    hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, F, d, sel, out);
-    return check_launch("ggcn_dropout_mask");
-}
-
-int graph_operands(const uint32_t *rowmask, int B, int T, void *ops, hipStream_t st)
-{
-    if (!rowmask || !ops) return fail(GGCN_EINVAL, "ggcn_graph_operands: null pointer");
-    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_graph_operands: B=%d T=%d must be positive", B, T);
-    if (T > 32) return fail(GGCN_EUNSUPPORTED, "ggcn_graph_operands: T=%d > 32 (larger graphs are applied from their row masks)", T);
-    if (!aligned16(ops)) return fail(GGCN_EINVAL, "ggcn_graph_operands: ops must be 16-byte aligned");
-    hipLaunchKernelGGL(graph_operands_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, rowmask, B, T,
-                       static_cast<char *>(ops));
-    return check_launch("ggcn_graph_operands");
-}
-
-int graph_operands2(const uint32_t *rowmask, int B, int T, int plane, void *ops2, hipStream_t st)
-{
-    if (!rowmask || !ops2) return fail(GGCN_EINVAL, "ggcn_graph_operands2: null pointer");
-    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_graph_operands2: B=%d T=%d must be positive", B, T);
-    if (T > 32) return fail(GGCN_EUNSUPPORTED, "ggcn_graph_operands2: T=%d > 32 (the two-layer block takes graphs of <= 32 nodes)", T);
-    if (plane != 0 && plane != 1) return fail(GGCN_EINVAL, "ggcn_graph_operands2: plane %d (0 = bf16 pairs, 1 = fp16 pairs)", plane);
-    if (!aligned16(ops2)) return fail(GGCN_EINVAL, "ggcn_graph_operands2: ops2 must be 16-byte aligned");
-    const dim3 grid((unsigned)((B + 3) / 4));
-    if (plane == 1) hipLaunchKernelGGL(graph_operands2_kernel<1>, grid, dim3(256), 0, st, rowmask, B, T, static_cast<char *>(ops2));
-    else hipLaunchKernelGGL(graph_operands2_kernel<0>, grid, dim3(256), 0, st, rowmask, B, T, static_cast<char *>(ops2));
-    return check_launch("ggcn_graph_operands2");
-}
-
-int graph_operands_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane, void *ops,
-                            int *flag, hipStream_t st)
-{
-    const char *who = "ggcn_graph_operands_weighted";
-    if (!rowptr || !colidx || !ops) return fail(GGCN_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d must be positive", who, B, T);
-    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (weighted graphs of more nodes: ggcn_linear + ggcn_aggregate)", who, T);
-    if (plane != 0 && plane != 1) return fail(GGCN_EINVAL, "%s: plane %d (0 = bf16 pairs, 1 = fp16 pairs)", who, plane);
-    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: the blocks must be 16-byte aligned", who);
-    if ((int64_t)B * T >= (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: B*T does not fit int32 node ids", who);
-    const dim3 grid((unsigned)((B + 3) / 4));
-    if (plane == 1) hipLaunchKernelGGL(graph_operands_w_kernel<1>, grid, dim3(256), 0, st, rowptr, colidx, vals, B, T, static_cast<char *>(ops), flag);
-    else hipLaunchKernelGGL(graph_operands_w_kernel<0>, grid, dim3(256), 0, st, rowptr, colidx, vals, B, T, static_cast<char *>(ops), flag);
-    return check_launch(who);
-}
-
 // The three two-layer blocks.  The entry described layer 1 in part[0] and layer 2 (through W12) in part[1]; every refusal comes before
 // the launch and names the entry.
 int launch_block(const char *who, FusedArgs &a, BlockKind kind, int precision, hipStream_t st)
@@ -626,15 +555,96 @@ int launch_block(const char *who, FusedArgs &a, BlockKind kind, int precision, h
     return launch_fused(who, a, precision, st, kind == kBlockWeighted);
 }
 
-int overlap_reduce(const float *partials, int B, int F, float *xy, hipStream_t st)
+__global__ __launch_bounds__(256) void dropout_mask_kernel(int64_t n, int F, DropSpec d, int sel, float *__restrict__ out)
 {
-    if (!partials || !xy) return fail(GGCN_EINVAL, "ggcn_overlap_reduce: null pointer");
-    if (B <= 0 || F <= 0) return fail(GGCN_EINVAL, "ggcn_overlap_reduce: B=%d F=%d must be positive", B, F);
-    hipLaunchKernelGGL(overlap_reduce_kernel, dim3(1), dim3(kRedThreads), 0, st, partials, B * ((F + 63) / 64), B, xy);
-    return check_launch("ggcn_overlap_reduce");
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = drop_keep(drop_hash((uint32_t)i, d.seed_lo, d.seed_hi), sel, d.thr, d.scale);
 }
 
 GGCN_RANGE_FLAG_TU(range_flag_fused)
 
 }  // namespace ggcn
 
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_csr_rowmask(const int32_t *rowptr, const int32_t *colidx, int B, int T, uint32_t *rowmask, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    if (!rowptr || !colidx || !rowmask) return fail(GGCN_EINVAL, "ggcn_csr_rowmask: null pointer");
+    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_csr_rowmask: B=%d T=%d must be positive", B, T);
+    if (T > GGCN_MASK_MAX_T)
+        return fail(GGCN_EUNSUPPORTED, "ggcn_csr_rowmask: T=%d > %d (row masks cover graphs of at most %d nodes)", T, GGCN_MASK_MAX_T, GGCN_MASK_MAX_T);
+    const int64_t n = (int64_t)B * T;
+    hipLaunchKernelGGL(rowmask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rowptr, colidx, n, T,
+                       rowmask);
+    return check_launch("ggcn_csr_rowmask");
+}
+
+int ggcn_dropout_mask(int64_t rows, int F, float p, uint64_t seed, int sel, float *out, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    if (!out) return fail(GGCN_EINVAL, "ggcn_dropout_mask: null pointer");
+    if (rows <= 0 || F <= 0 || sel < 0 || sel > 2 || !(p >= 0.0f && p < 1.0f))
+        return fail(GGCN_EINVAL, "ggcn_dropout_mask: rows=%lld F=%d sel=%d p=%g", (long long)rows, F, sel, (double)p);
+    const int64_t n = rows * F;
+    if (n >= ((int64_t)1 << 32)) return fail(GGCN_EUNSUPPORTED, "ggcn_dropout_mask: rows*F must fit 32 bits");
+    const DropSpec d = make_drop_spec(p, seed, 0, 0, 0);
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, F, d, sel, out);
+    return check_launch("ggcn_dropout_mask");
+}
+
+int ggcn_graph_operands(const uint32_t *rowmask, int B, int T, void *ops, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    if (!rowmask || !ops) return fail(GGCN_EINVAL, "ggcn_graph_operands: null pointer");
+    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_graph_operands: B=%d T=%d must be positive", B, T);
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "ggcn_graph_operands: T=%d > 32 (larger graphs are applied from their row masks)", T);
+    if (!aligned16(ops)) return fail(GGCN_EINVAL, "ggcn_graph_operands: ops must be 16-byte aligned");
+    hipLaunchKernelGGL(graph_operands_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, rowmask, B, T,
+                       static_cast<char *>(ops));
+    return check_launch("ggcn_graph_operands");
+}
+
+int ggcn_graph_operands2(const uint32_t *rowmask, int B, int T, int plane, void *ops2, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    if (!rowmask || !ops2) return fail(GGCN_EINVAL, "ggcn_graph_operands2: null pointer");
+    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_graph_operands2: B=%d T=%d must be positive", B, T);
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "ggcn_graph_operands2: T=%d > 32 (the two-layer block takes graphs of <= 32 nodes)", T);
+    if (plane != 0 && plane != 1) return fail(GGCN_EINVAL, "ggcn_graph_operands2: plane %d (0 = bf16 pairs, 1 = fp16 pairs)", plane);
+    if (!aligned16(ops2)) return fail(GGCN_EINVAL, "ggcn_graph_operands2: ops2 must be 16-byte aligned");
+    const dim3 grid((unsigned)((B + 3) / 4));
+    if (plane == 1) hipLaunchKernelGGL(graph_operands2_kernel<1>, grid, dim3(256), 0, st, rowmask, B, T, static_cast<char *>(ops2));
+    else hipLaunchKernelGGL(graph_operands2_kernel<0>, grid, dim3(256), 0, st, rowmask, B, T, static_cast<char *>(ops2));
+    return check_launch("ggcn_graph_operands2");
+}
+
+int ggcn_graph_operands_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane, void *ops,
+                                 int32_t *flag, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    const char *who = "ggcn_graph_operands_weighted";
+    if (!rowptr || !colidx || !ops) return fail(GGCN_EINVAL, "%s: null pointer", who);
+    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d must be positive", who, B, T);
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (weighted graphs of more nodes: ggcn_linear + ggcn_aggregate)", who, T);
+    if (plane != 0 && plane != 1) return fail(GGCN_EINVAL, "%s: plane %d (0 = bf16 pairs, 1 = fp16 pairs)", who, plane);
+    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: the blocks must be 16-byte aligned", who);
+    if ((int64_t)B * T >= (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: B*T does not fit int32 node ids", who);
+    const dim3 grid((unsigned)((B + 3) / 4));
+    if (plane == 1) hipLaunchKernelGGL(graph_operands_w_kernel<1>, grid, dim3(256), 0, st, rowptr, colidx, vals, B, T, static_cast<char *>(ops), flag);
+    else hipLaunchKernelGGL(graph_operands_w_kernel<0>, grid, dim3(256), 0, st, rowptr, colidx, vals, B, T, static_cast<char *>(ops), flag);
+    return check_launch(who);
+}
+
+int ggcn_overlap_reduce(const float *partials, int B, int F, float *xy, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    if (!partials || !xy) return fail(GGCN_EINVAL, "ggcn_overlap_reduce: null pointer");
+    if (B <= 0 || F <= 0) return fail(GGCN_EINVAL, "ggcn_overlap_reduce: B=%d F=%d must be positive", B, F);
+    hipLaunchKernelGGL(overlap_reduce_kernel, dim3(1), dim3(kRedThreads), 0, st, partials, B * ((F + 63) / 64), B, xy);
+    return check_launch("ggcn_overlap_reduce");
+}
+
+}  // extern "C"

@@ -608,12 +608,18 @@ __global__ __launch_bounds__(LTHR, 2) void layer_fused_long_kernel(const LongArg
 #undef GGCN_SB
 
 }  // namespace
+}  // namespace ggcn
 
-int layer_fused_h(const void *X, int64_t ldx, const void *wpack, const int32_t *rowptr, const int32_t *colidx,
-                  const float *vals, const float *bias, int B, int T, int K, int F, const float *store_gate,
-                  const float *pool_gate_a, const float *pool_gate_b, void *out, int64_t ldo, float *pool_a,
-                  float *pool_b, hipStream_t st)
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_layer_fused_h(const void *X, int64_t ldx, const void *wpack, const int32_t *rowptr, const int32_t *colidx,
+                       const float *vals, const float *bias, int B, int T, int K, int F, const float *store_gate,
+                       const float *pool_gate_a, const float *pool_gate_b, void *out, int64_t ldo, float *pool_a,
+                       float *pool_b, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_layer_fused_h";
     if (!X || !wpack || !rowptr || !colidx) return fail(GGCN_EINVAL, "%s: null input pointer", who);
     if (B <= 0 || T <= 0 || K <= 0 || F <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d K=%d F=%d must be positive", who, B, T, K, F);
@@ -659,4 +665,4 @@ int layer_fused_h(const void *X, int64_t ldx, const void *wpack, const int32_t *
     return check_launch(who);
 }
 
-}  // namespace ggcn
+}  // extern "C"

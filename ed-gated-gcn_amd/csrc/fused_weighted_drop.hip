@@ -297,9 +297,18 @@ int launch_fused_block_weighted(const char *who, const FusedArgs &a, int precisi
     return check_launch(who);
 }
 
-int graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane, void *ops2,
-                             int *flag, hipStream_t st)
+GGCN_RANGE_FLAG_TU(range_flag_weighted_drop)
+
+}  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, int plane, void *ops2,
+                                  int32_t *flag, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_graph_operands2_weighted";
     if (!rowptr || !colidx || !ops2) return fail(GGCN_EINVAL, "%s: null pointer", who);
     if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d must be positive", who, B, T);
@@ -313,6 +322,4 @@ int graph_operands2_weighted(const int32_t *rowptr, const int32_t *colidx, const
     return check_launch(who);
 }
 
-GGCN_RANGE_FLAG_TU(range_flag_weighted_drop)
-
-}  // namespace ggcn
+}  // extern "C"

@@ -432,30 +432,6 @@ int launch_fused_wide(const char *who, const FusedArgs &a, int precision, int sb
     return check_launch(who);
 }
 
-size_t graph_operands_weighted_wide_bytes(int B, int T)
-{
-    if (B <= 0 || T <= 32 || T > 128) return 0;
-    const size_t W = (size_t)(T + 31) / 32;
-    return (size_t)B * W * W * kWOpsBlock;
-}
-
-int graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops, int *flag,
-                                 hipStream_t st)
-{
-    const char *who = "ggcn_graph_operands_weighted_wide";
-    if (!rowptr || !colidx || !ops) return fail(GGCN_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d must be positive", who, B, T);
-    if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32 (one block per graph: ggcn_graph_operands_weighted)", who, T);
-    if (T > 128) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 128 (weighted graphs of more nodes: ggcn_linear + ggcn_aggregate)", who, T);
-    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: the blocks must be 16-byte aligned", who);
-    if ((int64_t)B * T >= (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: B*T does not fit int32 node ids", who);
-    const int W = (T + 31) >> 5;
-    const int64_t grid = ((int64_t)B * W * W + 3) / 4;
-    if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
-    hipLaunchKernelGGL(graph_operands_ww_kernel, dim3((unsigned)grid), dim3(256), 0, st, rowptr, colidx, vals, B, T, W, static_cast<char *>(ops), flag);
-    return check_launch(who);
-}
-
 // gcn.py:30-45 with a real-valued adjacency for graphs of 33..128 nodes in ONE launch: layer_fused_wide_kernel<.., WEIGHTED> on
 // ggcn_graph_operands_weighted_wide blocks (a.graph_ops; no row masks).  The shape and the part are checked by fused_part_checks
 // (fused_layer.hip), as launch_fused's are.  a.drop: the gates' keep streams (thr = 0: the launch without dropout)
@@ -502,3 +478,34 @@ int launch_fused_weighted_wide(const char *who, FusedArgs &a, int precision, hip
 GGCN_RANGE_FLAG_TU(range_flag_wide)
 
 }  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
+
+size_t ggcn_graph_operands_weighted_wide_bytes(int B, int T)
+{
+    if (B <= 0 || T <= 32 || T > 128) return 0;
+    const size_t W = (size_t)(T + 31) / 32;
+    return (size_t)B * W * W * kWOpsBlock;
+}
+
+int ggcn_graph_operands_weighted_wide(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops,
+                                      int32_t *flag, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    const char *who = "ggcn_graph_operands_weighted_wide";
+    if (!rowptr || !colidx || !ops) return fail(GGCN_EINVAL, "%s: null pointer", who);
+    if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d must be positive", who, B, T);
+    if (T <= 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d <= 32 (one block per graph: ggcn_graph_operands_weighted)", who, T);
+    if (T > 128) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 128 (weighted graphs of more nodes: ggcn_linear + ggcn_aggregate)", who, T);
+    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: the blocks must be 16-byte aligned", who);
+    if ((int64_t)B * T >= (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: B*T does not fit int32 node ids", who);
+    const int W = (T + 31) >> 5;
+    const int64_t grid = ((int64_t)B * W * W + 3) / 4;
+    if (grid > (int64_t)INT32_MAX) return fail(GGCN_EUNSUPPORTED, "%s: batch too large", who);
+    hipLaunchKernelGGL(graph_operands_ww_kernel, dim3((unsigned)grid), dim3(256), 0, st, rowptr, colidx, vals, B, T, W, static_cast<char *>(ops), flag);
+    return check_launch(who);
+}
+
+}  // extern "C"

@@ -399,18 +399,6 @@ __global__ __launch_bounds__(256) void graph_edge_lists_kernel(const uint32_t *_
 
 }  // namespace
 
-int graph_edge_lists(const uint32_t *rowmask, int B, int T, void *lists, hipStream_t st)
-{
-    if (!rowmask || !lists) return fail(GGCN_EINVAL, "ggcn_graph_edge_lists: null pointer");
-    if (B <= 0 || T <= 128 || T > 256) return fail(GGCN_EUNSUPPORTED, "ggcn_graph_edge_lists: B=%d T=%d (graphs of 129..256 nodes: the eight-wavefront layer)", B, T);
-    if (!aligned16(lists)) return fail(GGCN_EINVAL, "ggcn_graph_edge_lists: lists must be 16-byte aligned");
-    hipLaunchKernelGGL(graph_edge_lists_kernel, dim3((unsigned)B), dim3(256), 0, st, rowmask, T, static_cast<char *>(lists));
-    return check_launch("ggcn_graph_edge_lists");
-}
-
-namespace {
-}  // namespace
-
 int launch_fused_wide8(const char *who, const FusedArgs &a, int precision, bool fast, bool vst, int64_t gridw, hipStream_t st)
 {
 #define GGCN_LAUNCH8D(SC, AV, KF, VS, DR)                                                                                 \
@@ -457,3 +445,19 @@ int launch_fused_wide8(const char *who, const FusedArgs &a, int precision, bool 
 GGCN_RANGE_FLAG_TU(range_flag_wide8)
 
 }  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_graph_edge_lists(const uint32_t *rowmask, int B, int T, void *lists, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    if (!rowmask || !lists) return fail(GGCN_EINVAL, "ggcn_graph_edge_lists: null pointer");
+    if (B <= 0 || T <= 128 || T > 256) return fail(GGCN_EUNSUPPORTED, "ggcn_graph_edge_lists: B=%d T=%d (graphs of 129..256 nodes: the eight-wavefront layer)", B, T);
+    if (!aligned16(lists)) return fail(GGCN_EINVAL, "ggcn_graph_edge_lists: lists must be 16-byte aligned");
+    hipLaunchKernelGGL(graph_edge_lists_kernel, dim3((unsigned)B), dim3(256), 0, st, rowmask, T, static_cast<char *>(lists));
+    return check_launch("ggcn_graph_edge_lists");
+}
+
+}  // extern "C"

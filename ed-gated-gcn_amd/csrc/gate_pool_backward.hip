@@ -325,20 +325,6 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float *__restri
 
 }  // namespace
 
-size_t colsum_workspace_bytes(int F) { return F > 0 ? (size_t)kColsumSlabs * F * sizeof(float) : 0; }
-
-int colsum(const float *X, int64_t ld, int64_t M, int F, float *out, void *workspace, hipStream_t st)
-{
-    if (!X || !out || !workspace) return fail(GGCN_EINVAL, "ggcn_colsum: null pointer");
-    if (M <= 0 || F <= 0 || ld < F) return fail(GGCN_EINVAL, "ggcn_colsum: M=%lld F=%d ld=%lld", (long long)M, F, (long long)ld);
-    const int S = (int)(M < kColsumSlabs ? M : kColsumSlabs);
-    const int64_t rows = (M + S - 1) / S;
-    float *part = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)((F + 63) / 64), (unsigned)S), dim3(256), 0, st, X, ld, M, F, rows, part);
-    hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, part, S, F, out);
-    return check_launch("ggcn_colsum");
-}
-
 int gate_pool_backward(const float *out, int64_t ldo, const float *store_gate, const float *gate_a,
                        const float *gate_b, const float *d_out, int64_t ldd, const float *d_pa,
                        const float *d_pb, int B, int T, int F, float *dY, int64_t ldy, float *d_sg,
@@ -415,3 +401,24 @@ int gate_pool_backward_agg(const float *out, int64_t ldo, const float *store_gat
 }
 
 }  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
+
+size_t ggcn_colsum_workspace_bytes(int F) { return F > 0 ? (size_t)kColsumSlabs * F * sizeof(float) : 0; }
+
+int ggcn_colsum(const float *X, int64_t ld, int64_t M, int F, float *out, void *workspace, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    if (!X || !out || !workspace) return fail(GGCN_EINVAL, "ggcn_colsum: null pointer");
+    if (M <= 0 || F <= 0 || ld < F) return fail(GGCN_EINVAL, "ggcn_colsum: M=%lld F=%d ld=%lld", (long long)M, F, (long long)ld);
+    const int S = (int)(M < kColsumSlabs ? M : kColsumSlabs);
+    const int64_t rows = (M + S - 1) / S;
+    float *part = static_cast<float *>(workspace);
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)((F + 63) / 64), (unsigned)S), dim3(256), 0, st, X, ld, M, F, rows, part);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, part, S, F, out);
+    return check_launch("ggcn_colsum");
+}
+
+}  // extern "C"

@@ -125,9 +125,15 @@ __global__ __launch_bounds__(256) void rowmask_transpose_kernel(const uint32_t *
 }
 
 }  // namespace
+}  // namespace ggcn
 
-int rowmask_transpose(const uint32_t *rowmask, int B, int T, uint32_t *rowmask_t, hipStream_t st)
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_rowmask_transpose(const uint32_t *rowmask, int B, int T, uint32_t *rowmask_t, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!rowmask || !rowmask_t) return fail(GGCN_EINVAL, "ggcn_rowmask_transpose: null pointer");
     if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "ggcn_rowmask_transpose: B=%d T=%d must be positive", B, T);
     if (T > 32) return fail(GGCN_EUNSUPPORTED, "ggcn_rowmask_transpose: T=%d > 32 (one word per node)", T);
@@ -135,11 +141,12 @@ int rowmask_transpose(const uint32_t *rowmask, int B, int T, uint32_t *rowmask_t
     return check_launch("ggcn_rowmask_transpose");
 }
 
-int gate_pool_backward_mma(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
-                           const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops,
-                           const void *graph_ops_t, int B, int T, int F, float *dH, int64_t ldh, float *d_sg, float *d_ga,
-                           float *d_gb, float *d_bsum, float *dh_amax, hipStream_t st)
+int ggcn_gate_pool_backward_mma(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
+                                const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops,
+                                const void *graph_ops_t, int B, int T, int F, float *dH, int64_t ldh, float *d_sg, float *d_ga,
+                                float *d_gb, float *d_bsum, float *dh_amax, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_gate_pool_backward_mma";
     if (!out || !dH || !graph_ops || !graph_ops_t) return fail(GGCN_EINVAL, "%s: null pointer", who);
     const EntryRules rules = {who, false, 1, "", 32, "", false,
@@ -154,4 +161,4 @@ int gate_pool_backward_mma(const float *out, int64_t ldo, const float *store_gat
     return check_launch(who);
 }
 
-}  // namespace ggcn
+}  // extern "C"

@@ -198,25 +198,6 @@ __global__ __launch_bounds__(256) void graph_operands_wt_kernel(const int32_t *_
 
 }  // namespace
 
-size_t graph_operands_weighted_t_bytes(int B) { return B > 0 ? (size_t)B * kOpsBytesWT : 0; }
-
-int graph_operands_weighted_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops, int *flag,
-                              hipStream_t st)
-{
-    const char *who = "ggcn_graph_operands_weighted_t";
-    if (!rowptr) return fail(GGCN_EINVAL, "%s: rowptr is null", who);
-    if (!colidx) return fail(GGCN_EINVAL, "%s: colidx is null", who);
-    if (!ops) return fail(GGCN_EINVAL, "%s: graph_ops_wt is null", who);
-    if (B < 0) return fail(GGCN_EINVAL, "%s: B=%d must not be negative", who, B);
-    if (T < 1) return fail(GGCN_EINVAL, "%s: T=%d must be positive", who, T);
-    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (one 32 x 32 block per graph)", who, T);
-    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: graph_ops_wt must be 16-byte aligned", who);
-    if (B == 0) return GGCN_OK;
-    const int64_t grid = ((int64_t)B + 3) / 4;
-    hipLaunchKernelGGL(graph_operands_wt_kernel, dim3((unsigned)grid), dim3(256), 0, st, rowptr, colidx, vals, B, T, static_cast<char *>(ops), flag);
-    return check_launch(who);
-}
-
 int gate_pool_backward_weighted(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
                                 const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wt,
                                 const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
@@ -251,3 +232,29 @@ int gate_pool_backward_weighted(const float *out, int64_t ldo, const float *stor
 }
 
 }  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
+
+size_t ggcn_graph_operands_weighted_t_bytes(int B) { return B > 0 ? (size_t)B * kOpsBytesWT : 0; }
+
+int ggcn_graph_operands_weighted_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops,
+                                   int32_t *flag, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    const char *who = "ggcn_graph_operands_weighted_t";
+    if (!rowptr) return fail(GGCN_EINVAL, "%s: rowptr is null", who);
+    if (!colidx) return fail(GGCN_EINVAL, "%s: colidx is null", who);
+    if (!ops) return fail(GGCN_EINVAL, "%s: graph_ops_wt is null", who);
+    if (B < 0) return fail(GGCN_EINVAL, "%s: B=%d must not be negative", who, B);
+    if (T < 1) return fail(GGCN_EINVAL, "%s: T=%d must be positive", who, T);
+    if (T > 32) return fail(GGCN_EUNSUPPORTED, "%s: T=%d > 32 (one 32 x 32 block per graph)", who, T);
+    if (!aligned16(ops)) return fail(GGCN_EINVAL, "%s: graph_ops_wt must be 16-byte aligned", who);
+    if (B == 0) return GGCN_OK;
+    const int64_t grid = ((int64_t)B + 3) / 4;
+    hipLaunchKernelGGL(graph_operands_wt_kernel, dim3((unsigned)grid), dim3(256), 0, st, rowptr, colidx, vals, B, T, static_cast<char *>(ops), flag);
+    return check_launch(who);
+}
+
+}  // extern "C"

@@ -267,17 +267,23 @@ __global__ __launch_bounds__(256) void graph_operands_wwt_kernel(const int32_t *
 }
 
 }  // namespace
+}  // namespace ggcn
 
-size_t graph_operands_weighted_wide_t_bytes(int B, int T)
+using namespace ggcn;
+
+extern "C" {
+
+size_t ggcn_graph_operands_weighted_wide_t_bytes(int B, int T)
 {
     if (B <= 0 || T <= 32 || T > kMaxT) return 0;
     const size_t W = (size_t)(T + 31) / 32;
     return (size_t)B * (W * W * kBlockBytes + 4);   // the blocks, then one summary word per graph
 }
 
-int graph_operands_weighted_wide_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops, int *flag,
-                                   hipStream_t st)
+int ggcn_graph_operands_weighted_wide_t(const int32_t *rowptr, const int32_t *colidx, const float *vals, int B, int T, void *ops,
+                                        int32_t *flag, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_graph_operands_weighted_wide_t";
     if (!rowptr || !colidx || !ops) return fail(GGCN_EINVAL, "%s: null pointer", who);
     if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d must be positive", who, B, T);
@@ -292,11 +298,12 @@ int graph_operands_weighted_wide_t(const int32_t *rowptr, const int32_t *colidx,
     return check_launch(who);
 }
 
-int gate_pool_backward_weighted_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
-                                     const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wwt,
-                                     const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
-                                     float *d_ga, float *d_gb, float *d_bsum, hipStream_t st)
+int ggcn_gate_pool_backward_weighted_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
+                                          const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const void *graph_ops_wwt,
+                                          const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *dY, int64_t ldy, float *d_sg,
+                                          float *d_ga, float *d_gb, float *d_bsum, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_gate_pool_backward_weighted_wide";
     if (!out || !dH || !graph_ops_wwt || !inv) return fail(GGCN_EINVAL, "%s: null pointer", who);
     const EntryRules rules = {who, false, 33, "ggcn_gate_pool_backward_weighted", kMaxT, "", true,
@@ -313,4 +320,4 @@ int gate_pool_backward_weighted_wide(const float *out, int64_t ldo, const float 
     return check_launch(who);
 }
 
-}  // namespace ggcn
+}  // extern "C"

@@ -147,9 +147,15 @@ __global__ __launch_bounds__(512) void rowmask_transpose_wide_kernel(const uint3
 }
 
 }  // namespace
+}  // namespace ggcn
 
-int rowmask_transpose_wide(const uint32_t *rowmask, int B, int T, uint32_t *rowmask_t, hipStream_t st)
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_rowmask_transpose_wide(const uint32_t *rowmask, int B, int T, uint32_t *rowmask_t, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_rowmask_transpose_wide";
     if (!rowmask || !rowmask_t) return fail(GGCN_EINVAL, "%s: null pointer", who);
     if (B <= 0 || T <= 0) return fail(GGCN_EINVAL, "%s: B=%d T=%d must be positive", who, B, T);
@@ -159,11 +165,12 @@ int rowmask_transpose_wide(const uint32_t *rowmask, int B, int T, uint32_t *rowm
     return check_launch(who);
 }
 
-int gate_pool_backward_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
-                            const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const uint32_t *rowmask_t,
-                            const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *d_sg, float *d_ga, float *d_gb,
-                            float *d_bsum, hipStream_t st)
+int ggcn_gate_pool_backward_wide(const float *out, int64_t ldo, const float *store_gate, const float *gate_a, const float *gate_b,
+                                 const float *d_out, int64_t ldd, const float *d_pa, const float *d_pb, const uint32_t *rowmask_t,
+                                 const float *inv, int B, int T, int F, float *dH, int64_t ldh, float *d_sg, float *d_ga, float *d_gb,
+                                 float *d_bsum, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const char *who = "ggcn_gate_pool_backward_wide";
     if (!out || !dH || !rowmask_t || !inv) return fail(GGCN_EINVAL, "%s: null pointer", who);
     const EntryRules rules = {who, false, 33, "ggcn_gate_pool_backward_mma", kMaxT, "", true,
@@ -177,4 +184,4 @@ int gate_pool_backward_wide(const float *out, int64_t ldo, const float *store_ga
     return check_launch(who);
 }
 
-}  // namespace ggcn
+}  // extern "C"

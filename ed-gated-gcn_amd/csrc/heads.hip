@@ -584,15 +584,6 @@ __global__ __launch_bounds__(kHeadThreads) void dense_head_kernel(const float *_
 
 }  // namespace
 
-int transpose_f32(const float *W, int rows, int cols, int64_t ldw, float *Wt, hipStream_t st)
-{
-    if (!W || !Wt) return fail(GGCN_EINVAL, "ggcn_transpose: null pointer");
-    if (rows <= 0 || cols <= 0 || ldw < cols) return fail(GGCN_EINVAL, "ggcn_transpose: rows=%d cols=%d ldw=%lld", rows, cols, (long long)ldw);
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(256), 0, st,
-                       W, rows, cols, ldw, Wt);
-    return check_launch("ggcn_transpose");
-}
-
 // ggcn_gate_mlp (save = false) and ggcn_gate_mlp_save: the same checks under the entry's own name, the same launch geometry
 static int gate_mlp_launch(const char *who, bool save, const float *aspect, int64_t lda, int B, int H, const float *w1t_a,
                            const float *b1_a, const float *w2t_a, const float *b2_a, float *gate_a, const float *w1t_b,
@@ -613,26 +604,61 @@ static int gate_mlp_launch(const char *who, bool save, const float *aspect, int6
     return check_launch(who);
 }
 
-int gate_mlp(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a, const float *w2t_a,
-             const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b, const float *w2t_b,
-             const float *b2_b, float *gate_b, hipStream_t st)
+// ggcn_dense_head and, with its signal words, ggcn_dense_head_signal (capi.hip)
+int dense_head(const float *pooled, int64_t ldp, const float *Wt, int64_t ldw, const float *bias, int B, int H, int C,
+               float *logits, int64_t ldl, const float *partials, int F_block, float *xy, hipStream_t st, unsigned *signal)
+{
+    if (!pooled || !Wt || !logits) return fail(GGCN_EINVAL, "ggcn_dense_head: null pointer");
+    if ((partials != nullptr) != (xy != nullptr)) return fail(GGCN_EINVAL, "ggcn_dense_head: overlap_partials and xy go together");
+    if (B <= 0 || H <= 0 || C <= 0 || (partials && F_block <= 0)) return fail(GGCN_EINVAL, "ggcn_dense_head: B=%d H=%d C=%d F_block=%d", B, H, C, F_block);
+    if (C > 64) return fail(GGCN_EUNSUPPORTED, "ggcn_dense_head: C=%d classes (one lane per class: at most 64)", C);
+    if (ldp < H || ldw < C || ldl < C) return fail(GGCN_EINVAL, "ggcn_dense_head: leading dimension too small");
+    const int head_blocks = (B + kHeadRows - 1) / kHeadRows;
+    const size_t lds = ((size_t)kHeadRows * H + (size_t)kHeadWaves * kHeadRows * 64) * sizeof(float);
+    if (lds > 64 * 1024) return fail(GGCN_EUNSUPPORTED, "ggcn_dense_head: H=%d needs more than 64 KiB of LDS", H);
+    hipLaunchKernelGGL(dense_head_kernel, dim3((unsigned)(head_blocks + (partials ? 1 : 0))), dim3(kHeadThreads), lds, st, pooled, ldp, Wt, ldw, bias,
+                       B, H, C, logits, ldl, partials, partials ? B * ((F_block + 63) / 64) : 0, xy, head_blocks, signal);
+    return check_launch("ggcn_dense_head");
+}
+
+}  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_transpose(const float *W, int rows, int cols, int64_t ldw, float *Wt, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
+    if (!W || !Wt) return fail(GGCN_EINVAL, "ggcn_transpose: null pointer");
+    if (rows <= 0 || cols <= 0 || ldw < cols) return fail(GGCN_EINVAL, "ggcn_transpose: rows=%d cols=%d ldw=%lld", rows, cols, (long long)ldw);
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(256), 0, st,
+                       W, rows, cols, ldw, Wt);
+    return check_launch("ggcn_transpose");
+}
+
+int ggcn_gate_mlp(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a, const float *w2t_a,
+                  const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b, const float *w2t_b,
+                  const float *b2_b, float *gate_b, ggcn_stream_t stream)
 {
     return gate_mlp_launch("ggcn_gate_mlp", false, aspect, lda, B, H, w1t_a, b1_a, w2t_a, b2_a, gate_a, w1t_b, b1_b, w2t_b, b2_b, gate_b,
-                           nullptr, nullptr, st);
+                           nullptr, nullptr, as_stream(stream));
 }
 
-int gate_mlp_save(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a, const float *w2t_a,
-                  const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b, const float *w2t_b,
-                  const float *b2_b, float *gate_b, float *hid_a, float *hid_b, hipStream_t st)
+int ggcn_gate_mlp_save(const float *aspect, int64_t lda, int B, int H, const float *w1t_a, const float *b1_a, const float *w2t_a,
+                       const float *b2_a, float *gate_a, const float *w1t_b, const float *b1_b, const float *w2t_b,
+                       const float *b2_b, float *gate_b, float *hid_a, float *hid_b, ggcn_stream_t stream)
 {
     return gate_mlp_launch("ggcn_gate_mlp_save", true, aspect, lda, B, H, w1t_a, b1_a, w2t_a, b2_a, gate_a, w1t_b, b1_b, w2t_b, b2_b,
-                           gate_b, hid_a, hid_b, st);
+                           gate_b, hid_a, hid_b, as_stream(stream));
 }
 
-int gate_mlp_backward(const float *aspect, int64_t lda, int B, int H, const float *w1_a, const float *w2_a, const float *hid_a,
-                      const float *gate_a, const float *d_gate_a, const float *w1_b, const float *w2_b, const float *hid_b,
-                      const float *gate_b, const float *d_gate_b, float *d_aspect, int64_t ldda, float *Z, int64_t ldz, hipStream_t st)
+int ggcn_gate_mlp_backward(const float *aspect, int64_t lda, int B, int H, const float *w1_a, const float *w2_a, const float *hid_a,
+                           const float *gate_a, const float *d_gate_a, const float *w1_b, const float *w2_b, const float *hid_b,
+                           const float *gate_b, const float *d_gate_b, float *d_aspect, int64_t ldda, float *Z, int64_t ldz,
+                           ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!aspect) return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: null pointer");
     if (!d_gate_a && !d_gate_b) return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: no incoming gradient (both d_gate are NULL)");
     if (!d_aspect && !Z) return fail(GGCN_EINVAL, "ggcn_gate_mlp_backward: nothing to compute (d_aspect and Z are NULL)");
@@ -656,10 +682,11 @@ int gate_mlp_backward(const float *aspect, int64_t lda, int B, int H, const floa
     return check_launch("ggcn_gate_mlp_backward");
 }
 
-int scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
-                const float *fcw, int64_t ldw, const float *fcb, const float *dist, int64_t ldd, int B, int T, int H,
-                int C, float *scores, int64_t lds_, float *kl_part, hipStream_t st)
+int ggcn_scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
+                     const float *fcw, int64_t ldw, const float *fcb, const float *dist, int64_t ldd, int B, int T, int H,
+                     int C, float *scores, int64_t lds_, float *kl_part, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!X || !aspect || !logits || !fcw || !scores) return fail(GGCN_EINVAL, "ggcn_scores_head: null pointer");
     if ((kl_part != nullptr) != (dist != nullptr)) return fail(GGCN_EINVAL, "ggcn_scores_head: dist and kl_part go together");
     if (B <= 0 || T <= 0 || H <= 0 || C <= 0) return fail(GGCN_EINVAL, "ggcn_scores_head: B=%d T=%d H=%d C=%d", B, T, H, C);
@@ -672,12 +699,13 @@ int scores_head(const float *X, int64_t ldx, const float *aspect, int64_t lda, c
     return check_launch("ggcn_scores_head");
 }
 
-int scores_head_backward(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
-                         const float *fcw, int64_t ldw, const float *fcb, const float *dist, int64_t ldd, const float *scores,
-                         int64_t lds_, const float *kl_part, const float *g_scores, int64_t ldgs, const float *g_kl, int B, int T,
-                         int H, int C, float *dX, int64_t lddx, float *d_aspect, int64_t ldda, float *d_logits, int64_t lddl, float *G,
-                         int64_t ldg, float *dc0, hipStream_t st)
+int ggcn_scores_head_backward(const float *X, int64_t ldx, const float *aspect, int64_t lda, const float *logits, int64_t ldl,
+                              const float *fcw, int64_t ldw, const float *fcb, const float *dist, int64_t ldd, const float *scores,
+                              int64_t lds_, const float *kl_part, const float *g_scores, int64_t ldgs, const float *g_kl, int B, int T,
+                              int H, int C, float *dX, int64_t lddx, float *d_aspect, int64_t ldda, float *d_logits, int64_t lddl,
+                              float *G, int64_t ldg, float *dc0, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!X || !aspect || !logits || !fcw) return fail(GGCN_EINVAL, "ggcn_scores_head_backward: null pointer");
     if (g_kl && (!dist || !scores || !kl_part))
         return fail(GGCN_EINVAL, "ggcn_scores_head_backward: a gradient of kl needs dist, the saved scores and the saved kl_part");
@@ -698,15 +726,16 @@ int scores_head_backward(const float *X, int64_t ldx, const float *aspect, int64
     return check_launch("ggcn_scores_head_backward");
 }
 
-size_t scores_head_dweight_workspace_bytes(int B, int H, int C)
+size_t ggcn_scores_head_dweight_workspace_bytes(int B, int H, int C)
 {
     if (B <= 0 || H <= 0 || C <= 0) return sizeof(float);
     return (size_t)((B + kDwRows - 1) / kDwRows) * (size_t)C * (size_t)(2 * H + 1) * sizeof(float);
 }
 
-int scores_head_dweight(const float *logits, int64_t ldl, const float *G, int64_t ldg, const float *dc0, int B, int H, int C, float *dW,
-                        int64_t lddw, float *d_bias, void *workspace, hipStream_t st)
+int ggcn_scores_head_dweight(const float *logits, int64_t ldl, const float *G, int64_t ldg, const float *dc0, int B, int H, int C,
+                             float *dW, int64_t lddw, float *d_bias, void *workspace, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!logits || !G || !dc0 || !dW || !workspace) return fail(GGCN_EINVAL, "ggcn_scores_head_dweight: null pointer");
     if (B <= 0 || H <= 0 || C <= 0) return fail(GGCN_EINVAL, "ggcn_scores_head_dweight: B=%d H=%d C=%d", B, H, C);
     if (ldl < C || ldg < 2 * H || lddw < 2 * H) return fail(GGCN_EINVAL, "ggcn_scores_head_dweight: leading dimension too small");
@@ -720,20 +749,4 @@ int scores_head_dweight(const float *logits, int64_t ldl, const float *G, int64_
     return check_launch("ggcn_scores_head_dweight");
 }
 
-int dense_head(const float *pooled, int64_t ldp, const float *Wt, int64_t ldw, const float *bias, int B, int H, int C,
-               float *logits, int64_t ldl, const float *partials, int F_block, float *xy, hipStream_t st, unsigned *signal)
-{
-    if (!pooled || !Wt || !logits) return fail(GGCN_EINVAL, "ggcn_dense_head: null pointer");
-    if ((partials != nullptr) != (xy != nullptr)) return fail(GGCN_EINVAL, "ggcn_dense_head: overlap_partials and xy go together");
-    if (B <= 0 || H <= 0 || C <= 0 || (partials && F_block <= 0)) return fail(GGCN_EINVAL, "ggcn_dense_head: B=%d H=%d C=%d F_block=%d", B, H, C, F_block);
-    if (C > 64) return fail(GGCN_EUNSUPPORTED, "ggcn_dense_head: C=%d classes (one lane per class: at most 64)", C);
-    if (ldp < H || ldw < C || ldl < C) return fail(GGCN_EINVAL, "ggcn_dense_head: leading dimension too small");
-    const int head_blocks = (B + kHeadRows - 1) / kHeadRows;
-    const size_t lds = ((size_t)kHeadRows * H + (size_t)kHeadWaves * kHeadRows * 64) * sizeof(float);
-    if (lds > 64 * 1024) return fail(GGCN_EUNSUPPORTED, "ggcn_dense_head: H=%d needs more than 64 KiB of LDS", H);
-    hipLaunchKernelGGL(dense_head_kernel, dim3((unsigned)(head_blocks + (partials ? 1 : 0))), dim3(kHeadThreads), lds, st, pooled, ldp, Wt, ldw, bias,
-                       B, H, C, logits, ldl, partials, partials ? B * ((F_block + 63) / 64) : 0, xy, head_blocks, signal);
-    return check_launch("ggcn_dense_head");
-}
-
-}  // namespace ggcn
+}  // extern "C"

@@ -337,12 +337,17 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimd) void linear_pooled_kernel(
 }
 
 }  // namespace
+}  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
 
 // 1 = the launch is taken, -ggcn_status (message set) where ggcn_linear_pooled_layers refuses.  Host only: reads the n_layers
 // entries of `layers` and nothing behind any device pointer.  The launcher dispatches on this answer.
-int linear_pooled_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                              int64_t x_batch, int64_t ldx, const void *wpack, const float *Y, int64_t ldy, int B, int R, int C,
-                              int Dl, int F)
+int ggcn_linear_pooled_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                                   int64_t x_batch, int64_t ldx, const void *wpack, const float *Y, int64_t ldy, int B, int R, int C,
+                                   int Dl, int F)
 {
     const char *who = "ggcn_linear_pooled_layers";
     (void)sa_b; (void)sa_r; (void)sa_c;
@@ -374,11 +379,12 @@ int linear_pooled_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_
     return 1;
 }
 
-int linear_pooled_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                         int64_t x_batch, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int B, int R, int C, int Dl, int F,
-                         hipStream_t st)
+int ggcn_linear_pooled_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                              int64_t x_batch, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int B, int R, int C, int Dl,
+                              int F, ggcn_stream_t stream)
 {
-    const int form = linear_pooled_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, x_batch, ldx, wpack, Y, ldy, B, R, C, Dl, F);
+    const hipStream_t st = as_stream(stream);
+    const int form = ggcn_linear_pooled_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, x_batch, ldx, wpack, Y, ldy, B, R, C, Dl, F);
     if (form < 0) return -form;
     LayerPtrs ptrs = {};
     for (int l = 0; l < n_layers; ++l) ptrs.p[l] = static_cast<const float *>(layers[l]);
@@ -393,4 +399,4 @@ int linear_pooled_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_
     return check_launch("ggcn_linear_pooled_layers");
 }
 
-}  // namespace ggcn
+}  // extern "C"

@@ -477,7 +477,23 @@ int linear_f16_form(const void *X, int64_t ldx, int K)
 
 int64_t linear_split_grid(int64_t M, int F) { return grid_for((M + BM - 1) / BM, (F + BN - 1) / BN); }
 
-size_t weight_pack_bytes(int K, int F, int precision)
+// the fast shapes that ggcn_linear_scaled takes (K % 32 == 0, F % 4 == 0, 16-byte aligned rows); the caller keeps bf16x3 otherwise
+bool linear_scaled_takes(const float *X, int64_t ldx, const float *Y, int64_t ldy, int K, int F)
+{
+    return linear_split_form(4, true, X, ldx, Y, ldy, K, F) == (GGCN_FORM_XVEC | GGCN_FORM_KFULL | GGCN_FORM_VST);
+}
+
+GGCN_RANGE_FLAG_TU(range_flag_linear)
+
+}  // namespace ggcn
+
+using namespace ggcn;
+
+// The entries of this file and the launchers that capi.hip calls alternate below, in the order they have always had: a kernel
+// template is instantiated where it is first launched, and the device code keeps that order.
+extern "C" {
+
+size_t ggcn_weight_pack_bytes(int K, int F, int precision)
 {
     if (K <= 0 || F <= 0) return 0;
     const size_t stages = (size_t)bx3::round_up(K, bx3::BK) / bx3::BK;  // whole 32-deep stages
@@ -488,8 +504,10 @@ size_t weight_pack_bytes(int K, int F, int precision)
     return n_tiles * stages * 2 * 2 * bx3::FRAG_BYTES;
 }
 
-int weight_pack(const float *W, int64_t ldw, int K, int F, int precision, bool transposed, void *wpack, hipStream_t st)
+int ggcn_weight_pack(const float *W, int64_t ldw, int K, int F, int precision, int transposed_flag, void *wpack, ggcn_stream_t stream)
 {
+    const bool transposed = transposed_flag != 0;
+    const hipStream_t st = as_stream(stream);
     if (!W || !wpack) return fail(GGCN_EINVAL, "ggcn_weight_pack: null pointer");
     if (K <= 0 || F <= 0 || ldw < (transposed ? K : F))
         return fail(GGCN_EINVAL, "ggcn_weight_pack: bad shape K=%d F=%d ldw=%lld", K, F, (long long)ldw);
@@ -529,6 +547,10 @@ int weight_pack(const float *W, int64_t ldw, int K, int F, int precision, bool t
     return check_launch("ggcn_weight_pack");
 }
 
+}  // extern "C"
+
+namespace ggcn {
+
 // bf16 hi/lo image of a [K_valid x F] matrix laid out for k_steps_total k-steps (rows past K_valid are zeros):
 // the split-K weight gradient packs dH over a node axis padded to its chunk grid (dweight_bx3.hip)
 int weight_pack_rows(const float *W, int64_t ldw, int64_t K_valid, int F, int k_steps_total, void *pack, hipStream_t st)
@@ -551,15 +573,14 @@ int linear_packed(const float *X, int64_t ldx, const void *wpack, float *Y, int6
     return launch_linear<0, float>(X, ldx, wpack, Y, ldy, M, K, F, st);
 }
 
+}  // namespace ggcn
+
 // dX of the backward (train.py:120 through gcn.py:34) on the two-unit f16mx8 product: rows scaled into range by a power of two
-// derived on the device from *amax.  Fast shapes only (K % 32 == 0, F % 4 == 0, 16-byte aligned rows); the caller keeps bf16x3 otherwise.
-bool linear_scaled_takes(const float *X, int64_t ldx, const float *Y, int64_t ldy, int K, int F)
+// derived on the device from *amax.  Fast shapes only (linear_scaled_takes); the caller keeps bf16x3 otherwise.
+extern "C" int ggcn_linear_scaled(const float *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F,
+                                  const float *amax, ggcn_stream_t stream)
 {
-    return linear_split_form(4, true, X, ldx, Y, ldy, K, F) == (GGCN_FORM_XVEC | GGCN_FORM_KFULL | GGCN_FORM_VST);
-}
-int linear_scaled(const float *X, int64_t ldx, const void *wpack, float *Y, int64_t ldy, int64_t M, int K, int F, const float *amax,
-                  hipStream_t st)
-{
+    const hipStream_t st = as_stream(stream);
     if (!X || !wpack || !Y || !amax) return fail(GGCN_EINVAL, "ggcn_linear_scaled: null pointer");
     if (M <= 0 || K <= 0 || F <= 0 || ldx < K || ldy < F) return fail(GGCN_EINVAL, "ggcn_linear_scaled: M=%lld K=%d F=%d", (long long)M, K, F);
     if (!aligned16(wpack)) return fail(GGCN_EINVAL, "ggcn_linear_scaled: wpack must be 16-byte aligned");
@@ -574,6 +595,8 @@ int linear_scaled(const float *X, int64_t ldx, const void *wpack, float *Y, int6
                        static_cast<const char *>(wpack), Y, ldy, M, K, F, (int)m_tiles, n_wg, k_steps, amax);
     return check_launch("ggcn_linear_scaled");
 }
+
+namespace ggcn {
 
 int linear_packed_h(const void *X, int64_t ldx, const void *wpack, void *Y, int64_t ldy, int64_t M,
                     int K, int F, int precision, hipStream_t st)
@@ -596,7 +619,5 @@ int linear_out_bf16(const float *X, int64_t ldx, const void *wpack, void *Y, int
 {
     return launch_linear<0, float, __bf16>(X, ldx, wpack, static_cast<__bf16 *>(Y), ldy, M, K, F, st);
 }
-
-GGCN_RANGE_FLAG_TU(range_flag_linear)
 
 }  // namespace ggcn

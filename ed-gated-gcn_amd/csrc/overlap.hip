@@ -43,12 +43,18 @@ __global__ __launch_bounds__(256) void overlap_finish(const float *__restrict__ 
 }
 
 }  // namespace
+}  // namespace ggcn
 
-size_t overlap_workspace_bytes(int B) { return (size_t)(B > 0 ? B : 1) * sizeof(float); }
+using namespace ggcn;
 
-int gate_overlap(const float *x1, const float *y1, int B, int F, float *xy, void *workspace,
-                 hipStream_t st)
+extern "C" {
+
+size_t ggcn_overlap_workspace_bytes(int B) { return (size_t)(B > 0 ? B : 1) * sizeof(float); }
+
+int ggcn_gate_overlap(const float *x1, const float *y1, int B, int F, float *xy, void *workspace,
+                      ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!x1 || !y1 || !xy || !workspace) return fail(GGCN_EINVAL, "ggcn_gate_overlap: null pointer");
     if (B <= 0 || F <= 0) return fail(GGCN_EINVAL, "ggcn_gate_overlap: B=%d F=%d must be positive", B, F);
     float *partial = static_cast<float *>(workspace);
@@ -57,4 +63,4 @@ int gate_overlap(const float *x1, const float *y1, int B, int F, float *xy, void
     return check_launch("ggcn_gate_overlap");
 }
 
-}  // namespace ggcn
+}  // extern "C"

@@ -54,9 +54,15 @@ __global__ __launch_bounds__(1024) void lds_poison_kernel(uint32_t pattern, int 
 static __device__ unsigned int g_poison_sink;
 
 }  // namespace
+}  // namespace ggcn
 
-int poison_lds(uint32_t pattern, hipStream_t st)
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_debug_poison_lds(uint32_t pattern, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
         return fail(GGCN_ELAUNCH, "ggcn_debug_poison_lds: cannot read the device's CU count");
@@ -69,8 +75,9 @@ int poison_lds(uint32_t pattern, hipStream_t st)
     return check_launch("ggcn_debug_poison_lds");
 }
 
-int absmax(const void *X, int is_half, int64_t ld, int64_t M, int K, float *out, hipStream_t st)
+int ggcn_absmax(const void *X, int is_half, int64_t ld, int64_t M, int K, float *out, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     if (!X || !out) return fail(GGCN_EINVAL, "ggcn_absmax: null pointer");
     if (M <= 0 || K <= 0 || ld < K) return fail(GGCN_EINVAL, "ggcn_absmax: M=%lld K=%d ld=%lld", (long long)M, K, (long long)ld);
     hipError_t e = hipMemsetAsync(out, 0, 2 * sizeof(float), st);
@@ -84,4 +91,4 @@ int absmax(const void *X, int is_half, int64_t ld, int64_t M, int K, float *out,
     return check_launch("ggcn_absmax");
 }
 
-}  // namespace ggcn
+}  // extern "C"

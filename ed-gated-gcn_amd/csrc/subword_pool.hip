@@ -258,11 +258,46 @@ __global__ __launch_bounds__(256) void anchor_pool_layers_kernel(const float *__
     }
 }
 
-}  // namespace
-
-int subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const float *X, int64_t x_batch,
-                 int64_t ldx, float *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, hipStream_t st)
+template <typename XT>
+void launch_layers(bool vec, const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const LayerPtrs &ptrs, int n_layers,
+                   int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int Dl, hipStream_t st)
 {
+    const int units = (Dl + kUnit - 1) / kUnit;
+    const dim3 grid((unsigned)(B * R), (unsigned)((n_layers * units + 3) / 4));
+    if (vec)
+        hipLaunchKernelGGL((subword_pool_layers_kernel<true, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
+                           x_batch, ldx, static_cast<XT *>(Y), y_batch, ldy, R, C, Dl, units);
+    else
+        hipLaunchKernelGGL((subword_pool_layers_kernel<false, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
+                           x_batch, ldx, static_cast<XT *>(Y), y_batch, ldy, R, C, Dl, units);
+}
+
+template <typename XT>
+void launch_anchor(bool vec, const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const LayerPtrs &ptrs, int n_layers,
+                   int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides, float *Z, int64_t ldz,
+                   int64_t z_section, int B, int R, int C, int Dl, hipStream_t st)
+{
+    const int units = (Dl + kUnit - 1) / kUnit;
+    const dim3 grid((unsigned)B, (unsigned)((n_layers * units + 3) / 4));
+    if (vec)
+        hipLaunchKernelGGL((anchor_pool_layers_kernel<true, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
+                           x_batch, ldx, anchor, length, sides, Z, ldz, z_section, R, C, Dl, units);
+    else
+        hipLaunchKernelGGL((anchor_pool_layers_kernel<false, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
+                           x_batch, ldx, anchor, length, sides, Z, ldz, z_section, R, C, Dl, units);
+}
+
+}  // namespace
+}  // namespace ggcn
+
+using namespace ggcn;
+
+extern "C" {
+
+int ggcn_subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const float *X, int64_t x_batch,
+                      int64_t ldx, float *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, ggcn_stream_t stream)
+{
+    const hipStream_t st = as_stream(stream);
     if (!A || !X || !Y) return fail(GGCN_EINVAL, "ggcn_subword_pool: null pointer");
     if (B <= 0 || R <= 0 || C <= 0 || D <= 0)
         return fail(GGCN_EINVAL, "ggcn_subword_pool: B=%d R=%d C=%d D=%d must be positive", B, R, C, D);
@@ -281,9 +316,10 @@ int subword_pool(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const
     return check_launch("ggcn_subword_pool");
 }
 
-int subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *Xv, int64_t x_batch,
-                      int64_t ldx, void *Yv, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, hipStream_t st)
+int ggcn_subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *Xv, int64_t x_batch,
+                           int64_t ldx, void *Yv, int64_t y_batch, int64_t ldy, int B, int R, int C, int D, ggcn_stream_t stream)
 {
+    const hipStream_t st = as_stream(stream);
     const __bf16 *X = static_cast<const __bf16 *>(Xv);
     __bf16 *Y = static_cast<__bf16 *>(Yv);
     if (!A || !X || !Y) return fail(GGCN_EINVAL, "ggcn_subword_pool_bf16: null pointer");
@@ -307,9 +343,9 @@ int subword_pool_bf16(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, 
 
 // 1 = vector form, 0 = scalar form, -ggcn_status (message set) where ggcn_subword_pool_layers refuses.  Host only: reads the
 // n_layers entries of `layers` and nothing behind any device pointer.  The launcher dispatches on this answer.
-int subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                             int is_bf16, int64_t x_batch, int64_t ldx, const void *Y, int64_t y_batch, int64_t ldy, int B, int R,
-                             int C, int Dl)
+int ggcn_subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                                  int is_bf16, int64_t x_batch, int64_t ldx, const void *Y, int64_t y_batch, int64_t ldy, int B, int R,
+                                  int C, int Dl)
 {
     const char *who = "ggcn_subword_pool_layers";
     (void)sa_b; (void)sa_r; (void)sa_c;
@@ -341,28 +377,13 @@ int subword_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t
     return vec ? 1 : 0;
 }
 
-namespace {
-template <typename XT>
-void launch_layers(bool vec, const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const LayerPtrs &ptrs, int n_layers,
-                   int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C, int Dl, hipStream_t st)
+int ggcn_subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                             int is_bf16, int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C,
+                             int Dl, ggcn_stream_t stream)
 {
-    const int units = (Dl + kUnit - 1) / kUnit;
-    const dim3 grid((unsigned)(B * R), (unsigned)((n_layers * units + 3) / 4));
-    if (vec)
-        hipLaunchKernelGGL((subword_pool_layers_kernel<true, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
-                           x_batch, ldx, static_cast<XT *>(Y), y_batch, ldy, R, C, Dl, units);
-    else
-        hipLaunchKernelGGL((subword_pool_layers_kernel<false, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
-                           x_batch, ldx, static_cast<XT *>(Y), y_batch, ldy, R, C, Dl, units);
-}
-}  // namespace
-
-int subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                        int is_bf16, int64_t x_batch, int64_t ldx, void *Y, int64_t y_batch, int64_t ldy, int B, int R, int C,
-                        int Dl, hipStream_t st)
-{
-    const int form = subword_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, Y, y_batch, ldy, B, R,
-                                              C, Dl);
+    const hipStream_t st = as_stream(stream);
+    const int form = ggcn_subword_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, Y, y_batch, ldy, B,
+                                                   R, C, Dl);
     if (form < 0) return -form;
     LayerPtrs ptrs = {};
     for (int l = 0; l < n_layers; ++l) ptrs.p[l] = layers[l];
@@ -374,10 +395,10 @@ int subword_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c
 }
 
 // 1 = vector form, 0 = scalar form, -ggcn_status (message set) where ggcn_anchor_pool_layers refuses.  Host only, as
-// subword_pool_layers_form; its vector / scalar rule with Z, ldz and (with sides) z_section in the place of Y, y_batch and ldy.
-int anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                            int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
-                            const float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl)
+// ggcn_subword_pool_layers_form; its vector / scalar rule with Z, ldz and (with sides) z_section in the place of Y, y_batch and ldy.
+int ggcn_anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                                 int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
+                                 const float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl)
 {
     const char *who = "ggcn_anchor_pool_layers";
     (void)sa_b; (void)sa_r; (void)sa_c;
@@ -416,29 +437,13 @@ int anchor_pool_layers_form(const float *A, int64_t sa_b, int64_t sa_r, int64_t 
     return vec ? 1 : 0;
 }
 
-namespace {
-template <typename XT>
-void launch_anchor(bool vec, const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const LayerPtrs &ptrs, int n_layers,
-                   int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides, float *Z, int64_t ldz,
-                   int64_t z_section, int B, int R, int C, int Dl, hipStream_t st)
+int ggcn_anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
+                            int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides,
+                            float *Z, int64_t ldz, int64_t z_section, int B, int R, int C, int Dl, ggcn_stream_t stream)
 {
-    const int units = (Dl + kUnit - 1) / kUnit;
-    const dim3 grid((unsigned)B, (unsigned)((n_layers * units + 3) / 4));
-    if (vec)
-        hipLaunchKernelGGL((anchor_pool_layers_kernel<true, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
-                           x_batch, ldx, anchor, length, sides, Z, ldz, z_section, R, C, Dl, units);
-    else
-        hipLaunchKernelGGL((anchor_pool_layers_kernel<false, XT>), grid, dim3(256), 0, st, A, sa_b, sa_r, sa_c, ptrs, n_layers,
-                           x_batch, ldx, anchor, length, sides, Z, ldz, z_section, R, C, Dl, units);
-}
-}  // namespace
-
-int anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c, const void *const *layers, int n_layers,
-                       int is_bf16, int64_t x_batch, int64_t ldx, const int64_t *anchor, const int64_t *length, int sides, float *Z,
-                       int64_t ldz, int64_t z_section, int B, int R, int C, int Dl, hipStream_t st)
-{
-    const int form = anchor_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, anchor, length, sides, Z,
-                                             ldz, z_section, B, R, C, Dl);
+    const hipStream_t st = as_stream(stream);
+    const int form = ggcn_anchor_pool_layers_form(A, sa_b, sa_r, sa_c, layers, n_layers, is_bf16, x_batch, ldx, anchor, length, sides,
+                                                  Z, ldz, z_section, B, R, C, Dl);
     if (form < 0) return -form;
     LayerPtrs ptrs = {};
     for (int l = 0; l < n_layers; ++l) ptrs.p[l] = layers[l];
@@ -452,4 +457,4 @@ int anchor_pool_layers(const float *A, int64_t sa_b, int64_t sa_r, int64_t sa_c,
     return check_launch("ggcn_anchor_pool_layers");
 }
 
-}  // namespace ggcn
+}  // extern "C"

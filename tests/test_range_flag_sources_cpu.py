@@ -1,9 +1,11 @@
-"""Every translation unit that can raise the f16mx8 range flag has a reader, and ``ggcn_range_flag`` calls it (text only, no GPU).
+"""Every translation unit that can raise the f16mx8 range flag has a reader that registers itself with ``ggcn_range_flag`` (text
+only, no GPU).
 
 ``static __device__ unsigned int g_range_flag`` (``f16mx8_core.h``) is ONE COPY PER TRANSLATION UNIT: a ``.hip`` file's reports reach
-``ggcn_range_flag`` only if the file expands ``GGCN_RANGE_FLAG_TU(name)`` and ``capi.hip`` calls that ``name``.  A new ``.hip`` that
-instantiates ``mx8::mainloop`` and forgets either half compiles, runs and never reports.  This test reads ``csrc/*.hip`` with the
-project's own ``#include "..."`` lines resolved transitively, comments stripped.
+``ggcn_range_flag`` only if the file expands ``GGCN_RANGE_FLAG_TU(name)``, which defines the copy's reader and registers it when the
+library is loaded.  A new ``.hip`` that instantiates ``mx8::mainloop`` and forgets the macro compiles, runs and never reports.  This
+test reads ``csrc/*.hip`` with the project's own ``#include "..."`` lines resolved transitively, comments stripped.  That the reports
+arrive is ``test_gpu_range_report.py``'s to prove, at run time.
 
 What counts as "makes a verdict": an instantiation ``mx8::mainloop<`` / ``mx6::mainloop<``, a call ``range_verdict(`` or the word
 ``g_range_flag`` -- looked for in the ``.hip`` itself and in every header it includes EXCEPT the headers that define the flag or a
@@ -54,19 +56,6 @@ def _makes_verdict(hip):
     return any(VERDICT.search(_read(n)) for n in own)
 
 
-def _guarded_lines(text, guard):
-    """The lines of ``text`` between ``#ifdef guard`` and its ``#endif`` (no nesting in these files)."""
-    out, inside = [], False
-    for line in text.splitlines():
-        if re.match(r"\s*#\s*ifdef\s+%s\b" % guard, line) or re.match(r"\s*#\s*if\s+defined\(%s\)" % guard, line):
-            inside = True
-        elif inside and re.match(r"\s*#\s*endif", line):
-            inside = False
-        elif inside:
-            out.append(line)
-    return "\n".join(out)
-
-
 def _range_flag_body():
     text = _read("capi.hip")
     m = re.search(r"\bint\s+ggcn_range_flag\s*\([^)]*\)\s*\{", text)
@@ -78,10 +67,17 @@ def _range_flag_body():
     return text[m.end():i - 1]
 
 
+def _macro_definition():
+    """The ``#define GGCN_RANGE_FLAG_TU`` of ``f16mx8_core.h`` with its continuation lines."""
+    m = re.search(r"^\s*#\s*define\s+GGCN_RANGE_FLAG_TU\b(?:[^\n]*\\\n)*[^\n]*", _read("f16mx8_core.h"), flags=re.M)
+    assert m, "f16mx8_core.h no longer defines GGCN_RANGE_FLAG_TU"
+    return m.group(0)
+
+
 def _optional_sources():
-    """``.hip`` files the Makefile compiles under ``F16MX6=1`` only, the build that defines ``GGCN_WITH_F16MX6``.  ``common.h`` declares
-    every reader outside any ``#ifdef`` (a declaration costs nothing), so "declared under the guard" is read as "its file is built
-    under the guard": the file names between the Makefile's ``F16MX6`` conditional and its ``endif``, however they are laid out."""
+    """``.hip`` files the Makefile compiles under ``F16MX6=1`` only, the build that defines ``GGCN_WITH_F16MX6``: the file names
+    between the Makefile's ``F16MX6`` conditional and its ``endif``, however they are laid out.  The two source lists partition
+    ``csrc/*.hip``, and every object is linked by name, so no reader's registration can be left out of the library."""
     with open(os.path.join(CSRC, "Makefile")) as f:
         mk = re.sub(r"#[^\n]*", "", f.read())
     m = re.search(r"^ifn?eq[^\n]*F16MX6[^\n]*\n(.*?)^endif", mk, flags=re.S | re.M)
@@ -98,9 +94,7 @@ def test_the_headers_that_define_the_flag_and_the_main_loops():
 
 
 def test_every_file_that_makes_a_verdict_has_one_reader_that_ggcn_range_flag_calls():
-    common, body = _read("common.h"), _range_flag_body()
-    guarded_calls = _guarded_lines(body, MX6_GUARD)
-    optional = _optional_sources()
+    assert _optional_sources() == {"fused6.hip"}
     reporters = [h for h in _hips() if _makes_verdict(h)]
     # today's list, so that a change of it shows up here
     assert reporters == ["fused6.hip", "fused_block8.hip", "fused_layer.hip", "fused_weighted_drop.hip", "fused_wide.hip",
@@ -112,17 +106,19 @@ def test_every_file_that_makes_a_verdict_has_one_reader_that_ggcn_range_flag_cal
         name = found[0]
         assert name not in names, "%s and %s define the same reader %s" % (hip, names.get(name), name)
         names[name] = hip
-        assert re.search(r"\bint\s+%s\s*\(\s*unsigned\s+int\s*\*" % name, common), "%s (%s) is not declared in common.h" % (name, hip)
-        calls = len(re.findall(r"\b%s\s*\(" % name, body))
-        assert calls == 1, "ggcn_range_flag calls %s (%s) %d times: that file's reports never reach the user" % (name, hip, calls)
-        in_guard = re.search(r"\b%s\s*\(" % name, guarded_calls) is not None
-        assert in_guard == (hip in optional), "%s: built %s, called %s #ifdef %s" % (
-            hip, "under F16MX6=1 only" if hip in optional else "always", "inside" if in_guard else "outside", MX6_GUARD)
-    # the converse: ggcn_range_flag calls no reader that no file defines, and every reader defined anywhere is one of the above
-    called = set(re.findall(r"\b(range_flag_\w+)\s*\(", body))
-    assert called == set(names), "ggcn_range_flag calls %s; the files define %s" % (sorted(called), sorted(names))
+    # the converse: every reader defined anywhere is one of the above
     everywhere = {n: h for h in _hips() for n in READER.findall(_read(h))}
     assert everywhere == names, "a file without verdicts expands GGCN_RANGE_FLAG_TU: %s" % sorted(set(everywhere) - set(names))
+
+
+def test_the_macro_registers_its_reader_and_ggcn_range_flag_names_none():
+    """What replaced the declarations in ``common.h`` and the call list in ``capi.hip``: expanding the macro is all a file has to do."""
+    assert re.search(r"\bregister_range_flag_reader\s*\(\s*fn\s*\)", _macro_definition()), \
+        "GGCN_RANGE_FLAG_TU no longer registers the reader it defines"
+    body = _range_flag_body()
+    assert not re.search(r"\brange_flag_\w+", body), "ggcn_range_flag names a reader"
+    assert not re.search(r"^\s*#", body, flags=re.M), "ggcn_range_flag has a preprocessor line (the F16MX6 build needs none)"
+    assert not re.search(r"\brange_flag_\w+", _read("common.h")), "common.h declares a reader"
 
 
 def test_files_that_include_the_flag_header_without_making_a_verdict():
