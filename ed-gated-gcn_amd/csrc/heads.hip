@@ -483,8 +483,10 @@ __global__ __launch_bounds__(256) void head_dweight_finish_kernel(const float *_
 // rows go to LDS, lane = class, wavefront w takes k-slice w (Wt rows are read coalesced and all at once), the slices
 // meet in LDS in a fixed order: a row's logits do not depend on which batch (or shard) the row sits in.  The LAST workgroup
 // of the launch, when the caller passes them, adds the regulariser's partials of a ggcn_block_fused launch (bert_amir5.py:638)
-// in reduce_partials' order (fused_common.h) -- the one-workgroup ggcn_overlap_reduce launch rides along: at a 512-graph shard
-// the two tail launches were 13 us of a 95 us step, this one is ~4.
+// in a fixed order of its own (a 1024-thread stride, a wavefront reduction, the 16 wavefronts in sequence; reduce_partials in
+// fused_common.h strides by 256 and adds four wavefronts pairwise, so the two agree up to the order of additions) -- the
+// one-workgroup ggcn_overlap_reduce launch rides along: at a 512-graph shard the two tail launches were 13 us of a 95 us step,
+// this one is ~4.
 // ggcn_dense_head_signal: the launch counts itself done in memory.  signal[0] collects the workgroups of this launch (every
 // workgroup's results are fenced before it arrives; the last arriver clears it for the next launch), signal[1] counts finished
 // launches -- a stream gated on it by hipStreamWaitValue32(>= n) may read the logits and xy of the n-th launch without an event
@@ -535,7 +537,9 @@ __global__ __launch_bounds__(kHeadThreads) void dense_head_kernel(const float *_
         const int r = wave >> 1, hb = (H + 1) >> 1, kb = (wave & 1) * hb, ke = kb + hb < H ? kb + hb : H;
         const bool live = b0 + r < B;
         const float *src = pooled + (int64_t)(live ? b0 + r : 0) * ldp;
-        if ((hb & 3) == 0 && (ldp & 3) == 0 && (reinterpret_cast<uintptr_t>(pooled) & 15u) == 0) {
+        // 16 bytes at a time for H % 8 == 0 alone: both halves are then whole float4s.  (hb % 4 == 0 also holds for H = 8m - 1,
+        // where the second half's last float4 would take the pad column and store it on the next row's first element.)
+        if ((H & 7) == 0 && (ldp & 3) == 0 && (reinterpret_cast<uintptr_t>(pooled) & 15u) == 0) {
             for (int k = kb + 4 * lane; k < ke; k += 256) {
                 const float4 v = *reinterpret_cast<const float4 *>(src + k);
                 *reinterpret_cast<float4 *>(rows + r * H + k) = live ? v : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
